@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: NPPC K=5 FullSubNet+ train step, spectrogram-frames/s on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--dump-outputs DIR]
 
 N > 1 without an external launcher: bench.py starts its own N ranks (`python -m torch.distributed.run ... bench.py`) as a
 CHILD process before anything touches the GPU and exits with the child's code; under an external torch.distributed.run
@@ -12,7 +12,9 @@ of synthetic 16 kHz noisy speech that is already resident in HBM: noisy+clean ST
 forward, cIRM build/apply, K-direction net forward, Gram-Schmidt, NPPC loss, full backward, gradient all-reduce
 (N > 1), Adam.  Weak scaling: every rank runs the per-GPU batch, rank r on clips [B*r, B*r+B).  Weights: seeded random
 init (no checkpoint offline).  --config c3 = BASELINE config 3 (inpainting sibling, single GPU), same JSON schema.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; ms_per_step = wall time of the K timed steps / K.  --dump-outputs DIR writes what the last
+timed step computed (its returned arrays and the direction net's updated parameters) as DIR/<name>.npy, <= 64 MB in all,
+for output-for-output comparison of two builds: inputs and initial weights are seeded, identical from run to run.
 
 What the line's extra objects mean (definitions and byte/FLOP counts: DESIGN.md section 4):
   roofline        the kernel with the largest total duration per step (HIP events around every launch in an untimed
@@ -233,6 +235,56 @@ ROCPROF_NAME = {   # bench label prefix -> substring of the rocprofv3 kernel nam
 }
 
 
+DUMP_BUDGET_BYTES = 63_000_000     # --dump-outputs: all .npy payloads together (the files, headers included, stay < 64 MB)
+DUMP_SAMPLE_SEED = 20251015        # fixed: two builds sample the same elements of an over-budget array
+
+
+def step_outputs(step_result, net):
+    """what one train step hands its caller -> {name: host tensor}: the returned (reconst_err, objective, log) -- the log's
+    echoed inputs left out -- and the direction net's parameters after the step's update (one flat vector, in
+    named_parameters() order).  Copied off the device at once: later steps reuse the step-persistent workspaces."""
+    reconst_err, objective, log = step_result
+    out = {"reconst_err": reconst_err, "objective": objective}
+    for k, v in log.items():
+        if isinstance(v, torch.Tensor) and k not in ("noisy_complex", "clean_complex", "reconst_err", "objective"):
+            out[k] = v
+    out["direction_net_params"] = torch.cat([p.detach().reshape(-1).float() for _, p in net.named_parameters()])
+    host = {}
+    for k, v in out.items():
+        v = v.detach()
+        if v.is_complex():
+            v = torch.view_as_real(v)           # [..., 2] = (real, imag)
+        host[k] = v.to("cpu", torch.float64 if v.dtype in (torch.float64, torch.int64, torch.int32) else torch.float32)
+    return host
+
+
+def dump_outputs(dirname, arrays, meta=None):
+    """writes arrays {name: host tensor} as dirname/<name>.npy (float32 / float64) within DUMP_BUDGET_BYTES in all.  Arrays
+    that fit their share of the budget are written whole; the others as a fixed seeded sample of their flattened elements
+    (sorted flat indices, the same for every run of the same shape).  Returns what was written and how, for the JSON line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].numel() * arrays[k].element_size(), k))
+    left = DUMP_BUDGET_BYTES
+    manifest = {"dir": os.path.abspath(dirname), "budget_bytes": DUMP_BUDGET_BYTES, "sample_seed": DUMP_SAMPLE_SEED,
+                "sampling": "numpy.random.Generator(PCG64(sample_seed)).choice(numel, n, replace=False), sorted, on the "
+                            "C-order flattened array", "meta": meta or {}, "arrays": {}}
+    for i, k in enumerate(names):
+        a = arrays[k].numpy()
+        share = left // (len(names) - i)
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype), "numel": int(a.size)}
+        if a.nbytes > share:
+            n = int(share // a.itemsize)
+            idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(a.size, n, replace=False))
+            a = np.ascontiguousarray(a.reshape(-1)[idx])
+            entry["sampled"] = n
+        np.save(os.path.join(dirname, k + ".npy"), a)
+        left -= a.nbytes
+        manifest["arrays"][k] = entry
+    log(f"wrote {len(names)} arrays ({(DUMP_BUDGET_BYTES - left) / 1e6:.1f} MB) to {dirname}")
+    return manifest
+
+
 def self_launch(a):
     """--gpus N without an external launcher: start the N ranks as a child torch.distributed.run BEFORE any GPU call of
     this process (a process that initialised the GPU must never exec / must not hold the device the ranks need)"""
@@ -283,9 +335,13 @@ def main():
     ap.add_argument("--no-fp32", action="store_true", help="skip the precision-matched fp32 steps")
     ap.add_argument("--no-families", action="store_true", help="skip the per-launch HIP-event pass")
     ap.add_argument("--pipeline", action="store_true", help="pipeline_update mode of the trainer (A/B switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (<= 64 MB in all)")
     ap.add_argument("--dp-selftest", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dp-selftest-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))
@@ -302,7 +358,8 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_inpainting
         return bench_inpainting.main(["--steps", str(a.steps), "--warmup", str(a.warmup), "--precision", a.precision]
-                                     + (["--no-cpu-baseline"] if a.no_cpu_baseline else []))
+                                     + (["--no-cpu-baseline"] if a.no_cpu_baseline else [])
+                                     + (["--dump-outputs", a.dump_outputs] if a.dump_outputs else []))
     cb, cs, ck = {"c2": (BATCH, SECONDS, K_DIRS), "c5": (8, 30, 8)}[a.config]
     a.batch, a.seconds, a.dirs = a.batch or cb, a.seconds or cs, a.dirs or ck
     workload = {(BATCH, SECONDS, K_DIRS): "C2", (8, 30, 8): "C5"}.get((a.batch, a.seconds, a.dirs), "custom")
@@ -341,10 +398,13 @@ def main():
     ops_lstm.PROFILE = []
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        _, objective, _ = tr.train_step(batch)
+        last = tr.train_step(batch)
     tr.flush()                                   # the last step's parked update (weight gradients, exchange, Adam) is inside the timed region
     sync()
     dt = time.perf_counter() - t0
+    objective = last[1]
+    dumped = step_outputs(last, tr.nppc_model.audio_pc_wrapper.net) if (a.dump_outputs and rank == 0) else None
+    del last
     prof, ops_lstm.PROFILE = ops_lstm.PROFILE, None
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
@@ -365,6 +425,12 @@ def main():
         return
     ms_step = 1e3 * dt / a.steps
     log(f"timed region done: {ms_step:.2f} ms/step")
+    dump_info = None
+    if dumped is not None:
+        dump_info = dump_outputs(a.dump_outputs, dumped, meta={"config": a.config, "workload": workload, "precision": a.precision,
+                                                   "batch": a.batch, "seconds": a.seconds, "dirs": a.dirs,
+                                                   "steps": a.steps, "warmup": a.warmup, "n_gpus": world})
+        del dumped
 
     # ---- LSTM launches inside the timed region (HIP events on the launch stream) --------------------------------
     per = {}
@@ -449,6 +515,8 @@ def main():
     }
     if dp_info is not None:
         out["dp"] = dp_info
+    if dump_info is not None:
+        out["dumped_outputs"] = dump_info
     if world == 1 and a.precision == "bf16" and not a.no_fp32:
         # the reference computes in fp32: the same step in the product's fp32 parity mode (exact-f32 MFMA), outside the
         # timed region.  The bf16 trainer's step-persistent workspaces stay allocated (288 GB of HBM: both fit).

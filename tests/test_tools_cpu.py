@@ -65,3 +65,36 @@ def test_summarize_pmc_on_a_synthetic_counter_file(tmp_path):
     a = out[1].split(",")
     assert a[0] == "kern_a(int)" and a[1] == "2" and a[2] == "4096" and a[3] == "1024"
     assert float(a[4]) == 2 * 4096 / 1024 / 2 and float(a[5]) == 0.5          # MB per launch: fetch doubled (gfx950), write as is
+
+
+def test_dump_outputs_stays_within_budget_and_samples_deterministically(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files, small arrays whole, an over-budget array as the same seeded sample on
+    every run, complex log entries as (real, imag) pairs, the echoed inputs left out"""
+    import json
+    import numpy as np
+    import torch
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 40_000)
+    net = torch.nn.Linear(3, 2)
+    big = torch.arange(20_000, dtype=torch.float32).reshape(100, 200)
+    res = (torch.ones(4), torch.tensor(0.5, dtype=torch.float64),
+           {"w_mat": big, "pred_crm": torch.ones(3, dtype=torch.bfloat16),
+            "err_proj": torch.complex(torch.ones(4, 2), -torch.ones(4, 2)), "noisy_complex": torch.ones(8)})
+    host = b.step_outputs(res, net)
+    assert "noisy_complex" not in host and host["err_proj"].shape == (4, 2, 2)
+    assert host["objective"].dtype == torch.float64 and host["pred_crm"].dtype == torch.float32
+    assert host["direction_net_params"].numel() == 8
+    runs = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        man = b.dump_outputs(str(d), host)
+        assert sorted(p.name for p in d.iterdir()) == sorted(k + ".npy" for k in host)        # nothing but the arrays
+        runs.append({p.name: np.load(p) for p in d.glob("*.npy")})
+        assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 40_000 + 128 * len(runs[-1])      # + the .npy headers
+    json.dumps(man)                                                                      # goes into the JSON line
+    assert set(runs[0]) == {k + ".npy" for k in host} and all(v.dtype in (np.float32, np.float64) for v in runs[0].values())
+    assert "sampled" in man["arrays"]["w_mat"] and "sampled" not in man["arrays"]["reconst_err"]
+    np.testing.assert_array_equal(runs[0]["reconst_err.npy"], np.ones(4, np.float32))
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k])
+    w = runs[0]["w_mat.npy"]
+    assert w.size == man["arrays"]["w_mat"]["sampled"] and np.all(np.diff(w) > 0)    # sorted flat indices of an increasing array

@@ -113,7 +113,11 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=4.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (<= 64 MB in all)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     from nppc_audio import unet_engine
     L = int(a.seconds * 16000)
     F, T = NFFT // 2 + 1, 1 + (L + 2 * (NFFT // 2) - NFFT) // HOP
@@ -128,9 +132,17 @@ def main(argv=None):
     unet_engine.PROFILE = []
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        _, objective, _ = tr.train_step(batch)
+        last = tr.train_step(batch)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    objective = last[1]
+    import bench
+    dump_info = None
+    if a.dump_outputs:
+        dump_info = bench.dump_outputs(a.dump_outputs, bench.step_outputs(last, tr.nppc_model.pc_wrapper.net),
+                           meta={"config": "c3", "precision": a.precision, "batch": a.batch, "seconds": a.seconds,
+                                 "steps": a.steps, "warmup": a.warmup, "n_gpus": 1})
+    del last
     prof, unet_engine.PROFILE = unet_engine.PROFILE, None
     agg = {}
     for kind, flops, e0, e1 in prof:
@@ -144,7 +156,6 @@ def main(argv=None):
     frames = a.batch * T
     ms_step = 1e3 * dt / a.steps
     flops_step = sum(v[0] for v in agg.values()) / a.steps
-    import bench
     wl = "C3" if (a.batch, a.seconds, a.precision) == (32, 4.0, "bf16") else "custom"
     traffic, traffic_note = bench.pmc_traffic(ROCPROF_NAME.get(dom_name), wl, PMC_CSV, PMC_STAMP, expect="C3", aggregate=True)
     out = {
@@ -162,6 +173,8 @@ def main(argv=None):
                               "frac": flops_step / (ms_step * 1e-3) / 1e12 / PEAK[a.precision],
                               "note": "convolution FLOPs only (2*MACs of every conv launch of the step) / whole-step time"}},
     }
+    if dump_info is not None:
+        out["dumped_outputs"] = dump_info
     log(f"timed region done: {1e3 * dt / a.steps:.1f} ms/step")
     if not a.no_cpu_baseline:
         log("timing the CPU baseline (bounded sample)")

@@ -19,7 +19,7 @@ VMEM = re.compile(r"^(global|buffer|scratch|flat)_(load|store|atomic)")
 
 
 def isa_of(src):
-    out = os.path.join(tempfile.gettempdir(), "asm_rings_" + os.path.basename(src) + ".s")
+    out = os.path.join(tempfile.mkdtemp(prefix="asm_rings_"), os.path.basename(src) + ".s")     # private: /tmp is shared
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
                            "-I" + CSRC, "-Wno-unused-value", "-Wno-unused-command-line-argument", "-S", "--cuda-device-only",
                            "-o", out, src])
