@@ -226,6 +226,7 @@ int nppc_subband_stage(int prec, const void* src, int ldS, const void* fb, int l
                        void* x, int B, int F, int Tp, int Tv, int nb, int G, int KX, int ones_col, void* stream) {
   if (!src || !fb || !scale || !x || B <= 0 || G < 1 || 2 * nb + 4 + (ones_col ? 1 : 0) > KX || KX % 8) return NPPC_EBADARG;
   if (B > 1 && !(B > G)) return NPPC_EBADARG;
+  if (nb < 0 || nb >= F) return NPPC_EBADARG;      // reflect padding needs nb < F (as torch's reflect pad); reflect_idx reads LDS
   const int Geff = B > 1 ? G : 1;                    // the reference applies drop_band only when batch > 1
   const int Fo = Geff <= 1 ? F : (F - F % Geff) / Geff;
   const long Nseq = (long)B * Fo;
