@@ -17,7 +17,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INC, "-I"
 
 def _stamp(src):
     h = hashlib.sha1()
-    for p in [src, os.path.join(CSRC, "common.h"), os.path.join(INC, "nppc_hip.h")]:
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    for p in [src] + headers + [os.path.join(INC, "nppc_hip.h")]:
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(FLAGS).encode())

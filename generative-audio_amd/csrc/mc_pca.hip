@@ -7,28 +7,9 @@
 //     scikit-learn's sign rule (svd_flip on V: the largest-magnitude entry of every component is positive).
 // HBM-bound: every MC sample is read twice (Gram, components); the K x K eigenproblem is on-chip.
 #include "common.h"
+#include "philox.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------ Philox4x32-10
-struct u32x4 {
-  unsigned x, y, z, w;
-};
-
-__device__ __forceinline__ u32x4 philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1;
-    c3 = (unsigned)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return u32x4{c0, c1, c2, c3};
-}
 
 // in place on X [rows][ld], channels [0, C): x <- keep ? x / (1 - p) : 0, keep = (u32 >= p * 2^32); four channels per
 // thread share one Philox block (counter = row, channel / 4, stream).  keep_out (nullable) [rows][C] u8 for the tests.
@@ -41,8 +22,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(T* __restrict__ X, long ld
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
     const long r = e / c4;
     const int c = (int)(e % c4) * 4;
-    const u32x4 u = philox4x32((unsigned)r, (unsigned)((unsigned long long)r >> 32), (unsigned)(c / 4), stream_id, seed_lo,
-                               seed_hi);
+    const philox_u4 u = dropout_bits4(r, c / 4, stream_id, seed_lo, seed_hi);
     const unsigned uu[4] = {u.x, u.y, u.z, u.w};
     T* px = X + r * ld + c;
 #pragma unroll
@@ -328,8 +308,7 @@ extern "C" {
 int nppc_dropout(int prec, void* X, long ld, long rows, int C, float p, long seed, int stream_id,
                  unsigned char* keep_out, void* stream) {
   if (!X || rows <= 0 || C <= 0 || C % 4 || ld < C || p < 0.f || p >= 1.f) return NPPC_EBADARG;
-  const double t = (double)p * 4294967296.0;
-  const unsigned thresh = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+  const unsigned thresh = dropout_threshold(p);
   const float scale = 1.f / (1.f - p);
   const long n = rows * (C / 4);
   const dim3 grid((unsigned)(n / 256 + 1 > 65536 ? 65536 : n / 256 + 1));

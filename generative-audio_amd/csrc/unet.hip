@@ -14,6 +14,7 @@
 #include <algorithm>
 #include "common.h"
 #include "nppc_hip.h"
+#include "philox.h"
 
 namespace {
 
@@ -641,16 +642,37 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const T* __restrict__ X, lo
   store8<T>(Y + p * ldy + c8, yv);
 }
 
+// nn.Dropout that followed the block output in the forward (mc_pca.hip: dropout_kernel, in place): the keep bits are
+// regenerated from (seed; pixel row, channel / 4, stream), never stored
+struct DropBwd {
+  unsigned thresh, seed_lo, seed_hi, stream_id;
+  float scale;
+};
+
+// m[i] = keep ? 1 / (1 - p) : 0 for channels [8 * g8, 8 * g8 + 8) of pixel row r
+__device__ __forceinline__ void drop_scale8(long r, int g8, const DropBwd& d, float (&m)[8]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const philox_u4 u = dropout_bits4(r, 2 * g8 + h, d.stream_id, d.seed_lo, d.seed_hi);
+    m[4 * h + 0] = u.x >= d.thresh ? d.scale : 0.f;
+    m[4 * h + 1] = u.y >= d.thresh ? d.scale : 0.f;
+    m[4 * h + 2] = u.z >= d.thresh ? d.scale : 0.f;
+    m[4 * h + 3] = u.w >= d.thresh ? d.scale : 0.f;
+  }
+}
+
 // g = (dyA + dyB) * leaky'(y);  S[c] += sum g,  S[C + c] += sum g * xhat      (fp64 atomics), xhat = (x - mean) rstd
 // Round 4: the LeakyReLU mask y > 0 is RECOMPUTED from the raw convolution output, y = leaky(x scale + shift) with the very
 // expression bn_act_kernel used, instead of read from the stored activation: one tensor read less in each of the two backward
 // passes (Y is accepted for the ABI and not touched)
-template <typename T>
+// DROP: the block output went through nn.Dropout, g = (dyA + dyB) * keep / (1 - p) * leaky'(y); at p = 0 the factor is
+// exactly 1.0f and the result is bit-identical to DROP = false
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dyA, long ldA, const T* __restrict__ dyB,
                                                             long ldB, const T* __restrict__ Y, long ldy,
                                                             const T* __restrict__ X, long ldx, const float* __restrict__ ss,
                                                             int C, long P, int H, int W, float slope, int rows_per_block,
-                                                            double* __restrict__ S) {
+                                                            double* __restrict__ S, DropBwd drop = DropBwd{}) {
   __shared__ float red[2][256][8];
   const int cg = C / 8, rl = 256 / cg;
   const int g8 = threadIdx.x % cg, r = threadIdx.x / cg;
@@ -682,9 +704,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
 #pragma unroll
       for (int j = 0; j < 2; ++j)
         if (ok[j]) {
+          float km[8];
+          if (DROP) drop_scale8(p + j * rl, g8, drop, km);
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             float gq = dyB ? av[j][i] + bv[j][i] : av[j][i];
+            if (DROP) gq *= km[i];
             if (!(xv[j][i] * sc[i] + sh[i] > 0.f)) gq *= slope;
             s1[i] += gq;
             s2[i] += gq * ((xv[j][i] - mean[i]) * rstd[i]);
@@ -704,13 +729,13 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
 }
 
 // dx = scale * (g - S1/n - xhat * S2/n) on interior pixels;  block 0 also writes dgamma = S2, dbeta = S1
-template <typename T>
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dyA, long ldA, const T* __restrict__ dyB,
                                                            long ldB, const T* __restrict__ Y, long ldy,
                                                            const T* __restrict__ X, long ldx, const float* __restrict__ ss,
                                                            const double* __restrict__ S, T* __restrict__ dX, long lddx,
                                                            float* __restrict__ dgamma, float* __restrict__ dbeta, int C, long P,
-                                                           int H, int W, float slope, double n) {
+                                                           int H, int W, float slope, double n, DropBwd drop = DropBwd{}) {
   if (blockIdx.x == 0)
     for (int c = threadIdx.x; c < C; c += 256) {
       dgamma[c] = (float)S[C + c];
@@ -730,10 +755,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     for (int k = 0; k < 8; ++k) av[k] += bv[k];
   }
   load8<T>(X + p * ldx + c8, xv);
+  float km[8];
+  if (DROP) drop_scale8(p, c8 / 8, drop, km);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int c = c8 + k;
     float gq = av[k];
+    if (DROP) gq *= km[k];
     if (!(xv[k] * ss[c] + ss[C + c] > 0.f)) gq *= slope;
     const float xh = (xv[k] - ss[2 * C + c]) * ss[3 * C + c];
     const float m1 = (float)(S[c] * invn), m2 = (float)(S[C + c] * invn);
@@ -1546,6 +1574,41 @@ int nppc_bn_bwd(int prec, const void* dyA, long ldA, const void* dyB, long ldB, 
            (const TT*)X, ldx, ss, C, P, H, W, slope, rpb, S);
   LAUNCH_T(prec, bn_bwd_apply_kernel, dim3(ceil_div(P * (C / 8), 256)), (const TT*)dyA, ldA, (const TT*)dyB, ldB, (const TT*)Y,
            ldy, (const TT*)X, ldx, ss, (const double*)S, (TT*)dX, lddx, dgamma, dbeta, C, P, H, W, slope, n);
+  return NPPC_OK;
+}
+
+int nppc_bn_bwd_dropout(int prec, const void* dyA, long ldA, const void* dyB, long ldB, const void* Y, long ldy, const void* X,
+                        long ldx, const float* ss, double* S, void* dX, long lddx, float* dgamma, float* dbeta, int C, int B,
+                        int H, int W, float slope, float p, long seed, int stream_id, void* stream) {
+  if (!dyA || !Y || !X || !ss || !S || !dX || !dgamma || !dbeta || C % 8 || C / 8 > 256 || !(p >= 0.f && p < 1.f))
+    return NPPC_EBADARG;
+  const long P = (long)B * (H + 2) * (W + 2);
+  if (P >= (1L << 31)) return NPPC_EUNSUPPORTED;
+  const int rpb = bn_rows_per_block(P);
+  const double n = (double)B * H * W;
+  const DropBwd d{dropout_threshold(p), (unsigned)seed, (unsigned)((unsigned long long)seed >> 32), (unsigned)stream_id,
+                  1.f / (1.f - p)};
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(S, 0, sizeof(double) * 2 * C, s) != hipSuccess) return NPPC_ELAUNCH;
+  const dim3 gr(ceil_div(P, rpb)), ga(ceil_div(P * (C / 8), 256));
+  if (prec == NPPC_PREC_BF16) {
+    typedef bf16_t TT;
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<TT, true>), gr, dim3(256), 0, s, (const TT*)dyA, ldA, (const TT*)dyB, ldB,
+                       (const TT*)Y, ldy, (const TT*)X, ldx, ss, C, P, H, W, slope, rpb, S, d);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, true>), ga, dim3(256), 0, s, (const TT*)dyA, ldA, (const TT*)dyB, ldB,
+                       (const TT*)Y, ldy, (const TT*)X, ldx, ss, (const double*)S, (TT*)dX, lddx, dgamma, dbeta, C, P, H, W,
+                       slope, n, d);
+  } else if (prec == NPPC_PREC_F32) {
+    typedef float TT;
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<TT, true>), gr, dim3(256), 0, s, (const TT*)dyA, ldA, (const TT*)dyB, ldB,
+                       (const TT*)Y, ldy, (const TT*)X, ldx, ss, C, P, H, W, slope, rpb, S, d);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, true>), ga, dim3(256), 0, s, (const TT*)dyA, ldA, (const TT*)dyB, ldB,
+                       (const TT*)Y, ldy, (const TT*)X, ldx, ss, (const double*)S, (TT*)dX, lddx, dgamma, dbeta, C, P, H, W,
+                       slope, n, d);
+  } else {
+    return NPPC_EBADARG;
+  }
+  NPPC_CHECK_LAUNCH();
   return NPPC_OK;
 }
 

@@ -74,6 +74,12 @@ def conv_thin_part_elems():
     return n.value
 
 
+def masked_mse_work_elems():
+    n = c_l()
+    call("nppc_masked_mse_work_elems", ctypes.byref(n))
+    return n.value
+
+
 def dtype_of(prec):
     return torch.bfloat16 if prec == PREC_BF16 else torch.float32
 
@@ -195,12 +201,16 @@ SIGS = {
     "nppc_bn_finalize": [P, P, P, P, P, P, I, D, F, F, I, P],
     "nppc_bn_act": [I, P, L, P, L, P, I, I, I, I, F, P],
     "nppc_bn_bwd": [I, P, L, P, L, P, L, P, L, P, P, P, L, P, P, I, I, I, I, F, P],
+    "nppc_bn_bwd_dropout": [I, P, L, P, L, P, L, P, L, P, P, P, L, P, P, I, I, I, I, F, F, L, I, P],
     "nppc_maxpool2": [I, P, L, P, L, P, I, I, I, I, P],
     "nppc_maxpool2_bwd": [I, P, L, P, P, L, I, I, I, I, P],
     "nppc_upsample2": [I, P, L, P, L, I, I, I, I, I, I, P],
     "nppc_upsample2_bwd": [I, P, L, P, L, I, I, I, I, I, I, P],
     "nppc_unet_out": [I, P, L, P, P, L, P, L, I, I, I, I, I, P],
     "nppc_unet_out_bwd": [I, P, L, P, P, L, I, I, I, I, P],
+    "nppc_masked_mse_work_elems": [PL],
+    "nppc_masked_mse": [P, P, P, I, I, I, P, P, P],
+    "nppc_masked_mse_bwd": [P, P, P, P, P, P, I, I, I, P],
     "nppc_tcn_gn_bwd": [I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, L, L, L, I, P],
     "nppc_tcn_dwconv_bwd": [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, L, L, L, I, P],
     "nppc_tsse_bwd_ws_elems": [I, I, I, I, I, I, PL],

@@ -102,14 +102,11 @@ class UNet(nn.Module):
 
     def _dropout_state(self):
         """None, or the Philox stream of this stochastic pass when any nn.Dropout of the net is in train mode
-        (utils.enable_dropout, utils.py:334-338; restoration_model.train() in base_step2, nppc_trainer.py:268)."""
+        (utils.enable_dropout, utils.py:334-338; restoration_model.train() in base_step2, nppc_trainer.py:268; the
+        restorer trainer, restoration_trainer.py, differentiates through it: the backward regenerates the same bits)."""
         p = self.config.dropout
         if not p or not any(isinstance(m, nn.Dropout) and m.training for m in self.modules()):
             return None
-        if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
-            raise NotImplementedError(
-                "UNet (MI355X build): dropout is implemented for MC-dropout inference (no_grad / frozen weights); the "
-                "training path configures the direction U-Net with dropout 0 (config_nppc.yaml:33-36)")
         st = dict(p=p, seed=self.dropout_seed, pass_id=self.dropout_pass, tap=self.dropout_tap)
         self.dropout_pass += 1
         return st
@@ -159,6 +156,23 @@ class _UNetFn(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
+class _RestorationFn(torch.autograd.Function):
+    """RestorationWrapper with a train-mode net: x * mask + U-Net(x) * (1 - mask) in one launch sequence (nppc_unet_out mode 1);
+    the backward is _UNetFn's, whose nppc_unet_out_bwd applies the same (1 - mask): the exact derivative of the composite"""
+
+    @staticmethod
+    def forward(ctx, net, shape, mask, x, *params):
+        B, F, T = shape
+        out = torch.empty(B, 1, F, T, dtype=torch.float32, device=x.device)
+        net.run([x], F * T, shape, mask, out, F * T, xin=x, xin_bstride=F * T)
+        ctx.net = net
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _UNetFn.backward(ctx, dout)
+
+
 class RestorationWrapper(nn.Module):
     def __init__(self, base_net: UNet):
         super().__init__()
@@ -166,15 +180,20 @@ class RestorationWrapper(nn.Module):
 
     def forward(self, x_in: torch.Tensor, mask: torch.Tensor):
         """x_in [B,1,F,T] (single-channel input, the NPPC path's case), mask [B,1,F,T] (1 = known) ->
-        x_in * mask + net(x_in) * (1 - mask)   (unet.py:299-312).  Inference only."""
+        x_in * mask + net(x_in) * (1 - mask)   (unet.py:299-312).  Differentiable (wrt the net's parameters) with grad enabled
+        and the net in train mode (the restorer trainer); otherwise inference under torch.no_grad()."""
         H.require_gpu()
         if x_in.shape[1] != 1 or self.net.config.out_channels != 1:
             raise NotImplementedError("RestorationWrapper (MI355X build) implements the single-channel case of the NPPC path")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError("RestorationWrapper (MI355X build) is forward-only; wrap the call in torch.no_grad()")
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if grad and not self.net.training:
+            raise RuntimeError("RestorationWrapper (MI355X build) differentiates a train-mode net only; for inference wrap "
+                               "the call in torch.no_grad()")
         x = x_in.contiguous().float()
         B, _, F, T = x.shape
         m = mask[:, 0, 0, :].contiguous().float()
+        if grad:
+            return _RestorationFn.apply(self.net, (B, F, T), m, x, *[p for _, p in self.net.named_parameters()])
         out = torch.empty(B, 1, F, T, dtype=torch.float32, device=x.device)
         self.net.run([x], F * T, (B, F, T), m, out, F * T, xin=x, xin_bstride=F * T)
         return out

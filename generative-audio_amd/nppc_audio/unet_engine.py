@@ -4,7 +4,8 @@ Mirrors UNet.forward (nppc_audio/inpainting/networks/unet.py:277-290) block by b
 activations: one `UNetEngine` owns the packed weights, the activation / gradient buffers of every
 resolution level and the launch order of forward and backward.  The frozen restorer runs with its
 BatchNorm folded into the convolution epilogue (eval mode); the direction U-Net runs in train mode
-(batch statistics, running-buffer update) and keeps what its backward needs.
+(batch statistics, running-buffer update) and keeps what its backward needs; so does the restorer while it is
+trained (InpaintingTrainer), with its nn.Dropout layers active in the differentiated pass.
 """
 import os
 
@@ -239,8 +240,14 @@ class UNetEngine:
         saved[blk] = dict(x=x, ldx=ldx, raw_a=raw_a, act_a=act_a, raw_b=raw_b, out=out, ldo=ldo, ss_a=ss_a, ss_b=ss_b,
                           cin=cin, cout=cout, level=level, path=path)
 
+    @staticmethod
+    def _drop_stream(pass_id, blk):
+        """Philox stream of block `blk` in stochastic pass `pass_id` (shared by the forward and the fused backward)"""
+        return int(pass_id) * len(DROP_BLOCKS) + DROP_BLOCKS.index(blk)
+
     def _dropout(self, blk, x, ldx, cout, level, dropout):
-        """nn.Dropout at the end of the block's double_conv (tmp_utils.py:28-29), in place; MC-dropout inference only"""
+        """nn.Dropout at the end of the block's double_conv (tmp_utils.py:28-29), in place.  In a train-mode pass the
+        backward regenerates the same keep bits (nppc_bn_bwd_dropout): nothing is stored for it"""
         if not dropout or blk not in DROP_BLOCKS:
             return
         keep = None
@@ -248,10 +255,11 @@ class UNetEngine:
             keep = torch.empty(self.P[level] * cout, dtype=torch.uint8, device=self.dev)
             dropout["tap"][blk] = (keep, level, cout)
         H.call("nppc_dropout", self.prec, x, ldx, self.P[level], cout, float(dropout["p"]), int(dropout["seed"]),
-               int(dropout["pass_id"]) * len(DROP_BLOCKS) + DROP_BLOCKS.index(blk), keep, H.stream())
+               self._drop_stream(dropout["pass_id"], blk), keep, H.stream())
 
     def forward(self, shape, maps, map_bstride, mask, out, out_pstride, xin=None, xin_bstride=0, train=False, dropout=None):
-        """dropout: None or dict(p, seed, pass_id[, tap]) -- MC-dropout passes (utils.py:334-338, 561-577).
+        """dropout: None or dict(p, seed, pass_id[, tap]) -- MC-dropout passes (utils.py:334-338, 561-577) and the
+        restorer's training passes (restoration_trainer.py: nn.Dropout(0.2) in train mode, differentiated).
         maps: list of fp32 tensors holding [B][F*T] planes with batch stride `map_bstride` (the net's input
         channels); mask [B,T] fp32.  Writes out[(b*K+k)*out_pstride + f*T + t]:
           xin is None : U-Net(maps) * (1 - mask)                      (pc_wrapper.py:77-83)
@@ -302,7 +310,8 @@ class UNetEngine:
         H.call("nppc_unet_out", self.prec, raw_o.t, OUT_LD, mask, xin, xin_bstride, out, out_pstride, self.out_ch, B, F, T,
                0 if xin is None else 1, s)
         if train:
-            self.saved = None if dropout else dict(blocks=saved, pools=pools, u4=prev, mask=mask)
+            drop = (float(dropout["p"]), int(dropout["seed"]), int(dropout["pass_id"])) if dropout else None
+            self.saved = dict(blocks=saved, pools=pools, u4=prev, mask=mask, drop=drop)
 
     def _pool_idx(self, level, n):
         key = ("pool_idx", level)
@@ -377,8 +386,16 @@ class UNetEngine:
         s = H.stream()
         S = self.st[:2 * cout]
         draw = self.buf("draw", level, cout)
-        H.call("nppc_bn_bwd", self.prec, dyA, ldA, dyB, ldB, sv["out"], sv["ldo"], sv["raw_b"].t, cout, sv["ss_b"], S, draw.t,
-               cout, self.g(bnb + ".weight"), self.g(bnb + ".bias"), cout, B, h, w, LEAK, s)
+        drop = self.saved["drop"]
+        if drop is not None and blk in DROP_BLOCKS:
+            # the block output went through nn.Dropout in place: its keep bits are regenerated inside the BatchNorm backward
+            p, seed, pass_id = drop
+            H.call("nppc_bn_bwd_dropout", self.prec, dyA, ldA, dyB, ldB, sv["out"], sv["ldo"], sv["raw_b"].t, cout, sv["ss_b"], S,
+                   draw.t, cout, self.g(bnb + ".weight"), self.g(bnb + ".bias"), cout, B, h, w, LEAK, p, seed,
+                   self._drop_stream(pass_id, blk), s)
+        else:
+            H.call("nppc_bn_bwd", self.prec, dyA, ldA, dyB, ldB, sv["out"], sv["ldo"], sv["raw_b"].t, cout, sv["ss_b"], S,
+                   draw.t, cout, self.g(bnb + ".weight"), self.g(bnb + ".bias"), cout, B, h, w, LEAK, s)
         self._wgrad(nb, cout, cout, 3, draw.t, cout, sv["act_a"].t, cout, level)
         dact = self.buf("dact", level, cout)
         self._conv_bwd_data(nb, cout, cout, 3, draw.t, cout, dact.t, cout, level)

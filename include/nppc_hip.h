@@ -430,6 +430,12 @@ int nppc_bn_act(int prec, const void* X, long ldx, void* Y, long ldy, const floa
 int nppc_bn_bwd(int prec, const void* dyA, long ldA, const void* dyB, long ldB, const void* Y, long ldy, const void* X, long ldx,
                 const float* ss, double* S, void* dX, long lddx, float* dgamma, float* dbeta, int C, int B, int H, int W,
                 float slope, void* stream);
+/* nppc_bn_bwd for a block whose output went through nn.Dropout(p) in place (nppc_dropout with the same seed / stream_id):
+ * the keep bits are regenerated from Philox4x32-10(seed; pixel row, channel / 4, stream_id), not read from memory, and
+ * g = (dyA + dyB) * keep / (1 - p) before the LeakyReLU slope.  p = 0 gives nppc_bn_bwd's result bit for bit. */
+int nppc_bn_bwd_dropout(int prec, const void* dyA, long ldA, const void* dyB, long ldB, const void* Y, long ldy, const void* X,
+                        long ldx, const float* ss, double* S, void* dX, long lddx, float* dgamma, float* dbeta, int C, int B,
+                        int H, int W, float slope, float p, long seed, int stream_id, void* stream);
 int nppc_maxpool2(int prec, const void* X, long ldx, void* Y, long ldy, unsigned char* idx, int C, int B, int H, int W,
                   void* stream);
 int nppc_maxpool2_bwd(int prec, const void* dY, long ldy, const unsigned char* idx, void* dX, long ldx, int C, int B, int H, int W,
@@ -442,6 +448,17 @@ int nppc_unet_out(int prec, const void* raw, long ld, const float* mask, const f
                   long out_pstride, int K, int B, int H, int W, int mode, void* stream);
 int nppc_unet_out_bwd(int prec, const float* dout, long dout_pstride, const float* mask, void* draw, long ld, int K, int B,
                       int H, int W, void* stream);
+
+/* ---- restorer trainer (inpainting/trainer/restoration_trainer.py:189-191) ---------------------------------------------
+ * masked spectral MSE: out, clean [B][F][T] fp32, mask [B][T] (1 = known), broadcast over F:
+ * *loss = sum (out - clean)^2 (1 - m) / (F sum (1 - m) + 1e-6), fp64 partials folded in a fixed order (no float atomics,
+ * bit-identical on repeat).  work = *elems of nppc_masked_mse_work_elems doubles; it keeps the denominator for the
+ * backward, dout = 2 g (out - clean) (1 - m) / den with g (the incoming gradient of the loss) read from device memory. */
+int nppc_masked_mse_work_elems(long* elems);
+int nppc_masked_mse(const float* out, const float* clean, const float* mask, int B, int F, int T, double* work, float* loss,
+                    void* stream);
+int nppc_masked_mse_bwd(const float* out, const float* clean, const float* mask, const float* g, const double* work,
+                        float* dout, int B, int F, int T, void* stream);
 
 #ifdef __cplusplus
 }
