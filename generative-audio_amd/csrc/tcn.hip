@@ -658,6 +658,9 @@ static int launch_nt(int prec, int epi, const void* A, long lda, long sA, const 
   if ((epi == EPI_RESIDUAL || epi == EPI_MASK_POS) && !res) return NPPC_EBADARG;
   if (epi == EPI_RESIDUAL_GN) return NPPC_EBADARG;            // has its own entry point (nppc_gemm_nt_gn)
   if (ksplit < 1) ksplit = 1;
+  // a K slice only holds a partial sum: bias, PReLU, ReLU, residual, mask or statistics applied to it would be wrong, so a
+  // split K is the raw fp32 slab product alone (the caller reduces the slabs, engine.py _wgrad)
+  if (ksplit > 1 && (epi != EPI_PLAIN_F32 || bias || stats)) return NPPC_EUNSUPPORTED;
   if (K % (32 * ksplit)) return NPPC_EUNSUPPORTED;
   GemmArgs g{A, lda, sA, B, ldb, sB, C, ldc, sC, bias, sBias, res, ldres, sRes, slope, sSlope, stats, sStats,
              R, N, K / ksplit, Tp, Tv, Nv, relu_in, ksplit, nullptr, 0, 1.0, 0.f,

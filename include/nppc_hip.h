@@ -77,7 +77,8 @@ int nppc_scale_transpose(int prec, const float* x, const float* scale /*nullable
 /* ---- full-band TCN stack: TCNBlock x8 + Linear + ReLU ------------------------------------------------------
  * audio_zen/model/module/causal_conv.py:67-108, audio_zen/model/module/sequence_model.py:47-58,106-112
  * nppc_gemm_nt: C[R][N] = A[R][K] * B[N][K]^T (+ epilogue); epi: 0 plain, 1 bias+PReLU+GroupNorm statistics,
- * 2 bias+residual, 3 bias+ReLU, 4 fp32 output (split-K slabs), 5 mask by (res > 0).  ksplit > 1 splits K. */
+ * 2 bias+residual, 3 bias+ReLU, 4 fp32 output (split-K slabs), 5 mask by (res > 0).  ksplit > 1 splits K: epi 4 only, with
+ * no bias and no stats (NPPC_EUNSUPPORTED otherwise); slab z * ksplit + s starts at C + (z * ksplit + s) * sC. */
 int nppc_gemm_nt(int prec, int epi, const void* A, long lda, long sA, const void* B, long ldb, long sB, void* C, long ldc,
                  long sC, const float* bias, long sBias, const void* res, long ldres, long sRes, const float* slope,
                  long sSlope, double* stats, long sStats, int R, int N, int K, int Tp, int Tv, int Nv, int relu_in,
