@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: NPPC K=5 FullSubNet+ train step, spectrogram-frames/s on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write --dump-outputs, print the
+line.  --full adds what takes runs of its own, after the timed steps (one GPU): the untimed per-launch pass that ranks every
+kernel and times the HBM-bound families, the fp32 parity-mode steps and the CPU baseline (--no-families, --no-fp32 and
+--no-cpu-baseline leave one of them out).
 
 N > 1 without an external launcher: bench.py starts its own N ranks (`python -m torch.distributed.run ... bench.py`) as a
 CHILD process before anything touches the GPU and exits with the child's code; under an external torch.distributed.run
@@ -17,12 +22,13 @@ timed step computed (its returned arrays and the direction net's updated paramet
 for output-for-output comparison of two builds: inputs and initial weights are seeded, identical from run to run.
 
 What the line's extra objects mean (definitions and byte/FLOP counts: DESIGN.md section 4):
-  roofline        the kernel with the largest total duration per step (HIP events around every launch in an untimed
-                  pass rank the kernels; `achieved` of an LSTM kernel comes from HIP events inside the TIMED region);
+  roofline        the kernel with the largest total duration per step (--full: HIP events around every launch in an
+                  untimed pass rank the kernels; otherwise only the LSTM launches of the timed region are ranked, as
+                  `ranked_over` says; `achieved` of an LSTM kernel comes from HIP events inside the TIMED region);
                   on a < 1 % tie the lower fraction is reported.  roofline.step = whole-step algorithmic FLOP rate.
-  roofline.hbm_families   achieved GB/s of the HBM-bound kernel families = algorithmic bytes / HIP-event time
-  fp32            the precision-matched (reference dtype) step time, a few steps outside the timed region
-  cpu_baseline    the oracle (CPU restatement pinned to the reference by tests/golden) on a bounded sample
+  roofline.hbm_families   (--full) achieved GB/s of the HBM-bound kernel families = algorithmic bytes / HIP-event time
+  fp32            (--full) the precision-matched (reference dtype) step time, a few steps outside the timed region
+  cpu_baseline    (--full) the oracle (CPU restatement pinned to the reference by tests/golden) on a bounded sample
 """
 import argparse
 import hashlib
@@ -321,7 +327,7 @@ def dp_selftest(a, world, rank):
     sys.exit(0 if ok else 4)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -331,17 +337,40 @@ def main():
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--seconds", type=float, default=None)
     ap.add_argument("--dirs", type=int, default=None, help="number of PC directions K")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the precision-matched fp32 steps")
-    ap.add_argument("--no-families", action="store_true", help="skip the per-launch HIP-event pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the per-launch pass, the fp32 steps and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fp32", action="store_true", help="with --full: skip the precision-matched fp32 steps")
+    ap.add_argument("--no-families", action="store_true", help="with --full: skip the per-launch HIP-event pass")
     ap.add_argument("--pipeline", action="store_true", help="pipeline_update mode of the trainer (A/B switch)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (<= 64 MB in all)")
     ap.add_argument("--dp-selftest", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dp-selftest-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def extra_passes(a, world):
+    """what a run measures beyond its timed steps: nothing without --full; with it, on one GPU, every pass not switched
+    off (N > 1: the other ranks have left after the timed steps, more steps would wait for them forever)"""
+    on = a.full and world == 1
+    return {"families": on and not a.no_families,
+            "fp32": on and a.precision == "bf16" and not a.no_fp32,
+            "cpu_baseline": on and not a.no_cpu_baseline}
+
+
+def inpainting_argv(a, extra):
+    """--config c3: the command line of tools/bench_inpainting.py, which runs its CPU baseline unless told not to"""
+    return (["--steps", str(a.steps), "--warmup", str(a.warmup), "--precision", a.precision]
+            + ([] if extra["cpu_baseline"] else ["--no-cpu-baseline"])
+            + (["--dump-outputs", a.dump_outputs] if a.dump_outputs else []))
+
+
+def main():
+    a = parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))
@@ -352,14 +381,13 @@ def main():
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
     if a.dp_selftest:
         return dp_selftest(a, world, rank)
+    extra = extra_passes(a, world)
     if a.config == "c3":
         if world > 1:
             raise SystemExit("config c3 (inpainting) is single-GPU: train-mode BatchNorm couples the minibatch (DESIGN.md 8)")
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_inpainting
-        return bench_inpainting.main(["--steps", str(a.steps), "--warmup", str(a.warmup), "--precision", a.precision]
-                                     + (["--no-cpu-baseline"] if a.no_cpu_baseline else [])
-                                     + (["--dump-outputs", a.dump_outputs] if a.dump_outputs else []))
+        return bench_inpainting.main(inpainting_argv(a, extra))
     cb, cs, ck = {"c2": (BATCH, SECONDS, K_DIRS), "c5": (8, 30, 8)}[a.config]
     a.batch, a.seconds, a.dirs = a.batch or cb, a.seconds or cs, a.dirs or ck
     workload = {(BATCH, SECONDS, K_DIRS): "C2", (8, 30, 8): "C5"}.get((a.batch, a.seconds, a.dirs), "custom")
@@ -445,7 +473,7 @@ def main():
 
     # ---- untimed pass with HIP events around EVERY launch: ranks the kernels, times the HBM-bound families -------
     totals, fam = {}, None
-    if world == 1 and not a.no_families:          # (N > 1: the other ranks have left; more steps would wait for them forever)
+    if extra["families"]:
         NP = 3
         H.PROFILE = []
         for _ in range(NP):
@@ -479,6 +507,7 @@ def main():
         dom_name = min(ordered[:2], key=lambda kv: kern[kv[0]]["tflops"])[0]
     flops_step = step_flops(a.batch, T, a.dirs)
     roof = {"bound": "mfma", "kernel": dom_name, "peak": peak, "unit": "TFLOP/s", "traffic": None,
+            "ranked_over": "every launch (untimed per-launch pass)" if totals else "the LSTM launches of the timed region",
             "ranked_ms_per_step": {k: round(v, 3) for k, v in ordered[:12]},
             "all_lstm_kernels": kern,
             "step": {"algorithmic_flop": flops_step, "achieved": flops_step / (ms_step * 1e-3) / 1e12,
@@ -517,7 +546,7 @@ def main():
         out["dp"] = dp_info
     if dump_info is not None:
         out["dumped_outputs"] = dump_info
-    if world == 1 and a.precision == "bf16" and not a.no_fp32:
+    if extra["fp32"]:
         # the reference computes in fp32: the same step in the product's fp32 parity mode (exact-f32 MFMA), outside the
         # timed region.  The bf16 trainer's step-persistent workspaces stay allocated (288 GB of HBM: both fit).
         log("timing the fp32 parity mode (1 warm-up + 3 steps)")
@@ -537,7 +566,7 @@ def main():
                        "achieved_tflops": flops_step / (ms32 * 1e-3) / 1e12,
                        "frac_of_fp32_matrix_peak": flops_step / (ms32 * 1e-3) / 1e12 / PEAK_F32_TFLOPS}
         del tr32, batch32
-    if world == 1 and not a.no_cpu_baseline:
+    if extra["cpu_baseline"]:
         log("timing the CPU baseline (bounded sample)")
         out["cpu_baseline"] = cpu_baseline()
         out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]

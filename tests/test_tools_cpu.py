@@ -98,3 +98,30 @@ def test_dump_outputs_stays_within_budget_and_samples_deterministically(tmp_path
         np.testing.assert_array_equal(runs[0][k], runs[1][k])
     w = runs[0]["w_mat.npy"]
     assert w.size == man["arrays"]["w_mat"]["sampled"] and np.all(np.diff(w) > 0)    # sorted flat indices of an increasing array
+
+
+def test_a_plain_run_measures_nothing_beyond_its_timed_steps():
+    """`bench.py --gpus 1 --steps N --warmup W` stays lean; --full adds the per-launch pass, the fp32 steps and the CPU
+    baseline on one GPU, and each --no-* option still leaves its pass out there"""
+    b = _bench()
+    none = {"families": False, "fp32": False, "cpu_baseline": False}
+    assert b.extra_passes(b.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"]), 1) == none
+    assert b.extra_passes(b.parse_args(["--no-fp32"]), 1) == none
+    assert b.extra_passes(b.parse_args(["--full"]), 1) == {"families": True, "fp32": True, "cpu_baseline": True}
+    assert b.extra_passes(b.parse_args(["--full", "--gpus", "2"]), 2) == none
+    assert b.extra_passes(b.parse_args(["--full", "--precision", "fp32"]), 1)["fp32"] is False
+    assert b.extra_passes(b.parse_args(["--full", "--no-families", "--no-cpu-baseline"]), 1) == \
+        {"families": False, "fp32": True, "cpu_baseline": False}
+
+
+def test_config_c3_forwards_the_cpu_baseline_choice_to_the_inpainting_bench():
+    """--config c3 runs tools/bench_inpainting.py, which times its CPU baseline unless told not to: only --full lets it"""
+    b = _bench()
+
+    def argv(*args):
+        a = b.parse_args(["--config", "c3", *args])
+        return b.inpainting_argv(a, b.extra_passes(a, 1))
+    assert argv("--steps", "5", "--warmup", "2") == ["--steps", "5", "--warmup", "2", "--precision", "bf16", "--no-cpu-baseline"]
+    assert "--no-cpu-baseline" not in argv("--full")
+    assert "--no-cpu-baseline" in argv("--full", "--no-cpu-baseline")
+    assert argv("--dump-outputs", "d")[-2:] == ["--dump-outputs", "d"]
