@@ -212,6 +212,85 @@ __global__ void cirm_build_kernel(const float* __restrict__ nr, const float* __r
   }
 }
 
+// ---------------------------------------------------------------- cIRM MSE of the restorer trainer (trainer.py:337-343)
+// loss = mean over [B][2][Fo][T] of (gt - crm)^2, gt built per element exactly as cirm_build_kernel does (same formula, same
+// drop-band gather).  Deterministic without float atomics: CRM_BLOCKS workgroups grid-stride over the elements and write
+// fp64 partials, one workgroup folds them in a fixed tree order.
+constexpr int CRM_BLOCKS = 256;
+
+__device__ __forceinline__ void cirm_target(const float* __restrict__ nr, const float* __restrict__ ni,
+                                            const float* __restrict__ cr, const float* __restrict__ ci, size_t e, int B, int F,
+                                            int T, int G, int Fo, float eps, float* gr, float* gi, size_t* o) {
+  const int t = e % T;
+  size_t r = e / T;
+  const int fo = r % Fo;
+  const int bo = (int)(r / Fo);
+  int bs, fs;
+  dropband_src(bo, fo, B, G, &bs, &fs);
+  const size_t i = ((size_t)bs * F + fs) * T + t;
+  const float a = nr[i], b = ni[i], c = cr[i], d = ci[i];
+  const float den = a * a + b * b + eps;
+  *gr = compress_cirm((a * c + b * d) / den);
+  *gi = compress_cirm((a * d - b * c) / den);
+  *o = (((size_t)bo * 2) * Fo + fo) * T + t;
+}
+
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(256) void crm_mse_part_kernel(const float* __restrict__ nr, const float* __restrict__ ni,
+                                                           const float* __restrict__ cr, const float* __restrict__ ci,
+                                                           const float* __restrict__ crm, float* __restrict__ gt, int B, int F,
+                                                           int T, int G, int Fo, float eps, double* __restrict__ work) {
+  __shared__ double red[256];
+  const size_t total = (size_t)B * Fo * T, FoT = (size_t)Fo * T;
+  double s = 0.0;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)CRM_BLOCKS * 256) {
+    float gr, gi;
+    size_t o;
+    cirm_target(nr, ni, cr, ci, e, B, F, T, G, Fo, eps, &gr, &gi, &o);
+    const double dr = (double)gr - (double)crm[o], di = (double)gi - (double)crm[o + FoT];
+    s += dr * dr + di * di;
+    if (gt) {
+      gt[o] = gr;
+      gt[o + FoT] = gi;
+    }
+  }
+  s = block_sum_d(s, red);
+  if (threadIdx.x == 0) work[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void crm_mse_finish_kernel(const double* __restrict__ work, float* __restrict__ loss,
+                                                             double n) {
+  __shared__ double red[256];
+  const double s = block_sum_d(work[threadIdx.x], red);     // CRM_BLOCKS == 256: one partial per thread
+  if (threadIdx.x == 0) *loss = (float)(s / n);
+}
+
+// dcrm = 2 g (crm - gt) / N, g (the incoming gradient of the loss) read from device memory
+__global__ __launch_bounds__(256) void crm_mse_bwd_kernel(const float* __restrict__ nr, const float* __restrict__ ni,
+                                                          const float* __restrict__ cr, const float* __restrict__ ci,
+                                                          const float* __restrict__ crm, const float* __restrict__ g,
+                                                          float* __restrict__ dcrm, int B, int F, int T, int G, int Fo,
+                                                          float eps, double n) {
+  const size_t total = (size_t)B * Fo * T, FoT = (size_t)Fo * T;
+  const float coef = (float)(2.0 * (double)*g / n);
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    float gr, gi;
+    size_t o;
+    cirm_target(nr, ni, cr, ci, e, B, F, T, G, Fo, eps, &gr, &gi, &o);
+    dcrm[o] = coef * (crm[o] - gr);
+    dcrm[o + FoT] = coef * (crm[o + FoT] - gi);
+  }
+}
+
 __device__ __forceinline__ float decompress_cirm(float m) {
   m = fminf(fmaxf(m, -9.9f), 9.9f);
   return -10.f * logf((10.f - m) / (10.f + m));
@@ -460,6 +539,35 @@ int nppc_cirm_build_compress(const float* nr, const float* ni, const float* cr, 
   const int Fo = G <= 1 ? F : (F - F % G) / G;
   hipLaunchKernelGGL(cirm_build_kernel, dim3(ew_grid((size_t)B * Fo * T)), dim3(256), 0, (hipStream_t)stream, nr, ni, cr,
                      ci, out, B, F, T, G, Fo, eps);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_crm_mse_work_elems(long* elems) {
+  if (!elems) return NPPC_EBADARG;
+  *elems = CRM_BLOCKS;
+  return NPPC_OK;
+}
+
+int nppc_crm_mse(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, float* gt, int B, int F,
+                 int T, int G, float eps, double* work, float* loss, void* stream) {
+  if (!nr || !ni || !cr || !ci || !crm || !work || !loss || B <= 0 || F <= 0 || T <= 0 || G < 1) return NPPC_EBADARG;
+  const int Fo = G <= 1 ? F : (F - F % G) / G;
+  if (Fo <= 0) return NPPC_EBADARG;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(crm_mse_part_kernel, dim3(CRM_BLOCKS), dim3(256), 0, s, nr, ni, cr, ci, crm, gt, B, F, T, G, Fo, eps, work);
+  hipLaunchKernelGGL(crm_mse_finish_kernel, dim3(1), dim3(256), 0, s, work, loss, 2.0 * B * Fo * T);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_crm_mse_bwd(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, const float* g,
+                     float* dcrm, int B, int F, int T, int G, float eps, void* stream) {
+  if (!nr || !ni || !cr || !ci || !crm || !g || !dcrm || B <= 0 || F <= 0 || T <= 0 || G < 1) return NPPC_EBADARG;
+  const int Fo = G <= 1 ? F : (F - F % G) / G;
+  if (Fo <= 0) return NPPC_EBADARG;
+  hipLaunchKernelGGL(crm_mse_bwd_kernel, dim3(ew_grid((size_t)B * Fo * T)), dim3(256), 0, (hipStream_t)stream, nr, ni, cr, ci,
+                     crm, g, dcrm, B, F, T, G, Fo, eps, 2.0 * B * Fo * T);
   NPPC_CHECK_LAUNCH();
   return NPPC_OK;
 }

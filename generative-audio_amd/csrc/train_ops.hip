@@ -313,6 +313,63 @@ __global__ __launch_bounds__(256) void sb_bwd_scatter_kernel(const T* __restrict
   }
 }
 
+// ---------------------------------------------------------------- sub-band unfold backward (restorer: n_maps = 1)
+// The first W = 2nb+1 columns of the restorer's sub-band rows are the unfold of the attention-scaled magnitude X0 (the TCN
+// input of branch 0), a trainable tensor.  Gradient, accumulated in place into dX0[b][t][f] for t < Tv:
+//   dX0 += sc_b * sum_{kept rows f' of b, columns k : refl(f' + k - nb) = f} dx[t][n(b, f')][k]  -  sc_b * D[bo] * mult[f] / Nn
+// A gather: one workgroup per (frame, sample) stages the W columns of the sample's kept rows at their full-band bin f' in LDS
+// (zero for the bins of other drop-band groups and past Fo * G), then each thread sums ONE output bin over k in a fixed
+// order (direct source, low reflection, high reflection).  No atomics: the result is bit-identical on repeat.
+template <typename T>
+__global__ __launch_bounds__(256) void sb_unfold_bwd_kernel(const T* __restrict__ dx, const float* __restrict__ scale,
+                                                            const double* __restrict__ D, const float* __restrict__ mult,
+                                                            T* __restrict__ dX0, int ldX, int B, int F, int Tp, int nb, int G,
+                                                            int Fo, int KX, long Nseq, double Nn) {
+  extern __shared__ float su[];   // [F][W]
+  const int t = blockIdx.x, b = blockIdx.y, W = 2 * nb + 1;
+  int g = 0, bo = b;
+  if (G > 1) {
+    g = b % G;
+    int start = 0;
+    for (int gg = 0; gg < g; ++gg) start += (B - gg + G - 1) / G;
+    bo = start + b / G;
+  }
+  // bins that hold no row of this sample: zero
+  for (int e = threadIdx.x; e < F * W; e += 256) {
+    const int f = e / W;
+    const bool kept = G > 1 ? ((f % G) == g && f < Fo * G) : true;
+    if (!kept) su[e] = 0.f;
+  }
+  const int cpr = (W + 7) / 8;
+  const size_t base = ((size_t)t * Nseq + (size_t)bo * Fo) * KX;
+  for (int e = threadIdx.x; e < Fo * cpr; e += 256) {
+    const int r = e / cpr, c = e % cpr;
+    float a[8];
+    load8<T>(dx + base + (size_t)r * KX + 8 * c, a);
+    const int f = G > 1 ? g + r * G : r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (8 * c + i < W) su[f * W + 8 * c + i] = a[i];
+  }
+  __syncthreads();
+  const float sc = scale[b];
+  const float mterm = (float)((double)sc * D[bo] / Nn);
+  T* row = dX0 + ((size_t)b * Tp + t) * ldX;
+  for (int f = threadIdx.x; f < F; f += 256) {
+    float acc = 0.f;
+    for (int k = 0; k < W; ++k) {
+      const int fd = f + nb - k;                       // source index f' + k - nb = f
+      if (fd >= 0 && fd < F) acc += su[fd * W + k];
+      const int fl = -f + nb - k;                      // source index -f (< 0, reflected to f)
+      if (f > 0 && fl >= 0 && fl < F) acc += su[fl * W + k];
+      const int fh = 2 * (F - 1) - f + nb - k;         // source index 2(F-1) - f (>= F, reflected to f)
+      if (f <= F - 2 && fh >= 0 && fh < F) acc += su[fh * W + k];
+    }
+    const float v = sc * acc - mterm * mult[f];
+    row[f] = from_f32<T>(to_f32<T>(row[f]) + v);
+  }
+}
+
 // ---------------------------------------------------------------- slab reduction into parameter gradients
 // dst[map(r)][c] (+)= sum_s slabs[s][r][col0 + c],  r < rows, c < ncols
 // permH > 0: LSTM gate-row un-permutation, packed row r = u*4 + g' (i,g,f,o) -> torch row {0,2,1,3}[g']*permH + u
@@ -527,6 +584,31 @@ int nppc_subband_stage_bwd(int prec, const void* dx, const void* x, const void* 
     hipLaunchKernelGGL(sb_bwd_scatter_kernel<float>, grid, dim3(256), 0, s, (const float*)fb, scale, D, (float*)dpre, B, F, Tp, ldF,
                        strideFb, Geff, Fo, Nn);
   }
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_subband_unfold_bwd(int prec, const void* dx, const float* scale, const double* D, const float* mult, void* dX0,
+                            int ldX, int B, int F, int Tp, int Tv, int nb, int G, int KX, void* stream) {
+  if (!dx || !scale || !D || !mult || !dX0 || B <= 0 || F <= 0 || Tv <= 0 || Tv > Tp || ldX < F || G < 1 || KX % 8)
+    return NPPC_EBADARG;
+  if (nb < 1 || nb >= F || 2 * nb + 4 > KX) return NPPC_EBADARG;     // reflect padding needs nb < F, as in the forward
+  if (B > 1 && !(B > G)) return NPPC_EBADARG;
+  const int W = 2 * nb + 1;
+  const size_t sm = (size_t)F * W * sizeof(float);
+  if (sm > 64 * 1024) return NPPC_EUNSUPPORTED;
+  const int Geff = B > 1 ? G : 1;
+  const int Fo = Geff <= 1 ? F : (F - F % Geff) / Geff;
+  const long Nseq = (long)B * Fo;
+  const double Nn = (double)F * (2 * nb + 4) * Tv;
+  dim3 grid(Tv, B);
+  hipStream_t s = (hipStream_t)stream;
+  if (prec == NPPC_PREC_BF16)
+    hipLaunchKernelGGL(sb_unfold_bwd_kernel<bf16_t>, grid, dim3(256), sm, s, (const bf16_t*)dx, scale, D, mult, (bf16_t*)dX0,
+                       ldX, B, F, Tp, nb, Geff, Fo, KX, Nseq, Nn);
+  else
+    hipLaunchKernelGGL(sb_unfold_bwd_kernel<float>, grid, dim3(256), sm, s, (const float*)dx, scale, D, mult, (float*)dX0, ldX,
+                       B, F, Tp, nb, Geff, Fo, KX, Nseq, Nn);
   NPPC_CHECK_LAUNCH();
   return NPPC_OK;
 }

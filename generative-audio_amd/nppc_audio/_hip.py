@@ -80,6 +80,12 @@ def masked_mse_work_elems():
     return n.value
 
 
+def crm_mse_work_elems():
+    n = c_l()
+    call("nppc_crm_mse_work_elems", ctypes.byref(n))
+    return n.value
+
+
 def dtype_of(prec):
     return torch.bfloat16 if prec == PREC_BF16 else torch.float32
 
@@ -163,6 +169,7 @@ SIGS = {
     "nppc_colsum_scratch_elems": [I, I, I, PL],
     "nppc_sb_head_bwd": [I, P, P, P, P, P, P, L, I, I, I, I, I, P],
     "nppc_subband_stage_bwd": [I, P, P, P, P, P, P, I, I, I, I, I, L, I, I, I, P],
+    "nppc_subband_unfold_bwd": [I, P, P, P, P, P, I, I, I, I, I, I, I, I, P],
     "nppc_reduce_slabs": [P, I, L, L, P, L, I, I, I, I, I, L, L, I, P],
     "nppc_adam_step": [P, P, P, P, L, D, D, D, D, D, I, D, P],
     "nppc_adam_step_guarded": [P, P, P, P, L, D, D, D, D, D, I, D, P, I, P, P],
@@ -211,6 +218,9 @@ SIGS = {
     "nppc_masked_mse_work_elems": [PL],
     "nppc_masked_mse": [P, P, P, I, I, I, P, P, P],
     "nppc_masked_mse_bwd": [P, P, P, P, P, P, I, I, I, P],
+    "nppc_crm_mse_work_elems": [PL],
+    "nppc_crm_mse": [P, P, P, P, P, P, I, I, I, I, F, P, P, P],
+    "nppc_crm_mse_bwd": [P, P, P, P, P, P, P, I, I, I, I, F, P],
     "nppc_tcn_gn_bwd": [I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, L, L, L, I, P],
     "nppc_tcn_dwconv_bwd": [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, L, L, L, I, P],
     "nppc_tsse_bwd_ws_elems": [I, I, I, I, I, I, PL],

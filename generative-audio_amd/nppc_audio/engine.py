@@ -383,7 +383,7 @@ class FSNEngine:
             self.last_train = d
         return out
 
-    # ------------------------------------------------------------------ backward (direction net)
+    # ------------------------------------------------------------------ backward (direction net, trainable restorer)
     def _grad_buffer(self):
         """Flat gradient buffer that does NOT alias the parameters' current .grad (so autograd's accumulate
         semantics stay right whether or not the caller cleared the grads)."""
@@ -765,6 +765,12 @@ class FSNEngine:
             finish_mid(0, 4 if early else 8)
         if tn_ok:
             dXo = dXL[0]
+        if self.nm == 1:
+            # the restorer's sub-band rows unfold the attention-scaled magnitude X[0][0] (fullsubnet_plus.py:200-204), a
+            # trainable tensor: the gradient of those columns joins the TCN-input gradient of branch 0 (the direction net
+            # unfolds the raw magnitude, a constant: nothing to add there)
+            H.call("nppc_subband_unfold_bwd", prec, dx, d["sbscale"], Dsb, self.mult, dXo[0], ldC, B, F, Tp, Tv, self.nb, self.G,
+                   self.KX, s)
         # ---- 7. TSSE attention backward (parameter gradients only: the maps are data)
         sv = d["tsse_saved"]
         n_ws = ctypes.c_long()

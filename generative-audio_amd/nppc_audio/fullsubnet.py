@@ -133,6 +133,7 @@ class FullSubNet_Plus(nn.Module):
                                   self.output_size, config.sb_model_hidden_size, config.sequence_model)
         self._engine = None
         self._flat = None
+        self.flat_grad_only = False          # training: backward leaves the gradient in the flat buffer only (trainer)
 
     # -- HIP engine plumbing ---------------------------------------------------------------------
     def _prec(self):
@@ -161,11 +162,16 @@ class FullSubNet_Plus(nn.Module):
         return True
 
     def forward(self, noisy_mag, noisy_real, noisy_imag):
-        """[B,1,F,T] x3 -> compressed cIRM [B,2,F',T] (fullsubnet_plus.py:143-230).  Inference only:
-        the NPPC path always runs this net frozen under no_grad (nppc_model.py:94-95)."""
+        """[B,1,F,T] x3 -> compressed cIRM [B,2,F',T] (fullsubnet_plus.py:143-230).
+        Under no_grad or with frozen parameters this is the inference launch sequence the NPPC path runs
+        (nppc_model.py:94-95).  With gradients enabled and trainable parameters it is the train-mode forward, recorded
+        as ONE autograd function whose inputs are the parameters and whose backward is the engine's."""
         assert noisy_mag.dim() == 4
         assert noisy_mag.shape[1] == 1, f"{self.__class__.__name__} takes the mag feature as inputs."
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError("FullSubNet_Plus (MI355X build) is forward-only; wrap the call in torch.no_grad() "
-                               "(training this net is outside the NPPC hot path)")
-        return self.engine().forward([noisy_mag, noisy_real, noisy_imag], train=False)
+        maps = [m.detach() for m in (noisy_mag, noisy_real, noisy_imag)]
+        params = [p for _, p in self.named_parameters()]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            H.require_gpu()
+            from .networks import _DirectionNetFn     # the same autograd bridge as the direction net (n_maps = 1 here)
+            return _DirectionNetFn.apply(self, 3, *maps, *params)
+        return self.engine().forward(maps, train=False)

@@ -1,0 +1,234 @@
+"""Speech-enhancement restorer trainer on the MI355X kernels: the FullSubNet+ fine-tuning loop that
+FullSubNet_plus/config/train.toml selects (`trainer.path = Trainer_Finetune`,
+fullsubnet_plus/trainer/trainer.py:308-353; checkpoint layout audio_zen/trainer/base_trainer.py:160-201).
+
+Per step: STFT of noisy and clean (512 / 256 / 512), the compressed cIRM target with drop-band, the train-mode forward
+of `FullSubNet_Plus` (ONE autograd function whose backward is the engine's), mean-squared error, backward,
+clip_grad_norm_(10) and Adam(1e-3, (0.9, 0.999)).  The target + loss and its gradient are HIP kernels (nppc_crm_mse /
+_bwd); with Adam the clip + update is the fused clipped Adam over the flat parameter buffer (the clip coefficient stays
+on the device).  The checkpoint is what `nppc_model.preload_model` reads, so the trained restorer goes straight into
+`NPPCModelConfig.pretrained_restoration_model_path`.
+
+Differences, deliberately: no AMP (train.toml has use_amp = false, the scaler is an identity), no TensorBoard, no toml
+loader, no resume, one GPU; the data are the wav-folder `AudioDataset` mixed on the device (no reverberation); validation
+reports the mean loss (PESQ / STOI are not part of this build).
+"""
+import os
+from typing import List, Optional, Tuple
+
+import pydantic
+import torch
+import torch.nn as nn
+import torch.optim as optim
+
+from . import _hip as H
+from . import ops
+from . import ops_lstm
+from .data import AudioDataset, DataConfig, DataLoaderConfig, DeviceMixLoader
+from .fullsubnet import FullSubNet_Plus, FullSubNetPlusConfig
+from .nppc_model import StftConfig
+from .trainer import FlatAdamStepper, HipAdam, LoopLoader, OptimizerConfig
+
+__all__ = ["FullSubNetPlusTrainerConfig", "FullSubNetPlusTrainer", "CrmMSE", "crm_mse"]
+
+
+def _toml_optimizer():
+    return OptimizerConfig(type="Adam", args=dict(lr=1e-3, betas=(0.9, 0.999)))     # train.toml [optimizer]
+
+
+class FullSubNetPlusTrainerConfig(pydantic.BaseModel):
+    """Configuration of the FullSubNet+ restorer trainer (train.toml's [model], [optimizer], [trainer] and the
+    acoustics / dataset sections this build implements)"""
+    model_configuration: FullSubNetPlusConfig
+    data_configuration: Optional[DataConfig] = None       # wav folders; not needed when a dataset is passed
+    dataloader_configuration: DataLoaderConfig = pydantic.Field(default_factory=DataLoaderConfig)
+    optimizer_configuration: OptimizerConfig = pydantic.Field(default_factory=_toml_optimizer)
+    stft_configuration: StftConfig = pydantic.Field(default_factory=StftConfig)
+    clip_grad_norm_value: float = 10.0
+    device: str = "cuda"
+
+
+class CrmMSE(torch.autograd.Function):
+    """mse_loss(gt, cRM) (trainer.py:343) with gt = drop_band(compressed cIRM(noisy, clean), G) built inside the kernel.
+    crm [B,2,F',T] in drop-band order; noisy / clean STFT [B,F,T].  Returns (loss, gt); gt is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, crm, n_re, n_im, c_re, c_im, groups):
+        B, F, T = n_re.shape
+        work = torch.empty(H.crm_mse_work_elems(), dtype=torch.float64, device=crm.device)
+        loss = torch.empty((), dtype=torch.float32, device=crm.device)
+        gt = torch.empty_like(crm)
+        H.call("nppc_crm_mse", n_re, n_im, c_re, c_im, crm, gt, B, F, T, groups, ops.EPS32, work, loss, H.stream())
+        ctx.save_for_backward(crm, n_re, n_im, c_re, c_im)
+        ctx.groups = groups
+        ctx.mark_non_differentiable(gt)
+        return loss, gt
+
+    @staticmethod
+    def backward(ctx, g, _g_gt):
+        crm, n_re, n_im, c_re, c_im = ctx.saved_tensors
+        B, F, T = n_re.shape
+        dcrm = torch.empty_like(crm)
+        H.call("nppc_crm_mse_bwd", n_re, n_im, c_re, c_im, crm, g.float().contiguous(), dcrm, B, F, T, ctx.groups, ops.EPS32,
+               H.stream())
+        return dcrm, None, None, None, None, None
+
+
+def crm_mse(crm, n_re, n_im, c_re, c_im, groups):
+    """(loss, gt): loss = mean (gt - crm)^2, gt = drop_band(compressed cIRM, groups) [B,2,F',T]"""
+    H.require_gpu()
+    B, F, T = n_re.shape
+    Fo = F if groups <= 1 else (F - F % groups) // groups
+    if tuple(crm.shape) != (B, 2, Fo, T) or any(tuple(t.shape) != (B, F, T) for t in (n_im, c_re, c_im)):
+        raise ValueError(f"crm_mse: crm {tuple(crm.shape)} needs [{B}, 2, {Fo}, {T}] for STFTs of {(B, F, T)}, groups {groups}")
+    n_re, n_im, c_re, c_im = (ops._f32c(t) for t in (n_re, n_im, c_re, c_im))
+    return CrmMSE.apply(crm.contiguous().float(), n_re, n_im, c_re, c_im, int(groups))
+
+
+class FullSubNetPlusTrainer(nn.Module):
+    def __init__(self, config: FullSubNetPlusTrainerConfig, dataset=None):
+        super().__init__()
+        self.config = config
+        st = config.stft_configuration
+        if st.win_length != st.nfft:
+            raise NotImplementedError("win_length == nfft is the STFT configuration built for MI355X")
+        if st.nfft // 2 + 1 != config.model_configuration.num_freqs:
+            raise ValueError(f"nfft {st.nfft} gives {st.nfft // 2 + 1} bins, the model has num_freqs = "
+                             f"{config.model_configuration.num_freqs}")
+        bs, G = config.dataloader_configuration.batch_size, config.model_configuration.num_groups_in_drop_band
+        if bs <= G:
+            # drop_band asserts batch_size > num_groups on the target of every training batch (feature.py:263)
+            raise ValueError(f"Batch size = {bs}, num_groups = {G}. The batch size should larger than the num_groups.")
+        self.model = FullSubNet_Plus(config.model_configuration)       # raises for the configurations not built here
+        self.device = config.device
+        if config.device == "cuda":
+            self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+        self.model.to(self.device)
+        self.model.train()
+
+        okind = config.optimizer_configuration.type
+        if okind == "Adam":
+            self.optimizer = HipAdam(self.model.parameters(), **config.optimizer_configuration.args)
+        else:
+            self.optimizer = getattr(optim, okind)(self.model.parameters(), **config.optimizer_configuration.args)
+
+        if dataset is None:
+            if config.data_configuration is None:
+                raise ValueError("pass a dataset or a data_configuration (wav folders of clean speech and noise)")
+            dataset = AudioDataset(config.data_configuration.dataset)
+        self.dataset = dataset
+        self.dataloader = self.make_loader(dataset, config.dataloader_configuration)
+        self.step = 0
+        self.epoch = 0
+        self.loss_history: List[float] = []
+        self._flat_adam = None
+        self._sumsq = None
+
+    def make_loader(self, dataset, lc):
+        """(noisy [B,L], clean [B,L]) batches: an AudioDataset on a HIP device is mixed there (DeviceMixLoader)"""
+        if isinstance(dataset, AudioDataset) and str(self.device).startswith("cuda"):
+            base = (torch.utils.data.RandomSampler if lc.shuffle else torch.utils.data.SequentialSampler)(dataset)
+            return DeviceMixLoader(dataset, torch.utils.data.BatchSampler(base, lc.batch_size, drop_last=False),
+                                   device=self.device, pin_memory=lc.pin_memory)
+        return torch.utils.data.DataLoader(dataset, batch_size=lc.batch_size, shuffle=lc.shuffle, num_workers=lc.num_workers,
+                                           pin_memory=lc.pin_memory)
+
+    # ---------------------------------------------------------------------------------- reference API
+    def base_step(self, batch) -> Tuple[torch.Tensor, dict]:
+        """(noisy [B,L], clean [B,L]) -> (loss, log): trainer.py:328-343 (drop-band only when B > 1, like the forward)"""
+        noisy, clean = batch[0], batch[1]
+        st = self.config.stft_configuration
+        mag, n_re, n_im = ops.stft(noisy, st.nfft, st.hop_length)
+        _, c_re, c_im = ops.stft(clean, st.nfft, st.hop_length, want_mag=False)
+        B = n_re.shape[0]
+        G = self.config.model_configuration.num_groups_in_drop_band if B > 1 else 1
+        crm = self.model(mag[:, None], n_re[:, None], n_im[:, None])          # [B, 2, F', T]
+        loss, gt = crm_mse(crm, n_re, n_im, c_re, c_im, G)
+        log = {"cRM": crm.detach(), "gt": gt, "loss": loss.detach()}
+        return loss, log
+
+    def validate(self, loader):
+        """mean loss over the loader, no gradients (the inference launch sequence)"""
+        losses = []
+        with torch.no_grad():
+            for batch in loader:
+                loss, _ = self.base_step(self._to_device(batch))
+                losses.append(loss.item())
+        if not losses:
+            raise ValueError("the validation loader yields no batch")
+        return sum(losses) / len(losses)
+
+    # ---------------------------------------------------------------------------------- one optimisation step
+    def train_step(self, batch):
+        """zero_grad + forward + backward + clip_grad_norm_(clip_grad_norm_value) + optimizer step (trainer.py:325-349).
+        log['grad_norm'] is the total gradient norm before clipping (a device tensor).
+        The clipped Adam does not read the hand-off time-out counters of the cooperative LSTM kernels, so every step ends
+        with ops_lstm.check_coop_timeouts: a timed-out hand-off raises here instead of training on wrong numbers (the check
+        reads the counters on the host, i.e. it waits for the step)."""
+        net = self.model
+        fast = isinstance(self.optimizer, HipAdam)
+        net.flat_grad_only = fast
+        try:
+            self.optimizer.zero_grad()
+            loss, log = self.base_step(batch)
+            loss.backward()
+        finally:
+            net.flat_grad_only = False
+        if fast:
+            eng = net.engine()
+            gflat = eng.fp.grad
+            if self._sumsq is None:
+                self._sumsq = torch.zeros(1, dtype=torch.float64, device=gflat.device)
+            self._sumsq.zero_()
+            H.call("nppc_sumsq", gflat, gflat.numel(), self._sumsq, H.stream())
+            if self._flat_adam is None or self._flat_adam.eng is not eng:
+                self._flat_adam = FlatAdamStepper(self.optimizer, eng)
+            self._flat_adam.step(gflat, 1.0, clip=(self._sumsq, float(self.config.clip_grad_norm_value)))
+            log["grad_norm"] = self._sumsq.sqrt()
+        else:
+            log["grad_norm"] = torch.nn.utils.clip_grad_norm_(net.parameters(), self.config.clip_grad_norm_value)
+            self.optimizer.step()
+        self.step += 1
+        ops_lstm.check_coop_timeouts(f"step {self.step}")
+        return loss, log
+
+    def _to_device(self, batch):
+        return tuple(x.to(self.device, non_blocking=True) for x in batch[:2])
+
+    def train(self, n_steps=None, n_epochs=None, checkpoint_dir="checkpoints", save_flag=True):
+        """training loop (the name shadows nn.Module.train like the NPPC trainers; mode changes go through self.model).
+        Writes <checkpoint_dir>/latest_model.tar at the end when save_flag.  Returns the per-step loss history."""
+        assert n_steps is not None or n_epochs is not None, "Must specify either n_steps or n_epochs"
+        loop_loader = LoopLoader(dataloader=self.dataloader, n_steps=n_steps, n_epochs=n_epochs)
+        if len(loop_loader) == 0:
+            raise ValueError("the data loader yields no minibatch")
+        per_epoch = max(len(self.dataloader), 1)
+        history: List[float] = []
+        for it, batch in enumerate(loop_loader):
+            loss, _ = self.train_step(self._to_device(batch))
+            history.append(loss.item())
+            if (it + 1) % per_epoch == 0:
+                self.epoch += 1
+        self.loss_history.extend(history)
+        if history:
+            print(f"step {self.step}: Loss: {history[-1]:.4f}")
+        if save_flag:
+            os.makedirs(checkpoint_dir, exist_ok=True)
+            self.save_checkpoint(os.path.join(checkpoint_dir, "latest_model.tar"))
+        return history
+
+    def save_checkpoint(self, path, best_score=None):
+        """base_trainer.py:173-184 layout: {"epoch", "best_score", "optimizer", "scaler", "model"} (+ "step");
+        "model" loads strictly into FullSubNet_Plus and is what nppc_model.preload_model reads"""
+        checkpoint = {
+            "epoch": self.epoch,
+            "step": self.step,
+            "best_score": float("-inf") if best_score is None else best_score,
+            "optimizer": self.optimizer.state_dict(),
+            "scaler": {},                     # use_amp = false: the reference's disabled GradScaler has an empty state
+            "model": self.model.state_dict(),
+        }
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        torch.save(checkpoint, path)
+        print(f"Checkpoint saved to {path}")
+        return path

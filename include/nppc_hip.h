@@ -192,6 +192,13 @@ int nppc_subband_stage(int prec, const void* src, int ldS, const void* fb, int l
 int nppc_subband_stage_bwd(int prec, const void* dx, const void* x, const void* fb, const float* scale, double* D,
                            void* dpre, int B, int F, int Tp, int Tv, int ldF, long strideFb, int nb, int G, int KX,
                            void* stream);
+/* restorer (n_maps = 1) only: gradient of the unfolded, laplace-normalised attention columns (the first 2nb+1 of a
+ * sub-band row) with respect to the TCN input of the magnitude branch, ADDED into dX0 [B][Tp][ldX] (bf16 | fp32) for
+ * t < Tv: dX0[b][t][f] += sc_b sum dx[t][n(b,f')][k] - sc_b D[bo] mult[f] / Nn over the kept rows f' whose column k reads
+ * bin f (reflect padding, drop-band as in nppc_subband_stage).  scale / D as left by nppc_subband_mean /
+ * nppc_subband_stage_bwd, mult = unfold multiplicity [F].  A gather without atomics: bit-identical on repeat. */
+int nppc_subband_unfold_bwd(int prec, const void* dx, const float* scale, const double* D, const float* mult, void* dX0,
+                            int ldX, int B, int F, int Tp, int Tv, int nb, int G, int KX, void* stream);
 int nppc_sb_head(int prec, const void* h2, const void* wh, const float* bias, float* out, long Nseq, int Tn, int la,
                  int Hd, int O, int Fo, void* stream);
 int nppc_sb_head_bwd(int prec, const float* dout, const void* whT, const void* h2, void* dh2, float* dWh, float* dbh,
@@ -460,6 +467,18 @@ int nppc_masked_mse(const float* out, const float* clean, const float* mask, int
                     void* stream);
 int nppc_masked_mse_bwd(const float* out, const float* clean, const float* mask, const float* g, const double* work,
                         float* dout, int B, int F, int T, void* stream);
+
+/* ---- speech-enhancement restorer trainer (Trainer_Finetune._train_epoch, trainer.py:337-343) -------------------------
+ * cIRM MSE: noisy / clean STFT nr, ni, cr, ci [B][F][T] fp32, model output crm [B][2][Fo][T] in drop-band order (G groups,
+ * Fo = (F - F % G) / G, G = 1: no drop-band).  The compressed cIRM target is built per element as
+ * nppc_cirm_build_compress does; gt (nullable) receives it.  *loss = mean (gt - crm)^2 over the 2 B Fo T elements, fp64
+ * partials folded in a fixed order (no float atomics, bit-identical on repeat); work = *elems of nppc_crm_mse_work_elems
+ * doubles.  Backward: dcrm = 2 g (crm - gt) / N, g (the incoming gradient of the loss) read from device memory. */
+int nppc_crm_mse_work_elems(long* elems);
+int nppc_crm_mse(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, float* gt /*nullable*/,
+                 int B, int F, int T, int G, float eps, double* work, float* loss, void* stream);
+int nppc_crm_mse_bwd(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, const float* g,
+                     float* dcrm, int B, int F, int T, int G, float eps, void* stream);
 
 #ifdef __cplusplus
 }
