@@ -226,6 +226,11 @@ SIGS = {
     "nppc_tsse_bwd_ws_elems": [I, I, I, I, I, I, PL],
     "nppc_tsse_bwd": [I, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                       I, I, I, I, I, I, I, P],
+    "nppc_sisdr_sums": [P, P, P, I, L, P, P, P],
+    "nppc_resample_poly": [P, P, I, L, P, I, I, I, P, L, P],
+    "nppc_stoi_frames": [P, P, I, L, I, P, P, P, P, P],
+    "nppc_stoi_bands": [P, P, L, P, P, I, I, P, P, P],
+    "nppc_stoi_corr": [P, P, P, I, I, P, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

@@ -1,0 +1,160 @@
+"""Speech-enhancement metrics on the device: STOI and SI-SDR of ragged batches (audio_zen/metrics.py:61-89,
+use_pre_trained_model/model_validator/model_validator.py:56-65).
+
+Every function takes [B, L] or [L] device tensors (clean / reference first, estimate second) and an optional per-item
+`lengths` ([B] ints: the samples of row b past lengths[b] are padding and never read), and returns a [B] float64 device
+tensor.  An item's value depends on its own samples only and is bit-identical in any batch and on every run.
+
+- `si_sdr`: audio_zen's SI_SDR (no mean removal, no eps; +inf when the estimate is an exact multiple of the reference).
+- `si_sdr_zero_mean`: ModelValidator.calculate_metrics' SI-SDR (both signals mean-removed, eps 1e-6).
+- `stoi`: classic STOI (extended=False) at 16 kHz, the algorithm pystoi 0.3 implements, stated step by step in DESIGN.md
+  ("Speech-enhancement metrics").  pystoi is not available to this project: agreement with pystoi itself is unverified;
+  the kernels are tested stage by stage against a float64 numpy restatement of that contract.
+
+PESQ (WB / NB) and MOSNET are registered names that raise NotImplementedError, so a metric list taken from train.toml fails
+loudly instead of silently dropping a metric.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _hip as H
+
+__all__ = ["si_sdr", "si_sdr_zero_mean", "si_sdr_both", "stoi", "stoi_stages", "resample_window", "REGISTERED_METRICS"]
+
+SR = 16000
+UP, DOWN = 5, 8                 # 16 kHz -> 10 kHz
+N_FRAME, HOP, NUMBAND = 256, 128, 15
+
+_TAPS = {}
+
+
+def resample_window(p=UP, q=DOWN):
+    """pystoi's _resample_window_oct(p, q) normalised to unit sum (the window resample_oct hands to resample_poly):
+    Kaiser-windowed sinc, cutoff 1 / (2 max(p, q)), 60 dB rejection; 581 taps for 5 / 8"""
+    g = math.gcd(p, q)
+    p, q = p // g, q // g
+    rejection_db = 60.0
+    stopband_cutoff_f = 1.0 / (2 * max(p, q))
+    roll_off_width = stopband_cutoff_f / 10
+    L = int(np.ceil((rejection_db - 8) / (28.714 * roll_off_width)))
+    t = np.arange(-L, L + 1)
+    ideal = 2 * p * stopband_cutoff_f * np.sinc(2 * stopband_cutoff_f * t)
+    h = np.kaiser(2 * L + 1, 0.1102 * (rejection_db - 8.7)) * ideal
+    return h / np.sum(h)
+
+
+def _taps(device):
+    key = str(device)
+    if key not in _TAPS:
+        _TAPS[key] = torch.from_numpy(resample_window()).to(device)
+    return _TAPS[key]
+
+
+def _batch(ref, est, lengths):
+    """(ref, est) as [B, L] fp32 contiguous device rows and lengths as a [B] int32 device tensor"""
+    H.require_gpu()
+    if not (isinstance(ref, torch.Tensor) and isinstance(est, torch.Tensor) and ref.is_cuda and est.is_cuda):
+        raise RuntimeError("nppc_audio.metrics takes HIP device tensors")
+    if ref.shape != est.shape or ref.dim() not in (1, 2):
+        raise ValueError(f"reference {tuple(ref.shape)} and estimate {tuple(est.shape)} must be the same [B, L] or [L]")
+    if ref.dim() == 1:
+        ref, est = ref[None], est[None]
+    ref, est = ref.contiguous().float(), est.contiguous().float()
+    B, L = ref.shape
+    if B == 0 or L == 0:
+        raise ValueError("empty batch")
+    if lengths is None:
+        lens = torch.full((B,), L, dtype=torch.int32, device=ref.device)
+    else:
+        if not isinstance(lengths, torch.Tensor) or not lengths.is_cuda:
+            host = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1)
+            if host.numel() != B or int(host.min()) < 1 or int(host.max()) > L:
+                raise ValueError(f"lengths must be {B} values in [1, {L}]")
+        lens = torch.as_tensor(lengths).to(device=ref.device, dtype=torch.int32).reshape(-1).contiguous()
+        if lens.numel() != B:
+            raise ValueError(f"lengths must hold {B} values")
+    return ref, est, lens
+
+
+def si_sdr_both(ref, est, lengths=None, return_sums=False):
+    """[B, 2] float64: column 0 = audio_zen SI_SDR, column 1 = ModelValidator's mean-removed SI-SDR (one launch)"""
+    ref, est, lens = _batch(ref, est, lengths)
+    B, L = ref.shape
+    out = torch.empty(B, 2, dtype=torch.float64, device=ref.device)
+    sums = torch.empty(B, 9, dtype=torch.float64, device=ref.device) if return_sums else None
+    H.call("nppc_sisdr_sums", ref, est, lens, B, L, sums, out, H.stream())
+    return (out, sums) if return_sums else out
+
+
+def si_sdr(ref, est, lengths=None):
+    """audio_zen/metrics.py:61-85 per item: 10 log10(|a s|^2 / |e - a s|^2), a = <s, e> / |s|^2 -> [B] float64"""
+    return si_sdr_both(ref, est, lengths)[:, 0]
+
+
+def si_sdr_zero_mean(ref, est, lengths=None):
+    """model_validator.py:60-65 per item: mean-removed, a = <e, s> / (|s|^2 + 1e-6),
+    20 log10(|a s| / (|a s - e| + 1e-6)) -> [B] float64"""
+    return si_sdr_both(ref, est, lengths)[:, 1]
+
+
+def stoi_stages(clean, est, sr=SR, lengths=None):
+    """the STOI launch sequence with every intermediate kept: resampled signals xr / yr [B, Lr] and their lengths lr,
+    frame energies / slot (kept position or -1) / kidx / K of the silence mask, band magnitudes x_tob / y_tob
+    [B, 15, nfr] (the first K - 1 frames of each item are defined) and stoi [B]"""
+    if sr != SR:
+        raise ValueError(f"stoi: sr = {sr} is not supported; the resampler is designed for 16000 Hz input (5 / 8 to 10 kHz)")
+    x, y, lens = _batch(clean, est, lengths)
+    B, L = x.shape
+    dev = x.device
+    Lr = -(-L * UP // DOWN)
+    nfr = max(1, -(-(Lr - N_FRAME) // HOP))
+    h = _taps(dev)
+    xr = torch.empty(B, Lr, dtype=torch.float64, device=dev)
+    yr = torch.empty_like(xr)
+    H.call("nppc_resample_poly", x, lens, B, L, h, h.numel(), UP, DOWN, xr, Lr, H.stream())
+    H.call("nppc_resample_poly", y, lens, B, L, h, h.numel(), UP, DOWN, yr, Lr, H.stream())
+    lr = torch.div(lens * UP + (DOWN - 1), DOWN, rounding_mode="floor").to(torch.int32)
+    energy = torch.empty(B, nfr, dtype=torch.float64, device=dev)
+    slot = torch.empty(B, nfr, dtype=torch.int32, device=dev)
+    kidx = torch.empty_like(slot)
+    K = torch.empty(B, dtype=torch.int32, device=dev)
+    H.call("nppc_stoi_frames", xr, lr, B, Lr, nfr, energy, slot, kidx, K, H.stream())
+    x_tob = torch.empty(B, NUMBAND, nfr, dtype=torch.float64, device=dev)
+    y_tob = torch.empty_like(x_tob)
+    H.call("nppc_stoi_bands", xr, yr, Lr, kidx, K, B, nfr, x_tob, y_tob, H.stream())
+    out = torch.empty(B, dtype=torch.float64, device=dev)
+    H.call("nppc_stoi_corr", x_tob, y_tob, K, B, nfr, out, H.stream())
+    return dict(xr=xr, yr=yr, lr=lr, energy=energy, slot=slot, kidx=kidx, K=K, x_tob=x_tob, y_tob=y_tob, stoi=out)
+
+
+def stoi(clean, est, sr=SR, lengths=None):
+    """classic STOI (pystoi.stoi(clean, est, 16000, extended=False) as DESIGN.md states it) per item -> [B] float64;
+    1e-5 for an item with fewer than 30 STFT frames after silence removal"""
+    return stoi_stages(clean, est, sr, lengths)["stoi"]
+
+
+def _not_built(name, reason):
+    def metric(ref, est, sr=SR, lengths=None):
+        raise NotImplementedError(f"{name}: {reason}")
+    metric.__name__ = name
+    return metric
+
+
+def _stoi_metric(ref, est, sr=SR, lengths=None):
+    return stoi(ref, est, sr=sr, lengths=lengths)
+
+
+def _si_sdr_metric(ref, est, sr=SR, lengths=None):
+    return si_sdr(ref, est, lengths=lengths)
+
+
+# audio_zen/metrics.py:143-149: only registered metrics can be used; each is metric(ref, est, sr=..) -> [B] float64 here
+REGISTERED_METRICS = {
+    "SI_SDR": _si_sdr_metric,
+    "STOI": _stoi_metric,
+    "WB_PESQ": _not_built("WB_PESQ", "PESQ (ITU-T P.862) is not implemented in this build"),
+    "NB_PESQ": _not_built("NB_PESQ", "PESQ (ITU-T P.862) is not implemented in this build"),
+    "MOSNET": _not_built("MOSNET", "MOSNet needs a pretrained network this build does not have"),
+}

@@ -10,8 +10,10 @@ on the device).  The checkpoint is what `nppc_model.preload_model` reads, so the
 `NPPCModelConfig.pretrained_restoration_model_path`.
 
 Differences, deliberately: no AMP (train.toml has use_amp = false, the scaler is an identity), no TensorBoard, no toml
-loader, no resume, one GPU; the data are the wav-folder `AudioDataset` mixed on the device (no reverberation); validation
-reports the mean loss (PESQ / STOI are not part of this build).
+loader, no resume, one GPU; the data are the wav-folder `AudioDataset` mixed on the device (no reverberation).  `validate`
+reports the mean loss; `validate_metrics` follows _validation_epoch (trainer.py:366-446) and scores the enhanced
+waveforms with STOI and SI-SDR on the device (nppc_audio.metrics); PESQ is not part of this build, so the epoch score that
+picks best_model.tar is the mean enhanced STOI.
 """
 import os
 from typing import List, Optional, Tuple
@@ -22,6 +24,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 from . import _hip as H
+from . import metrics
 from . import ops
 from . import ops_lstm
 from .data import AudioDataset, DataConfig, DataLoaderConfig, DeviceMixLoader
@@ -123,6 +126,8 @@ class FullSubNetPlusTrainer(nn.Module):
         self.loss_history: List[float] = []
         self._flat_adam = None
         self._sumsq = None
+        self.best_score = float("-inf")
+        self.val_history: List[dict] = []
 
     def make_loader(self, dataset, lc):
         """(noisy [B,L], clean [B,L]) batches: an AudioDataset on a HIP device is mixed there (DeviceMixLoader)"""
@@ -157,6 +162,49 @@ class FullSubNetPlusTrainer(nn.Module):
         if not losses:
             raise ValueError("the validation loader yields no batch")
         return sum(losses) / len(losses)
+
+    def full_band_output(self, mag, n_re, n_im):
+        """compressed cIRM [B,2,F,T] of the inference forward WITHOUT drop-band.  The forward drop-bands any batch of
+        B > 1 when num_groups_in_drop_band > 1 (fullsubnet_plus.py:212-214); the reference validates with batch size 1,
+        so such a batch runs one clip at a time here."""
+        B = mag.shape[0]
+        with torch.no_grad():
+            if B > 1 and self.config.model_configuration.num_groups_in_drop_band > 1:
+                return torch.cat([self.model(mag[b:b + 1, None], n_re[b:b + 1, None], n_im[b:b + 1, None])
+                                  for b in range(B)])
+            return self.model(mag[:, None], n_re[:, None], n_im[:, None])
+
+    def validate_metrics(self, loader):
+        """Trainer_Finetune._validation_epoch (trainer.py:366-446) + metrics_visualization (base_trainer.py:264-303) on
+        (noisy [B,L], clean [B,L]) batches: the loss on the cIRM WITHOUT drop-band (full_band_output, crm_mse with one
+        group), the enhanced waveform (decompressed mask applied to the noisy STFT, inverse STFT), and STOI and audio_zen's
+        SI-SDR of the noisy and of the enhanced waveform against the clean one.  Returns {"loss", "STOI_noisy", "STOI",
+        "SI_SDR_noisy", "SI_SDR", "score"}: loss = mean of the batch losses (the reference's per-clip mean at batch size
+        1), the metrics = means over items.  The reference's score is (STOI + (WB_PESQ + 0.5) / 5) / 2; without PESQ it is
+        the mean enhanced STOI here.  Everything stays on the device until one host copy at the end."""
+        st = self.config.stft_configuration
+        losses, scores = [], {k: [] for k in ("STOI_noisy", "STOI", "SI_SDR_noisy", "SI_SDR")}
+        with torch.no_grad():
+            for batch in loader:
+                noisy, clean = self._to_device(batch)
+                mag, n_re, n_im = ops.stft(noisy, st.nfft, st.hop_length)
+                _, c_re, c_im = ops.stft(clean, st.nfft, st.hop_length, want_mag=False)
+                crm = self.full_band_output(mag, n_re, n_im)
+                loss, _ = crm_mse(crm, n_re, n_im, c_re, c_im, 1)
+                enhanced = ops.model_outputs_to_waveforms(crm, n_re[:, None], n_im[:, None], noisy.shape[-1], st.nfft,
+                                                          st.hop_length)
+                losses.append(loss.double())
+                scores["STOI_noisy"].append(metrics.stoi(clean, noisy))
+                scores["STOI"].append(metrics.stoi(clean, enhanced))
+                scores["SI_SDR_noisy"].append(metrics.si_sdr(clean, noisy))
+                scores["SI_SDR"].append(metrics.si_sdr(clean, enhanced))
+        if not losses:
+            raise ValueError("the validation loader yields no batch")
+        names = ["loss"] + list(scores)
+        vals = torch.stack([torch.stack(losses).mean()] + [torch.cat(v).mean() for v in scores.values()]).cpu().tolist()
+        out = dict(zip(names, vals))
+        out["score"] = out["STOI"]
+        return out
 
     # ---------------------------------------------------------------------------------- one optimisation step
     def train_step(self, batch):
@@ -195,9 +243,12 @@ class FullSubNetPlusTrainer(nn.Module):
     def _to_device(self, batch):
         return tuple(x.to(self.device, non_blocking=True) for x in batch[:2])
 
-    def train(self, n_steps=None, n_epochs=None, checkpoint_dir="checkpoints", save_flag=True):
+    def train(self, n_steps=None, n_epochs=None, checkpoint_dir="checkpoints", save_flag=True, val_loader=None):
         """training loop (the name shadows nn.Module.train like the NPPC trainers; mode changes go through self.model).
-        Writes <checkpoint_dir>/latest_model.tar at the end when save_flag.  Returns the per-step loss history."""
+        Writes <checkpoint_dir>/latest_model.tar at the end when save_flag.  Returns the per-step loss history.
+        With a val_loader, every completed epoch ends with validate_metrics (train.toml validation_interval = 1; the
+        results go to self.val_history) and, when its score >= the best so far (save_max_metric_score = true),
+        <checkpoint_dir>/best_model.tar in the layout of save_checkpoint with that best_score (base_trainer.py:160-215)."""
         assert n_steps is not None or n_epochs is not None, "Must specify either n_steps or n_epochs"
         loop_loader = LoopLoader(dataloader=self.dataloader, n_steps=n_steps, n_epochs=n_epochs)
         if len(loop_loader) == 0:
@@ -209,6 +260,8 @@ class FullSubNetPlusTrainer(nn.Module):
             history.append(loss.item())
             if (it + 1) % per_epoch == 0:
                 self.epoch += 1
+                if val_loader is not None:
+                    self._validate_epoch(val_loader, checkpoint_dir)
         self.loss_history.extend(history)
         if history:
             print(f"step {self.step}: Loss: {history[-1]:.4f}")
@@ -216,6 +269,17 @@ class FullSubNetPlusTrainer(nn.Module):
             os.makedirs(checkpoint_dir, exist_ok=True)
             self.save_checkpoint(os.path.join(checkpoint_dir, "latest_model.tar"))
         return history
+
+    def _validate_epoch(self, val_loader, checkpoint_dir):
+        m = self.validate_metrics(val_loader)
+        m["epoch"] = self.epoch
+        self.val_history.append(m)
+        print(f"epoch {self.epoch}: validation loss {m['loss']:.4f}, STOI {m['STOI']:.4f} (noisy {m['STOI_noisy']:.4f}), "
+              f"SI-SDR {m['SI_SDR']:.2f} dB (noisy {m['SI_SDR_noisy']:.2f} dB)")
+        if m["score"] >= self.best_score:
+            self.best_score = m["score"]
+            self.save_checkpoint(os.path.join(checkpoint_dir, "best_model.tar"), best_score=m["score"])
+        return m
 
     def save_checkpoint(self, path, best_score=None):
         """base_trainer.py:173-184 layout: {"epoch", "best_score", "optimizer", "scaler", "model"} (+ "step");

@@ -480,6 +480,30 @@ int nppc_crm_mse(const float* nr, const float* ni, const float* cr, const float*
 int nppc_crm_mse_bwd(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, const float* g,
                      float* dcrm, int B, int F, int T, int G, float eps, void* stream);
 
+/* ---- speech-enhancement metrics (audio_zen/metrics.py:61-85 SI_SDR + :88-89 STOI; model_validator.py:56-65) ----------
+ * Ragged batches: rows [B][ld] fp32 padded, lengths[B] (device int); no sample past an item's length is read, one item's
+ * values do not depend on the rest of the batch, no atomics (bit-identical on repeat).  All arithmetic after the fp32 input
+ * samples is fp64.
+ * SI-SDR: out[B][2] = (audio_zen SI_SDR, ModelValidator's mean-removed SI-SDR); sums (nullable) [B][9] = sum s, sum e,
+ * sum s^2, sum e^2, sum s e, sum s~^2, sum e~ s~, sum (e - a1 s)^2, sum (a2 s~ - e~)^2 (s = ref, e = est, ~ = mean removed). */
+int nppc_sisdr_sums(const float* ref, const float* est, const int* lengths, int B, long ld, double* sums /*nullable*/,
+                    double* out, void* stream);
+/* scipy.signal.resample_poly(x, up, down, window=h): h [ntaps] fp64 (<= 4096 taps, odd length), y [B][ldy] fp64, item b
+ * gets ceil(lengths[b] up / down) samples (clipped to ldy), zeros after them */
+int nppc_resample_poly(const float* x, const int* lengths, int B, long ldx, const double* h, int ntaps, int up, int down,
+                       double* y, long ldy, void* stream);
+/* STOI at 10 kHz (DESIGN.md "Speech-enhancement metrics"), on the resampled clean xr / estimate yr [B][ldr], lr[B] = their
+ * lengths, nfr >= every item's frame count max(0, ceil((lr - 256) / 128)):
+ * frames: energy [B][nfr] of the windowed clean frames (dB), slot [B][nfr] = kept position or -1, kidx [B][nfr] = frame of
+ *         the k-th kept frame (-1 past K), K [B] = kept frames;
+ * bands:  third-octave magnitudes x_tob, y_tob [B][15][nfr] of the K - 1 STFT frames of the silence-removed signals;
+ * corr:   out [B] = STOI, 1e-5 for items with fewer than 30 STFT frames */
+int nppc_stoi_frames(const double* xr, const int* lr, int B, long ldr, int nfr, double* energy, int* slot, int* kidx, int* K,
+                     void* stream);
+int nppc_stoi_bands(const double* xr, const double* yr, long ldr, const int* kidx, const int* K, int B, int nfr, double* x_tob,
+                    double* y_tob, void* stream);
+int nppc_stoi_corr(const double* x_tob, const double* y_tob, const int* K, int B, int nfr, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
