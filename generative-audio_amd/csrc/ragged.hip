@@ -1,0 +1,630 @@
+// Ragged (variable-length) inference of the FullSubNet+ restorer (n_maps = 1): a padded batch [B][Lmax] whose item b
+// is L_b samples / T_b = 1 + L_b / hop frames long.  Each kernel here is the per-item form of a uniform kernel
+// (frontend.hip, spec.hip, tcn.hip, subband.hip): it reads an item's own length from a device int[B] and computes
+// exactly what the uniform kernel computes for that item run alone.  Padding past an item's end is never read, and
+// what these kernels write past it is zero.  No float atomics: every sum has one writer and a fixed order.
+// The uniform GEMMs, the staging and the LSTM run at the batch's longest length.
+#include "common.h"
+#include "nppc_hip.h"
+
+namespace {
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---------------------------------------------------------------- STFT (frontend.hip: stft_kernel, per-item length)
+// wave [B][ld] (item b: its first L_b samples), out [B][F][T] with T = 1 + Lmax / hop; frames t >= T_b written as 0.
+constexpr int RSTFT_FR = 8;
+
+template <int LOGN>
+__global__ __launch_bounds__(256) void stft_ragged_kernel(const float* __restrict__ wave, long ld, const int* __restrict__ lengths,
+                                                          float* __restrict__ out_re, float* __restrict__ out_im,
+                                                          float* __restrict__ out_mag, int hop, int T) {
+  constexpr int N = 1 << LOGN;
+  constexpr int F = N / 2 + 1;
+  __shared__ float2 buf[RSTFT_FR][N + 1];
+  __shared__ float2 tw[N / 2];
+  __shared__ float win[N];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y;
+  const int t0 = blockIdx.x * RSTFT_FR;
+  const int L = clampi(lengths[b], 1, (int)ld);       // (the host validates L_b > N/2; the clamp only keeps reads in the row)
+  const int Tb = min(1 + L / hop, T);
+  if (t0 >= Tb) {                                      // the whole block is past the item's end
+    for (int e = tid; e < F * RSTFT_FR; e += 256) {
+      const int f = e / RSTFT_FR, t = t0 + e % RSTFT_FR;
+      if (t < T) {
+        const size_t o = ((size_t)b * F + f) * T + t;
+        out_re[o] = 0.f;
+        out_im[o] = 0.f;
+        if (out_mag) out_mag[o] = 0.f;
+      }
+    }
+    return;
+  }
+  for (int i = tid; i < N / 2; i += 256) {
+    double s, c;
+    sincospi(-2.0 * i / N, &s, &c);
+    tw[i] = make_float2((float)c, (float)s);
+  }
+  for (int i = tid; i < N; i += 256) win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / N));
+  __syncthreads();
+  const float* wv = wave + (size_t)b * ld;
+  for (int e = tid; e < RSTFT_FR * N; e += 256) {
+    const int j = e / N, n = e % N;
+    const int t = t0 + j;
+    float v = 0.f;
+    if (t < Tb) {
+      int sidx = t * hop + n - N / 2;
+      if (sidx < 0) sidx = -sidx;
+      if (sidx >= L) sidx = 2 * (L - 1) - sidx;       // reflect at the item's own end
+      v = wv[clampi(sidx, 0, L - 1)] * win[n];
+    }
+    const int r = __brev((unsigned)n) >> (32 - LOGN);
+    buf[j][r] = make_float2(v, 0.f);
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int s = 0; s < LOGN; ++s) {
+    const int half = 1 << s;
+    for (int e = tid; e < RSTFT_FR * (N / 2); e += 256) {
+      const int j = e / (N / 2), k = e % (N / 2);
+      const int grp = k >> s, pos = k & (half - 1);
+      const int i0 = (grp << (s + 1)) + pos, i1 = i0 + half;
+      const float2 w = tw[pos << (LOGN - 1 - s)];
+      const float2 a = buf[j][i0], c = buf[j][i1];
+      const float xr = c.x * w.x - c.y * w.y, xi = c.x * w.y + c.y * w.x;
+      buf[j][i0] = make_float2(a.x + xr, a.y + xi);
+      buf[j][i1] = make_float2(a.x - xr, a.y - xi);
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < F * RSTFT_FR; e += 256) {
+    const int f = e / RSTFT_FR, j = e % RSTFT_FR;
+    const int t = t0 + j;
+    if (t < T) {
+      const float2 v = t < Tb ? buf[j][f] : make_float2(0.f, 0.f);
+      const size_t o = ((size_t)b * F + f) * T + t;
+      out_re[o] = v.x;
+      out_im[o] = v.y;
+      if (out_mag) out_mag[o] = t < Tb ? sqrtf(v.x * v.x + v.y * v.y) : 0.f;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- iSTFT (frontend.hip: istft_kernel, per-item length)
+// re / im [B][F][T] (item b: frames t < T_b), out [B][ld]: samples n < L_b as torch.istft(length=L_b) of the item's own
+// T_b frames (window envelope of those frames only), samples L_b <= n < ld written as 0.
+constexpr int RISTFT_FR = 4;
+
+template <int LOGN>
+__global__ __launch_bounds__(256) void istft_ragged_kernel(const float* __restrict__ re, const float* __restrict__ im,
+                                                           float* __restrict__ out, long ld, const int* __restrict__ lengths,
+                                                           int T, int hop) {
+  constexpr int N = 1 << LOGN;
+  constexpr int F = N / 2 + 1;
+  constexpr int MAXFR = RISTFT_FR + 7;
+  __shared__ float2 buf[MAXFR][N + 1];
+  __shared__ float2 tw[N / 2];
+  __shared__ float win[N];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int L = clampi(lengths[b], 0, (int)ld);
+  const int Tb = min(1 + L / hop, T);
+  const int ov = N / hop;
+  const int nfr = RISTFT_FR + ov - 1;
+  const int p0 = blockIdx.x * RISTFT_FR * hop;
+  const int tfirst = p0 / hop - (ov - 1);
+  if (p0 - N / 2 >= L) {                               // every sample of the block is past the item's end
+    for (int e = tid; e < RISTFT_FR * hop; e += 256) {
+      const int nidx = p0 + e - N / 2;
+      if (nidx >= 0 && nidx < ld) out[(size_t)b * ld + nidx] = 0.f;
+    }
+    return;
+  }
+  for (int i = tid; i < N / 2; i += 256) {
+    double s, c;
+    sincospi(2.0 * i / N, &s, &c);
+    tw[i] = make_float2((float)c, (float)s);
+  }
+  for (int i = tid; i < N; i += 256) win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / N));
+  __syncthreads();
+  for (int e = tid; e < nfr * N; e += 256) {
+    const int j = e / N, k = e % N;
+    const int t = tfirst + j;
+    float2 v = make_float2(0.f, 0.f);
+    if (t >= 0 && t < Tb) {
+      const int kk = k < F ? k : N - k;
+      const size_t o = ((size_t)b * F + kk) * T + t;
+      v = make_float2(re[o], k < F ? im[o] : -im[o]);
+      if (k == 0 || k == N / 2) v.y = 0.f;
+    }
+    buf[j][__brev((unsigned)k) >> (32 - LOGN)] = v;
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int s = 0; s < LOGN; ++s) {
+    const int half = 1 << s;
+    for (int e = tid; e < nfr * (N / 2); e += 256) {
+      const int j = e / (N / 2), k = e % (N / 2);
+      const int grp = k >> s, pos = k & (half - 1);
+      const int i0 = (grp << (s + 1)) + pos, i1 = i0 + half;
+      const float2 w = tw[pos << (LOGN - 1 - s)];
+      const float2 a = buf[j][i0], c = buf[j][i1];
+      const float xr = c.x * w.x - c.y * w.y, xi = c.x * w.y + c.y * w.x;
+      buf[j][i0] = make_float2(a.x + xr, a.y + xi);
+      buf[j][i1] = make_float2(a.x - xr, a.y - xi);
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < RISTFT_FR * hop; e += 256) {
+    const int p = p0 + e;
+    const int nidx = p - N / 2;
+    if (nidx < 0 || nidx >= ld) continue;
+    if (nidx >= L) {
+      out[(size_t)b * ld + nidx] = 0.f;
+      continue;
+    }
+    float num = 0.f, den = 0.f;
+    for (int j = 0; j < nfr; ++j) {
+      const int t = tfirst + j;
+      const int off = p - t * hop;
+      if (t >= 0 && t < Tb && off >= 0 && off < N) {
+        const float w = win[off];
+        num += w * buf[j][off].x * (1.0f / N);
+        den += w * w;
+      }
+    }
+    out[(size_t)b * ld + nidx] = den > 1e-11f ? num / den : 0.f;
+  }
+}
+
+// ---------------------------------------------------------------- TSSE front (spec.hip, inference form, per-item frames)
+struct MapSet { const float* x[6]; };
+
+struct TsseW {
+  const float* cw[3];
+  const float* cb[3];
+  int ks[3];
+  const float* fcw;
+  const float* fcb;
+  const float* w1;
+  const float* b1;
+  const float* w2;
+  const float* b2;
+};
+
+constexpr int TSSE_MAXC = 1024;
+
+// sums[j][b][c] = sum_{t < T_b} x_j[b][c][t]  (map rows of stride T = the padded frame count)
+__global__ __launch_bounds__(256) void rowsum_ragged_kernel(MapSet ms, double* __restrict__ sums, const int* __restrict__ frames,
+                                                            int B, int C, int T) {
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= (long)B * C) return;
+  const int lane = threadIdx.x & 63;
+  const int Tb = clampi(frames[r / C], 1, T);
+  const float* p = ms.x[blockIdx.y] + (size_t)r * T;
+  double s = 0.0;
+  for (int t = lane; t < Tb; t += 64) s += (double)p[t];
+  s = wave_sum(s);
+  if (lane == 0) sums[(size_t)blockIdx.y * B * C + r] = s;
+}
+
+// tsse_fwd_kernel of spec.hip without the saved tensors, item b over its own T_b frames (+ la look-ahead zeros)
+__global__ __launch_bounds__(1024) void tsse_fwd_ragged_kernel(MapSet ms, const double* __restrict__ rowsum, TsseW w, long sW,
+                                                               int nm, float* __restrict__ scale, const int* __restrict__ frames,
+                                                               int C, int C2, int T, int la) {
+  __shared__ double red[16];
+  __shared__ float sq[TSSE_MAXC];
+  __shared__ float h1[TSSE_MAXC / 2];
+  __shared__ float ns_s;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  {
+    const int j = blockIdx.y, z = j % 3, m = j / 3, B = gridDim.x;
+    for (int i = 0; i < 3; ++i) { w.cw[i] += (long)z * sW; w.cb[i] += (long)z * sW; }
+    w.fcw += (long)z * sW; w.fcb += (long)z * sW;
+    w.w1 += (long)z * sW; w.b1 += (long)z * sW;
+    w.w2 += (long)z * sW; w.b2 += (long)z * sW;
+    rowsum += (size_t)j * B * C;
+    scale += ((size_t)z * nm + m) * B * C;
+  }
+  const float* __restrict__ x = ms.x[blockIdx.y];
+  const int Tn = clampi(frames[b], 1, T);
+  const int Tp = Tn + la;
+  double part = 0.0;
+  for (int c = tid; c < C; c += blockDim.x) part += rowsum[(size_t)b * C + c];
+  part = wave_sum(part);
+  if ((tid & 63) == 0) red[tid >> 6] = part;
+  __syncthreads();
+  if (tid == 0) {
+    double tot_all = 0.0;
+    for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) tot_all += red[wv];
+    const float mu = (float)(tot_all / ((double)C * Tp));
+    ns_s = 1.0f / (mu + 1e-5f);
+  }
+  __syncthreads();
+  const float ns = ns_s;
+  for (int c = tid; c < C; c += blockDim.x) {
+    const float* xr = x + ((size_t)b * C + c) * T;
+    const double tot = rowsum[(size_t)b * C + c];
+    float acc = w.fcb[0];
+    for (int i = 0; i < 3; ++i) {
+      const int ks = w.ks[i];
+      const int Lout = Tp - ks + 1;
+      double conv = 0.0;
+      for (int k = 0; k < ks; ++k) {
+        double pre = 0.0, suf = 0.0;
+        for (int t = 0; t < k; ++t) pre += (t < Tn) ? (double)xr[t] : 0.0;
+        for (int m = 0; m < ks - 1 - k; ++m) {
+          const int t = Tp - 1 - m;
+          suf += (t < Tn && t >= 0) ? (double)xr[t] : 0.0;
+        }
+        conv += (double)w.cw[i][c * ks + k] * (tot - pre - suf);
+      }
+      const float pv = w.cb[i][c] + ns * (float)(conv / Lout);
+      acc += w.fcw[i] * fmaxf(pv, 0.f);
+    }
+    sq[c] = acc;
+  }
+  __syncthreads();
+  for (int j = tid; j < C2; j += blockDim.x) {
+    float a = w.b1[j];
+    const float* wr = w.w1 + (size_t)j * C;
+    for (int c = 0; c < C; ++c) a += wr[c] * sq[c];
+    h1[j] = fmaxf(a, 0.f);
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += blockDim.x) {
+    float a = w.b2[c];
+    const float* wr = w.w2 + (size_t)c * C2;
+    for (int j = 0; j < C2; ++j) a += wr[j] * h1[j];
+    const float sg = 1.0f / (1.0f + expf(-a));
+    scale[(size_t)b * C + c] = ns * sg;
+  }
+}
+
+// y[z][b][t][m*C + c] = x_j[b][c][t] * scale[z][m][b][c] for t < T_b, 0 for T_b <= t < Tp: EVERY row of the buffer is
+// written (it is reused across calls of other lengths)
+template <typename TT>
+__global__ __launch_bounds__(256) void scale_transpose_ragged_kernel(MapSet ms, const float* __restrict__ scale,
+                                                                     TT* __restrict__ y, const int* __restrict__ frames, int B,
+                                                                     int nm, long sY, int C, int Tn, int Tp, int ld) {
+  __shared__ float tile[32][33];
+  const int j = blockIdx.z / B, b = blockIdx.z % B, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
+  const float* __restrict__ x = ms.x[j];
+  const int z = j % 3, m = j / 3;
+  scale += ((size_t)z * nm + m) * B * C;
+  y += (size_t)z * sY;
+  const int coff = m * C;
+  const int Tb = clampi(frames[b], 1, Tn);
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    float v = 0.f;
+    if (c < C && t < Tb) v = x[((size_t)b * C + c) * Tn + t] * scale[(size_t)b * C + c];
+    tile[i][tx] = v;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (t < Tp && c < C) y[((size_t)b * Tp + t) * ld + coff + c] = from_f32<TT>(tile[tx][i]);
+  }
+}
+
+// ---------------------------------------------------------------- TCN depthwise stage (tcn.hip: dwconv_kernel)
+// The depthwise conv is CENTRED (padding = dilation): frame t reads t + dil, so the frames of a longer item would leak
+// into a shorter one's last frames.  Per item: z = GN1(y1) on frames t < Tv_b = T_b + la, 0 outside; out rows
+// t >= Tv_b are 0.  No statistics here: nppc_tcn_gn_stats_ragged computes them from the stored output.
+constexpr int RDW_FRAMES = 32;
+
+template <typename TT>
+__global__ __launch_bounds__(256) void dwconv_ragged_kernel(const TT* __restrict__ in, TT* __restrict__ out,
+                                                            const double* __restrict__ st1, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, const float* __restrict__ wd,
+                                                            const float* __restrict__ bd, const float* __restrict__ slope2,
+                                                            const int* __restrict__ frames, int la, int Cc, int ld, int Tp,
+                                                            int Tv, int dil, float eps, long strideAct, long strideSt,
+                                                            long strideP) {
+  const int z = blockIdx.z, b = blockIdx.y;
+  in += (size_t)z * strideAct;
+  out += (size_t)z * strideAct;
+  st1 += (size_t)z * strideSt;
+  gamma += (size_t)z * strideP; beta += (size_t)z * strideP; bd += (size_t)z * strideP; wd += (size_t)z * strideP;
+  const float a2 = slope2[(size_t)z * strideP];
+  const int Tvb = clampi(frames[b] + la, 1, Tv);
+  const double cnt = (double)Cc * Tv;                  // the sums were rescaled to Tv frames (gn_stats_ragged_kernel)
+  const double m = st1[b * 2] / cnt;
+  const double var = st1[b * 2 + 1] / cnt - m * m;
+  const float mean = (float)m, rstd = (float)(1.0 / sqrt((var > 0 ? var : 0) + (double)eps));
+  const int cpr = Cc / 8;
+  const int rpi = 256 / cpr;
+  const int tl = threadIdx.x / cpr, c8 = (threadIdx.x % cpr) * 8;
+  if (tl >= rpi) return;
+  float g8[8], be8[8], b8[8], w8[3][8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    g8[i] = gamma[c8 + i] * rstd;
+    be8[i] = beta[c8 + i] - mean * g8[i];
+    b8[i] = bd[c8 + i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w8[k][i] = wd[(c8 + i) * 3 + k];
+  }
+  const int t1 = min((int)(blockIdx.x + 1) * RDW_FRAMES, Tp);
+  for (int t = blockIdx.x * RDW_FRAMES + tl; t < t1; t += rpi) {
+    float o[8];
+    if (t < Tvb) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = b8[i];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int ts = t + (k - 1) * dil;
+        if (ts >= 0 && ts < Tvb) {
+          float v[8];
+          load8<TT>(in + ((size_t)b * Tp + ts) * ld + c8, v);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) o[i] += w8[k][i] * (v[i] * g8[i] + be8[i]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = o[i] > 0.f ? o[i] : a2 * o[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = 0.f;
+    }
+    store8<TT>(out + ((size_t)b * Tp + t) * ld + c8, o);
+  }
+}
+
+// GroupNorm(1, C) statistics of item b from the STORED activation act[z][b][t][c] (the rounded values the uniform kernels
+// sum), over its own rows t < Tv_b, rescaled by Tv / Tv_b so the consumers' m = s1 / (C Tv) is the item's own mean.
+// One workgroup per (item, branch), fp64 accumulation in a fixed order; the entry replaces whatever the uniform launch added.
+template <typename TT>
+__global__ __launch_bounds__(1024) void gn_stats_ragged_kernel(const TT* __restrict__ act, double* __restrict__ st,
+                                                               const int* __restrict__ frames, int la, int Cc, int ld, int Tp,
+                                                               int Tv, long strideAct, long strideSt) {
+  __shared__ double red[2][16];
+  const int z = blockIdx.y, b = blockIdx.x, tid = threadIdx.x;
+  act += (size_t)z * strideAct + (size_t)b * Tp * ld;
+  st += (size_t)z * strideSt + (size_t)b * 2;
+  const int Tvb = clampi(frames[b] + la, 1, Tv);
+  const int cpr = Cc / 8;
+  double s1 = 0.0, s2 = 0.0;
+  for (long e = tid; e < (long)Tvb * cpr; e += 1024) {
+    const int t = (int)(e / cpr), c8 = (int)(e % cpr) * 8;
+    float v[8];
+    load8<TT>(act + (size_t)t * ld + c8, v);
+    float p1 = 0.f, p2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { p1 += v[i]; p2 += v[i] * v[i]; }
+    s1 += (double)p1;
+    s2 += (double)p2;
+  }
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0, q = 0.0;
+    for (int w = 0; w < 16; ++w) { a += red[0][w]; q += red[1][w]; }
+    const double r = (double)Tv / Tvb;
+    st[0] = a * r;
+    st[1] = q * r;
+  }
+}
+
+// ---------------------------------------------------------------- sub-band norm (subband.hip: subband_mean_kernel)
+// scale[b] = 1 / (mean over (F, nfeat, Tv_b) of the concatenated sub-band input + 1e-5), one workgroup per item
+template <typename TT>
+__global__ __launch_bounds__(1024) void subband_mean_ragged_kernel(const TT* __restrict__ src, int ldS, const TT* __restrict__ fb,
+                                                                   int ldF, long strideFb, const float* __restrict__ mult,
+                                                                   float* __restrict__ scale, const int* __restrict__ frames,
+                                                                   int la, int F, int Tp, int Tv, int nfeat) {
+  __shared__ double red[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Tvb = clampi(frames[b] + la, 1, Tv);
+  double s = 0.0;
+  for (long e = tid; e < (long)Tvb * F; e += 1024) {
+    const int t = (int)(e / F), f = (int)(e % F);
+    const size_t row = (size_t)b * Tp + t;
+    float v = mult[f] * to_f32<TT>(src[row * ldS + f]);
+    v += to_f32<TT>(fb[row * ldF + f]) + to_f32<TT>(fb[strideFb + row * ldF + f]) + to_f32<TT>(fb[2 * strideFb + row * ldF + f]);
+    s += (double)v;
+  }
+  s = wave_sum(s);
+  if ((tid & 63) == 0) red[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0;
+    for (int w = 0; w < 16; ++w) tot += red[w];
+    const float mu = (float)(tot / ((double)F * nfeat * Tvb));
+    scale[b] = 1.0f / (mu + 1e-5f);
+  }
+}
+
+// ---------------------------------------------------------------- output crop: x[b][r][t] = 0 for t >= T_b
+__global__ __launch_bounds__(256) void crop_frames_kernel(float* __restrict__ x, long rows, int T, const int* __restrict__ frames,
+                                                          int B) {
+  const size_t total = (size_t)B * rows * T;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const int t = (int)(e % T);
+    const int b = (int)(e / ((size_t)rows * T));
+    if (t >= frames[b]) x[e] = 0.f;
+  }
+}
+
+// ---------------------------------------------------------------- per-item cIRM MSE (frontend.hip: crm_mse, G = 1)
+__device__ __forceinline__ float compress_cirm_r(float m) {
+  m = m <= -100.f ? -100.f : m;
+  const float e = expf(-0.1f * m);
+  return 10.f * (1.f - e) / (1.f + e);
+}
+
+// loss[b] = mean over [2][F][T_b] of (gt - crm)^2, gt = compress(cIRM(noisy, clean)) with crm_mse's formula; one workgroup
+// per item, fixed-order fp64 reduction
+__global__ __launch_bounds__(1024) void crm_mse_ragged_kernel(const float* __restrict__ nr, const float* __restrict__ ni,
+                                                              const float* __restrict__ cr, const float* __restrict__ ci,
+                                                              const float* __restrict__ crm, const int* __restrict__ frames,
+                                                              int F, int T, float eps, double* __restrict__ loss) {
+  __shared__ double red[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Tb = clampi(frames[b], 1, T);
+  const size_t FT = (size_t)F * T;
+  double s = 0.0;
+  for (long e = tid; e < (long)F * Tb; e += 1024) {
+    const int f = (int)(e / Tb), t = (int)(e % Tb);
+    const size_t i = ((size_t)b * F + f) * T + t;
+    const float a = nr[i], bb = ni[i], c = cr[i], d = ci[i];
+    const float den = a * a + bb * bb + eps;
+    const float gr = compress_cirm_r((a * c + bb * d) / den);
+    const float gi = compress_cirm_r((a * d - bb * c) / den);
+    const size_t o = (size_t)b * 2 * FT + (size_t)f * T + t;
+    const double dr = (double)gr - (double)crm[o], di = (double)gi - (double)crm[o + FT];
+    s += dr * dr + di * di;
+  }
+  s = wave_sum(s);
+  if ((tid & 63) == 0) red[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0;
+    for (int w = 0; w < 16; ++w) tot += red[w];
+    loss[b] = tot / (2.0 * F * Tb);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int nppc_stft_ragged(const float* wave, long ld, const int* lengths, float* re, float* im, float* mag, int B, int T, int nfft,
+                     int hop, void* stream) {
+  if (!wave || !lengths || !re || !im || B <= 0 || T <= 0 || hop <= 0 || ld <= nfft / 2) return NPPC_EBADARG;
+  dim3 grid(ceil_div(T, RSTFT_FR), B);
+  hipStream_t s = (hipStream_t)stream;
+  switch (nfft) {
+    case 64: hipLaunchKernelGGL(stft_ragged_kernel<6>, grid, dim3(256), 0, s, wave, ld, lengths, re, im, mag, hop, T); break;
+    case 128: hipLaunchKernelGGL(stft_ragged_kernel<7>, grid, dim3(256), 0, s, wave, ld, lengths, re, im, mag, hop, T); break;
+    case 256: hipLaunchKernelGGL(stft_ragged_kernel<8>, grid, dim3(256), 0, s, wave, ld, lengths, re, im, mag, hop, T); break;
+    case 512: hipLaunchKernelGGL(stft_ragged_kernel<9>, grid, dim3(256), 0, s, wave, ld, lengths, re, im, mag, hop, T); break;
+    default: return NPPC_EUNSUPPORTED;
+  }
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_istft_ragged(const float* re, const float* im, float* out, long ld, const int* lengths, int B, int T, int nfft, int hop,
+                      void* stream) {
+  if (!re || !im || !out || !lengths || B <= 0 || T <= 0 || hop <= 0 || ld <= 0 || nfft % hop || nfft / hop > 8)
+    return NPPC_EBADARG;
+  const long total = ld + nfft / 2;
+  dim3 grid(ceil_div(total, (long)RISTFT_FR * hop), B);
+  hipStream_t s = (hipStream_t)stream;
+  switch (nfft) {
+    case 64: hipLaunchKernelGGL(istft_ragged_kernel<6>, grid, dim3(256), 0, s, re, im, out, ld, lengths, T, hop); break;
+    case 128: hipLaunchKernelGGL(istft_ragged_kernel<7>, grid, dim3(256), 0, s, re, im, out, ld, lengths, T, hop); break;
+    case 256: hipLaunchKernelGGL(istft_ragged_kernel<8>, grid, dim3(256), 0, s, re, im, out, ld, lengths, T, hop); break;
+    case 512: hipLaunchKernelGGL(istft_ragged_kernel<9>, grid, dim3(256), 0, s, re, im, out, ld, lengths, T, hop); break;
+    default: return NPPC_EUNSUPPORTED;
+  }
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_tsse_fwd_maps_ragged(int prec, const float* const* maps, int nmaps, double* rowsum, const float* cw0, const float* cb0,
+                              const float* cw1, const float* cb1, const float* cw2, const float* cb2, int ks0, int ks1, int ks2,
+                              const float* fcw, const float* fcb, const float* w1, const float* b1, const float* w2,
+                              const float* b2, long sW, float* scale, void* X0, long sY, const int* frames, int B, int C, int T,
+                              int look_ahead, int Tp, int ld, void* stream) {
+  if (!maps || !rowsum || !scale || !X0 || !frames || B <= 0 || C <= 0 || C > TSSE_MAXC || (nmaps != 3 && nmaps != 6))
+    return NPPC_EBADARG;
+  if (!cw0 || !cb0 || !cw1 || !cb1 || !cw2 || !cb2 || !fcw || !fcb || !w1 || !b1 || !w2 || !b2) return NPPC_EBADARG;
+  if (ks0 > T || ks1 > T || ks2 > T) return NPPC_EUNSUPPORTED;
+  const int nm = nmaps / 3;
+  if (nm * C > ld || T > Tp) return NPPC_EBADARG;
+  hipStream_t s = (hipStream_t)stream;
+  MapSet ms{};
+  for (int j = 0; j < nmaps; ++j) { if (!maps[j]) return NPPC_EBADARG; ms.x[j] = maps[j]; }
+  hipLaunchKernelGGL(rowsum_ragged_kernel, dim3(ceil_div((long)B * C, 4), nmaps), dim3(256), 0, s, ms, rowsum, frames, B, C, T);
+  TsseW w{{cw0, cw1, cw2}, {cb0, cb1, cb2}, {ks0, ks1, ks2}, fcw, fcb, w1, b1, w2, b2};
+  const int nt = round_up(C, 64) > 1024 ? 1024 : round_up(C, 64);
+  hipLaunchKernelGGL(tsse_fwd_ragged_kernel, dim3(B, nmaps), dim3(nt), 0, s, ms, rowsum, w, sW, nm, scale, frames, C, C / 2, T,
+                     look_ahead);
+  dim3 grid(ceil_div(Tp, 32), ceil_div(C, 32), B * nmaps);
+  if (prec == NPPC_PREC_BF16)
+    hipLaunchKernelGGL(scale_transpose_ragged_kernel<bf16_t>, grid, dim3(256), 0, s, ms, scale, (bf16_t*)X0, frames, B, nm, sY, C,
+                       T, Tp, ld);
+  else if (prec == NPPC_PREC_F32)
+    hipLaunchKernelGGL(scale_transpose_ragged_kernel<float>, grid, dim3(256), 0, s, ms, scale, (float*)X0, frames, B, nm, sY, C, T,
+                       Tp, ld);
+  else
+    return NPPC_EBADARG;
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_tcn_dwconv_ragged(int prec, const void* in, void* out, const double* st1, const float* gamma, const float* beta,
+                           const float* wd, const float* bd, const float* slope2, const int* frames, int la, int B, int Cc, int ld,
+                           int Tp, int Tv, int dil, float eps, long sAct, long sSt, long sP, int batch, void* stream) {
+  if (!in || !out || !st1 || !frames || B <= 0 || batch <= 0 || Cc % 8 || Cc / 8 > 256 || ld % 8 || Tv > Tp) return NPPC_EBADARG;
+  dim3 grid(ceil_div(Tp, RDW_FRAMES), B, batch);
+  hipStream_t s = (hipStream_t)stream;
+  if (prec == NPPC_PREC_BF16)
+    hipLaunchKernelGGL(dwconv_ragged_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, st1, gamma, beta, wd,
+                       bd, slope2, frames, la, Cc, ld, Tp, Tv, dil, eps, sAct, sSt, sP);
+  else if (prec == NPPC_PREC_F32)
+    hipLaunchKernelGGL(dwconv_ragged_kernel<float>, grid, dim3(256), 0, s, (const float*)in, (float*)out, st1, gamma, beta, wd,
+                       bd, slope2, frames, la, Cc, ld, Tp, Tv, dil, eps, sAct, sSt, sP);
+  else
+    return NPPC_EBADARG;
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_tcn_gn_stats_ragged(int prec, const void* act, double* stats, const int* frames, int la, int B, int Cc, int ld, int Tp,
+                             int Tv, long sAct, long sSt, int batch, void* stream) {
+  if (!act || !stats || !frames || B <= 0 || batch <= 0 || Cc % 8 || ld % 8 || Cc > ld || Tv > Tp) return NPPC_EBADARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (prec == NPPC_PREC_BF16)
+    hipLaunchKernelGGL(gn_stats_ragged_kernel<bf16_t>, dim3(B, batch), dim3(1024), 0, s, (const bf16_t*)act, stats, frames, la, Cc,
+                       ld, Tp, Tv, sAct, sSt);
+  else if (prec == NPPC_PREC_F32)
+    hipLaunchKernelGGL(gn_stats_ragged_kernel<float>, dim3(B, batch), dim3(1024), 0, s, (const float*)act, stats, frames, la, Cc,
+                       ld, Tp, Tv, sAct, sSt);
+  else
+    return NPPC_EBADARG;
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_subband_mean_ragged(int prec, const void* src, int ldS, const void* fb, int ldF, long strideFb, const float* mult,
+                             float* scale, const int* frames, int la, int B, int F, int Tp, int Tv, int nfeat, void* stream) {
+  if (!src || !fb || !mult || !scale || !frames || B <= 0 || F <= 0 || Tv > Tp || F > ldS || F > ldF) return NPPC_EBADARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (prec == NPPC_PREC_BF16)
+    hipLaunchKernelGGL(subband_mean_ragged_kernel<bf16_t>, dim3(B), dim3(1024), 0, s, (const bf16_t*)src, ldS, (const bf16_t*)fb,
+                       ldF, strideFb, mult, scale, frames, la, F, Tp, Tv, nfeat);
+  else if (prec == NPPC_PREC_F32)
+    hipLaunchKernelGGL(subband_mean_ragged_kernel<float>, dim3(B), dim3(1024), 0, s, (const float*)src, ldS, (const float*)fb, ldF,
+                       strideFb, mult, scale, frames, la, F, Tp, Tv, nfeat);
+  else
+    return NPPC_EBADARG;
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_crop_frames_ragged(float* x, long rows, int T, const int* frames, int B, void* stream) {
+  if (!x || !frames || rows <= 0 || T <= 0 || B <= 0) return NPPC_EBADARG;
+  const size_t total = (size_t)B * rows * T;
+  const int grid = (int)(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096);
+  hipLaunchKernelGGL(crop_frames_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, rows, T, frames, B);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_crm_mse_ragged(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, const int* frames,
+                        int B, int F, int T, float eps, double* loss, void* stream) {
+  if (!nr || !ni || !cr || !ci || !crm || !frames || !loss || B <= 0 || F <= 0 || T <= 0) return NPPC_EBADARG;
+  hipLaunchKernelGGL(crm_mse_ragged_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, nr, ni, cr, ci, crm, frames, F, T, eps,
+                     loss);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+}  // extern "C"

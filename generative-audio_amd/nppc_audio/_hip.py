@@ -231,6 +231,14 @@ SIGS = {
     "nppc_stoi_frames": [P, P, I, L, I, P, P, P, P, P],
     "nppc_stoi_bands": [P, P, L, P, P, I, I, P, P, P],
     "nppc_stoi_corr": [P, P, P, I, I, P, P],
+    "nppc_stft_ragged": [P, L, P, P, P, P, I, I, I, I, P],
+    "nppc_istft_ragged": [P, P, P, L, P, I, I, I, I, P],
+    "nppc_tsse_fwd_maps_ragged": [I, P, I, P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, L, P, P, L, P, I, I, I, I, I, I, P],
+    "nppc_tcn_dwconv_ragged": [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, L, L, L, I, P],
+    "nppc_tcn_gn_stats_ragged": [I, P, P, P, I, I, I, I, I, I, L, L, I, P],
+    "nppc_subband_mean_ragged": [I, P, I, P, I, L, P, P, P, I, I, I, I, I, I, P],
+    "nppc_crop_frames_ragged": [P, L, I, P, I, P],
+    "nppc_crm_mse_ragged": [P, P, P, P, P, P, I, I, I, F, P, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

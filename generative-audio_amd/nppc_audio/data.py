@@ -9,7 +9,7 @@ reference; `DeviceMixLoader` (what NPPCAudioTrainer uses on a HIP device) draws 
 un-mixed crops and mixes a whole minibatch with ONE nppc_mix_snr launch.
 """
 from pathlib import Path
-from typing import Tuple, Union
+from typing import NamedTuple, Tuple, Union
 
 import numpy as np
 import pydantic
@@ -231,3 +231,32 @@ def mix_with_snr_on_device(clean, noise, snr_db, target_dB_FS=-25.0, target_item
         assert target_item.shape == (B,)
     H.call("nppc_mix_snr", clean, noise, snr_db, float(target_dB_FS), target_item, noisy_out, clean_out, B, L, H.stream())
     return noisy_out, clean_out
+
+
+class RaggedBatch(NamedTuple):
+    """a batch of clips of different lengths: noisy, clean [B, Lmax] zero-padded, lengths [B] int64 (host).  Consumers
+    (ModelValidator.validate_dataloader, FullSubNetPlusTrainer.validate_metrics) recognise it by TYPE: a plain tuple
+    keeps its existing meaning, so a reference item (noisy, clean, name, ...) is never read as lengths."""
+    noisy: torch.Tensor
+    clean: torch.Tensor
+    lengths: torch.Tensor
+
+
+def pad_collate(items):
+    """DataLoader collate_fn: (noisy[L_i], clean[L_i], ...) items -> RaggedBatch zero-padded to the longest item (entries
+    after the first two are dropped)"""
+    if not items:
+        raise ValueError("pad_collate needs at least one item")
+    noisy = [torch.as_tensor(it[0]).reshape(-1).float() for it in items]
+    clean = [torch.as_tensor(it[1]).reshape(-1).float() for it in items]
+    for i, (n, c) in enumerate(zip(noisy, clean)):
+        if n.numel() != c.numel():
+            raise ValueError(f"item {i}: noisy has {n.numel()} samples, clean {c.numel()}")
+    lengths = torch.tensor([n.numel() for n in noisy], dtype=torch.int64)
+    Lmax = int(lengths.max())
+    N = torch.zeros(len(items), Lmax, dtype=torch.float32)
+    C = torch.zeros(len(items), Lmax, dtype=torch.float32)
+    for i, (n, c) in enumerate(zip(noisy, clean)):
+        N[i, :n.numel()] = n
+        C[i, :c.numel()] = c
+    return RaggedBatch(N, C, lengths)

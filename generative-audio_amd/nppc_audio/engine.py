@@ -249,8 +249,8 @@ class FSNEngine:
         self.packed_version = ver
 
     # ------------------------------------------------------------------ buffers
-    def _buffers(self, B, T, train):
-        key = (B, T, train)
+    def _buffers(self, B, T, train, ragged=False):
+        key = (B, T, train, ragged)
         if key in self.bufs:
             return self.bufs[key]
         dev, dt = self.dev, self.dt
@@ -270,7 +270,7 @@ class FSNEngine:
             d["rawmag"] = torch.zeros(B, Tp, self.ldF, dtype=dt, device=dev)
         d["sbscale"] = torch.empty(B, dtype=torch.float32, device=dev)
         d["sbwork"] = torch.zeros(2 * B, dtype=torch.float64, device=dev)     # nppc_subband_mean: sums + arrival counters
-        G = self.G if B > 1 else 1
+        G = self.G if (B > 1 and not ragged) else 1       # a ragged batch is B clips run alone: no drop-band
         Fo = self.F if G <= 1 else (self.F - self.F % G) // G
         d["G"], d["Fo"], d["Nseq"] = G, Fo, B * Fo
         d["x_rows"] = torch.zeros(padded_rows(Tv * B * Fo, B * Fo), self.KX, dtype=dt, device=dev)   # GEMM operand
@@ -283,20 +283,33 @@ class FSNEngine:
         return d
 
     # ------------------------------------------------------------------ forward
-    def forward(self, maps, train=False, mtile=None):
+    def forward(self, maps, train=False, mtile=None, frames=None):
         """maps: 3*n_maps tensors [B,1,F,T] fp32 ordered (mag, real, imag)[, (enh mag, real, imag)].
-        Returns the net output [B', O, F', T] fp32 (B' in drop-band order) and keeps what backward needs."""
+        Returns the net output [B', O, F', T] fp32 (B' in drop-band order) and keeps what backward needs.
+
+        frames: None, or a device int32 [B] of per-item frame counts T_b <= T (ragged inference, n_maps = 1): item b's
+        output is the output of its first T_b frames run alone (no drop-band), frames t >= T_b of it are 0.  T comes from
+        the padded input's shape: nothing is read back from the device."""
         H.require_gpu()
         assert len(maps) == 3 * self.nm
         for m in maps:
             assert m.dim() == 4, "inputs are [B, 1, F, T]"      # fullsubnet_plus.py:157
             assert m.shape[1] == 1 and m.shape[2] == self.F
         B, _, F, T = maps[0].shape
-        if B > 1:
+        ragged = frames is not None
+        if ragged:
+            if train:
+                raise RuntimeError("ragged batches (frames=) are inference only: no train-mode forward")
+            if self.nm != 1:
+                raise NotImplementedError("ragged batches are built for the restorer (n_maps = 1)")
+            if not (frames.is_cuda and frames.dtype == torch.int32 and frames.shape == (B,)):
+                raise ValueError(f"frames must be a device int32 tensor of shape ({B},)")
+            frames = frames.contiguous()
+        elif B > 1:
             assert B > self.G, f"Batch size = {B}, num_groups = {self.G}."   # feature.py:263
         self.join_side()                      # own side-stream work (re-pack of the updated weights) before anything reads it
         self.pack_weights()
-        d = self._buffers(B, T, train)
+        d = self._buffers(B, T, train, ragged)
         s = H.stream()
         Tv, Tp, prec = d["Tv"], d["Tp"], self.prec
         C, ldC, ldF, sP = self.C, self.ldC, self.ldF, self.sP
@@ -307,13 +320,18 @@ class FSNEngine:
         # 1-3: laplace norm + TSSE attention scale, transposed into the TCN input: all 3 * n_maps maps in three launches
         att = "channel_attention."
         sv_ = [sv[k] if sv else None for k in ("ns", "pre", "sq", "h1", "sg")]
-        H.call("nppc_tsse_fwd_maps", prec, H.ptr_array(maps), 3 * self.nm, d["rs"],
-               self.p(att + "smallConv1d.0.weight"), self.p(att + "smallConv1d.0.bias"),
-               self.p(att + "middleConv1d.0.weight"), self.p(att + "middleConv1d.0.bias"),
-               self.p(att + "largeConv1d.0.weight"), self.p(att + "largeConv1d.0.bias"), self.ks[0], self.ks[1], self.ks[2],
-               self.p(att + "feature_concate_fc.weight"), self.p(att + "feature_concate_fc.bias"),
-               self.p(att + "fc1.weight"), self.p(att + "fc1.bias"), self.p(att + "fc2.weight"), self.p(att + "fc2.bias"),
-               self.sAtt, d["scale"], *sv_, d["X"][0], R * ldC, B, F, T, self.la, Tp, ldC, s)
+        tsse_w = (self.p(att + "smallConv1d.0.weight"), self.p(att + "smallConv1d.0.bias"),
+                  self.p(att + "middleConv1d.0.weight"), self.p(att + "middleConv1d.0.bias"),
+                  self.p(att + "largeConv1d.0.weight"), self.p(att + "largeConv1d.0.bias"), self.ks[0], self.ks[1], self.ks[2],
+                  self.p(att + "feature_concate_fc.weight"), self.p(att + "feature_concate_fc.bias"),
+                  self.p(att + "fc1.weight"), self.p(att + "fc1.bias"), self.p(att + "fc2.weight"), self.p(att + "fc2.bias"),
+                  self.sAtt)
+        if ragged:
+            H.call("nppc_tsse_fwd_maps_ragged", prec, H.ptr_array(maps), 3 * self.nm, d["rs"], *tsse_w, d["scale"], d["X"][0],
+                   R * ldC, frames, B, F, T, self.la, Tp, ldC, s)
+        else:
+            H.call("nppc_tsse_fwd_maps", prec, H.ptr_array(maps), 3 * self.nm, d["rs"], *tsse_w, d["scale"], *sv_, d["X"][0],
+                   R * ldC, B, F, T, self.la, Tp, ldC, s)
         if self.nm == 2:
             H.call("nppc_scale_transpose", prec, maps[0], None, d["rawmag"], B, F, T, Tp, ldF, 0, s)
         # 4: eight TCN blocks, the three branches batched over blockIdx.z
@@ -329,9 +347,20 @@ class FSNEngine:
             H.call("nppc_gemm_nt", prec, EPI_PRELU_STATS, Xin, ldC, R * ldC, self.W1p[i], ldC, TCN_HIDDEN * ldC,
                    y1, TCN_HIDDEN, sAct, self.p(pre + "conv1x1.bias"), sP, None, 0, 0, self.p(pre + "prelu1.weight"), sP,
                    st1, B * 2, R, TCN_HIDDEN, self.KC, Tp, Tv, TCN_HIDDEN, 0, 3, 1, s)
-            H.call("nppc_tcn_dwconv", prec, y1, y2, st1, st2, self.p(pre + "norm1.weight"), self.p(pre + "norm1.bias"),
-                   self.p(pre + "depthwise_conv.weight"), self.p(pre + "depthwise_conv.bias"),
-                   self.p(pre + "prelu2.weight"), B, TCN_HIDDEN, TCN_HIDDEN, Tp, Tv, dil, 1e-8, sAct, B * 2, sP, 3, s)
+            dw = (self.p(pre + "norm1.weight"), self.p(pre + "norm1.bias"), self.p(pre + "depthwise_conv.weight"),
+                  self.p(pre + "depthwise_conv.bias"), self.p(pre + "prelu2.weight"))
+            if ragged:
+                # GroupNorm sums of each item's own rows (replacing the uniform launch's), and the centred depthwise conv
+                # stopped at each item's end: the only two places where frames past an item could reach into it
+                H.call("nppc_tcn_gn_stats_ragged", prec, y1, st1, frames, self.la, B, TCN_HIDDEN, TCN_HIDDEN, Tp, Tv, sAct,
+                       B * 2, 3, s)
+                H.call("nppc_tcn_dwconv_ragged", prec, y1, y2, st1, *dw, frames, self.la, B, TCN_HIDDEN, TCN_HIDDEN, Tp, Tv,
+                       dil, 1e-8, sAct, B * 2, sP, 3, s)
+                H.call("nppc_tcn_gn_stats_ragged", prec, y2, st2, frames, self.la, B, TCN_HIDDEN, TCN_HIDDEN, Tp, Tv, sAct,
+                       B * 2, 3, s)
+            else:
+                H.call("nppc_tcn_dwconv", prec, y1, y2, st1, st2, *dw, B, TCN_HIDDEN, TCN_HIDDEN, Tp, Tv, dil, 1e-8, sAct,
+                       B * 2, sP, 3, s)
             H.call("nppc_gemm_nt_gn", prec, y2, TCN_HIDDEN, sAct, self.W2p[i], TCN_HIDDEN, ldC * TCN_HIDDEN, Xout, ldC, R * ldC,
                    self.u2[i], self.v2[i], ldC, Xin, ldC, R * ldC, st2, B * 2, float(TCN_HIDDEN * Tv), 1e-8, R, ldC,
                    TCN_HIDDEN, Tp, Tv, C, 3, s)
@@ -345,8 +374,12 @@ class FSNEngine:
             src, ldS = d["X"][0, 0], ldC          # attention-scaled, normalised magnitude (fullsubnet_plus.py:203)
         else:
             src, ldS = d["rawmag"], ldF           # RAW padded magnitude (networks.py:133)
-        H.call("nppc_subband_mean", prec, src, ldS, d["fb"], ldF, R * ldF, self.mult, d["sbscale"], d["sbwork"], B, F, Tp,
-               Tv, self.I, s)
+        if ragged:
+            H.call("nppc_subband_mean_ragged", prec, src, ldS, d["fb"], ldF, R * ldF, self.mult, d["sbscale"], frames, self.la,
+                   B, F, Tp, Tv, self.I, s)
+        else:
+            H.call("nppc_subband_mean", prec, src, ldS, d["fb"], ldF, R * ldF, self.mult, d["sbscale"], d["sbwork"], B, F, Tp,
+                   Tv, self.I, s)
         # mtile None: cooperative kernel when the shape allows; it also takes the output head to fuse (bf16 pair kernel)
         head = (self.Whp, self.O) if (FUSED_HEAD > int(train) and prec == H.PREC_BF16 and self.Opad == 16) else None
         # the frozen net's fused-head inference launch reads rows of 40 columns (the same buffer, viewed narrower): the
@@ -356,7 +389,7 @@ class FSNEngine:
         if xld != self.KX:
             x_tm = d["x_rows"].view(-1)[:Tv * d["Nseq"] * xld].view(Tv, d["Nseq"], xld)
         H.call("nppc_subband_stage", prec, src, ldS, d["fb"], ldF, R * ldF, d["sbscale"], x_tm, B, F, Tp, Tv,
-               self.nb, self.G, xld, int(train), s)
+               self.nb, d["G"] if ragged else self.G, xld, int(train), s)
         # 7: two-layer LSTM over T' steps for the B*F' sequences
         if self.pre_lstm_hook is not None:
             # everything another stream still has in flight must be joined BEFORE a cooperative (CU-pair) kernel goes out:
@@ -375,6 +408,8 @@ class FSNEngine:
         else:
             H.call("nppc_sb_head", prec, lo["h2"], self.Whp, self.p("sb_model.fc_output_layer.bias"), out, d["Nseq"], Tv,
                    self.la, self.Hd, self.O, d["Fo"], s)
+        if ragged:                            # the output crop: frames t >= T_b of item b are 0
+            H.call("nppc_crop_frames_ragged", out, self.O * d["Fo"], T, frames, B, s)
         self.last = d
         if train:
             self._gen += 1

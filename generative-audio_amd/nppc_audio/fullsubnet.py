@@ -105,6 +105,19 @@ def _check_supported(cfg):
         raise ValueError("precision must be 'bf16' or 'fp32'")
 
 
+def check_frames(frames, B, T, kersize):
+    """host check of a ragged batch's frame counts against the padded frame count T: every item needs what the single-clip
+    forward needs (T_b >= the largest TSSE kernel)"""
+    if len(frames) != B:
+        raise ValueError(f"frames has {len(frames)} entries for a batch of {B}")
+    kmax = max(kersize)
+    for b, t in enumerate(frames):
+        if t > T:
+            raise ValueError(f"item {b}: {t} frames, more than the padded input's {T}")
+        if t < kmax:
+            raise ValueError(f"item {b}: {t} frames, fewer than the largest TSSE kernel ({kmax})")
+
+
 class FullSubNet_Plus(nn.Module):
     n_maps = 1
 
@@ -161,15 +174,29 @@ class FullSubNet_Plus(nn.Module):
                 return False
         return True
 
-    def forward(self, noisy_mag, noisy_real, noisy_imag):
+    def forward(self, noisy_mag, noisy_real, noisy_imag, frames=None):
         """[B,1,F,T] x3 -> compressed cIRM [B,2,F',T] (fullsubnet_plus.py:143-230).
         Under no_grad or with frozen parameters this is the inference launch sequence the NPPC path runs
         (nppc_model.py:94-95).  With gradients enabled and trainable parameters it is the train-mode forward, recorded
-        as ONE autograd function whose inputs are the parameters and whose backward is the engine's."""
+        as ONE autograd function whose inputs are the parameters and whose backward is the engine's.
+
+        frames (extension, inference only): per-item frame counts [B] of a padded batch (ops.stft_frames).  Item b's
+        output is that of its first T_b frames run alone, at all F bins (no drop-band), and 0 at frames t >= T_b.  A host
+        tensor or list is checked against T here; a device int32 tensor is used as is, without reading it back."""
         assert noisy_mag.dim() == 4
         assert noisy_mag.shape[1] == 1, f"{self.__class__.__name__} takes the mag feature as inputs."
         maps = [m.detach() for m in (noisy_mag, noisy_real, noisy_imag)]
         params = [p for _, p in self.named_parameters()]
+        if frames is not None:
+            if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+                raise RuntimeError("the ragged forward (frames=) is inference only: call it under torch.no_grad() or with "
+                                   "frozen parameters")
+            B, T = noisy_mag.shape[0], noisy_mag.shape[-1]
+            if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+                frames = torch.as_tensor(frames, dtype=torch.int64).reshape(-1)
+                check_frames(frames.tolist(), B, T, self.kersize)
+                frames = frames.to(torch.int32)
+            return self.engine().forward(maps, train=False, frames=frames.to(noisy_mag.device, torch.int32))
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             H.require_gpu()
             from .networks import _DirectionNetFn     # the same autograd bridge as the direction net (n_maps = 1 here)

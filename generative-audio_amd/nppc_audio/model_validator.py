@@ -16,6 +16,7 @@ import torch
 from . import _hip as H
 from . import metrics
 from . import ops
+from .data import RaggedBatch
 from .fullsubnet import FullSubNetPlusConfig
 from .nppc_model import StftConfig, load_pretrained_model
 
@@ -47,15 +48,25 @@ class ModelValidator:
         self.model.to(self.device)
         self.model.eval()
 
-    def enhance_audio(self, noisy: torch.Tensor, clean: torch.Tensor = None) -> torch.Tensor:
+    def enhance_audio(self, noisy: torch.Tensor, clean: torch.Tensor = None, lengths=None) -> torch.Tensor:
         """noisy [B, L] or [L] -> enhanced waveforms [B, L] on the device (model_validator.py:79-130, batched): the
         compressed cIRM of the inference forward, decompressed and applied to the noisy STFT (true complex product),
-        inverse STFT with length L.  `clean` is accepted for the reference's signature; the enhancement does not use it."""
+        inverse STFT with length L.  `clean` is accepted for the reference's signature; the enhancement does not use it.
+
+        lengths [B] (clips of different lengths padded to L, data.pad_collate): item b is enhanced as the clip
+        noisy[b, :lengths[b]] alone would be; its samples past lengths[b] are 0 and its padding is never read."""
         H.require_gpu()
         st = self.config.audio_config.stft_configuration
         noisy = noisy.to(self.device)
         if noisy.dim() == 1:
             noisy = noisy[None]
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).reshape(-1).cpu()
+            with torch.no_grad():
+                mag, re, im = ops.stft(noisy, st.nfft, st.hop_length, lengths=lengths)
+                crm = self.model(mag[:, None], re[:, None], im[:, None], frames=ops.stft_frames(lengths, st.hop_length))
+                return ops.model_outputs_to_waveforms(crm, re[:, None], im[:, None], noisy.shape[-1], st.nfft, st.hop_length,
+                                                      lengths=lengths)
         with torch.no_grad():
             mag, re, im = ops.stft(noisy, st.nfft, st.hop_length)
             crm = self.model(mag[:, None], re[:, None], im[:, None])
@@ -81,14 +92,17 @@ class ModelValidator:
 
     def validate_dataloader(self, dataloader) -> Dict[str, float]:
         """mean over all items of every metric (model_validator.py:132-170); one batched launch sequence per batch and one
-        device-to-host copy at the end"""
+        device-to-host copy at the end.  A `data.RaggedBatch` batch is enhanced and scored per item over its own length."""
         stoi_all, sdr_all = [], []
         for batch in dataloader:
+            lengths = batch.lengths if isinstance(batch, RaggedBatch) else None    # by type: a plain tuple has no lengths
             noisy, clean = batch[0].to(self.device), batch[1].to(self.device)
             if noisy.dim() == 1:
                 noisy, clean = noisy[None], clean[None]
-            enhanced = self.enhance_audio(noisy)
-            m = self.calculate_metrics_batch(clean, enhanced, sr=self.config.audio_config.sr)
+            enhanced = self.enhance_audio(noisy, lengths=lengths)
+            if lengths is not None:
+                lengths = torch.as_tensor(lengths).to(self.device, torch.int32)
+            m = self.calculate_metrics_batch(clean, enhanced, sr=self.config.audio_config.sr, lengths=lengths)
             stoi_all.append(m["STOI"])
             sdr_all.append(m["SI_SDR"])
         if not stoi_all:

@@ -17,9 +17,35 @@ def _f32c(x):
     return x.contiguous().float()
 
 
-def stft(wave, nfft, hop, want_mag=True):
+def stft_frames(lengths, hop):
+    """frame count of the centred STFT of `lengths` samples: 1 + L // hop (int, list or tensor, elementwise)"""
+    if isinstance(lengths, torch.Tensor):
+        return 1 + torch.div(lengths, hop, rounding_mode="floor")
+    if isinstance(lengths, (list, tuple)):
+        return [1 + int(n) // hop for n in lengths]
+    return 1 + int(lengths) // hop
+
+
+def ragged_lengths(lengths, B, Lmax, min_len, device):
+    """(device int32 [B], host list) of a ragged batch's per-item lengths, checked on the host: 0 < min_len < L_b <= Lmax.
+    A device tensor is read back once for the check."""
+    host = torch.as_tensor(lengths).reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else [int(n) for n in lengths]
+    if len(host) != B:
+        raise ValueError(f"lengths has {len(host)} entries for a batch of {B}")
+    for b, n in enumerate(host):
+        if n != int(n) or n > Lmax:
+            raise ValueError(f"item {b}: length {n} exceeds the padded length {Lmax}")
+        if n <= min_len:
+            raise ValueError(f"item {b}: length {n} is too short (needs more than {min_len} samples)")
+    return torch.tensor(host, dtype=torch.int32).to(device), [int(n) for n in host]
+
+
+def stft(wave, nfft, hop, want_mag=True, lengths=None):
     """utils.py:107-147 / trainer.py:349-355: centred, periodic-hann, onesided STFT.
-    wave [B,L] -> (mag|None, real, imag) each [B,F,T]."""
+    wave [B,L] -> (mag|None, real, imag) each [B,F,T].
+
+    lengths [B] (ragged batch, wave zero- or otherwise padded to L): item b is the STFT of its first L_b samples alone
+    (reflect padding at its own end) in frames t < 1 + L_b // hop; later frames are 0 and samples past L_b are not read."""
     wave = _f32c(wave)
     if wave.dim() == 1:
         wave = wave[None]
@@ -28,6 +54,10 @@ def stft(wave, nfft, hop, want_mag=True):
     re = torch.empty(B, F, T, dtype=torch.float32, device=wave.device)
     im = torch.empty_like(re)
     mag = torch.empty_like(re) if want_mag else None
+    if lengths is not None:
+        dl, _ = ragged_lengths(lengths, B, L, nfft // 2, wave.device)
+        H.call("nppc_stft_ragged", wave, L, dl, re, im, mag, B, T, nfft, hop, H.stream())
+        return mag, re, im
     H.call("nppc_stft", wave, re, im, mag, B, L, nfft, hop, H.stream())
     return mag, re, im
 
@@ -79,21 +109,44 @@ def cirm_decompress_apply(crm, n_re, n_im):
     return emag, ere, eim
 
 
-def istft(re, im, nfft, hop, length):
+def istft(re, im, nfft, hop, length, lengths=None):
     """torch.istft(n_fft, hop, win_length=n_fft, hann window, center=True, length=length): [B,F,T] x2 -> [B,length]
-    (utils.py:60-70, nppc_audio/validator.py:136-143)."""
+    (utils.py:60-70, nppc_audio/validator.py:136-143).
+
+    lengths [B] (ragged batch, L_b <= length, 1 + L_b // hop <= T): item b is torch.istft(length=L_b) of its first
+    1 + L_b // hop frames alone; samples L_b .. length-1 are 0."""
     re, im = _f32c(re), _f32c(im)
     B, F, T = re.shape
     assert F == nfft // 2 + 1
     out = torch.empty(B, length, dtype=torch.float32, device=re.device)
+    if lengths is not None:
+        dl, host = ragged_lengths(lengths, B, length, 0, re.device)
+        for b, n in enumerate(host):
+            if stft_frames(n, hop) > T:
+                raise ValueError(f"item {b}: length {n} needs {stft_frames(n, hop)} frames, the input has {T}")
+        H.call("nppc_istft_ragged", re, im, out, length, dl, B, T, nfft, hop, H.stream())
+        return out
     H.call("nppc_istft", re, im, out, B, T, nfft, hop, length, H.stream())
     return out
 
 
-def model_outputs_to_waveforms(enhanced_masks, noisy_reals, noisy_imags, orig_length, nfft=512, hop=256):
-    """utils.py:37-72: compressed cIRM [B,2,F,T] + noisy STFT [B,1,F,T] -> enhanced waveforms [B, orig_length]."""
+def model_outputs_to_waveforms(enhanced_masks, noisy_reals, noisy_imags, orig_length, nfft=512, hop=256, lengths=None):
+    """utils.py:37-72: compressed cIRM [B,2,F,T] + noisy STFT [B,1,F,T] -> enhanced waveforms [B, orig_length].
+    lengths [B]: a ragged batch (istft's `lengths`); samples past an item's length are 0."""
     _, ere, eim = cirm_decompress_apply(enhanced_masks, noisy_reals.squeeze(1), noisy_imags.squeeze(1))
-    return istft(ere, eim, nfft, hop, orig_length)
+    return istft(ere, eim, nfft, hop, orig_length, lengths=lengths)
+
+
+def crm_mse_ragged(n_re, n_im, c_re, c_im, crm, frames):
+    """per-item cIRM MSE of a ragged batch (no drop-band): [B,F,T] x4 + compressed cIRM [B,2,F,T] + device int32 frames [B]
+    -> fp64 [B], item b averaged over its 2 x F x T_b elements (the target of cirm_build_compress)."""
+    n_re, n_im, c_re, c_im, crm = (_f32c(t) for t in (n_re, n_im, c_re, c_im, crm))
+    B, F, T = n_re.shape
+    assert crm.shape == (B, 2, F, T), "the ragged forward keeps all F bins"
+    frames = frames.to(device=n_re.device, dtype=torch.int32).contiguous()
+    out = torch.empty(B, dtype=torch.float64, device=n_re.device)
+    H.call("nppc_crm_mse_ragged", n_re, n_im, c_re, c_im, crm, frames, B, F, T, EPS32, out, H.stream())
+    return out
 
 
 def crm_directions_to_spectrograms(w_mat, noisy_re, noisy_im):

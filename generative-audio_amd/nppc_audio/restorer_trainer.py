@@ -27,7 +27,7 @@ from . import _hip as H
 from . import metrics
 from . import ops
 from . import ops_lstm
-from .data import AudioDataset, DataConfig, DataLoaderConfig, DeviceMixLoader
+from .data import AudioDataset, DataConfig, DataLoaderConfig, DeviceMixLoader, RaggedBatch
 from .fullsubnet import FullSubNet_Plus, FullSubNetPlusConfig
 from .nppc_model import StftConfig
 from .trainer import FlatAdamStepper, HipAdam, LoopLoader, OptimizerConfig
@@ -181,11 +181,20 @@ class FullSubNetPlusTrainer(nn.Module):
         SI-SDR of the noisy and of the enhanced waveform against the clean one.  Returns {"loss", "STOI_noisy", "STOI",
         "SI_SDR_noisy", "SI_SDR", "score"}: loss = mean of the batch losses (the reference's per-clip mean at batch size
         1), the metrics = means over items.  The reference's score is (STOI + (WB_PESQ + 0.5) / 5) / 2; without PESQ it is
-        the mean enhanced STOI here.  Everything stays on the device until one host copy at the end."""
+        the mean enhanced STOI here.  Everything stays on the device until one host copy at the end.
+
+        A `data.RaggedBatch` (clips of different lengths, data.pad_collate) runs the ragged forward: every item is scored
+        as if run alone, and its cIRM MSE over its own frames counts as one clip of the loss mean."""
         st = self.config.stft_configuration
         losses, scores = [], {k: [] for k in ("STOI_noisy", "STOI", "SI_SDR_noisy", "SI_SDR")}
         with torch.no_grad():
             for batch in loader:
+                if isinstance(batch, RaggedBatch):
+                    loss, sc = self._ragged_metrics(batch)
+                    losses.append(loss)
+                    for k in scores:
+                        scores[k].append(sc[k])
+                    continue
                 noisy, clean = self._to_device(batch)
                 mag, n_re, n_im = ops.stft(noisy, st.nfft, st.hop_length)
                 _, c_re, c_im = ops.stft(clean, st.nfft, st.hop_length, want_mag=False)
@@ -193,7 +202,7 @@ class FullSubNetPlusTrainer(nn.Module):
                 loss, _ = crm_mse(crm, n_re, n_im, c_re, c_im, 1)
                 enhanced = ops.model_outputs_to_waveforms(crm, n_re[:, None], n_im[:, None], noisy.shape[-1], st.nfft,
                                                           st.hop_length)
-                losses.append(loss.double())
+                losses.append(loss.double().reshape(1))
                 scores["STOI_noisy"].append(metrics.stoi(clean, noisy))
                 scores["STOI"].append(metrics.stoi(clean, enhanced))
                 scores["SI_SDR_noisy"].append(metrics.si_sdr(clean, noisy))
@@ -201,10 +210,27 @@ class FullSubNetPlusTrainer(nn.Module):
         if not losses:
             raise ValueError("the validation loader yields no batch")
         names = ["loss"] + list(scores)
-        vals = torch.stack([torch.stack(losses).mean()] + [torch.cat(v).mean() for v in scores.values()]).cpu().tolist()
+        vals = torch.stack([torch.cat(losses).mean()] + [torch.cat(v).mean() for v in scores.values()]).cpu().tolist()
         out = dict(zip(names, vals))
         out["score"] = out["STOI"]
         return out
+
+    def _ragged_metrics(self, batch):
+        """validate_metrics of one RaggedBatch: (per-item cIRM MSE [B] fp64, per-item scores)"""
+        st = self.config.stft_configuration
+        noisy, clean = (x.to(self.device, non_blocking=True) for x in batch[:2])
+        lengths = batch.lengths
+        mag, n_re, n_im = ops.stft(noisy, st.nfft, st.hop_length, lengths=lengths)
+        _, c_re, c_im = ops.stft(clean, st.nfft, st.hop_length, want_mag=False, lengths=lengths)
+        frames = ops.stft_frames(torch.as_tensor(lengths, dtype=torch.int64).cpu(), st.hop_length)
+        crm = self.model(mag[:, None], n_re[:, None], n_im[:, None], frames=frames)     # [B, 2, F, T], no drop-band
+        dl = torch.as_tensor(lengths).to(self.device, torch.int32)
+        loss = ops.crm_mse_ragged(n_re, n_im, c_re, c_im, crm, frames.to(self.device, torch.int32))
+        enhanced = ops.model_outputs_to_waveforms(crm, n_re[:, None], n_im[:, None], noisy.shape[-1], st.nfft, st.hop_length,
+                                                  lengths=lengths)
+        sc = {"STOI_noisy": metrics.stoi(clean, noisy, lengths=dl), "STOI": metrics.stoi(clean, enhanced, lengths=dl),
+              "SI_SDR_noisy": metrics.si_sdr(clean, noisy, lengths=dl), "SI_SDR": metrics.si_sdr(clean, enhanced, lengths=dl)}
+        return loss, sc
 
     # ---------------------------------------------------------------------------------- one optimisation step
     def train_step(self, batch):

@@ -504,6 +504,44 @@ int nppc_stoi_bands(const double* xr, const double* yr, long ldr, const int* kid
                     double* y_tob, void* stream);
 int nppc_stoi_corr(const double* x_tob, const double* y_tob, const int* K, int B, int nfr, double* out, void* stream);
 
+
+/* ---- ragged inference of the FullSubNet+ restorer (csrc/ragged.hip) -----------------------------------
+ * A padded batch: item b is L_b = lengths[b] samples (device int[B]) and T_b = 1 + L_b / hop frames; frames[b] (device
+ * int[B]) = T_b.  Item b's results equal the uniform entry point's for that item alone; nothing past an item's end is
+ * read, and what is written past it is 0.  No float atomics (bit-identical on repeat).
+ * STFT: wave [B][ld] (ld >= Lmax) -> re, im, mag (nullable) [B][F][T], T = 1 + Lmax / hop; frames t >= T_b are 0.
+ * iSTFT: torch.istft(length=L_b) of the item's T_b frames: re, im [B][F][T] -> out [B][ld], samples >= L_b are 0. */
+int nppc_stft_ragged(const float* wave, long ld, const int* lengths, float* re, float* im, float* mag /*nullable*/, int B, int T,
+                     int nfft, int hop, void* stream);
+int nppc_istft_ragged(const float* re, const float* im, float* out, long ld, const int* lengths, int B, int T, int nfft, int hop,
+                      void* stream);
+/* inference form of nppc_tsse_fwd_maps (no saved tensors): item b's laplace mean over F x (T_b + la), each TSSE conv pooled
+ * over its T_b + la - k + 1 outputs; X0 rows t < T_b = scaled map, rows T_b <= t < Tp written as 0 */
+int nppc_tsse_fwd_maps_ragged(int prec, const float* const* maps, int nmaps, double* rowsum, const float* cw0, const float* cb0,
+                              const float* cw1, const float* cb1, const float* cw2, const float* cb2, int ks0, int ks1, int ks2,
+                              const float* fcw, const float* fcb, const float* w1, const float* b1, const float* w2,
+                              const float* b2, long sW, float* scale, void* X0, long sY, const int* frames, int B, int C, int T,
+                              int look_ahead, int Tp, int ld, void* stream);
+/* TCN depthwise stage of nppc_tcn_dwconv per item: the centred conv sees zeros at and past Tv_b = T_b + la (as it sees them
+ * past Tv in the uniform launch), rows t >= Tv_b are written as 0; it accumulates no statistics. */
+int nppc_tcn_dwconv_ragged(int prec, const void* in, void* out, const double* st1, const float* gamma, const float* beta,
+                           const float* wd, const float* bd, const float* slope2, const int* frames, int la, int B, int Cc, int ld,
+                           int Tp, int Tv, int dil, float eps, long sAct, long sSt, long sP, int batch, void* stream);
+/* GroupNorm(1, C) sums (sum, sumsq) [batch][B][2] of the stored activation act [batch][B][Tp][ld] over item b's rows
+ * t < T_b + la, scaled by Tv / (T_b + la): consumers that divide by C * Tv get the item's own mean and variance.  The
+ * sums are overwritten. */
+int nppc_tcn_gn_stats_ragged(int prec, const void* act, double* stats, const int* frames, int la, int B, int Cc, int ld, int Tp,
+                             int Tv, long sAct, long sSt, int batch, void* stream);
+/* nppc_subband_mean per item over its T_b + la frames (no workspace, no atomics) */
+int nppc_subband_mean_ragged(int prec, const void* src, int ldS, const void* fb, int ldF, long strideFb, const float* mult,
+                             float* scale, const int* frames, int la, int B, int F, int Tp, int Tv, int nfeat, void* stream);
+/* x [B][rows][T] fp32: x[b][r][t] = 0 for t >= frames[b] (the output crop of the ragged forward) */
+int nppc_crop_frames_ragged(float* x, long rows, int T, const int* frames, int B, void* stream);
+/* per-item cIRM MSE, no drop-band: loss[b] (fp64) = mean over [2][F][T_b] of (gt - crm)^2, gt as in nppc_crm_mse;
+ * nr, ni, cr, ci [B][F][T], crm [B][2][F][T] */
+int nppc_crm_mse_ragged(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, const int* frames,
+                        int B, int F, int T, float eps, double* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
