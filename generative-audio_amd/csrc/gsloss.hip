@@ -727,7 +727,7 @@ int nppc_gram(const float* a, const float* b_or_null, const float* gt, const flo
 // out_i = sum_m M1[i][m] A_m + sum_m M2[i][m] B_m   (M*: [B][KV][KV] complex double; KV = K + (gt ? 1 : 0))
 int nppc_combine(const float* a, const double* M1, const float* b, const double* M2, const float* gt, const float* pred,
                  float* out, int B, int K, long N, void* stream) {
-  if (!a || !M1 || !out || B <= 0 || K < 1) return NPPC_EBADARG;
+  if (!a || !M1 || !out || B <= 0 || K < 1 || N <= 0) return NPPC_EBADARG;
   const int KV = K + (gt ? 1 : 0);
   VecSet A{a, gt, pred}, Bs{b, nullptr, nullptr};
   hipStream_t s = (hipStream_t)stream;
@@ -737,7 +737,7 @@ int nppc_combine(const float* a, const double* M1, const float* b, const double*
 }
 
 int nppc_gs_solve(const double* G, double* C, double* Ch, int B, int K, int KV, void* stream) {
-  if (!G || !C || !Ch || K > KMAX || KV < K) return NPPC_EBADARG;
+  if (!G || !C || !Ch || B <= 0 || K < 1 || K > KMAX || KV < K) return NPPC_EBADARG;
   const dim3 grid(ceil_div(B, 64));
   hipStream_t s = (hipStream_t)stream;
   static const bool wave_solve = [] { const char* e = getenv("NPPC_GS_WAVE_SOLVE"); return !(e && e[0] == '0'); }();   // A/B switch
@@ -759,7 +759,7 @@ int nppc_gs_solve(const double* G, double* C, double* Ch, int B, int K, int KV, 
 }
 
 int nppc_gs_bwd_solve(const double* G, const double* P, const double* Ch, double* D, int B, int K, int KV, void* stream) {
-  if (!G || !P || !Ch || !D || K > KMAX || KV < K) return NPPC_EBADARG;
+  if (!G || !P || !Ch || !D || B <= 0 || K < 1 || K > KMAX || KV < K) return NPPC_EBADARG;
   const dim3 grid(ceil_div(B, 64));
   hipStream_t s = (hipStream_t)stream;
   static const bool wave_solve = [] { const char* e = getenv("NPPC_GS_WAVE_SOLVE"); return !(e && e[0] == '0'); }();
@@ -782,7 +782,7 @@ int nppc_gs_bwd_solve(const double* G, const double* P, const double* Ch, double
 
 int nppc_loss_solve(const double* G, float* err_norm, float* proj_re, float* proj_im, float* proj_mag, float* w_norms,
                     float* reconst, float* sm, double* coefA, double* coefE, int B, int K, void* stream) {
-  if (!G || !err_norm || !coefA || !coefE || K + 1 > KMAX) return NPPC_EBADARG;
+  if (!G || !err_norm || !coefA || !coefE || B <= 0 || K < 1 || K + 1 > KMAX) return NPPC_EBADARG;
   hipLaunchKernelGGL(loss_solve_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, G, err_norm, proj_re,
                      proj_im, proj_mag, w_norms, reconst, sm, coefA, coefE, B, K, 1e-8, 0, 0.f, (float*)nullptr);
   NPPC_CHECK_LAUNCH();
@@ -794,7 +794,7 @@ int nppc_loss_solve(const double* G, float* err_norm, float* proj_re, float* pro
 int nppc_loss_solve_eps(const double* G, float* err_norm, float* proj_re, float* proj_im, float* proj_mag, float* w_norms,
                         float* reconst, float* sm, double* coefA, double* coefE, int B, int K, double eps, int eps_in_norms,
                         void* stream) {
-  if (!G || !err_norm || !coefA || !coefE || K + 1 > KMAX || !(eps >= 0)) return NPPC_EBADARG;
+  if (!G || !err_norm || !coefA || !coefE || B <= 0 || K < 1 || K + 1 > KMAX || !(eps >= 0)) return NPPC_EBADARG;
   hipLaunchKernelGGL(loss_solve_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, G, err_norm, proj_re,
                      proj_im, proj_mag, w_norms, reconst, sm, coefA, coefE, B, K, eps, eps_in_norms, 0.f, (float*)nullptr);
   NPPC_CHECK_LAUNCH();
@@ -806,7 +806,7 @@ int nppc_loss_solve_eps(const double* G, float* err_norm, float* proj_re, float*
 int nppc_loss_solve_obj(const double* G, float* err_norm, float* proj_re, float* proj_im, float* proj_mag, float* w_norms,
                         float* reconst, float* sm, double* coefA, double* coefE, int B, int K, double eps, int eps_in_norms,
                         float lam, float* objective, void* stream) {
-  if (!G || !err_norm || !coefA || !coefE || !objective || K + 1 > KMAX || !(eps >= 0)) return NPPC_EBADARG;
+  if (!G || !err_norm || !coefA || !coefE || !objective || B <= 0 || K < 1 || K + 1 > KMAX || !(eps >= 0)) return NPPC_EBADARG;
   if (B > 1024) return NPPC_EUNSUPPORTED;
   hipLaunchKernelGGL(loss_solve_kernel, dim3(1), dim3(round_up(B, 64)), 0, (hipStream_t)stream, G, err_norm, proj_re, proj_im,
                      proj_mag, w_norms, reconst, sm, coefA, coefE, B, K, eps, eps_in_norms, lam, objective);
@@ -816,7 +816,7 @@ int nppc_loss_solve_obj(const double* G, float* err_norm, float* proj_re, float*
 
 int nppc_loss_bwd_coef(const double* coefA, const double* coefE, const float* grec, float gobj_over_B, float gsm, double* M1,
                        int B, int K, void* stream) {
-  if (!coefA || !coefE || !M1) return NPPC_EBADARG;
+  if (!coefA || !coefE || !M1 || B <= 0 || K < 1) return NPPC_EBADARG;
   hipLaunchKernelGGL(loss_bwd_coef_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, coefA, coefE, grec,
                      gobj_over_B, gsm, M1, B, K, (const float*)nullptr);
   NPPC_CHECK_LAUNCH();
@@ -825,7 +825,7 @@ int nppc_loss_bwd_coef(const double* coefA, const double* coefE, const float* gr
 
 int nppc_loss_bwd_coef_dev(const double* coefA, const double* coefE, const float* grec, const float* gobj, float inv_B,
                            float sm_weight, double* M1, int B, int K, void* stream) {
-  if (!coefA || !coefE || !M1 || !gobj) return NPPC_EBADARG;
+  if (!coefA || !coefE || !M1 || !gobj || B <= 0 || K < 1) return NPPC_EBADARG;
   hipLaunchKernelGGL(loss_bwd_coef_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, coefA, coefE, grec, inv_B,
                      sm_weight, M1, B, K, gobj);
   NPPC_CHECK_LAUNCH();
