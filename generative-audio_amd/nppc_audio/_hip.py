@@ -239,6 +239,9 @@ SIGS = {
     "nppc_subband_mean_ragged": [I, P, I, P, I, L, P, P, P, I, I, I, I, I, I, P],
     "nppc_crop_frames_ragged": [P, L, I, P, I, P],
     "nppc_crm_mse_ragged": [P, P, P, P, P, P, I, I, I, F, P, P],
+    "nppc_istft_any": [P, P, L, P, L, I, I, I, I, I, P],
+    "nppc_pc_variation_waves": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
+    "nppc_metrics_batch": [P, P, P, P, P, P, P, I, I, L, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

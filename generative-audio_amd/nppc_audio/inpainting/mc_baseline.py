@@ -170,3 +170,63 @@ def compute_metrics(nppc_directions, mc_dropout_directions, pred_spec_mag, mean_
         'mc_dropout': {'rmse': float(np.sqrt(G[e_mc, e_mc])), 'residual_error': residual(b)},
         'principal_angles': (np.arccos(np.clip(sv, -1, 1)) * 180 / np.pi).tolist(),
     }
+
+
+def metrics_from_gram(G, n):
+    """host half of compute_metrics_batch, runs without a GPU: G [B, 2n+3, 2n+3] (or one [2n+3, 2n+3]) fp64 Gram
+    matrices of the rows {nppc [n], mc [n], pred - clean, the same on the gap, (mean - clean) on the gap} -> list of
+    compute_metrics' dicts.  The same n x n algebra as compute_metrics (whitening instead of QR: same singular values)."""
+    import numpy as np
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim == 2:
+        G = G[None]
+    if G.ndim != 3 or G.shape[1:] != (2 * n + 3, 2 * n + 3):
+        raise ValueError(f"expected [B, {2 * n + 3}, {2 * n + 3}] Gram matrices, got {G.shape}")
+    e, e_np, e_mc = 2 * n, 2 * n + 1, 2 * n + 2
+    a, b = np.arange(n), np.arange(n, 2 * n)
+    out = []
+    for Gi in G:
+        def residual(idx):
+            norms = np.sqrt(np.diag(Gi)[idx]) + 1e-6
+            c = Gi[idx, e] / norms                                    # W^T e
+            gh = Gi[np.ix_(idx, idx)] / np.outer(norms, norms)
+            return float(np.sqrt(max(Gi[e, e] - 2.0 * (c * c).sum() + c @ gh @ c, 0.0)))
+
+        def whiten(idx):
+            lam, U = np.linalg.eigh(Gi[np.ix_(idx, idx)])
+            keep = lam > 1e-12 * lam.max()
+            return U[:, keep] / np.sqrt(lam[keep])                    # columns w: (w^T A) rows are orthonormal
+
+        sv = np.linalg.svd(whiten(a).T @ Gi[np.ix_(a, b)] @ whiten(b), compute_uv=False)
+        out.append({
+            'nppc': {'rmse': float(np.sqrt(Gi[e_np, e_np])), 'residual_error': residual(a)},
+            'mc_dropout': {'rmse': float(np.sqrt(Gi[e_mc, e_mc])), 'residual_error': residual(b)},
+            'principal_angles': (np.arccos(np.clip(sv, -1, 1)) * 180 / np.pi).tolist(),
+        })
+    return out
+
+
+def metrics_gram_batch(nppc_directions, mc_dropout_directions, pred_spec_mag, mean_prediction, clean_spec_mag, mask):
+    """device half of compute_metrics_batch: directions [B,n,F,T] x2, pred / mean / clean / mask [B,1,F,T] ->
+    G [B, 2n+3, 2n+3] fp64 on the device (one launch for the whole batch, no host copy, fixed summation order)"""
+    H.require_gpu()
+    B, n = nppc_directions.shape[:2]
+    N = nppc_directions[0, 0].numel()
+    if mc_dropout_directions.shape != nppc_directions.shape:
+        raise ValueError(f"direction sets differ: {tuple(nppc_directions.shape)} / {tuple(mc_dropout_directions.shape)}")
+    for t in (pred_spec_mag, mean_prediction, clean_spec_mag, mask):
+        if t.shape[0] != B or t[0].numel() != N:
+            raise ValueError(f"expected [B,1,F,T] tensors of {N} elements per item, got {tuple(t.shape)}")
+    f32 = lambda t: t.contiguous().float()
+    G = torch.empty(B, 2 * n + 3, 2 * n + 3, dtype=torch.float64, device=nppc_directions.device)
+    H.call("nppc_metrics_batch", f32(nppc_directions), f32(mc_dropout_directions), f32(pred_spec_mag), f32(clean_spec_mag),
+           f32(mean_prediction), f32(mask), G, B, n, N, H.stream())
+    return G
+
+
+def compute_metrics_batch(nppc_directions, mc_dropout_directions, pred_spec_mag, mean_prediction, clean_spec_mag, mask):
+    """compute_metrics for every item of a batch: one launch builds all Gram matrices, ONE device-to-host copy, the
+    n x n algebra on the host (metrics_from_gram) -> list of B dicts.  Agrees with compute_metrics item by item to
+    summation-order rounding (the two paths fold their fp64 partial sums in different orders)."""
+    G = metrics_gram_batch(nppc_directions, mc_dropout_directions, pred_spec_mag, mean_prediction, clean_spec_mag, mask)
+    return metrics_from_gram(G.cpu().numpy(), nppc_directions.shape[1])

@@ -107,6 +107,8 @@ class NPPCAudioInpaintingTrainer(nn.Module):
             self.optimizer = getattr(optim, okind)(self.nppc_model.parameters(), **config.optimizer_configuration.args)
         self._flat_adam = None
         self._sumsq = None
+        self.val_loss_history = []
+        self.val_reconst_err_history = []
 
     # ---------------------------------------------------------------------------------- reference API
     def base_step(self, batch):
@@ -176,21 +178,56 @@ class NPPCAudioInpaintingTrainer(nn.Module):
 
     def train(self, n_steps=None, n_epochs=None, checkpoint_dir="checkpoints", save_flag=True, val_dataloader=None,
               log_every=None):
-        """training loop (the name shadows nn.Module.train exactly like the reference, nppc_trainer.py:115)"""
+        """training loop (the name shadows nn.Module.train exactly like the reference, nppc_trainer.py:115).
+        val_dataloader: validated whenever the step counter, read before the step, is a multiple of log_interval
+        (:170-176); the results are appended to self.val_loss_history / self.val_reconst_err_history, which belong to the
+        trainer and keep growing over successive train() calls (the reference keeps them in locals and drops them)."""
         os.makedirs(checkpoint_dir, exist_ok=True)
         loop_loader = LoopLoader(dataloader=self.dataloader, n_steps=n_steps, n_epochs=n_epochs)
         log_every = log_every or self.config.log_interval
         for it, batch in enumerate(loop_loader):
             masked_spec, mask_frames, clean_spec = batch[:3]
             batch = (masked_spec.to(self.device), mask_frames.to(self.device), clean_spec.to(self.device))
+            step_before = self.step                                   # the reference tests its counter before advancing it
             reconst_err, objective, log_dict = self.train_step(batch)
             if it % log_every == 0 or it + 1 == len(loop_loader):
                 print(f'step {self.step}: Objective: {objective.item():.4f} | '
                       f'Second Moment MSE: {log_dict["second_moment_mse"].mean().item():.4f} | '
                       f'Reconstract Error: {reconst_err.mean().item():.4f}')
+            if val_dataloader is not None and step_before % self.config.log_interval == 0:      # nppc_trainer.py:170-176
+                val_loss, val_reconst_err = self.validate(val_dataloader)
+                self.val_loss_history.append(val_loss)
+                self.val_reconst_err_history.append(val_reconst_err)
+                print(f" | Validation objective at Step {step_before}: {val_loss:.4f}")
+                print(f" | Validation Reconstract Error at Step {step_before}: {val_reconst_err:.4f}")
         if save_flag:
             timestamp = datetime.now().strftime("%Y%m%d_%H%M%S")
             self.save_checkpoint(os.path.join(checkpoint_dir, f"checkpoint_final_{timestamp}.pt"))
+
+    def validate(self, val_dataloader):
+        """nppc_trainer.py:689-706: mean objective and mean reconstruction error of base_step over a held-out loader, in
+        eval mode under no_grad -> (avg_objective, avg_reconst_err).  Batches are (masked_spec, mask, clean_spec) or the
+        five-tuple of the reference's collate_fn (the first three are used).  Nothing the optimiser or a later training
+        step sees changes: no gradient, no BatchNorm running-buffer update, and the training flags are put back as they
+        were (the reference ends with .train(); the frozen restorer stays in eval mode either way)."""
+        model = self.nppc_model
+        was_training = {m: m.training for m in model.modules()}
+        model.eval()
+        val_losses, val_reconst_err = [], []
+        try:
+            with torch.no_grad():
+                for batch in val_dataloader:
+                    masked_spec, mask, clean_spec = (x.to(self.device) for x in batch[:3])
+                    reconst_err, objective, _ = self.base_step((masked_spec, mask, clean_spec))
+                    val_losses.append(objective.item())
+                    val_reconst_err.append(reconst_err.mean().item())
+        finally:
+            for m, flag in was_training.items():
+                m.training = flag
+            model._memo = None                                    # the memoised restorer output belongs to a held-out batch
+        if not val_losses:
+            raise ValueError("the validation dataloader yielded no batches")
+        return sum(val_losses) / len(val_losses), sum(val_reconst_err) / len(val_reconst_err)
 
     def save_checkpoint(self, checkpoint_path):
         checkpoint = {

@@ -1,0 +1,173 @@
+"""Inpainting NPPC validator on the MI355X kernels: mirrors nppc_audio/inpainting/validator/validator_nppc_model.py
+(NPPCModelValidatorConfig :905-910, NPPCModelValidator :913-1027, save_pc_audio_variations :528-659,
+compute_metrics :742-828, save_metrics_to_json :831-859).
+
+The reference validates one held-out sample at a time: direction net, MC-dropout + PCA baseline, compute_metrics on the
+host, K x A inverse STFTs one by one.  Here a whole uniform batch goes through each stage at once: the baseline is
+mc_baseline.calculate_unet_baseline (batched PCA), the metrics come from one Gram launch per batch
+(mc_baseline.metrics_gram_batch) and ONE device-to-host copy per `validate_dataloader` call, and the K x A + 1 waveforms
+of `pc_audio_variations` come from one launch whose complex spectrograms never reach memory.
+
+Outside this build: whisper / phoneme transcription, pitch and spectrogram plots, wav files, splicing a variation into
+the full source file (get_with_full_audio), wandb.
+"""
+import json
+from pathlib import Path
+from typing import Optional
+
+import numpy as np
+import pydantic
+import torch
+
+from ... import _hip as H
+from ... import ops
+from .. import mc_baseline as MB
+from ..nppc.nppc_model import NPPCModel, NPPCModelConfig
+from ..utils import preprocess_data
+
+__all__ = ["NPPCModelValidatorConfig", "NPPCModelValidator", "pc_audio_variations", "compute_metrics",
+           "compute_metrics_batch", "save_metrics_to_json", "default_alphas"]
+
+compute_metrics = MB.compute_metrics
+compute_metrics_batch = MB.compute_metrics_batch
+
+
+def default_alphas(device=None):
+    """the reference's sweep, validator_nppc_model.py:972"""
+    return torch.arange(-3, 3.5, 0.5, device=device)
+
+
+def pc_audio_variations(clean_spec_mag_norm_log, pred_spec_mag, pc_directions_mag, clean_spec, alphas, mean, std,
+                        n_fft=255, hop_length=128, length=None):
+    """save_pc_audio_variations (:553-619) for a batch, waveforms only.
+    clean_spec_mag_norm_log, pred_spec_mag [B,1,F,T]; pc_directions_mag [B,K,F,T]; clean_spec [B,2,F,T]; alphas [A];
+    mean, std: the batch-global statistics of preprocess_data(..., plot_mean_std=True), device scalars (read on the
+    device, no host synchronisation)  ->  (variations [B,K,A,L], clean_audio [B,L]) fp32:
+        variations[b,k,a] = istft(exp((pred[b] + alphas[a] * pc[b,k]) * std + mean) * exp(i angle(clean[b])))
+        clean_audio[b]    = istft((exp(clean_norm[b] * std + mean) - 1e-6) * exp(i angle(clean[b])))
+    As in the reference the variations do not subtract the 1e-6 the clean path subtracts, and angle(0) = 0.
+    L = `length`, default torch.istft's own (hop (T - 1), + 1 for odd n_fft)."""
+    H.require_gpu()
+    f32 = lambda t: t.contiguous().float()
+    pred, pc, cn, cs = f32(pred_spec_mag), f32(pc_directions_mag), f32(clean_spec_mag_norm_log), f32(clean_spec)
+    B, K, F, T = pc.shape
+    if F != n_fft // 2 + 1:
+        raise ValueError(f"{F} frequency bins do not fit n_fft {n_fft}")
+    if pred.shape != (B, 1, F, T) or cn.shape != (B, 1, F, T) or cs.shape != (B, 2, F, T):
+        raise ValueError(f"shapes {tuple(pred.shape)}, {tuple(cn.shape)}, {tuple(cs.shape)} do not fit directions {tuple(pc.shape)}")
+    dev = pc.device
+    alphas = torch.as_tensor(alphas, dtype=torch.float32).to(dev).contiguous().reshape(-1)
+    A = alphas.numel()
+    if A == 0:
+        raise ValueError("no alphas given")
+    L = ops.check_istft_any_config(n_fft, hop_length, T, length)
+    as_scalar = lambda v: torch.as_tensor(v, dtype=torch.float32).to(dev).reshape(1).contiguous()
+    out = torch.empty(B, K, A, L, dtype=torch.float32, device=dev)
+    clean_wave = torch.empty(B, L, dtype=torch.float32, device=dev)
+    with ops.envelope_refusal(n_fft, hop_length, T, L):
+        H.call("nppc_pc_variation_waves", pred, pc, cn, cs, as_scalar(mean), as_scalar(std), alphas, out, clean_wave, B, K, A,
+               T, n_fft, hop_length, L, H.stream())
+    return out, clean_wave
+
+
+def save_metrics_to_json(metrics, save_dir, sample_idx):
+    """:831-859: <save_dir>/validation_metrics/sample_<idx>.json, {'nppc': {...}, 'mc_dropout': {...},
+    'principal_angles': [...]}"""
+    json_metrics = {}
+    for method, values in metrics.items():
+        if method == 'principal_angles':
+            json_metrics[method] = [float(angle) for angle in values]
+        else:
+            json_metrics[method] = {k: float(v) if isinstance(v, (torch.Tensor, np.ndarray)) else v for k, v in values.items()}
+    metrics_dir = Path(save_dir) / "validation_metrics"
+    metrics_dir.mkdir(parents=True, exist_ok=True)
+    with open(metrics_dir / f"sample_{sample_idx}.json", 'w') as f:
+        json.dump(json_metrics, f, indent=4)
+
+
+class NPPCModelValidatorConfig(pydantic.BaseModel):
+    checkpoint_path: str
+    device: str = "cuda"
+    save_dir: Optional[str] = "validation_nppc_results"
+    model_configuration: NPPCModelConfig
+    max_dirs_to_plot: Optional[int] = None
+
+
+class NPPCModelValidator:
+    """Loads a checkpoint written by NPPCAudioInpaintingTrainer.save_checkpoint ({'model_state_dict': ...}) and scores it
+    on held-out batches.
+
+    The MC-dropout baseline gathers the gap elements of every item into one [K, B, N_masked] stack, so every item of a
+    batch must have the same number of gap (mask == 0) elements; it raises ValueError otherwise."""
+
+    def __init__(self, config: NPPCModelValidatorConfig):
+        self.config = config
+        self.device = config.device
+        if config.device == 'cuda':
+            self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+        checkpoint = torch.load(Path(config.checkpoint_path).absolute(), map_location="cpu")
+        self.model = NPPCModel(config.model_configuration)
+        self.model.load_state_dict(checkpoint["model_state_dict"])
+        self.model.to(self.device)
+        self.model.eval()
+
+    def _run_batch(self, masked_spec, mask, clean_spec, n_mc_samples, n_components):
+        """every device stage of one batch; the Gram matrices stay on the device"""
+        H.require_gpu()
+        self.model.eval()
+        with torch.no_grad():
+            masked_spec, mask, clean_spec = (t.to(self.device) for t in (masked_spec, mask, clean_spec))
+            clean_norm, mask4, masked_norm, mean, std = preprocess_data(clean_spec, masked_spec, mask, plot_mean_std=True)
+            mask4 = mask4.contiguous()
+            pc_directions = self.model(masked_norm, mask4)
+            pred = self.model.get_pred_spec_mag_norm(masked_norm, mask4)
+            if n_components != pc_directions.shape[1]:
+                raise ValueError(f"n_components = {n_components} but the model has {pc_directions.shape[1]} directions: "
+                                 "the metrics compare subspaces of the same dimension")
+            restorer = self.model.pretrained_restoration_model
+            try:
+                mc = MB.calculate_unet_baseline(restorer, masked_norm, mask4, n_mc_samples=n_mc_samples,
+                                                n_components=n_components)
+            finally:
+                restorer.eval()                                     # enable_dropout left the Dropout modules in train mode
+            gram = MB.metrics_gram_batch(pc_directions, mc['scaled_principal_components'], pred, mc['mean_prediction'],
+                                         clean_norm, mask4)
+        return {'pc_directions': pc_directions, 'pred_spec_mag_norm': pred, 'clean_spec_mag_norm': clean_norm,
+                'mask': mask4, 'mean': mean, 'std': std, 'mc_dropout': mc, 'gram': gram, 'clean_spec': clean_spec}
+
+    def validate_batch(self, masked_spec, mask, clean_spec, n_mc_samples=50, n_components=5, alphas=None, n_fft=255,
+                       hop_length=128):
+        """validate_sample + _validate_with_baseline (:930-1027) for a uniform batch: masked_spec, clean_spec [B,2,F,T],
+        mask [B,T] (1 = known; the same number of gap frames in every item) -> dict with 'pc_directions' [B,K,F,T],
+        'pred_spec_mag_norm', 'clean_spec_mag_norm', 'mask' [B,1,F,T], 'mean', 'std', 'mc_dropout' (calculate_unet_baseline's
+        dict), 'metrics' (list of B compute_metrics dicts) and, when `alphas` is given, 'audio_variations' [B,K,A,L] and
+        'clean_audio' [B,L] (pc_audio_variations)."""
+        out = self._run_batch(masked_spec, mask, clean_spec, n_mc_samples, n_components)
+        out['metrics'] = MB.metrics_from_gram(out.pop('gram').cpu().numpy(), n_components)
+        clean_spec = out.pop('clean_spec')
+        if alphas is not None:
+            with torch.no_grad():
+                out['audio_variations'], out['clean_audio'] = pc_audio_variations(
+                    out['clean_spec_mag_norm'], out['pred_spec_mag_norm'], out['pc_directions'], clean_spec, alphas,
+                    out['mean'], out['std'], n_fft=n_fft, hop_length=hop_length)
+        return out
+
+    def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False):
+        """every item of every batch ((masked_spec, mask, clean_spec) or utils.collate_fn's five-tuple): the Gram
+        matrices stay on the device until the loader is exhausted, then ONE copy to the host and the n x n algebra.
+        -> {'per_item': [compute_metrics dicts], 'mean': {'nppc': {...}, 'mc_dropout': {...}, 'principal_angles': [...]},
+            'n_items': int}; save=True also writes validation_metrics/sample_<i>.json under config.save_dir."""
+        grams = []
+        for batch in dataloader:
+            grams.append(self._run_batch(*batch[:3], n_mc_samples, n_components)['gram'])
+        if not grams:
+            raise ValueError("the dataloader yielded no batches")
+        per_item = MB.metrics_from_gram(torch.cat(grams).cpu().numpy(), n_components)
+        mean = {m: {k: float(np.mean([it[m][k] for it in per_item])) for k in ('rmse', 'residual_error')}
+                for m in ('nppc', 'mc_dropout')}
+        n_ang = min(len(it['principal_angles']) for it in per_item)
+        mean['principal_angles'] = [float(np.mean([it['principal_angles'][j] for it in per_item])) for j in range(n_ang)]
+        if save and self.config.save_dir is not None:
+            for i, it in enumerate(per_item):
+                save_metrics_to_json(it, self.config.save_dir, i)
+        return {'per_item': per_item, 'mean': mean, 'n_items': len(per_item)}

@@ -109,15 +109,90 @@ def cirm_decompress_apply(crm, n_re, n_im):
     return emag, ere, eim
 
 
-def istft(re, im, nfft, hop, length, lengths=None):
+def istft_natural_length(nfft, hop, T):
+    """samples torch.istft(center=True) returns with length=None: hop (T - 1), plus 1 for odd n_fft"""
+    return hop * (T - 1) + (nfft & 1)
+
+
+def istft_envelope_min(nfft, hop, T, length):
+    """smallest window envelope sum_t hann^2 inside the samples torch.istft keeps (it raises below 1e-11); host numpy"""
+    import numpy as np
+    w2 = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(nfft) / nfft)) ** 2
+    env = np.zeros(nfft + hop * (T - 1))
+    for t in range(T):
+        env[t * hop:t * hop + nfft] += w2
+    kept = env[nfft // 2:nfft // 2 + length]
+    return float(kept.min()) if kept.size else 0.0
+
+
+def _istft_fft_kernel_takes(nfft, hop):
+    return nfft in (64, 128, 256, 512) and hop > 0 and nfft % hop == 0 and nfft // hop <= 8
+
+
+def istft_any(re, im, nfft, hop, length=None, out=None):
+    """torch.istft(n_fft, hop, win_length=n_fft, hann window, center=True, length=length) for any n_fft <= 512,
+    1 <= hop <= n_fft, ceil(n_fft / hop) <= 8 (the inpainting configuration is 255 / 128): [B,F,T] x2 -> [B,length].
+    length=None: torch's default, hop (T - 1) (+ 1 for odd n_fft); a longer length zero-fills the tail as torch does.
+    out: optional [B, >= length] fp32 device tensor to write into (nothing past `length` is written).
+    ValueError where torch raises: the window envelope inside the kept range is below 1e-11."""
+    re, im = _f32c(re), _f32c(im)
+    B, F, T = re.shape
+    if F != nfft // 2 + 1 or im.shape != re.shape:
+        raise ValueError(f"istft: planes {tuple(re.shape)} / {tuple(im.shape)} do not fit n_fft {nfft}")
+    length = check_istft_any_config(nfft, hop, T, length)
+    if out is None:
+        out = torch.empty(B, length, dtype=torch.float32, device=re.device)
+    assert out.dim() == 2 and out.shape[0] == B and out.shape[1] >= length and out.dtype == torch.float32
+    with envelope_refusal(nfft, hop, T, length):
+        H.call("nppc_istft_any", re, im, F * T, out, out.shape[1], B, T, nfft, hop, length, H.stream())
+    return out
+
+
+def check_istft_any_config(nfft, hop, T, length):
+    """the shape rules of nppc_istft_any as ValueErrors; -> the length to produce (torch's default for None)"""
+    if nfft < 2 or nfft > 512 or not (1 <= hop <= nfft) or -(-nfft // hop) > 8:
+        raise ValueError(f"istft: n_fft {nfft} / hop {hop} outside 2 <= n_fft <= 512, 1 <= hop <= n_fft, ceil(n_fft / hop) <= 8")
+    length = istft_natural_length(nfft, hop, T) if length is None else int(length)
+    if T < 1 or length <= 0:
+        raise ValueError(f"istft: {T} frame(s) of n_fft {nfft} / hop {hop} give no samples")
+    return length
+
+
+class envelope_refusal:
+    """Around a launch whose other arguments were checked already: the entry point's one remaining NPPC_EBADARG is the
+    window envelope (computed once, in C, before the launch), reported as the ValueError torch.istft would raise."""
+
+    def __init__(self, nfft, hop, T, length):
+        self.args = (nfft, hop, T, length)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, err, tb):
+        if kind is RuntimeError and "bad argument" in str(err):
+            nfft, hop, T, length = self.args
+            low = istft_envelope_min(nfft, hop, T, length)
+            if low >= 1e-11:
+                return False
+            raise ValueError(f"istft: window overlap add min {low:.3g} < 1e-11 for n_fft {nfft}, hop {hop}, {T} frames "
+                             "(torch.istft raises here too)") from err
+        return False
+
+
+def istft(re, im, nfft, hop, length=None, lengths=None):
     """torch.istft(n_fft, hop, win_length=n_fft, hann window, center=True, length=length): [B,F,T] x2 -> [B,length]
-    (utils.py:60-70, nppc_audio/validator.py:136-143).
+    (utils.py:60-70, nppc_audio/validator.py:136-143).  Power-of-two n_fft with n_fft % hop == 0 runs the radix-2 kernel;
+    every other configuration (any n_fft <= 512, see istft_any) the direct inverse DFT.  length=None: torch's default.
 
     lengths [B] (ragged batch, L_b <= length, 1 + L_b // hop <= T): item b is torch.istft(length=L_b) of its first
     1 + L_b // hop frames alone; samples L_b .. length-1 are 0."""
+    if lengths is None and not _istft_fft_kernel_takes(nfft, hop):
+        return istft_any(re, im, nfft, hop, length)
     re, im = _f32c(re), _f32c(im)
     B, F, T = re.shape
     assert F == nfft // 2 + 1
+    if length is None:
+        length = istft_natural_length(nfft, hop, T)
     out = torch.empty(B, length, dtype=torch.float32, device=re.device)
     if lengths is not None:
         dl, host = ragged_lengths(lengths, B, length, 0, re.device)

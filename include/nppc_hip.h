@@ -542,6 +542,29 @@ int nppc_crop_frames_ragged(float* x, long rows, int T, const int* frames, int B
 int nppc_crm_mse_ragged(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, const int* frames,
                         int B, int F, int T, float eps, double* loss, void* stream);
 
+/* ---- inpainting validator (csrc/inpaint_validator.hip, DESIGN.md section 8 "Inpainting validator") --------------------
+ * nppc_istft_any: torch.istft(n_fft, hop, win_length = n_fft, periodic hann, center=True, length=L) for ANY n_fft <= 512,
+ * 1 <= hop <= n_fft, ceil(n_fft / hop) <= 8: re, im [B][F][T] planes, item b at re + b * sb (sb >= F T floats) ->
+ * out [B][ld] (ld >= L; nothing past L is written).  Samples at and past n_fft + hop (T - 1) - n_fft / 2 are 0 (torch pads
+ * there); frames with t hop >= L + n_fft / 2 are never read.  Direct inverse DFT from LDS, exact twiddle phases, fp64
+ * accumulation, every sample gathers its frames in ascending order: no atomics, an item's samples do not depend on the batch.
+ * NPPC_EBADARG when the window envelope inside the kept range is below 1e-11 (torch raises there). */
+int nppc_istft_any(const float* re, const float* im, long sb, float* out, long ld, int B, int T, int nfft, int hop, int L,
+                   void* stream);
+/* save_pc_audio_variations (inpainting/validator/validator_nppc_model.py:553-619) without files: pred, clean_norm [B][F][T],
+ * pc [B][K][F][T], clean_spec [B][2][F][T], mean / stdev device scalars, alphas [A] (device) ->
+ * out [B][K][A][L] = istft(exp((pred + alpha pc_k) stdev + mean) e^{i angle(clean)}),
+ * clean_wave [B][L] = istft((exp(clean_norm stdev + mean) - 1e-6) e^{i angle(clean)}); angle(0) = 0.  The K A + 1 complex
+ * spectrograms exist in LDS only; same transform, limits and determinism as nppc_istft_any. */
+int nppc_pc_variation_waves(const float* pred, const float* pc, const float* clean_norm, const float* clean_spec,
+                            const float* mean, const float* stdev, const float* alphas, float* out, float* clean_wave, int B,
+                            int K, int A, int T, int nfft, int hop, int L, void* stream);
+/* compute_metrics for a batch: G [B][2n+3][2n+3] (fp64) = Gram matrix of item b's rows {nppc [n], mc [n], pred - clean, the
+ * same on the gap only, (mean - clean) on the gap only} (the rows of nppc_metric_rows, formed on the fly); nppc, mc
+ * [B][n][N], pred, clean, mean, mask [B][N]; n <= 8.  One launch, one workgroup per (row, item), fixed summation order. */
+int nppc_metrics_batch(const float* nppc, const float* mc, const float* pred, const float* clean, const float* mean,
+                       const float* mask, double* G, int B, int n, long N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
