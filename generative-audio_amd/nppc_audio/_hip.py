@@ -242,6 +242,8 @@ SIGS = {
     "nppc_istft_any": [P, P, L, P, L, I, I, I, I, I, P],
     "nppc_pc_variation_waves": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "nppc_metrics_batch": [P, P, P, P, P, P, P, I, I, L, P],
+    "nppc_rir_convolve": [P, P, P, P, I, I, I, P],
+    "nppc_dns_snr_mix": [P, P, P, P, F, P, P, I, I, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

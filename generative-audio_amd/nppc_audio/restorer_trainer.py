@@ -10,7 +10,10 @@ on the device).  The checkpoint is what `nppc_model.preload_model` reads, so the
 `NPPCModelConfig.pretrained_restoration_model_path`.
 
 Differences, deliberately: no AMP (train.toml has use_amp = false, the scaler is an identity), no TensorBoard, no toml
-loader, no resume, one GPU; the data are the wav-folder `AudioDataset` mixed on the device (no reverberation).  `validate`
+loader, no resume, one GPU.  The data: train.toml's `[train_dataset]`, the DNS dynamic mixer with reverberation, is
+`dns_data.DynamicMixDataset` (pass one, or set `train_dataset_configuration`), reverberated and mixed on the device by
+`DeviceReverbMixLoader` with drop_last = true (train.toml:59); the NPPC-side wav-folder `AudioDataset` (no reverberation)
+keeps its `DeviceMixLoader` route.  `validate`
 reports the mean loss; `validate_metrics` follows _validation_epoch (trainer.py:366-446) and scores the enhanced
 waveforms with STOI and SI-SDR on the device (nppc_audio.metrics); PESQ is not part of this build, so the epoch score that
 picks best_model.tar is the mean enhanced STOI.
@@ -28,6 +31,7 @@ from . import metrics
 from . import ops
 from . import ops_lstm
 from .data import AudioDataset, DataConfig, DataLoaderConfig, DeviceMixLoader, RaggedBatch
+from .dns_data import DeviceReverbMixLoader, DNSDatasetConfig, DynamicMixDataset
 from .fullsubnet import FullSubNet_Plus, FullSubNetPlusConfig
 from .nppc_model import StftConfig
 from .trainer import FlatAdamStepper, HipAdam, LoopLoader, OptimizerConfig
@@ -44,6 +48,8 @@ class FullSubNetPlusTrainerConfig(pydantic.BaseModel):
     acoustics / dataset sections this build implements)"""
     model_configuration: FullSubNetPlusConfig
     data_configuration: Optional[DataConfig] = None       # wav folders; not needed when a dataset is passed
+    # train.toml [train_dataset.args] (DNS dynamic mixing); used when no dataset is passed
+    train_dataset_configuration: Optional[DNSDatasetConfig] = None
     dataloader_configuration: DataLoaderConfig = pydantic.Field(default_factory=DataLoaderConfig)
     optimizer_configuration: OptimizerConfig = pydantic.Field(default_factory=_toml_optimizer)
     stft_configuration: StftConfig = pydantic.Field(default_factory=StftConfig)
@@ -116,9 +122,12 @@ class FullSubNetPlusTrainer(nn.Module):
             self.optimizer = getattr(optim, okind)(self.model.parameters(), **config.optimizer_configuration.args)
 
         if dataset is None:
-            if config.data_configuration is None:
+            if config.train_dataset_configuration is not None:
+                dataset = DynamicMixDataset(config.train_dataset_configuration)
+            elif config.data_configuration is None:
                 raise ValueError("pass a dataset or a data_configuration (wav folders of clean speech and noise)")
-            dataset = AudioDataset(config.data_configuration.dataset)
+            else:
+                dataset = AudioDataset(config.data_configuration.dataset)
         self.dataset = dataset
         self.dataloader = self.make_loader(dataset, config.dataloader_configuration)
         self.step = 0
@@ -130,7 +139,13 @@ class FullSubNetPlusTrainer(nn.Module):
         self.val_history: List[dict] = []
 
     def make_loader(self, dataset, lc):
-        """(noisy [B,L], clean [B,L]) batches: an AudioDataset on a HIP device is mixed there (DeviceMixLoader)"""
+        """(noisy [B,L], clean [B,L]) batches: an AudioDataset on a HIP device is mixed there (DeviceMixLoader), a
+        DynamicMixDataset is reverberated and mixed there (DeviceReverbMixLoader; drop_last like train.toml:59, a last
+        partial batch of <= num_groups items would trip drop-band's assertion)"""
+        if isinstance(dataset, DynamicMixDataset) and str(self.device).startswith("cuda"):
+            base = (torch.utils.data.RandomSampler if lc.shuffle else torch.utils.data.SequentialSampler)(dataset)
+            return DeviceReverbMixLoader(dataset, torch.utils.data.BatchSampler(base, lc.batch_size, drop_last=True),
+                                         device=self.device, pin_memory=lc.pin_memory)
         if isinstance(dataset, AudioDataset) and str(self.device).startswith("cuda"):
             base = (torch.utils.data.RandomSampler if lc.shuffle else torch.utils.data.SequentialSampler)(dataset)
             return DeviceMixLoader(dataset, torch.utils.data.BatchSampler(base, lc.batch_size, drop_last=False),

@@ -565,6 +565,21 @@ int nppc_pc_variation_waves(const float* pred, const float* pc, const float* cle
 int nppc_metrics_batch(const float* nppc, const float* mc, const float* pred, const float* clean, const float* mean,
                        const float* mask, double* G, int B, int n, long N, void* stream);
 
+/* ---- DNS dynamic mixing (fullsubnet_plus/dataset/dataset_train.py) ------------------------------------------------
+ * Batched, ragged, causal, truncated convolution with room impulse responses (:151, fftconvolve(clean, rir)[:L]):
+ * out[b][n] = sum_{k = 0..min(n, len_b - 1)} rir[b][k] * clean[b][n - k], len_b = min(rir_len[b], ldr, L); clean, out
+ * [B][L], rir [B][ldr], rir_len [B] on the device.  rir_len[b] == 0: out[b] is a bit-exact copy of clean[b].  Nothing at
+ * or past rir[b][rir_len[b]] is read.  Direct form in fp64, taps in ascending order: an item's result does not depend
+ * on B, ldr or the other items.  out must not alias clean. */
+int nppc_rir_convolve(const float* clean, const float* rir, const int* rir_len, float* out, int B, int L, int ldr,
+                      void* stream);
+/* Dataset.snr_mix after the convolution (:153-182) for a batch: norm_amplitude and tailor_dB_FS(target_dbfs) of clean
+ * and noise, SNR scaling by snr_db[b], tailor_dB_FS of the mixture to noisy_target_dbfs[b], and the clip rule (any
+ * |noisy| > 0.999: both divided by max|noisy| / (0.99 - 1e-6)); eps = 1e-6 everywhere.  clean, noise, noisy_out,
+ * clean_out [B][L]; the outputs must not alias the inputs.  fp64 sums in a fixed order, one workgroup per clip. */
+int nppc_dns_snr_mix(const float* clean, const float* noise, const float* snr_db, const float* noisy_target_dbfs,
+                     float target_dbfs, float* noisy_out, float* clean_out, int B, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
