@@ -239,6 +239,11 @@ SIGS = {
     "nppc_subband_mean_ragged": [I, P, I, P, I, L, P, P, P, I, I, I, I, I, I, P],
     "nppc_crop_frames_ragged": [P, L, I, P, I, P],
     "nppc_crm_mse_ragged": [P, P, P, P, P, P, I, I, I, F, P, P],
+    "nppc_rawmag_stage_ragged": [I, P, P, P, I, I, I, I, I, P],
+    "nppc_gram_ragged_work_elems": [I, I, I, I, PL],
+    "nppc_gram_ragged": [P, P, P, P, P, L, P, I, I, I, I, P],
+    "nppc_combine_ragged": [P, P, P, P, I, I, I, I, P],
+    "nppc_cirm_build_compress_ragged": [P, P, P, P, P, P, I, I, I, F, P],
     "nppc_istft_any": [P, P, L, P, L, I, I, I, I, I, P],
     "nppc_pc_variation_waves": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "nppc_metrics_batch": [P, P, P, P, P, P, P, I, I, L, P],

@@ -287,9 +287,9 @@ class FSNEngine:
         """maps: 3*n_maps tensors [B,1,F,T] fp32 ordered (mag, real, imag)[, (enh mag, real, imag)].
         Returns the net output [B', O, F', T] fp32 (B' in drop-band order) and keeps what backward needs.
 
-        frames: None, or a device int32 [B] of per-item frame counts T_b <= T (ragged inference, n_maps = 1): item b's
+        frames: None, or a device int32 [B] of per-item frame counts T_b <= T (ragged inference, either net): item b's
         output is the output of its first T_b frames run alone (no drop-band), frames t >= T_b of it are 0.  T comes from
-        the padded input's shape: nothing is read back from the device (DESIGN.md §7e)."""
+        the padded input's shape: nothing is read back from the device (DESIGN.md §7e, §7g)."""
         H.require_gpu()
         assert len(maps) == 3 * self.nm
         for m in maps:
@@ -300,8 +300,6 @@ class FSNEngine:
         if ragged:
             if train:
                 raise RuntimeError("ragged batches (frames=) are inference only: no train-mode forward")
-            if self.nm != 1:
-                raise NotImplementedError("ragged batches are built for the restorer (n_maps = 1)")
             if not (frames.is_cuda and frames.dtype == torch.int32 and frames.shape == (B,)):
                 raise ValueError(f"frames must be a device int32 tensor of shape ({B},)")
             frames = frames.contiguous()
@@ -332,7 +330,10 @@ class FSNEngine:
         else:
             H.call("nppc_tsse_fwd_maps", prec, H.ptr_array(maps), 3 * self.nm, d["rs"], *tsse_w, d["scale"], *sv_, d["X"][0],
                    R * ldC, B, F, T, self.la, Tp, ldC, s)
-        if self.nm == 2:
+        if self.nm == 2 and ragged:
+            # every row of the (reused) buffer: the item's own frames, zeros from T_b on
+            H.call("nppc_rawmag_stage_ragged", prec, maps[0], d["rawmag"], frames, B, F, T, Tp, ldF, s)
+        elif self.nm == 2:
             H.call("nppc_scale_transpose", prec, maps[0], None, d["rawmag"], B, F, T, Tp, ldF, 0, s)
         # 4: eight TCN blocks, the three branches batched over blockIdx.z
         d["stats"].zero_()

@@ -21,7 +21,8 @@ import torch
 
 from . import _hip as H
 
-__all__ = ["si_sdr", "si_sdr_zero_mean", "si_sdr_both", "stoi", "stoi_stages", "resample_window", "REGISTERED_METRICS"]
+__all__ = ["si_sdr", "si_sdr_zero_mean", "si_sdr_both", "stoi", "stoi_stages", "resample_window", "REGISTERED_METRICS",
+           "nppc_direction_scores"]
 
 SR = 16000
 UP, DOWN = 5, 8                 # 16 kHz -> 10 kHz
@@ -158,3 +159,42 @@ REGISTERED_METRICS = {
     "NB_PESQ": _not_built("NB_PESQ", "PESQ (ITU-T P.862) is not implemented in this build"),
     "MOSNET": _not_built("MOSNET", "MOSNet needs a pretrained network this build does not have"),
 }
+
+
+def nppc_direction_scores(err_norm, err_proj_mag, w_norms):
+    """How good are NPPC directions on held-out clips?  Pure host fp64 algebra on the loss's own per-item outputs (runs
+    without a GPU): err_norm [B] = |e|, the norm of the restorer's error e = gt - pred in the compressed-cIRM domain;
+    err_proj_mag [B, K] = |<w_k, e>| / (|w_k| |e|), the loss's normalised projection of e on direction k; w_norms [B, K]
+    = |w_k| / |e|, the loss's normalised predicted spread.  The directions of an item are orthogonal (Gram-Schmidt), so
+    squared projections add up.
+
+      captured[b, k]  = sum_{j <= k} err_proj_mag[b, j]^2     share of the item's SQUARED error inside the span of its
+                                                              first k + 1 directions (the loss's normalisation: already
+                                                              divided by err_norm^2; times err_norm[b]^2 = absolute)
+      residual[b, k]  = 1 - captured[b, k]                    residual[b, K - 1] is the loss's reconst_err[b]
+      calibration[b, k] = err_proj_mag[b, k] / w_norms[b, k]  observed / predicted spread along direction k
+
+    and over the whole set:
+      captured_mean / residual_mean [K]: means over the items (residual_mean[K - 1] = the mean reconst_err);
+      captured_pooled / residual_pooled [K]: sum_b captured[b, k] err_norm[b]^2 / sum_b err_norm[b]^2, the share of the
+        set's total squared error (long and badly restored clips weigh more);
+      calibration [K] = sqrt(mean_b err_proj_mag[b, k]^2) / sqrt(mean_b w_norms[b, k]^2): 1.0 means the predicted spread
+        matches the observed one, below 1 the direction is over-confident about its own size.
+    Returns a dict of float64 numpy arrays."""
+    en = np.asarray(err_norm, dtype=np.float64).reshape(-1)
+    pm = np.asarray(err_proj_mag, dtype=np.float64)
+    wn = np.asarray(w_norms, dtype=np.float64)
+    if pm.ndim != 2 or pm.shape != wn.shape or pm.shape[0] != en.shape[0]:
+        raise ValueError(f"expected err_norm [B], err_proj_mag [B, K], w_norms [B, K]; got {en.shape}, {pm.shape}, {wn.shape}")
+    if pm.shape[0] == 0:
+        raise ValueError("nppc_direction_scores needs at least one item")
+    captured = np.cumsum(pm * pm, axis=1)
+    e2 = en * en
+    tot = e2.sum()
+    pooled = (captured * e2[:, None]).sum(axis=0) / tot if tot > 0 else np.full(pm.shape[1], np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cal_item = pm / wn
+        cal = np.sqrt((pm * pm).mean(axis=0)) / np.sqrt((wn * wn).mean(axis=0))
+    return {"captured": captured, "residual": 1.0 - captured, "calibration_item": cal_item,
+            "captured_mean": captured.mean(axis=0), "residual_mean": 1.0 - captured.mean(axis=0),
+            "captured_pooled": pooled, "residual_pooled": 1.0 - pooled, "calibration": cal}

@@ -62,13 +62,21 @@ class MultiDirectionFullSubNet_Plus(FullSubNet_Plus):
         self.fb_model_real = _SeqModel(2 * F, F, config.fb_model_hidden_size, "TCN")
         self.fb_model_imag = _SeqModel(2 * F, F, config.fb_model_hidden_size, "TCN")
 
-    def forward(self, noisy_mag, noisy_real, noisy_imag, enhanced_mag=None, enhanced_real=None, enhanced_imag=None):
-        """six [B,1,F,T] maps -> [B, 2*n_directions, F', T]"""
+    def forward(self, noisy_mag, noisy_real, noisy_imag, enhanced_mag=None, enhanced_real=None, enhanced_imag=None,
+                frames=None):
+        """six [B,1,F,T] maps -> [B, 2*n_directions, F', T]
+
+        frames (extension, inference only): device int32 [B] frame counts of a padded batch.  Item b's output is that of
+        its first T_b frames run alone, at all F bins (no drop-band), and 0 at frames t >= T_b."""
         maps = [noisy_mag, noisy_real, noisy_imag, enhanced_mag, enhanced_real, enhanced_imag]
         if any(m is None for m in maps):
             raise TypeError("MultiDirectionFullSubNet_Plus needs the three enhanced maps (networks.py:83-85 pads them)")
         H.require_gpu()
         params = [p for _, p in self.named_parameters()]
+        if frames is not None:
+            if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+                raise RuntimeError("the ragged forward (frames=) is inference only: call it under torch.no_grad()")
+            return self.engine().forward([m.detach() for m in maps], train=False, frames=frames)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             return _DirectionNetFn.apply(self, 6, *[m.detach() for m in maps], *params)
         return self.engine().forward([m.detach() for m in maps], train=False)

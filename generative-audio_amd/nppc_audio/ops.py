@@ -86,6 +86,17 @@ def cirm_build_compress(n_re, n_im, c_re, c_im, num_groups=1):
     return out
 
 
+def cirm_build_compress_ragged(n_re, n_im, c_re, c_im, frames):
+    """cirm_build_compress of a ragged batch, no drop-band: [B,F,T] x4 + device int32 frames [B] -> [B,2,F,T]; item b is
+    built on its frames t < T_b and is 0 from T_b on (the inputs are not read there)."""
+    n_re, n_im, c_re, c_im = (_f32c(t) for t in (n_re, n_im, c_re, c_im))
+    B, F, T = n_re.shape
+    frames = frames.to(device=n_re.device, dtype=torch.int32).contiguous()
+    out = torch.empty(B, 2, F, T, dtype=torch.float32, device=n_re.device)
+    H.call("nppc_cirm_build_compress_ragged", n_re, n_im, c_re, c_im, out, frames, B, F, T, EPS32, H.stream())
+    return out
+
+
 def cirm_decompress_apply_conj(crm, n_re, n_im, want_dec=False):
     """mask.py:57-60 then utils.py:241-249 (-> :75-79 with real/imag swapped = conj(mask)*noisy).
     crm [B,2,F,T] compressed; n_re/n_im [B,F,T] -> (dec [B,F,T,2]|None, enh_mag, enh_real, enh_imag)."""

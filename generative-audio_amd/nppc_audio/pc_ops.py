@@ -1,4 +1,7 @@
-"""autograd.Function wrappers of the Gram-Schmidt and NPPC-loss kernels (csrc/gsloss.hip)."""
+"""autograd.Function wrappers of the Gram-Schmidt and NPPC-loss kernels (csrc/gsloss.hip), and their ragged, forward-only
+forms (csrc/nppc_ragged.hip)."""
+import ctypes
+
 import torch
 
 from . import _hip as H
@@ -115,6 +118,66 @@ class NPPCLoss(torch.autograd.Function):
         dw = torch.empty_like(w)
         H.call("nppc_combine", w, M1, None, None, gt, pred, dw, B, K, N, s)
         return dw, None, None, None, None, None
+
+
+def _check_ragged(frames, B, *tensors):
+    H.require_gpu()
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("the ragged Gram-Schmidt / NPPC loss are forward only: call them under torch.no_grad()")
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.int32 and frames.shape == (B,)):
+        raise ValueError(f"frames must be a device int32 tensor of shape ({B},)")
+    return frames.contiguous()
+
+
+def gram_ragged(x, frames, gt=None, pred=None):
+    """fp64 Gram matrices [B,KV,KV,2] of x [B,K,2,F,T] (+ e = gt - pred [B,2,F,T] as index K) summed over f < F,
+    t < frames[b]: one fixed reduction order per item, nothing at t >= T_b is loaded."""
+    B, K, _, F, T = x.shape
+    frames = _check_ragged(frames, B, x)
+    KV = K + (gt is not None)
+    n = ctypes.c_long()
+    H.call("nppc_gram_ragged_work_elems", B, K, int(gt is not None), F, ctypes.byref(n))
+    work = torch.empty(n.value, dtype=torch.float64, device=x.device)
+    G = torch.empty(B, KV, KV, 2, dtype=torch.float64, device=x.device)
+    H.call("nppc_gram_ragged", x, gt, pred, G, work, n.value, frames, B, K, F, T, H.stream())
+    return G
+
+
+def gram_schmidt_to_crm_ragged(x, frames):
+    """gram_schmidt_to_crm of a ragged batch, forward only: x [B,K,2,F,T], item b orthogonalised over its frames
+    t < frames[b] (device int32 [B]) exactly as alone; w is 0 from T_b on.  The coefficient solve is nppc_gs_solve."""
+    B, K, _, F, T = x.shape
+    _check_ragged(frames, B, x)
+    x = x.detach().contiguous().float()
+    s = H.stream()
+    G = gram_ragged(x, frames)
+    C, Ch = torch.empty_like(G), torch.empty_like(G)
+    H.call("nppc_gs_solve", G, C, Ch, B, K, K, s)
+    w = torch.empty_like(x)
+    H.call("nppc_combine_ragged", x, C, w, frames, B, K, F, T, s)
+    return w
+
+
+def nppc_loss_ragged(w_mat, gt, pred, frames, lam, eps=1e-8, eps_in_norms=0):
+    """NPPCLoss.forward of a ragged batch, forward only: the same eight outputs, per-item tensors computed from the Gram
+    matrix of [w_0 .. w_{K-1}, gt - pred] over the item's own frames (nppc_loss_solve_eps on it, unchanged).  Nothing in
+    the loss averages over elements: every term is a ratio of the item's own norms and inner products.  objective =
+    mean_b reconst + lam * mean_{b,i} sm, items weighted equally."""
+    B, K = w_mat.shape[:2]
+    _check_ragged(frames, B, w_mat, gt, pred)
+    w = w_mat.detach().contiguous().float()
+    gt, pred = gt.detach().contiguous().float(), pred.detach().contiguous().float()
+    dev = w.device
+    G = gram_ragged(w, frames, gt, pred)
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    err_norm, reconst = f(B), f(B)
+    pr, pi, pm, wn, sm = f(B, K), f(B, K), f(B, K), f(B, K), f(B, K)
+    coefA = torch.empty(B, K, 4, dtype=torch.float64, device=dev)
+    coefE = torch.empty(B, K, 2, dtype=torch.float64, device=dev)
+    H.call("nppc_loss_solve_eps", G, err_norm, pr, pi, pm, wn, reconst, sm, coefA, coefE, B, K, float(eps),
+           int(eps_in_norms), H.stream())
+    objective = reconst.mean() + lam * sm.mean()
+    return reconst, objective, err_norm, pr, pi, pm, wn, sm
 
 
 def second_moment_weight(step, grace, lam):

@@ -26,10 +26,11 @@ import torch.optim as optim
 from . import _hip as H
 from . import ops
 from . import ops_lstm
-from .data import AudioDataset, DataConfig, DataLoaderConfig, DeviceMixLoader
+from . import metrics
+from .data import AudioDataset, DataConfig, DataLoaderConfig, DeviceMixLoader, RaggedBatch
 from .dp import FlatGradientReducer, mean_reduce_parameter_grads
 from .nppc_model import NPPCModel, NPPCModelConfig
-from .pc_ops import NPPCLoss, second_moment_weight
+from .pc_ops import NPPCLoss, nppc_loss_ragged, second_moment_weight
 
 
 class OptimizerConfig(pydantic.BaseModel):
@@ -85,8 +86,18 @@ def get_true_and_pred_crm(model, clean_waveform, noisy_waveform, num_groups_in_d
     return gt, pred
 
 
-def nppc_base_step(model, batch, step, grace, lam_cfg):
-    """trainer.py:234-317 as a free function: (reconst_err [B], objective [], log dict)."""
+def nppc_base_step(model, batch, step, grace, lam_cfg, lengths=None):
+    """trainer.py:234-317 as a free function: (reconst_err [B], objective [], log dict).
+
+    lengths [B] (or a `data.RaggedBatch`, which carries them): a batch of clips of different lengths, padded to one
+    width.  The step then runs under torch.no_grad() on the ragged kernels: every item is scored as if
+    it were run alone -- all F bins (no drop-band), its own frames only -- and the log holds the same per-item tensors;
+    maps in the log are 0 from an item's last frame on."""
+    if isinstance(batch, RaggedBatch):
+        lengths = batch.lengths if lengths is None else lengths
+        batch = (batch.noisy, batch.clean)
+    if lengths is not None:
+        return _nppc_base_step_ragged(model, batch, step, grace, lam_cfg, lengths)
     noisy_waveform, clean_waveform = batch
     w_mat = model(noisy_waveform)                          # [B, n_dirs, 2, F', T]
     groups = model.config.audio_pc_wrapper_configuration.multi_direction_configuration.num_groups_in_drop_band
@@ -105,6 +116,33 @@ def nppc_base_step(model, batch, step, grace, lam_cfg):
         'reconst_err': reconst_err.detach(),
         'second_moment_mse': sm.detach(),
         'objective': objective.detach(),
+    }
+    return reconst_err, objective, log
+
+
+@torch.no_grad()
+def _nppc_base_step_ragged(model, batch, step, grace, lam_cfg, lengths):
+    noisy_waveform, clean_waveform = batch
+    st = model.config.stft_configuration
+    w_mat = model(noisy_waveform, lengths=lengths)         # [B, n_dirs, 2, F, T], 0 from T_b on
+    f = model._front(noisy_waveform, lengths=lengths)      # the memo of the forward above
+    _, c_re, c_im = ops.stft(clean_waveform, st.nfft, st.hop_length, want_mag=False, lengths=f["lengths"])
+    gt_crm = ops.cirm_build_compress_ragged(f["re"], f["im"], c_re, c_im, f["frames"])
+    pred_crm = f["pred_crm"]
+    lam = second_moment_weight(step, grace, lam_cfg)
+    reconst_err, objective, err_norm, pr, pi, pm, w_norms, sm = nppc_loss_ragged(w_mat, gt_crm, pred_crm, f["frames"], lam)
+    log = {
+        'noisy_complex': noisy_waveform,
+        'clean_complex': clean_waveform,
+        'pred_crm': pred_crm,
+        'w_mat': w_mat,
+        'err_norm': err_norm,
+        'err_proj': torch.complex(pr, pi),
+        'err_proj_mag': pm,
+        'w_norms': w_norms,
+        'reconst_err': reconst_err,
+        'second_moment_mse': sm,
+        'objective': objective,
     }
     return reconst_err, objective, log
 
@@ -270,11 +308,81 @@ class NPPCAudioTrainer(nn.Module):
         self._seed = None
         self._pending = None
         self._poison = None
+        self.val_history = []
+        self.best_val_reconst_err = float("inf")
+        self._val = None
 
     # ---------------------------------------------------------------------------------- reference API
-    def base_step(self, batch):
+    def base_step(self, batch, lengths=None):
         return nppc_base_step(self.nppc_model, batch, self.step, self.config.second_moment_loss_grace,
-                              self.config.second_moment_loss_lambda)
+                              self.config.second_moment_loss_lambda, lengths=lengths)
+
+    # ---------------------------------------------------------------------------------- held-out validation
+    def validate(self, dataloader):
+        """Scores the current directions on held-out clips: `dataloader` yields `data.RaggedBatch`es (clips of different
+        lengths, data.pad_collate) or uniform (noisy [B,L], clean [B,L]) batches, which are ragged batches of equal
+        lengths.  Every clip is scored as if run alone (no drop-band, its own frames), whatever batch it arrives in.
+
+        Runs in eval mode under no_grad, after flush(): weights, Adam state, the parked-update machinery and the RNG are
+        what they were before the call.  The per-item results stay on the device until ONE [n_clips, 2 + 3K] host copy at
+        the end of the loader.  Returns a dict (JSON-serialisable; `metrics.nppc_direction_scores` of the per-item
+        values) and appends it to self.val_history."""
+        self.flush()
+        # (nn.Module.eval() / .train() of the trainer itself would land in the training loop `train` below)
+        modes = [(m, m.training) for m in self.nppc_model.modules()]
+        self.nppc_model.eval()
+        rows = []
+        cuda = []
+        if str(self.device).startswith("cuda") and torch.cuda.is_available():
+            idx = torch.device(self.device).index
+            cuda = [torch.cuda.current_device() if idx is None else idx]
+        try:
+            with torch.no_grad(), torch.random.fork_rng(devices=cuda):
+                for batch in dataloader:
+                    if isinstance(batch, RaggedBatch):
+                        noisy, clean, lengths = batch.noisy, batch.clean, batch.lengths
+                    else:
+                        noisy, clean = batch[0], batch[1]
+                        lengths = [noisy.shape[-1]] * (noisy.shape[0] if noisy.dim() > 1 else 1)
+                    noisy, clean = (x.to(self.device, non_blocking=True) for x in (noisy, clean))
+                    _, _, log = self.base_step((noisy, clean), lengths=lengths)
+                    rows.append(torch.cat([log["err_norm"][:, None], log["reconst_err"][:, None], log["err_proj_mag"],
+                                           log["w_norms"], log["second_moment_mse"]], dim=1))
+                if not rows:
+                    raise ValueError("the validation loader yields no batch")
+                block = torch.cat(rows).cpu().double().numpy()       # the one host copy of the loader
+        finally:
+            for m, mode in modes:
+                m.training = mode
+        self._check_timeouts(f"validation at step {self.step}")
+        K = (block.shape[1] - 2) // 3
+        en, rec, pm, wn, sm = block[:, 0], block[:, 1], block[:, 2:2 + K], block[:, 2 + K:2 + 2 * K], block[:, 2 + 2 * K:]
+        sc = metrics.nppc_direction_scores(en, pm, wn)
+        lam = second_moment_weight(self.step, self.config.second_moment_loss_grace, self.config.second_moment_loss_lambda)
+        out = {
+            "step": self.step, "n_clips": int(block.shape[0]),
+            "reconst_err": float(rec.mean()), "second_moment_mse": float(sm.mean()),
+            "objective": float(rec.mean() + lam * sm.mean()), "err_norm": float(en.mean()),
+            "captured": sc["captured_mean"].tolist(), "residual": sc["residual_mean"].tolist(),
+            "captured_pooled": sc["captured_pooled"].tolist(), "residual_pooled": sc["residual_pooled"].tolist(),
+            "calibration": sc["calibration"].tolist(),
+            "per_item": {"err_norm": en.tolist(), "reconst_err": rec.tolist(), "err_proj_mag": pm.tolist(),
+                         "w_norms": wn.tolist(), "second_moment_mse": sm.tolist()},
+        }
+        self.val_history.append(out)
+        return out
+
+    def _validate_and_keep_best(self, val_dataloader, checkpoint_dir):
+        m = self.validate(val_dataloader)
+        if self.rank == 0:
+            print(f'step {self.step}: validation on {m["n_clips"]} clips | Reconstract Error: {m["reconst_err"]:.4f} | '
+                  f'Second Moment MSE: {m["second_moment_mse"]:.4f} | calibration: '
+                  + " ".join(f"{c:.2f}" for c in m["calibration"]))
+            if m["reconst_err"] < self.best_val_reconst_err:
+                self.best_val_reconst_err = m["reconst_err"]
+                torch.save({'model_state_dict': self.nppc_model.state_dict(), 'step': self.step,
+                            'reconst_err': m["reconst_err"]}, os.path.join(checkpoint_dir, "best_model.pth"))
+        return m
 
     def _calculate_final_objective(self, reconst_err, second_moment_mse):
         lam = second_moment_weight(self.step, self.config.second_moment_loss_grace, self.config.second_moment_loss_lambda)
@@ -360,7 +468,22 @@ class NPPCAudioTrainer(nn.Module):
             eng.prepack_on_side()
             reng.pre_lstm_hook = eng.join_side
 
-    def train(self, n_steps=None, n_epochs=None, checkpoint_dir="checkpoints", log_every=None):
+    def train(self, n_steps=None, n_epochs=None, checkpoint_dir="checkpoints", log_every=None, val_dataloader=None,
+              validate_every=None):
+        """val_dataloader: held-out clips (see `validate`), scored every `validate_every` optimisation steps and once more
+        at the end if the last step was not scored; validate_every=None: at each checkpoint, i.e. with the final one.
+        The history goes to <checkpoint_dir>/val_history_<timestamp>.json next to the training metrics, and
+        <checkpoint_dir>/best_model.pth = {'model_state_dict', 'step', 'reconst_err'} keeps the weights with the lowest
+        mean reconst_err.  Without a val_dataloader nothing changes.
+        Every rank validates (the whole loader, not a shard: the time-out check in `validate` is collective); rank 0 alone
+        prints, tracks `best_val_reconst_err` and writes best_model.pth and the history file.  `val_history` and the best
+        score belong to the trainer, not to one call: a second `train` goes on appending, and each history file holds the
+        whole list so far."""
+        if val_dataloader is None and validate_every is not None:
+            raise ValueError("validate_every needs a val_dataloader")
+        if validate_every is not None and validate_every < 1:
+            raise ValueError("validate_every must be a positive number of steps")
+        self._val = (val_dataloader, validate_every, checkpoint_dir) if val_dataloader is not None else None
         os.makedirs(checkpoint_dir, exist_ok=True)
         loop_loader = LoopLoader(dataloader=self.dataloader, n_steps=n_steps, n_epochs=n_epochs)
         log_every = log_every or self.config.log_interval
@@ -373,8 +496,15 @@ class NPPCAudioTrainer(nn.Module):
             self._train_loop(loop_loader, log_every)
         finally:
             self.pipeline_update = False
+            self._val = None
         log_dict = self._last_log
         timestamp = datetime.now().strftime("%Y%m%d_%H%M%S")
+        if val_dataloader is not None:
+            if not self.val_history or self.val_history[-1]["step"] != self.step:
+                self._validate_and_keep_best(val_dataloader, checkpoint_dir)
+            if self.rank == 0:
+                with open(os.path.join(checkpoint_dir, f"val_history_{timestamp}.json"), 'w') as f:
+                    json.dump(self.val_history, f, indent=1)
         if self.rank == 0 and log_dict is not None:
             self._get_and_save_metrics(checkpoint_dir, log_dict, n_epochs, n_steps, timestamp)
             self.save_checkpoint(os.path.join(checkpoint_dir, f"checkpoint_final_{timestamp}.pt"))
@@ -412,6 +542,9 @@ class NPPCAudioTrainer(nn.Module):
                       f'Second Moment MSE: {log_dict["second_moment_mse"].mean().item():.4f} | '
                       f'Reconstract Error: {reconst_err.mean().item():.4f}')
             self._last_log = log_dict
+            val = self._val
+            if val is not None and val[1] is not None and self.step % val[1] == 0:
+                self._validate_and_keep_best(val[0], val[2])
         self.flush()
 
     def _get_and_save_metrics(self, checkpoint_dir, log_dict, n_epochs, n_steps, timestamp):

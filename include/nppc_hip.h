@@ -542,6 +542,28 @@ int nppc_crop_frames_ragged(float* x, long rows, int T, const int* frames, int B
 int nppc_crm_mse_ragged(const float* nr, const float* ni, const float* cr, const float* ci, const float* crm, const int* frames,
                         int B, int F, int T, float eps, double* loss, void* stream);
 
+/* ---- ragged NPPC validation step (csrc/nppc_ragged.hip) ------------------------------------------------
+ * Item b of a padded batch lives in frames t < T_b = frames[b] (device int[B]) of planes [..][F][T].  Its results equal
+ * those of the item alone (B = 1, T = T_b) BIT FOR BIT: elements at t >= T_b are never loaded, every sum has one writer
+ * and an order that depends on (F, T_b) only (no float or double atomics).  Forward only. */
+/* raw magnitude x [B][F][T] -> y [B][Tp][ld] (the sub-band source of the direction net): rows t < T_b transposed, rows
+ * T_b <= t < Tp written as 0 */
+int nppc_rawmag_stage_ragged(int prec, const float* x, void* y, const int* frames, int B, int F, int T, int Tp, int ld,
+                             void* stream);
+/* doubles of workspace nppc_gram_ragged needs */
+int nppc_gram_ragged_work_elems(int B, int K, int with_e, int F, long* n);
+/* out [B][KV][KV] complex double = <a_i, a_n> summed over f < F, t < T_b; a [B][K][2][F][T]; with gt / pred [B][2][F][T]
+ * the set has e = gt - pred as index K (KV = K + 1 <= 9).  `out` is overwritten (no need to zero it). */
+int nppc_gram_ragged(const float* a, const float* gt /*nullable*/, const float* pred /*nullable*/, double* out, double* work,
+                     long work_elems, const int* frames, int B, int K, int F, int T, void* stream);
+/* out_i = sum_m M1[b][i][m] a_m on t < T_b, 0 on T_b <= t < T; a, out [B][K][2][F][T], M1 [B][K][K] complex double;
+ * K <= 8 (NPPC_EUNSUPPORTED beyond) */
+int nppc_combine_ragged(const float* a, const double* M1, float* out, const int* frames, int B, int K, int F, int T,
+                        void* stream);
+/* nppc_cirm_build_compress without drop-band: out [B][2][F][T], 0 on t >= T_b (inputs not read there) */
+int nppc_cirm_build_compress_ragged(const float* nr, const float* ni, const float* cr, const float* ci, float* out,
+                                    const int* frames, int B, int F, int T, float eps, void* stream);
+
 /* ---- inpainting validator (csrc/inpaint_validator.hip, DESIGN.md section 8 "Inpainting validator") --------------------
  * nppc_istft_any: torch.istft(n_fft, hop, win_length = n_fft, periodic hann, center=True, length=L) for ANY n_fft <= 512,
  * 1 <= hop <= n_fft, ceil(n_fft / hop) <= 8: re, im [B][F][T] planes, item b at re + b * sb (sb >= F T floats) ->
