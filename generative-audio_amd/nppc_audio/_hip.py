@@ -249,6 +249,10 @@ SIGS = {
     "nppc_metrics_batch": [P, P, P, P, P, P, P, I, I, L, P],
     "nppc_rir_convolve": [P, P, P, P, I, I, I, P],
     "nppc_dns_snr_mix": [P, P, P, P, F, P, P, I, I, P],
+    "nppc_pyin_shape": [I, L, D, D, D, I, I, I, D, D, PI, PI, PI, PI, PI, PL],
+    "nppc_pyin_cmnd": [P, P, P, I, L, I, I, I, I, I, P],
+    "nppc_pyin_observe": [P, P, P, P, P, I, I, L, I, I, I, I, I, I, D, D, D, D, P],
+    "nppc_pyin_viterbi": [P, P, P, P, P, P, I, I, L, I, I, I, I, D, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

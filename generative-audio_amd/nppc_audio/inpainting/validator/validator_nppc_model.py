@@ -8,8 +8,11 @@ mc_baseline.calculate_unet_baseline (batched PCA), the metrics come from one Gra
 (mc_baseline.metrics_gram_batch) and ONE device-to-host copy per `validate_dataloader` call, and the K x A + 1 waveforms
 of `pc_audio_variations` come from one launch whose complex spectrograms never reach memory.
 
-Outside this build: whisper / phoneme transcription, pitch and spectrogram plots, wav files, splicing a variation into
-the full source file (get_with_full_audio), wandb.
+`validate_batch(..., pitch=True)` adds the f0 contours of plot_pitch_comparison (:19-270) for the clean waveform and every
+variation, tracked on the device (nppc_audio/pitch.py), and what each direction does to them.
+
+Outside this build: whisper / phoneme transcription, the plots themselves (pitch and spectrogram), wav files, splicing a
+variation into the full source file (get_with_full_audio), wandb.
 """
 import json
 from pathlib import Path
@@ -21,6 +24,7 @@ import torch
 
 from ... import _hip as H
 from ... import ops
+from ... import pitch as PT
 from .. import mc_baseline as MB
 from ..nppc.nppc_model import NPPCModel, NPPCModelConfig
 from ..utils import preprocess_data
@@ -136,12 +140,19 @@ class NPPCModelValidator:
                 'mask': mask4, 'mean': mean, 'std': std, 'mc_dropout': mc, 'gram': gram, 'clean_spec': clean_spec}
 
     def validate_batch(self, masked_spec, mask, clean_spec, n_mc_samples=50, n_components=5, alphas=None, n_fft=255,
-                       hop_length=128):
+                       hop_length=128, pitch=False):
         """validate_sample + _validate_with_baseline (:930-1027) for a uniform batch: masked_spec, clean_spec [B,2,F,T],
         mask [B,T] (1 = known; the same number of gap frames in every item) -> dict with 'pc_directions' [B,K,F,T],
         'pred_spec_mag_norm', 'clean_spec_mag_norm', 'mask' [B,1,F,T], 'mean', 'std', 'mc_dropout' (calculate_unet_baseline's
         dict), 'metrics' (list of B compute_metrics dicts) and, when `alphas` is given, 'audio_variations' [B,K,A,L] and
-        'clean_audio' [B,L] (pc_audio_variations)."""
+        'clean_audio' [B,L] (pc_audio_variations).
+
+        pitch=True (needs `alphas`; ValueError otherwise) adds 'pitch': pYIN contours at the reference's setting (fmin 80,
+        fmax 400, sr 16000; plot_pitch_comparison :60-66) of the clean waveform and of every variation, from one batched
+        call: {'f0_clean' [B,T'], 'voiced_flag_clean', 'voiced_prob_clean', 'f0' [B,K,A,T'], 'voiced_flag', 'voiced_prob',
+        'summary' (pitch.pitch_variation_summary, [B,K,A] tensors)}, T' = 1 + L // 512.  Everything else is unchanged."""
+        if pitch and alphas is None:
+            raise ValueError("pitch=True tracks the f0 of the PC audio variations: pass `alphas` (e.g. default_alphas())")
         out = self._run_batch(masked_spec, mask, clean_spec, n_mc_samples, n_components)
         out['metrics'] = MB.metrics_from_gram(out.pop('gram').cpu().numpy(), n_components)
         clean_spec = out.pop('clean_spec')
@@ -150,6 +161,9 @@ class NPPCModelValidator:
                 out['audio_variations'], out['clean_audio'] = pc_audio_variations(
                     out['clean_spec_mag_norm'], out['pred_spec_mag_norm'], out['pc_directions'], clean_spec, alphas,
                     out['mean'], out['std'], n_fft=n_fft, hop_length=hop_length)
+                if pitch:
+                    out['pitch'] = PT.contours_of_variations(out['clean_audio'], out['audio_variations'],
+                                                             **PT.REFERENCE_SETTING)
         return out
 
     def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False):

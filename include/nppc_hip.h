@@ -602,6 +602,35 @@ int nppc_rir_convolve(const float* clean, const float* rir, const int* rir_len, 
 int nppc_dns_snr_mix(const float* clean, const float* noise, const float* snr_db, const float* noisy_target_dbfs,
                      float target_dbfs, float* noisy_out, float* clean_out, int B, int L, void* stream);
 
+/* ---- batched pYIN f0 tracking (csrc/pitch.hip; specification tests/pyin_ref.py) ------------------
+ * Supported: 2 <= frame_length <= 2048, 1 <= win_length < frame_length, hop_length >= 1,
+ * 1 <= min_period < max_period < frame_length - win_length, n_pitch_bins <= 768, n_thresholds <= 1024; anything else is
+ * NPPC_EBADARG.  Item n of y [N][L] has lengths[n] samples (device int [N], nullable: L) and 1 + lengths[n] / hop_length
+ * frames of its own; T = 1 + L / hop_length.  No atomics; an item's results do not depend on the batch. */
+/* Shapes of a call, without a GPU: min_period = max(floor(sr / fmax), 1), max_period = min(ceil(sr / fmin), frame_length -
+ * win_length - 1), P = max_period - min_period + 1, n_pitch_bins = floor(12 ceil(1 / resolution) log2(fmax / fmin)) + 1,
+ * width = 2 round(max_transition_rate 12 hop_length / sr) ceil(1 / resolution) + 1 (round half to even), ws_bytes = the
+ * bytes of the Viterbi back-pointers [N][T][2 n_pitch_bins] uint16.  Output pointers may be null. */
+int nppc_pyin_shape(int N, long L, double sr, double fmin, double fmax, int frame_length, int win_length, int hop_length,
+                    double resolution, double max_transition_rate, int* T, int* P, int* min_period, int* n_pitch_bins,
+                    int* width, long* ws_bytes);
+/* y [N][L] -> dprime [N][T][P] fp32: the cumulative-mean-normalised difference d'(tau), tau = min_period..max_period, of
+ * every frame of the signal zero-padded by frame_length / 2 on both sides; d(tau) < 1e-6 counts as 0; rows of frames past
+ * an item's own are 0. */
+int nppc_pyin_cmnd(const float* y, const int* lengths, float* dprime, int N, long L, int frame_length, int win_length,
+                   int hop_length, int min_period, int max_period, void* stream);
+/* dprime [N][T][P] -> obs [N][T][2 n_pitch_bins] fp32 (voiced bins, then the unvoiced states) and voiced_prob [N][T];
+ * beta_w [n_thresholds] (device, fp64) = the threshold weights.  Rows of frames past an item's own are 0. */
+int nppc_pyin_observe(const float* dprime, const int* lengths, const double* beta_w, float* obs, float* voiced_prob, int N,
+                      int T, long L, int hop_length, int P, int min_period, int n_thresholds, int n_pitch_bins,
+                      int bins_per_semitone, double sr, double fmin, double boltzmann, double no_trough_prob, void* stream);
+/* obs -> f0 [N][T] fp32 (NaN where unvoiced), voiced_flag [N][T] uint8; frames past an item's own: NaN / 0.  hmm_tab
+ * (device, fp64) = log tri [width], log rowsum [n_pitch_bins], log stay, log switch, log init; backptr = ws_bytes of
+ * nppc_pyin_shape. */
+int nppc_pyin_viterbi(const float* obs, const int* lengths, const double* hmm_tab, unsigned short* backptr, float* f0,
+                      unsigned char* voiced_flag, int N, int T, long L, int hop_length, int n_pitch_bins,
+                      int bins_per_semitone, int width, double fmin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
