@@ -231,6 +231,11 @@ SIGS = {
     "nppc_stoi_frames": [P, P, I, L, I, P, P, P, P, P],
     "nppc_stoi_bands": [P, P, L, P, P, I, I, P, P, P],
     "nppc_stoi_corr": [P, P, P, I, I, P, P],
+    "nppc_bss_shape": [L, I, PI, PI, PI, PL, PL],
+    "nppc_bss_corr": [P, P, P, I, L, I, P, L, P],
+    "nppc_bss_solve": [P, P, I, L, I, P, P, P, P, P],
+    "nppc_bss_project": [P, P, P, I, L, I, P, P, P, L, P, P, P, P],
+    "nppc_bss_scale": [P, P, P, I, L, P, P, P],
     "nppc_stft_ragged": [P, L, P, P, P, P, I, I, I, I, P],
     "nppc_istft_ragged": [P, P, P, L, P, I, I, I, I, P],
     "nppc_tsse_fwd_maps_ragged": [I, P, I, P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, L, P, P, L, P, I, I, I, I, I, I, P],

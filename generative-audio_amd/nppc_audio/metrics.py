@@ -1,4 +1,4 @@
-"""Speech-enhancement metrics on the device: STOI and SI-SDR of ragged batches (audio_zen/metrics.py:61-89,
+"""Speech-enhancement metrics on the device: STOI, SI-SDR and BSS-eval SDR of ragged batches (audio_zen/metrics.py:8-89,
 use_pre_trained_model/model_validator/model_validator.py:56-65).
 
 Every function takes [B, L] or [L] device tensors (clean / reference first, estimate second) and an optional per-item
@@ -11,6 +11,12 @@ tensor.  An item's value depends on its own samples only and is bit-identical in
   ("Speech-enhancement metrics").  pystoi is not available to this project: agreement with pystoi itself is unverified;
   the kernels are tested stage by stage against a float64 numpy restatement of that contract.
 
+- `sdr`: audio_zen's SDR, i.e. mir_eval.separation.bss_eval_sources for one source (the estimate projected on the span of
+  `filter_length` = 512 delayed copies of the reference), as DESIGN.md section 7d "BSS-eval SDR" states it.  mir_eval is
+  not available to this project: agreement with mir_eval itself is unverified; the kernels are tested stage by stage
+  against a float64 numpy restatement of that contract (tests/bss_eval_ref.py).
+- `scale_bss_eval`: audio_zen's _scale_bss_eval without SIR / SAR (si_sdr, sd_sdr, snr, srr).
+
 PESQ (WB / NB) and MOSNET are registered names that raise NotImplementedError, so a metric list taken from train.toml fails
 loudly instead of silently dropping a metric.
 """
@@ -22,11 +28,18 @@ import torch
 from . import _hip as H
 
 __all__ = ["si_sdr", "si_sdr_zero_mean", "si_sdr_both", "stoi", "stoi_stages", "resample_window", "REGISTERED_METRICS",
-           "nppc_direction_scores"]
+           "nppc_direction_scores", "sdr", "sdr_stages", "scale_bss_eval", "BSS_MAX_FILTER", "BSS_CORR_CHUNK",
+           "BSS_CORR_TILE", "BSS_PROJ_CHUNK"]
 
 SR = 16000
 UP, DOWN = 5, 8                 # 16 kHz -> 10 kHz
 N_FRAME, HOP, NUMBAND = 256, 128, 15
+
+# csrc/bss_eval.hip (nppc_bss_shape reports the same numbers; tests/test_bss_eval_cpu.py keeps the two in step)
+BSS_MAX_FILTER = 512            # longest projection filter
+BSS_CORR_CHUNK = 8192           # samples per workgroup of the correlation kernel (one row of partial sums each)
+BSS_CORR_TILE = 1024            # samples that workgroup stages in LDS at a time
+BSS_PROJ_CHUNK = 1024           # output samples per workgroup of the projection kernel
 
 _TAPS = {}
 
@@ -136,6 +149,63 @@ def stoi(clean, est, sr=SR, lengths=None):
     return stoi_stages(clean, est, sr, lengths)["stoi"]
 
 
+def _filter_length(filter_length):
+    if isinstance(filter_length, bool) or not isinstance(filter_length, (int, np.integer)) \
+            or not 1 <= filter_length <= BSS_MAX_FILTER:
+        raise ValueError(f"filter_length = {filter_length!r} must be an integer in [1, {BSS_MAX_FILTER}]")
+    return int(filter_length)
+
+
+def sdr_stages(ref, est, lengths=None, filter_length=512):
+    """the BSS-eval SDR launch sequence with every intermediate kept.  Per item (s = ref, e = est, n samples, P =
+    filter_length, M = n + P - 1): r [B, P] = sum_m s[m] s[m - t] and d [B, P] = sum_m e[m] s[m - t], c [B, P] the solution
+    of toeplitz(r) c = d (Levinson-Durbin), num / den [B] = sum over all M samples of proj^2 / (e - proj)^2 with
+    proj[m] = sum_t c[t] s[m - t], sdr [B] = 10 log10(num / den) (+inf when den == 0), status [B] int32 (non-zero: the
+    solve broke down and num, den, sdr are NaN).  All float64."""
+    P = _filter_length(filter_length)
+    ref, est, lens = _batch(ref, est, lengths)
+    B, L = ref.shape
+    dev = ref.device
+    n_corr = -(-L // BSS_CORR_CHUNK) * 2 * P
+    n_proj = -(-(L + P - 1) // BSS_PROJ_CHUNK) * 2
+    part = torch.empty(B * n_corr, dtype=torch.float64, device=dev)
+    r = torch.empty(B, P, dtype=torch.float64, device=dev)
+    d, c = torch.empty_like(r), torch.empty_like(r)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    H.call("nppc_bss_corr", ref, est, lens, B, L, P, part, part.numel(), H.stream())
+    H.call("nppc_bss_solve", part, lens, B, L, P, r, d, c, status, H.stream())
+    part2 = torch.empty(B * n_proj, dtype=torch.float64, device=dev)
+    num = torch.empty(B, dtype=torch.float64, device=dev)
+    den, out = torch.empty_like(num), torch.empty_like(num)
+    H.call("nppc_bss_project", ref, est, lens, B, L, P, c, status, part2, part2.numel(), num, den, out, H.stream())
+    return dict(r=r, d=d, c=c, status=status, num=num, den=den, sdr=out)
+
+
+def sdr(ref, est, lengths=None, filter_length=512):
+    """audio_zen/metrics.py:56-58 per item: mir_eval.separation.bss_eval_sources(ref[None], est[None])[0] as DESIGN.md
+    section 7d states it (the classical SDR: a linear distortion of the reference shorter than filter_length samples, a
+    delay included, is forgiven) -> [B] float64.  +inf when the estimate lies in the span exactly.  NaN for an item whose
+    reference is all zeros (mir_eval raises ValueError there; a batched launch cannot) or whose Toeplitz solve breaks down
+    (a non-positive pivot or prediction error); the other items are unaffected.  Unverified against mir_eval itself."""
+    return sdr_stages(ref, est, lengths, filter_length)["sdr"]
+
+
+def scale_bss_eval(ref, est, lengths=None, return_sums=False):
+    """audio_zen/metrics.py:8-53 with compute_sir_sar=False per item, alpha = <s, e> / |s|^2 -> dict of [B] float64:
+    si_sdr = 10 log10(|alpha s|^2 / |e - alpha s|^2), sd_sdr = snr + 10 log10(alpha^2), snr = 10 log10(|s|^2 / |e - s|^2),
+    srr = -10 log10((1 - 1 / alpha)^2).  Every energy is summed directly in fp64 (no expansion, so no cancellation);
+    return_sums adds "sums" [B, 4] = |s|^2, <s, e>, |e - s|^2, |e - alpha s|^2."""
+    ref, est, lens = _batch(ref, est, lengths)
+    B, L = ref.shape
+    out = torch.empty(B, 4, dtype=torch.float64, device=ref.device)
+    sums = torch.empty(B, 4, dtype=torch.float64, device=ref.device) if return_sums else None
+    H.call("nppc_bss_scale", ref, est, lens, B, L, sums, out, H.stream())
+    res = {"si_sdr": out[:, 0], "sd_sdr": out[:, 1], "snr": out[:, 2], "srr": out[:, 3]}
+    if return_sums:
+        res["sums"] = sums
+    return res
+
+
 def _not_built(name, reason):
     def metric(ref, est, sr=SR, lengths=None):
         raise NotImplementedError(f"{name}: {reason}")
@@ -151,10 +221,15 @@ def _si_sdr_metric(ref, est, sr=SR, lengths=None):
     return si_sdr(ref, est, lengths=lengths)
 
 
+def _sdr_metric(ref, est, sr=SR, lengths=None):
+    return sdr(ref, est, lengths=lengths)
+
+
 # audio_zen/metrics.py:143-149: only registered metrics can be used; each is metric(ref, est, sr=..) -> [B] float64 here
 REGISTERED_METRICS = {
     "SI_SDR": _si_sdr_metric,
     "STOI": _stoi_metric,
+    "SDR": _sdr_metric,
     "WB_PESQ": _not_built("WB_PESQ", "PESQ (ITU-T P.862) is not implemented in this build"),
     "NB_PESQ": _not_built("NB_PESQ", "PESQ (ITU-T P.862) is not implemented in this build"),
     "MOSNET": _not_built("MOSNET", "MOSNet needs a pretrained network this build does not have"),

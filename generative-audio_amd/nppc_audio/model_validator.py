@@ -5,7 +5,7 @@ The reference enhances and scores one clip at a time on the host (pesq, pystoi, 
 at once (ops.stft, the FullSubNet_Plus inference forward, ops.model_outputs_to_waveforms) and scored on the device
 (nppc_audio.metrics: STOI and the mean-removed SI-SDR of calculate_metrics); the per-item scores stay on the device until
 the end of `validate_dataloader`, which copies them to the host once.  PESQ is not part of this build, so the metrics are
-{"STOI", "SI_SDR"}.
+{"STOI", "SI_SDR"}; `extra_metrics=("SDR",)` adds the BSS-eval SDR of audio_zen/metrics.py:56-58 (metrics.sdr).
 """
 import json
 from typing import Dict, Literal
@@ -20,7 +20,9 @@ from .data import RaggedBatch
 from .fullsubnet import FullSubNetPlusConfig
 from .nppc_model import StftConfig, load_pretrained_model
 
-__all__ = ["AudioConfig", "ModelValidatorConfig", "ModelValidator"]
+__all__ = ["AudioConfig", "ModelValidatorConfig", "ModelValidator", "EXTRA_METRICS"]
+
+EXTRA_METRICS = ("SDR",)        # names calculate_metrics_batch can add to {"STOI", "SI_SDR"}
 
 
 class AudioConfig(pydantic.BaseModel):      # utils.py:20-22
@@ -76,24 +78,42 @@ class ModelValidator:
         if sr != metrics.SR:
             raise ValueError(f"sr = {sr}: the metrics are built for 16000 Hz audio")
 
-    def calculate_metrics_batch(self, clean: torch.Tensor, enhanced: torch.Tensor, sr: int = 16000, lengths=None):
-        """per-item device scores {"STOI": [B], "SI_SDR": [B]} float64 (no host synchronisation)"""
-        self._check_sr(sr)
-        clean, enhanced = clean.to(self.device), enhanced.to(self.device)
-        return {"STOI": metrics.stoi(clean, enhanced, sr=sr, lengths=lengths),
-                "SI_SDR": metrics.si_sdr_zero_mean(clean, enhanced, lengths=lengths)}
+    @staticmethod
+    def _check_extra(extra_metrics):
+        extra = tuple(extra_metrics)
+        for name in extra:
+            if name not in EXTRA_METRICS:
+                raise ValueError(f"extra metric {name!r}: only {sorted(EXTRA_METRICS)} can be added")
+        return extra
 
-    def calculate_metrics(self, clean, enhanced, sr: int = 16000) -> Dict[str, float]:
-        """model_validator.py:34-77 for one clip: {"STOI", "SI_SDR"} (the mean-removed SI-SDR of the reference)"""
+    def calculate_metrics_batch(self, clean: torch.Tensor, enhanced: torch.Tensor, sr: int = 16000, lengths=None,
+                                extra_metrics=()):
+        """per-item device scores {"STOI": [B], "SI_SDR": [B]} float64 (no host synchronisation); every name of
+        extra_metrics (only "SDR": metrics.sdr) adds a key of the same kind"""
+        self._check_sr(sr)
+        extra = self._check_extra(extra_metrics)
+        clean, enhanced = clean.to(self.device), enhanced.to(self.device)
+        m = {"STOI": metrics.stoi(clean, enhanced, sr=sr, lengths=lengths),
+             "SI_SDR": metrics.si_sdr_zero_mean(clean, enhanced, lengths=lengths)}
+        for name in extra:
+            m[name] = metrics.REGISTERED_METRICS[name](clean, enhanced, sr=sr, lengths=lengths)
+        return m
+
+    def calculate_metrics(self, clean, enhanced, sr: int = 16000, extra_metrics=()) -> Dict[str, float]:
+        """model_validator.py:34-77 for one clip: {"STOI", "SI_SDR"} (the mean-removed SI-SDR of the reference), and the
+        extra_metrics of calculate_metrics_batch"""
         clean = torch.as_tensor(clean).reshape(-1)
         enhanced = torch.as_tensor(enhanced).reshape(-1)
-        m = self.calculate_metrics_batch(clean[None], enhanced[None], sr)
+        m = self.calculate_metrics_batch(clean[None], enhanced[None], sr, extra_metrics=extra_metrics)
         return {k: float(v[0]) for k, v in m.items()}
 
-    def validate_dataloader(self, dataloader) -> Dict[str, float]:
+    def validate_dataloader(self, dataloader, extra_metrics=()) -> Dict[str, float]:
         """mean over all items of every metric (model_validator.py:132-170); one batched launch sequence per batch and one
-        device-to-host copy at the end.  A `data.RaggedBatch` batch is enhanced and scored per item over its own length."""
+        device-to-host copy at the end.  A `data.RaggedBatch` batch is enhanced and scored per item over its own length.
+        extra_metrics as in calculate_metrics_batch: their means follow "STOI" and "SI_SDR" in the result."""
+        extra = self._check_extra(extra_metrics)
         stoi_all, sdr_all = [], []
+        extra_all = {name: [] for name in extra}
         for batch in dataloader:
             lengths = batch.lengths if isinstance(batch, RaggedBatch) else None    # by type: a plain tuple has no lengths
             noisy, clean = batch[0].to(self.device), batch[1].to(self.device)
@@ -102,13 +122,19 @@ class ModelValidator:
             enhanced = self.enhance_audio(noisy, lengths=lengths)
             if lengths is not None:
                 lengths = torch.as_tensor(lengths).to(self.device, torch.int32)
-            m = self.calculate_metrics_batch(clean, enhanced, sr=self.config.audio_config.sr, lengths=lengths)
+            m = self.calculate_metrics_batch(clean, enhanced, sr=self.config.audio_config.sr, lengths=lengths,
+                                             extra_metrics=extra)
             stoi_all.append(m["STOI"])
             sdr_all.append(m["SI_SDR"])
+            for name in extra:
+                extra_all[name].append(m[name])
         if not stoi_all:
             raise ValueError("the dataloader yields no batch")
-        means = torch.stack((torch.cat(stoi_all).mean(), torch.cat(sdr_all).mean())).cpu()
+        means = torch.stack([torch.cat(stoi_all).mean(), torch.cat(sdr_all).mean()]
+                            + [torch.cat(extra_all[name]).mean() for name in extra]).cpu()
         avg = {"STOI": float(means[0]), "SI_SDR": float(means[1])}
+        for i, name in enumerate(extra):
+            avg[name] = float(means[2 + i])
         print("\nValidation Results:")
         for metric, value in avg.items():
             print(f"{metric}: {value:.4f}")

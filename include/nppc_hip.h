@@ -504,6 +504,35 @@ int nppc_stoi_bands(const double* xr, const double* yr, long ldr, const int* kid
                     double* y_tob, void* stream);
 int nppc_stoi_corr(const double* x_tob, const double* y_tob, const int* K, int B, int nfr, double* out, void* stream);
 
+/* ---- BSS-eval SDR (csrc/bss_eval.hip, DESIGN.md section 7d "BSS-eval SDR"; audio_zen/metrics.py:56-58 = mir_eval's
+ * bss_eval_sources for one source) and _scale_bss_eval (audio_zen/metrics.py:8-53) --------------------------------------
+ * Same ragged convention as above.  Per item, s = ref, e = est, n = lengths[b], 1 <= P <= 512 the filter length,
+ * M = n + P - 1: r[t] = sum_m s[m] s[m - t], d[t] = sum_m e[m] s[m - t] (t < P), toeplitz(r) c = d,
+ * proj[m] = sum_t c[t] s[m - t], num = sum_{m < M} proj^2, den = sum_{m < M} (e - proj)^2 (e = 0 at m >= n),
+ * SDR = 10 log10(num / den), +inf when den == 0.  All fp64, no atomics, partial sums added in ascending order. */
+/* chunk sizes (samples per workgroup of the corr kernel, samples it stages in LDS at a time, output samples per workgroup
+ * of the project kernel) and the doubles of workspace PER ITEM the corr and project launches need; no GPU needed; output
+ * pointers may be null.  P > 512 is NPPC_EUNSUPPORTED. */
+int nppc_bss_shape(long ld, int P, int* corr_chunk, int* corr_tile, int* proj_chunk, long* corr_elems_per_item,
+                   long* proj_elems_per_item);
+/* part [B][ceil(ld / corr_chunk)][2][P]: the r and d sums of every chunk of m that starts inside the item (rows of chunks
+ * past the item's length are not written, and not read by the solve) */
+int nppc_bss_corr(const float* ref, const float* est, const int* lengths, int B, long ld, int P, double* part,
+                  long part_elems, void* stream);
+/* part of nppc_bss_corr -> r, d, c [B][P] (Levinson-Durbin, one workgroup per item), status [B]: 0, or 1 when r[0] <= 0
+ * (an all-zero reference), a prediction error is not positive or a value is not finite */
+int nppc_bss_solve(const double* part, const int* lengths, int B, long ld, int P, double* r, double* d, double* c,
+                   int* status, void* stream);
+/* c, status -> num, den, sdr [B]; part [B][ceil((ld + P - 1) / proj_chunk)][2] is workspace.  status != 0: all three NaN. */
+int nppc_bss_project(const float* ref, const float* est, const int* lengths, int B, long ld, int P, const double* c,
+                     const int* status, double* part, long part_elems, double* num, double* den, double* sdr,
+                     void* stream);
+/* _scale_bss_eval(compute_sir_sar=False) per item, alpha = <s, e> / |s|^2: out [B][4] = si_sdr = 10 log10(|alpha s|^2 /
+ * |e - alpha s|^2), sd_sdr = snr + 10 log10(alpha^2), snr = 10 log10(|s|^2 / |e - s|^2), srr = -10 log10((1 - 1 / alpha)^2);
+ * sums (nullable) [B][4] = |s|^2, <s, e>, |e - s|^2, |e - alpha s|^2, each summed directly */
+int nppc_bss_scale(const float* ref, const float* est, const int* lengths, int B, long ld, double* sums /*nullable*/,
+                   double* out, void* stream);
+
 
 /* ---- ragged inference of the FullSubNet+ restorer (csrc/ragged.hip) -----------------------------------
  * A padded batch: item b is L_b = lengths[b] samples (device int[B]) and T_b = 1 + L_b / hop frames; frames[b] (device
