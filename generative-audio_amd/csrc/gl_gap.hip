@@ -1,0 +1,538 @@
+// Gap-constrained Griffin-Lim for gfx950: the phase of the gap frames of an inpainted spectrogram is
+// iterated against a target magnitude while the complex STFT of every known frame is held fixed.
+//   nppc_gl_gap_shape   argument rules, effective span cap, LDS and workspace sizes; runs without a GPU
+//   nppc_gl_phase_init  phase_advance_init: the phase of the known frame next to a gap run, advanced by 2 pi f hop / n_fft
+//   nppc_gl_gap         target magnitudes [B][V][F][T]
+//   nppc_gl_gap_pc      magnitudes exp((pred + alpha_a pc_k) std + mean) formed on the fly, plus the alpha = 0 prediction
+// Launches of one call, all on the caller's stream, no host synchronisation:
+//   gl_span_kernel   per item: bounding gap frames, span, status; the known spectrum with its gap frames zeroed
+//   istft_any_kernel (nppc_istft_any) of that spectrum -> the samples no gap frame reaches, bit for bit what istft_any gives
+//   gl_base_kernel   per item and padded-coordinate sample of the span: fp64 overlap-add of the KNOWN frames and the envelope
+//   gl_fill_kernel   copies the known waveform to every variation outside the gap's reach (NaN for an item over the cap)
+//   gl_gap_kernel    one workgroup per (item, variation): all iterations with the gap spectra C, the previous transform P
+//                    (momentum only), the target magnitudes, the span's time segment and the twiddles resident in LDS
+// Both transforms are direct DFTs out of LDS as in inpaint_validator.hip / frontend.hip: twiddles exp(2 pi i j / N) in fp64
+// indexed by (k n) mod N in integers, fp64 accumulation, fp32 state.  Every sum has one writer and a fixed order: no
+// atomics; a waveform does not depend on the batch or on the run.
+#include "common.h"
+#include "nppc_hip.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int GL_T = 256;                        // threads of gl_gap_kernel
+constexpr int GL_WAVES = GL_T / 64;
+constexpr size_t GL_LDS_BUDGET = 160 * 1024;     // LDS of one CU
+constexpr int GL_NLIVE = 2 * NPPC_GL_MAX_SPAN_FRAMES;   // byte of the flag area that holds the number of live frames
+static_assert(GL_NLIVE < 256, "the flag area is al256(cap) >= 256 bytes");
+constexpr int GL_INFO = 8;                       // ints per item: t_lo, t_hi, s_lo, s_hi, status, has_gap, o_a, o_b
+
+struct GlGeom {
+  int N, F, hop, T, L;
+  int Lk;        // samples the overlap-add reaches, min(L, N + hop (T - 1) - N / 2); [Lk, L) is zero as in torch.istft
+  int pad, r;    // N / 2; ceil(N / hop) - 1
+  int cap;       // effective span cap (gap bounding range + 2 r)
+  int Gmax;      // cap - 2 r: frame slots of C, P, M
+  int Pmax;      // (cap - 1) hop + N: padded-coordinate samples of the largest span
+  int n_iter, mom;
+  double c;      // momentum / (1 + momentum)
+};
+
+struct GlWork {
+  int* info;       // [B][GL_INFO]
+  float* kspec;    // [B][2][F][T]: known spectrum, gap frames zeroed
+  float* kwave;    // [B][L]
+  double* base;    // [B][Pmax]
+  double* den;     // [B][Pmax]: envelope * N; 0 = the sample is zero (past Lk)
+};
+
+// where the target magnitude of (item, variation) comes from
+struct GlMag {
+  const float* target;                       // [B][V][F][T], or null:
+  const float *pred, *pc, *mean, *stdev, *alphas;
+  int K, A;
+};
+
+size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+
+size_t gl_lds_bytes(int N, int F, int hop, int r, int cap, int mom) {
+  const size_t G = cap - 2 * r;
+  return sizeof(double2) * N + sizeof(double) * 2 * GL_WAVES + G * F * (sizeof(float2) * (mom ? 2 : 1) + sizeof(float)) +
+         sizeof(float) * ((size_t)(cap - 1) * hop + N) + al256(cap);
+}
+
+// -> NPPC_OK or an error with *why: 1 F, 2 frame count, 3 overlap / n_fft limit, 4 n_iter or momentum, 5 anything else
+int gl_geom(int B, int V, int F, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span, GlGeom* g,
+            size_t* lds, size_t* work, int* why) {
+  *why = 5;
+  if (B <= 0 || B > 65535 || V <= 0 || V > 65535 || T <= 0 || nfft < 2 || hop < 1 || hop > nfft || L <= 0 || max_span < 0)
+    return NPPC_EBADARG;
+  *why = 3;
+  if (nfft > 512 || (nfft + hop - 1) / hop > 8) return NPPC_EUNSUPPORTED;
+  *why = 1;
+  if (F != nfft / 2 + 1) return NPPC_EBADARG;
+  *why = 2;
+  if (1 + L / hop != T) return NPPC_EBADARG;
+  *why = 4;
+  if (n_iter < 0 || !(momentum >= 0.0) || !(momentum < 1e30)) return NPPC_EBADARG;
+  *why = 5;
+  if (L < nfft) return NPPC_EBADARG;                                        // one reflection reaches every padded sample
+  g->N = nfft, g->F = F, g->hop = hop, g->T = T, g->L = L;
+  const long full = (long)nfft + (long)hop * (T - 1) - nfft / 2;
+  g->Lk = (int)(L < full ? L : full);
+  g->pad = nfft / 2;
+  g->r = (nfft + hop - 1) / hop - 1;
+  g->n_iter = n_iter;
+  g->mom = momentum > 0.0;
+  g->c = momentum / (1.0 + momentum);
+  int cap = max_span == 0 || max_span > NPPC_GL_MAX_SPAN_FRAMES ? NPPC_GL_MAX_SPAN_FRAMES : max_span;
+  while (cap > 2 * g->r && gl_lds_bytes(nfft, F, hop, g->r, cap, g->mom) > GL_LDS_BUDGET) --cap;
+  if (cap <= 2 * g->r) return max_span == 0 ? NPPC_EUNSUPPORTED : NPPC_EBADARG;
+  g->cap = cap;
+  g->Gmax = cap - 2 * g->r;
+  g->Pmax = (cap - 1) * hop + nfft;
+  *lds = gl_lds_bytes(nfft, F, hop, g->r, cap, g->mom);
+  *work = al256(sizeof(int) * GL_INFO * (size_t)B) + al256(sizeof(float) * 2 * (size_t)B * F * T) +
+          al256(sizeof(float) * (size_t)B * L) + 2 * al256(sizeof(double) * (size_t)B * g->Pmax);
+  return NPPC_OK;
+}
+
+GlWork gl_carve(void* work, const GlGeom& g, int B) {
+  char* p = (char*)work;
+  GlWork w;
+  w.info = (int*)p, p += al256(sizeof(int) * GL_INFO * (size_t)B);
+  w.kspec = (float*)p, p += al256(sizeof(float) * 2 * (size_t)B * g.F * g.T);
+  w.kwave = (float*)p, p += al256(sizeof(float) * (size_t)B * g.L);
+  w.base = (double*)p, p += al256(sizeof(double) * (size_t)B * g.Pmax);
+  w.den = (double*)p;
+  return w;
+}
+
+__device__ __forceinline__ void gl_twiddles(double2* tw, int N, int nthr) {
+  for (int i = threadIdx.x; i < N; i += nthr) {
+    double sn, cs;
+    sincospi(2.0 * i / N, &sn, &cs);
+    tw[i] = make_double2(cs, sn);
+  }
+}
+
+// output sample that padded coordinate p holds under torch's reflect padding (pad < L: one reflection is enough)
+__device__ __forceinline__ int gl_reflect(int p, int pad, int L) {
+  int o = p - pad;
+  if (o < 0) o = -o;
+  if (o >= L) o = 2 * (L - 1) - o;
+  return o;
+}
+
+// sample n of N * irfft(sp): bins 1 .. kmax with their conjugates, bin 0 and the Nyquist bin real, as gather_sample of
+// inpaint_validator.hip
+template <typename Load>
+__device__ __forceinline__ double gl_idft_sample(const double2* tw, int N, int n, Load sp) {
+  const int kmax = (N - 1) / 2;
+  double ar = 0.0, ai = 0.0;
+  int idx = n;
+  for (int k = 1; k <= kmax; ++k) {
+    const double2 w = tw[idx];
+    const float2 x = sp(k);
+    ar += (double)x.x * w.x;
+    ai += (double)x.y * w.y;
+    idx += n;
+    if (idx >= N) idx -= N;
+  }
+  double x = (double)sp(0).x + 2.0 * (ar - ai);
+  if (!(N & 1)) x += (n & 1) ? -(double)sp(N / 2).x : (double)sp(N / 2).x;
+  return x;
+}
+
+// ---------------------------------------------------------------------------------------------------- per-item set-up
+__global__ __launch_bounds__(256) void gl_span_kernel(const float* __restrict__ known, const float* __restrict__ mask,
+                                                       int* __restrict__ info, float* __restrict__ kspec,
+                                                       int* __restrict__ status, GlGeom g) {
+  __shared__ int lo_s[4], hi_s[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* m = mask + (size_t)b * g.T;
+  int lo = g.T, hi = -1;
+  for (int t = tid; t < g.T; t += 256)
+    if (m[t] == 0.f) {
+      lo = t < lo ? t : lo;
+      hi = t > hi ? t : hi;
+    }
+  for (int o = 32; o > 0; o >>= 1) {
+    const int l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+    lo = l2 < lo ? l2 : lo;
+    hi = h2 > hi ? h2 : hi;
+  }
+  if ((tid & 63) == 0) lo_s[tid >> 6] = lo, hi_s[tid >> 6] = hi;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) {
+      lo = lo_s[w] < lo ? lo_s[w] : lo;
+      hi = hi_s[w] > hi ? hi_s[w] : hi;
+    }
+    int* o = info + b * GL_INFO;
+    const int has = hi >= 0;
+    const int bad = has && hi - lo + 1 + 2 * g.r > g.cap;
+    const int s_lo = has ? (lo - g.r > 0 ? lo - g.r : 0) : 0;
+    const int s_hi = has ? (hi + g.r < g.T - 1 ? hi + g.r : g.T - 1) : 0;
+    int oa = lo * g.hop - g.pad, ob = hi * g.hop + g.N - g.pad;
+    oa = oa < 0 ? 0 : oa;
+    ob = ob > g.L ? g.L : ob;
+    o[0] = lo, o[1] = hi, o[2] = s_lo, o[3] = s_hi, o[4] = bad, o[5] = has, o[6] = has ? oa : 0, o[7] = has ? ob : 0;
+    status[b] = bad;
+  }
+  const size_t FT = (size_t)g.F * g.T;
+  const float* src = known + (size_t)b * 2 * FT;
+  float* dst = kspec + (size_t)b * 2 * FT;
+  for (size_t e = tid; e < 2 * FT; e += 256) dst[e] = m[e % g.T] == 0.f ? 0.f : src[e];   // gap frames are never read
+}
+
+__global__ __launch_bounds__(256) void gl_base_kernel(const float* __restrict__ kspec, const float* __restrict__ mask,
+                                                       const int* __restrict__ info, double* __restrict__ base,
+                                                       double* __restrict__ den, GlGeom g) {
+  extern __shared__ double2 gl_lds[];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int* it = info + b * GL_INFO;
+  if (it[4] || !it[5]) return;
+  const int s_lo = it[2], s_hi = it[3];
+  const int Lp = (s_hi - s_lo) * g.hop + g.N;
+  if ((int)blockIdx.x * 256 >= Lp) return;
+  gl_twiddles(gl_lds, g.N, 256);
+  __syncthreads();
+  const int i = blockIdx.x * 256 + tid;
+  if (i >= Lp) return;
+  const int o = gl_reflect(s_lo * g.hop + i, g.pad, g.L);
+  double num = 0.0, dn = 0.0;
+  if (o < g.Lk) {
+    const int p = o + g.pad, a = p - g.N + 1;
+    const int t0 = a <= 0 ? 0 : (a + g.hop - 1) / g.hop;
+    int t1 = p / g.hop;
+    t1 = t1 > g.T - 1 ? g.T - 1 : t1;
+    const float* m = mask + (size_t)b * g.T;
+    const float* re = kspec + (size_t)b * 2 * g.F * g.T;
+    const float* im = re + (size_t)g.F * g.T;
+    for (int t = t0; t <= t1; ++t) {
+      const int n = p - t * g.hop;
+      const double w = 0.5 - 0.5 * gl_lds[n].x;
+      dn += w * w;
+      if (m[t] == 0.f) continue;
+      num += w * gl_idft_sample(gl_lds, g.N, n, [&](int k) { return make_float2(re[(size_t)k * g.T + t], im[(size_t)k * g.T + t]); });
+    }
+  }
+  base[(size_t)b * g.Pmax + i] = num;
+  den[(size_t)b * g.Pmax + i] = dn * (double)g.N;
+}
+
+__global__ __launch_bounds__(256) void gl_fill_kernel(const float* __restrict__ kwave, const int* __restrict__ info,
+                                                       float* __restrict__ out, int V, GlGeom g) {
+  const int b = blockIdx.z, v = blockIdx.y, o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= g.L) return;
+  const int* it = info + b * GL_INFO;
+  float* row = out + ((size_t)b * V + v) * g.L;
+  if (it[4])
+    row[o] = __builtin_nanf("");
+  else if (!it[5] || o < it[6] || o >= it[7])
+    row[o] = kwave[(size_t)b * g.L + o];
+}
+
+// ------------------------------------------------------------------------------------------------------ the iterations
+__device__ __forceinline__ double gl_block_sum(double v, double* red) {   // fixed order; every thread gets the sum
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = red[0];
+  for (int w = 1; w < GL_WAVES; ++w) s += red[w];
+  return s;
+}
+
+__global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __restrict__ known, const float* __restrict__ mask,
+                                                       const float* __restrict__ phase, int phase_per_v,
+                                                       const int* __restrict__ info, const double* __restrict__ base,
+                                                       const double* __restrict__ den, float* __restrict__ out,
+                                                       double* __restrict__ dist, double* __restrict__ tnorm, int V, GlGeom g) {
+  extern __shared__ double2 gl_lds[];
+  const int tid = threadIdx.x, v = blockIdx.x, b = blockIdx.y;
+  const int N = g.N, F = g.F, hop = g.hop;
+  const int* it = info + b * GL_INFO;
+  double* drow = dist + ((size_t)b * V + v) * g.n_iter;
+  if (it[4] || !it[5]) {                                       // over the cap: NaN; no gap: the known waveform, d = 0
+    const double val = it[4] ? (double)__builtin_nanf("") : 0.0;
+    for (int n = tid; n < g.n_iter; n += GL_T) drow[n] = val;
+    if (tid == 0) tnorm[(size_t)b * V + v] = val;
+    return;
+  }
+  const int t_lo = it[0], t_hi = it[1], s_lo = it[2], s_hi = it[3], o_a = it[6], o_b = it[7];
+  const int G = t_hi - t_lo + 1, ns = s_hi - s_lo + 1, Lp = (ns - 1) * hop + N, p_lo = s_lo * hop;
+
+  double2* tw = gl_lds;
+  double* red = reinterpret_cast<double*>(tw + N);
+  float2* C = reinterpret_cast<float2*>(red + 2 * GL_WAVES);
+  float2* P = C + (size_t)g.Gmax * F;
+  float* M = reinterpret_cast<float*>(P + (g.mom ? (size_t)g.Gmax * F : 0));
+  float* xp = M + (size_t)g.Gmax * F;
+  unsigned char* flag = reinterpret_cast<unsigned char*>(xp + g.Pmax);   // per span frame: 1 gap, 2 neighbour, 0 neither
+  unsigned char* live = flag + NPPC_GL_MAX_SPAN_FRAMES;        // span frames with a flag; their count at flag[GL_NLIVE]
+
+  const size_t FT = (size_t)F * g.T;
+  const float* m = mask + (size_t)b * g.T;
+  const float* kre = known + (size_t)b * 2 * FT;
+  const float* kim = kre + FT;
+  gl_twiddles(tw, N, GL_T);
+  for (int j = tid; j < ns; j += GL_T) {
+    const int t = s_lo + j;
+    int f = 1;
+    if (m[t] != 0.f) {
+      f = 0;
+      const int a = t - g.r < 0 ? 0 : t - g.r, e = t + g.r > g.T - 1 ? g.T - 1 : t + g.r;
+      for (int u = a; u <= e; ++u) f = m[u] == 0.f ? 2 : f;
+    }
+    flag[j] = (unsigned char)f;
+  }
+  __syncthreads();
+  if (tid == 0) {                                              // the frames the forward transform visits, in ascending order
+    int nl = 0;
+    for (int j = 0; j < ns; ++j)
+      if (flag[j]) live[nl++] = (unsigned char)j;
+    flag[GL_NLIVE] = (unsigned char)nl;
+  }
+  // C_0 = M exp(i phi0) on the gap frames
+  const float* ph = phase + (phase_per_v ? ((size_t)b * V + v) * FT : (size_t)b * FT);
+  const float* tm = nullptr;
+  const float* dir = nullptr;
+  double alpha = 0.0, mean = 0.0, sd = 1.0;
+  if (ms.target)
+    tm = ms.target + ((size_t)b * V + v) * FT;
+  else {
+    tm = ms.pred + (size_t)b * FT;
+    mean = (double)*ms.mean, sd = (double)*ms.stdev;
+    if (v < ms.K * ms.A) {
+      dir = ms.pc + ((size_t)b * ms.K + v / ms.A) * FT;
+      alpha = (double)ms.alphas[v % ms.A];
+    }
+  }
+  double tn = 0.0;
+  for (int e = tid; e < G * F; e += GL_T) {
+    const int k = e / G, j = e % G, t = t_lo + j;
+    float2 c0 = make_float2(0.f, 0.f);
+    float mg = 0.f;
+    if (m[t] == 0.f) {
+      const size_t o = (size_t)k * g.T + t;
+      double mag = (double)tm[o];
+      if (!ms.target) mag = exp((mag + (dir ? alpha * (double)dir[o] : 0.0)) * sd + mean);
+      mg = (float)mag;
+      double sn, cs;
+      sincos((double)ph[o], &sn, &cs);
+      c0 = make_float2((float)((double)mg * cs), (float)((double)mg * sn));
+      tn += (double)mg * (double)mg;
+    }
+    C[j * F + k] = c0;
+    M[j * F + k] = mg;
+    if (g.mom) P[j * F + k] = make_float2(0.f, 0.f);
+  }
+  tn = gl_block_sum(tn, red);                                  // its barriers also publish tw, flag, C, M, P
+  if (tid == 0) tnorm[(size_t)b * V + v] = sqrt(tn);
+
+  const double* bs = base + (size_t)b * g.Pmax;
+  const double* dn = den + (size_t)b * g.Pmax;
+  for (int n = 0;; ++n) {
+    // x_n = istft(C_n) on the span, in padded coordinates: known frames from `base`, gap frames from C in ascending order
+    for (int i = tid; i < Lp; i += GL_T) {
+      const int o = p_lo + i - g.pad;
+      if (o < 0 || o >= g.L) {                                 // a reflected sample whose mirror is in the span: copied below
+        const int mi = gl_reflect(p_lo + i, g.pad, g.L) + g.pad - p_lo;
+        if (mi >= 0 && mi < Lp) continue;
+      }
+      const double d = dn[i];
+      float x = 0.f;
+      if (d != 0.0) {
+        const int p = gl_reflect(p_lo + i, g.pad, g.L) + g.pad, a = p - N + 1;
+        int t0 = a <= 0 ? 0 : (a + hop - 1) / hop, t1 = p / hop;
+        t0 = t0 < t_lo ? t_lo : t0;
+        t1 = t1 > t_hi ? t_hi : t1;
+        double num = bs[i];
+        for (int t = t0; t <= t1; ++t) {
+          if (flag[t - s_lo] != 1) continue;
+          const int nn = p - t * hop;
+          const float2* sp = C + (size_t)(t - t_lo) * F;
+          num += (0.5 - 0.5 * tw[nn].x) * gl_idft_sample(tw, N, nn, [&](int k) { return sp[k]; });
+        }
+        x = (float)(num / d);
+      }
+      xp[i] = x;
+    }
+    __syncthreads();
+    for (int i = tid; i < Lp; i += GL_T) {                      // the mirrored head and tail from their in-span originals
+      const int o = p_lo + i - g.pad;
+      if (o >= 0 && o < g.L) continue;
+      const int mi = gl_reflect(p_lo + i, g.pad, g.L) + g.pad - p_lo;
+      if (mi >= 0 && mi < Lp) xp[i] = xp[mi];
+    }
+    __syncthreads();
+    if (n == g.n_iter) break;
+    // R_n = stft(x_n) on the gap and neighbour frames, two live frames per thread on one twiddle stream; then the projections
+    double dacc = 0.0;
+    const int nlive = flag[GL_NLIVE], npair = (nlive + 1) / 2;
+    for (int q = tid; q < npair * F; q += GL_T) {
+      const int k = q % F, pr = 2 * (q / F);
+      const int j0 = live[pr], j1 = pr + 1 < nlive ? live[pr + 1] : j0;
+      const int f0 = flag[j0], f1 = pr + 1 < nlive ? flag[j1] : 0;
+      const float* x0 = xp + (size_t)j0 * hop;
+      const float* x1 = xp + (size_t)j1 * hop;
+      double r0 = 0.0, i0 = 0.0, r1 = 0.0, i1 = 0.0;
+      int idx = 0;
+      for (int nn = 0; nn < N; ++nn) {
+        const double2 w = tw[idx];
+        const double hw = 0.5 - 0.5 * tw[nn].x;
+        const double a0 = hw * (double)x0[nn], a1 = hw * (double)x1[nn];
+        r0 += a0 * w.x;
+        i0 -= a0 * w.y;
+        r1 += a1 * w.x;
+        i1 -= a1 * w.y;
+        idx += k;
+        if (idx >= N) idx -= N;
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int f = h ? f1 : f0, t = s_lo + (h ? j1 : j0);
+        const double rr = h ? r1 : r0, ri = h ? i1 : i0;
+        if (f == 1) {
+          const int s = (t - t_lo) * F + k;
+          const double mg = (double)M[s];
+          const double e = sqrt(rr * rr + ri * ri) - mg;
+          dacc += e * e;
+          double ar = rr, ai = ri;
+          if (g.mom) {
+            const float2 pv = P[s];
+            ar -= g.c * (double)pv.x;
+            ai -= g.c * (double)pv.y;
+            P[s] = make_float2((float)rr, (float)ri);
+          }
+          const double sc = mg / (sqrt(ar * ar + ai * ai) + 1e-16);
+          C[s] = make_float2((float)(ar * sc), (float)(ai * sc));
+        } else if (f == 2) {
+          const size_t o = (size_t)k * g.T + t;
+          const double er = rr - (double)kre[o], ei = ri - (double)kim[o];
+          dacc += er * er + ei * ei;
+        }
+      }
+    }
+    dacc = gl_block_sum(dacc, red);                            // its barriers also publish C and P
+    if (tid == 0) drow[n] = sqrt(dacc);
+  }
+  float* row = out + ((size_t)b * V + v) * g.L;
+  for (int o = o_a + tid; o < o_b; o += GL_T) row[o] = xp[o + g.pad - p_lo];
+}
+
+__global__ __launch_bounds__(256) void gl_phase_init_kernel(const float* __restrict__ known, const float* __restrict__ mask,
+                                                             float* __restrict__ phase, int F, int T, int N, int hop) {
+  const int b = blockIdx.y;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= F * T) return;
+  const int k = e / T, t = e % T;
+  const float* m = mask + (size_t)b * T;
+  float out = 0.f;
+  if (m[t] == 0.f) {
+    int t0 = t - 1;
+    while (t0 >= 0 && m[t0] == 0.f) --t0;
+    if (t0 < 0) {                                              // the run starts at frame 0: the known frame to its right
+      t0 = t + 1;
+      while (t0 < T && m[t0] == 0.f) ++t0;
+    }
+    if (t0 < T) {
+      const size_t FT = (size_t)F * T;
+      const float* re = known + (size_t)b * 2 * FT;
+      const double a0 = atan2((double)re[FT + (size_t)k * T + t0], (double)re[(size_t)k * T + t0]);
+      long q = ((long)k * hop % N) * (long)(t - t0) % N;       // f hop (t - t0) mod N, exact
+      if (q < 0) q += N;
+      double a = a0 + 2.0 * M_PI * (double)q / (double)N;
+      if (a > M_PI) a -= 2.0 * M_PI;
+      out = (float)a;
+    }
+  }
+  phase[(size_t)b * F * T + e] = out;
+}
+
+int gl_run(const GlMag& ms, const float* known, const float* mask, const float* phase, int phase_per_v, float* out, double* dist,
+           double* tnorm, int* status, void* work, long work_bytes, int B, int V, int T, int nfft, int hop, int L, int n_iter,
+           double momentum, int max_span, void* stream) {
+  if (!known || !mask || !phase || !out || !tnorm || !status || !work || (n_iter > 0 && !dist)) return NPPC_EBADARG;
+  GlGeom g;
+  size_t lds, need;
+  int why;
+  const int rc = gl_geom(B, V, nfft / 2 + 1, T, nfft, hop, L, n_iter, momentum, max_span, &g, &lds, &need, &why);
+  if (rc != NPPC_OK) return rc;
+  if (work_bytes < (long)need) return NPPC_EBADARG;
+  const GlWork w = gl_carve(work, g, B);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(gl_span_kernel, dim3(B), dim3(256), 0, s, known, mask, w.info, w.kspec, status, g);
+  NPPC_CHECK_LAUNCH();
+  const long FT = (long)g.F * T;
+  const int rk = nppc_istft_any(w.kspec, w.kspec + FT, 2 * FT, w.kwave, L, B, T, nfft, hop, L, stream);
+  if (rk != NPPC_OK) return rk;
+  hipLaunchKernelGGL(gl_base_kernel, dim3(ceil_div(g.Pmax, 256), B), dim3(256), sizeof(double2) * nfft, s, w.kspec, mask, w.info,
+                     w.base, w.den, g);
+  NPPC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(gl_fill_kernel, dim3(ceil_div(L, 256), V, B), dim3(256), 0, s, w.kwave, w.info, out, V, g);
+  NPPC_CHECK_LAUNCH();
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)gl_gap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return NPPC_ELAUNCH;
+  hipLaunchKernelGGL(gl_gap_kernel, dim3(V, B), dim3(GL_T), lds, s, ms, known, mask, phase, phase_per_v, w.info, w.base, w.den, out,
+                     dist, tnorm, V, g);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nppc_gl_gap_shape(int B, int V, int F, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span, int* why,
+                      int* r, int* span_cap, long* lds_bytes, long* work_bytes) {
+  GlGeom g;
+  size_t lds, work;
+  int y = 0;
+  const int rc = gl_geom(B, V, F, T, nfft, hop, L, n_iter, momentum, max_span, &g, &lds, &work, &y);
+  if (why) *why = rc == NPPC_OK ? 0 : y;
+  if (rc != NPPC_OK) return rc;
+  if (r) *r = g.r;
+  if (span_cap) *span_cap = g.cap;
+  if (lds_bytes) *lds_bytes = (long)lds;
+  if (work_bytes) *work_bytes = (long)work;
+  return NPPC_OK;
+}
+
+int nppc_gl_phase_init(const float* known_spec, const float* mask, float* phase, int B, int T, int nfft, int hop, void* stream) {
+  if (!known_spec || !mask || !phase || B <= 0 || B > 65535 || T <= 0 || nfft < 2 || nfft > 512 || hop < 1 || hop > nfft)
+    return NPPC_EBADARG;
+  const int F = nfft / 2 + 1;
+  hipLaunchKernelGGL(gl_phase_init_kernel, dim3(ceil_div((long)F * T, 256), B), dim3(256), 0, (hipStream_t)stream, known_spec,
+                     mask, phase, F, T, nfft, hop);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_gl_gap(const float* target_mag, const float* known_spec, const float* mask, const float* init_phase,
+                int phase_per_variation, float* out, double* dist, double* target_norm, int* status, void* work,
+                long work_bytes, int B, int V, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span,
+                void* stream) {
+  if (!target_mag) return NPPC_EBADARG;
+  GlMag ms = {};
+  ms.target = target_mag;
+  return gl_run(ms, known_spec, mask, init_phase, phase_per_variation != 0, out, dist, target_norm, status, work, work_bytes, B, V,
+                T, nfft, hop, L, n_iter, momentum, max_span, stream);
+}
+
+int nppc_gl_gap_pc(const float* pred, const float* pc, const float* mean, const float* stdev, const float* alphas,
+                   const float* known_spec, const float* mask, const float* init_phase, float* out, double* dist,
+                   double* target_norm, int* status, void* work, long work_bytes, int B, int K, int A, int T, int nfft, int hop,
+                   int L, int n_iter, double momentum, int max_span, void* stream) {
+  if (!pred || !pc || !mean || !stdev || !alphas || K <= 0 || A <= 0 || (long)K * A + 1 > 65535) return NPPC_EBADARG;
+  GlMag ms = {};
+  ms.pred = pred, ms.pc = pc, ms.mean = mean, ms.stdev = stdev, ms.alphas = alphas, ms.K = K, ms.A = A;
+  return gl_run(ms, known_spec, mask, init_phase, 0, out, dist, target_norm, status, work, work_bytes, B, K * A + 1, T, nfft, hop,
+                L, n_iter, momentum, max_span, stream);
+}
+
+}  // extern "C"

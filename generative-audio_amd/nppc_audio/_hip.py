@@ -258,6 +258,10 @@ SIGS = {
     "nppc_pyin_cmnd": [P, P, P, I, L, I, I, I, I, I, P],
     "nppc_pyin_observe": [P, P, P, P, P, I, I, L, I, I, I, I, I, I, D, D, D, D, P],
     "nppc_pyin_viterbi": [P, P, P, P, P, P, I, I, L, I, I, I, I, D, P],
+    "nppc_gl_gap_shape": [I, I, I, I, I, I, I, I, D, I, PI, PI, PI, PL, PL],
+    "nppc_gl_phase_init": [P, P, P, I, I, I, I, P],
+    "nppc_gl_gap": [P, P, P, P, I, P, P, P, P, P, L, I, I, I, I, I, I, I, D, I, P],
+    "nppc_gl_gap_pc": [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, I, I, D, I, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

@@ -8,6 +8,9 @@ mc_baseline.calculate_unet_baseline (batched PCA), the metrics come from one Gra
 (mc_baseline.metrics_gram_batch) and ONE device-to-host copy per `validate_dataloader` call, and the K x A + 1 waveforms
 of `pc_audio_variations` come from one launch whose complex spectrograms never reach memory.
 
+`validate_batch(..., phase="griffin_lim")` adds waveforms that do not use the clean phase at all (inpainting/phase.py:
+Griffin-Lim restricted to the gap, the damaged recording's STFT held fixed), which is what a recording with a real gap allows.
+
 `validate_batch(..., pitch=True)` adds the f0 contours of plot_pitch_comparison (:19-270) for the clean waveform and every
 variation, tracked on the device (nppc_audio/pitch.py), and what each direction does to them.
 
@@ -26,6 +29,7 @@ from ... import _hip as H
 from ... import ops
 from ... import pitch as PT
 from .. import mc_baseline as MB
+from .. import phase as PH
 from ..nppc.nppc_model import NPPCModel, NPPCModelConfig
 from ..utils import preprocess_data
 
@@ -140,7 +144,7 @@ class NPPCModelValidator:
                 'mask': mask4, 'mean': mean, 'std': std, 'mc_dropout': mc, 'gram': gram, 'clean_spec': clean_spec}
 
     def validate_batch(self, masked_spec, mask, clean_spec, n_mc_samples=50, n_components=5, alphas=None, n_fft=255,
-                       hop_length=128, pitch=False):
+                       hop_length=128, pitch=False, phase="clean", gl_iters=32):
         """validate_sample + _validate_with_baseline (:930-1027) for a uniform batch: masked_spec, clean_spec [B,2,F,T],
         mask [B,T] (1 = known; the same number of gap frames in every item) -> dict with 'pc_directions' [B,K,F,T],
         'pred_spec_mag_norm', 'clean_spec_mag_norm', 'mask' [B,1,F,T], 'mean', 'std', 'mc_dropout' (calculate_unet_baseline's
@@ -150,9 +154,19 @@ class NPPCModelValidator:
         pitch=True (needs `alphas`; ValueError otherwise) adds 'pitch': pYIN contours at the reference's setting (fmin 80,
         fmax 400, sr 16000; plot_pitch_comparison :60-66) of the clean waveform and of every variation, from one batched
         call: {'f0_clean' [B,T'], 'voiced_flag_clean', 'voiced_prob_clean', 'f0' [B,K,A,T'], 'voiced_flag', 'voiced_prob',
-        'summary' (pitch.pitch_variation_summary, [B,K,A] tensors)}, T' = 1 + L // 512.  Everything else is unchanged."""
+        'summary' (pitch.pitch_variation_summary, [B,K,A] tensors)}, T' = 1 + L // 512.  Everything else is unchanged.
+
+        phase="griffin_lim" (needs `alphas`; ValueError otherwise) adds 'audio_variations_blind' [B,K,A,L],
+        'restored_audio_blind' [B,L] and 'phase_info' (phase.pc_audio_variations_blind: `gl_iters` iterations of
+        gap-constrained Griffin-Lim from the damaged recording's STFT, no clean phase).  The default phase="clean" returns
+        exactly what it returned before; pitch tracking keeps using the clean-phase waveforms."""
+        if phase not in ("clean", "griffin_lim"):
+            raise ValueError(f"phase = {phase!r}: 'clean' or 'griffin_lim'")
         if pitch and alphas is None:
             raise ValueError("pitch=True tracks the f0 of the PC audio variations: pass `alphas` (e.g. default_alphas())")
+        if phase == "griffin_lim" and alphas is None:
+            raise ValueError("phase='griffin_lim' synthesises the PC audio variations: pass `alphas` (e.g. default_alphas())")
+        masked_dev = masked_spec.to(self.device) if phase == "griffin_lim" else None
         out = self._run_batch(masked_spec, mask, clean_spec, n_mc_samples, n_components)
         out['metrics'] = MB.metrics_from_gram(out.pop('gram').cpu().numpy(), n_components)
         clean_spec = out.pop('clean_spec')
@@ -164,6 +178,11 @@ class NPPCModelValidator:
                 if pitch:
                     out['pitch'] = PT.contours_of_variations(out['clean_audio'], out['audio_variations'],
                                                              **PT.REFERENCE_SETTING)
+                if phase == "griffin_lim":
+                    out['audio_variations_blind'], out['restored_audio_blind'], out['phase_info'] = \
+                        PH.pc_audio_variations_blind(out['pred_spec_mag_norm'], out['pc_directions'], masked_dev, out['mask'],
+                                                     alphas, out['mean'], out['std'], n_iter=gl_iters, n_fft=n_fft,
+                                                     hop_length=hop_length)
         return out
 
     def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False):

@@ -660,6 +660,38 @@ int nppc_pyin_viterbi(const float* obs, const int* lengths, const double* hmm_ta
                       unsigned char* voiced_flag, int N, int T, long L, int hop_length, int n_pitch_bins,
                       int bins_per_semitone, int width, double fmin, void* stream);
 
+/* ---- gap-constrained Griffin-Lim (csrc/gl_gap.hip; specification tests/gl_gap_ref.py) ------------
+ * Phase retrieval for the gap frames of an inpainted spectrogram: the target magnitude holds on the gap frames (mask == 0),
+ * the complex STFT known_spec [B][2][F][T] holds on the known frames, only the gap frames' phase is iterated (momentum 0:
+ * classic Griffin-Lim; 0.99: the fast variant).  STFT conventions of nppc_istft_any / nppc_stft_pair; 1 + L / hop == T.
+ * One workgroup per (item, variation) keeps the span = bounding range of the item's gap frames + r = ceil(n_fft / hop) - 1
+ * neighbours per side in LDS for all iterations.  An item whose span has more frames than the cap gets NaN in out, dist and
+ * target_norm and status[b] = 1; the other items are unaffected.  No atomics, no host synchronisation; a waveform does not
+ * depend on the batch.  Only gap frames of target_mag / init_phase and known frames of known_spec are read. */
+#define NPPC_GL_MAX_SPAN_FRAMES 32
+/* The argument rules, without a GPU.  max_span: 0 = NPPC_GL_MAX_SPAN_FRAMES, else a lower cap (less LDS, more workgroups
+ * per CU).  *why (nullable) names the broken rule: 1 F != n_fft / 2 + 1, 2 1 + L / hop != T, 3 n_fft > 512 or
+ * ceil(n_fft / hop) > 8, 4 n_iter < 0 or momentum < 0, 5 anything else.  *span_cap = the cap in force (the LDS budget of
+ * 160 KB can lower it), *lds_bytes = dynamic LDS of the main kernel, *work_bytes = the workspace a call needs. */
+int nppc_gl_gap_shape(int B, int V, int F, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span, int* why,
+                      int* r, int* span_cap, long* lds_bytes, long* work_bytes);
+/* phase_advance_init: phase [B][F][T] = angle(known[f][t0]) + 2 pi f hop (t - t0) / n_fft on gap frames, t0 = the known frame
+ * left of the gap run (right of it for a run that starts at frame 0); 0 on known frames and where no frame is known */
+int nppc_gl_phase_init(const float* known_spec, const float* mask, float* phase, int B, int T, int nfft, int hop, void* stream);
+/* target_mag [B][V][F][T], mask [B][T] (1 = known), init_phase [B][V][F][T] (phase_per_variation) or [B][F][T] ->
+ * out [B][V][L], dist [B][V][n_iter] (fp64: distance of stft(x_n) to the constraint set), target_norm [B][V] (fp64) */
+int nppc_gl_gap(const float* target_mag, const float* known_spec, const float* mask, const float* init_phase,
+                int phase_per_variation, float* out, double* dist, double* target_norm, int* status, void* work,
+                long work_bytes, int B, int V, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span,
+                void* stream);
+/* the same with V = K A + 1 magnitudes formed on the fly: v < K A: exp((pred + alphas[v % A] pc[v / A]) stdev + mean), v = K A:
+ * exp(pred stdev + mean); pred [B][F][T], pc [B][K][F][T], mean / stdev device scalars, alphas [A] (device), init_phase
+ * [B][F][T] */
+int nppc_gl_gap_pc(const float* pred, const float* pc, const float* mean, const float* stdev, const float* alphas,
+                   const float* known_spec, const float* mask, const float* init_phase, float* out, double* dist,
+                   double* target_norm, int* status, void* work, long work_bytes, int B, int K, int A, int T, int nfft, int hop,
+                   int L, int n_iter, double momentum, int max_span, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
