@@ -262,6 +262,12 @@ SIGS = {
     "nppc_gl_phase_init": [P, P, P, I, I, I, I, P],
     "nppc_gl_gap": [P, P, P, P, I, P, P, P, P, P, L, I, I, I, I, I, I, I, D, I, P],
     "nppc_gl_gap_pc": [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, I, I, D, I, P],
+    "nppc_gap_count": [P, P, I, L, P],
+    "nppc_gap_index": [P, P, I, L, I, P],
+    "nppc_gap_gather": [P, P, P, I, L, I, P],
+    "nppc_gap_scatter": [P, P, P, I, I, L, I, P],
+    "nppc_pca_ragged_work_elems": [I, I, I, I, PL],
+    "nppc_pca_ragged": [P, P, I, I, I, I, P, P, P, P, P, P, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

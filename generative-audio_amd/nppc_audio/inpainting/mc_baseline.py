@@ -4,6 +4,7 @@ Mirrors the reference's root utils.py: enable_dropout (:334-338), compute_pca_sk
 calculate_unet_baseline (:548-648).  The stochastic U-Net passes run on the HIP engine (Philox dropout after
 down3/down4/up1/up2), the per-item PCA of the K samples is one batched launch sequence (Gram + Jacobi + components)
 instead of B scikit-learn fits on the host; gather / scatter of the gap elements is torch indexing (plumbing).
+The `*_ragged` functions do the same for batches whose items have different numbers of gap elements.
 """
 import ctypes
 
@@ -86,6 +87,140 @@ def calculate_unet_baseline(model, masked_spec, mask, n_mc_samples=50, n_compone
         "mean_prediction": _scatter_gap(mean, hole, F, T).unsqueeze(1),
         "principal_components": _scatter_gap(pcs, hole, F, T),
         "scaled_principal_components": _scatter_gap(scaled, hole, F, T),
+        "importance_weights": weights,
+        "singular_vals": svals,
+    }
+
+
+# ------------------------------------------------------------------------------------------------ ragged gaps
+# The same baseline for batches whose items have DIFFERENT numbers of gap elements (csrc/mc_pca_ragged.hip, DESIGN.md
+# section 8d): the reference's dataset cuts 2048 samples at a random start, which zeroes 17 or 18 frames (fewer at the
+# ends of a clip), so its batches are rarely uniform.  Everything is padded to Nmax = the largest count of the batch.
+def _hole_counts_host(mask, B):
+    return (mask.reshape(B, -1) == 0).sum(dim=1).tolist()
+
+
+def _check_counts(counts_host, B, Nmax=None):
+    if len(counts_host) != B:
+        raise ValueError(f"counts has {len(counts_host)} entries for a batch of {B} items")
+    for b, c in enumerate(counts_host):
+        if c < 1:
+            raise ValueError(f"item {b} has no gap (mask == 0) element: the MC-dropout + PCA baseline needs at least one")
+        if Nmax is not None and c > Nmax:
+            raise ValueError(f"counts[{b}] = {c} exceeds the padded width {Nmax} of the stack")
+
+
+def _gap_index(mask):
+    """gap_index plus the host copy of the counts (the ONE host read of a ragged batch)"""
+    B = mask.shape[0]
+    if mask.dim() < 2 or B == 0 or mask[0].numel() == 0:
+        raise ValueError(f"expected a mask of [B, ...] with B >= 1, got {tuple(mask.shape)}")
+    if not mask.is_cuda:
+        _check_counts(_hole_counts_host(mask, B), B)             # refused before anything asks for the device
+    H.require_gpu()
+    m = mask.reshape(B, -1).contiguous().float()
+    N = m.shape[1]
+    s = H.stream()
+    counts = torch.empty(B, dtype=torch.int32, device=m.device)
+    H.call("nppc_gap_count", m, counts, B, N, s)
+    host = counts.tolist()
+    _check_counts(host, B)
+    Nmax = max(host)
+    idx = torch.empty(B, Nmax, dtype=torch.int32, device=m.device)
+    H.call("nppc_gap_index", m, idx, B, N, Nmax, s)
+    return idx, counts, host
+
+
+def gap_index(mask):
+    """mask [B, ...] (any mask; 0 = gap) -> (idx [B, Nmax] int32, counts [B] int32) on the device: idx[b, :counts[b]] are
+    the row-major positions of item b's gap elements (the order of boolean indexing and masked_scatter_), -1 after them;
+    Nmax = max(counts).  One host read (the counts, to size idx).  ValueError for an item without a gap."""
+    idx, counts, _ = _gap_index(mask)
+    return idx, counts
+
+
+def gather_gap(values, idx, out=None):
+    """values [B, ...] (N elements per item) -> [B, Nmax]: values through idx, 0 at padded positions (no host read)"""
+    H.require_gpu()
+    B, Nmax = idx.shape
+    v = values.reshape(B, -1).contiguous().float()
+    if out is None:
+        out = torch.empty(B, Nmax, dtype=torch.float32, device=v.device)
+    H.call("nppc_gap_gather", v, idx, out, B, v.shape[1], Nmax, H.stream())
+    return out
+
+
+def scatter_gap_ragged(values, idx, F, T):
+    """_scatter_gap through idx: values [B, Nmax] -> [B, F, T] or [B, n, Nmax] -> [B, n, F, T], zeros outside the gap"""
+    H.require_gpu()
+    B, Nmax = idx.shape
+    v = values.contiguous().float()
+    if v.dim() not in (2, 3) or v.shape[0] != B or v.shape[-1] != Nmax:
+        raise ValueError(f"values {tuple(values.shape)} do not fit an index of {tuple(idx.shape)}")
+    R = v.shape[1] if v.dim() == 3 else 1
+    out = torch.empty(B, R, F * T, dtype=torch.float32, device=v.device)
+    H.call("nppc_gap_scatter", v, idx, out, B, R, F * T, Nmax, H.stream())
+    return out.reshape(B, R, F, T) if v.dim() == 3 else out.reshape(B, F, T)
+
+
+def _pca_ragged(stack, counts, n_components):
+    K, B, Nmax = stack.shape
+    n = min(int(n_components), K)
+    dev = stack.device
+    elems = ctypes.c_long()
+    H.call("nppc_pca_ragged_work_elems", K, B, Nmax, n, ctypes.byref(elems))
+    work = torch.empty(elems.value, dtype=torch.float64, device=dev)
+    mean = torch.empty(B, Nmax, dtype=torch.float32, device=dev)
+    comps = torch.empty(B, n, Nmax, dtype=torch.float32, device=dev)
+    scaled = torch.empty_like(comps)
+    svals = torch.empty(B, n, dtype=torch.float32, device=dev)
+    weights = torch.empty_like(svals)
+    H.call("nppc_pca_ragged", stack, counts, K, B, Nmax, n, mean, comps, scaled, svals, weights, work, H.stream())
+    return comps, scaled, weights, mean, svals
+
+
+def compute_pca_ragged(stack, counts, n_components=5):
+    """compute_pca_batch for a padded stack [K, B, Nmax] whose item b owns its first counts[b] elements -> the same
+    5-tuple with the last dimension padded to Nmax (zeros past counts[b]).  The Gram is summed without atomics over fixed
+    chunks that start at the item's element 0: item b equals, bit for bit, the same call on that item alone, and two
+    runs agree bit for bit.  Checking `counts` costs one host read when it lives on the device (none when it is a host
+    tensor or a list); ValueError for a count < 1 or > Nmax or for the wrong number of counts."""
+    if stack.dim() != 3:
+        raise ValueError(f"expected a [K, B, Nmax] stack, got {tuple(stack.shape)}")
+    K, B, Nmax = stack.shape
+    host = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
+    _check_counts(host, B, Nmax)
+    H.require_gpu()
+    stack = stack.contiguous().float()
+    if not (isinstance(counts, torch.Tensor) and counts.is_cuda):
+        counts = torch.tensor(host, dtype=torch.int32).to(stack.device)
+    return _pca_ragged(stack, counts.contiguous().to(torch.int32), n_components)
+
+
+def mc_dropout_samples_ragged(model, masked_spec, mask, n_mc_samples=50):
+    """mc_dropout_samples for unequal gap counts: -> (stack [K, B, Nmax], idx [B, Nmax], counts [B]).  The same K
+    forward passes in the same order (the dropout pass counter advances as in mc_dropout_samples); the gap is gathered
+    by a kernel through idx, so the loop makes no host read."""
+    idx, counts, _ = _gap_index(mask)
+    enable_dropout(model)
+    B, Nmax = idx.shape
+    stack = torch.empty(n_mc_samples, B, Nmax, dtype=torch.float32, device=idx.device)
+    with torch.no_grad():
+        for k in range(n_mc_samples):
+            gather_gap(model(masked_spec, mask), idx, out=stack[k])          # pred [B, 1, F, T]
+    return stack, idx, counts
+
+
+def calculate_unet_baseline_ragged(model, masked_spec, mask, n_mc_samples=50, n_components=5):
+    """calculate_unet_baseline for a batch whose items may have different numbers of gap elements: the same dict, every
+    item's mean and components over its own gap.  One host read per batch (the gap counts)."""
+    B, _, F, T = masked_spec.shape
+    stack, idx, counts = mc_dropout_samples_ragged(model, masked_spec, mask, n_mc_samples)
+    pcs, scaled, weights, mean, svals = _pca_ragged(stack, counts, n_components)
+    return {
+        "mean_prediction": scatter_gap_ragged(mean, idx, F, T).unsqueeze(1),
+        "principal_components": scatter_gap_ragged(pcs, idx, F, T),
+        "scaled_principal_components": scatter_gap_ragged(scaled, idx, F, T),
         "importance_weights": weights,
         "singular_vals": svals,
     }

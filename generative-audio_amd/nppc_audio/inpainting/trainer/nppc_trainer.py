@@ -115,19 +115,21 @@ class NPPCAudioInpaintingTrainer(nn.Module):
         return inpainting_base_step(self.nppc_model, batch, self.step, self.config.second_moment_loss_grace,
                                     self.config.second_moment_loss_lambda)
 
-    def base_step2(self, batch, n_mc_samples=50):
+    def base_step2(self, batch, n_mc_samples=50, ragged_gaps=False):
         """nppc_trainer.py:244-336: the alternative target -- the NPPC directions are fitted to the MC-dropout + PCA
         components of the restorer (50 stochastic passes with the WHOLE restorer in train mode, as the reference's
-        `restoration_model.train()` does: BatchNorm uses batch statistics and its running buffers move)."""
-        from ..mc_baseline import PairProjectionLoss, calculate_unet_baseline
+        `restoration_model.train()` does: BatchNorm uses batch statistics and its running buffers move).
+        ragged_gaps=True accepts a batch whose items have different numbers of gap frames
+        (mc_baseline.calculate_unet_baseline_ragged); the default raises ValueError for one, as before."""
+        from ..mc_baseline import PairProjectionLoss, calculate_unet_baseline, calculate_unet_baseline_ragged
         masked_spec, mask, clean_spec = batch
         clean_norm, mask4, masked_norm = preprocess_data(clean_spec, masked_spec, mask)
         w_mat = self.nppc_model(masked_norm, mask4)                      # [B, n_dirs, F, T]
         restoration_model = self.nppc_model.pretrained_restoration_model
         restoration_model.train()
         try:
-            mc = calculate_unet_baseline(restoration_model, masked_norm, mask4, n_mc_samples=n_mc_samples,
-                                         n_components=w_mat.shape[1])
+            baseline = calculate_unet_baseline_ragged if ragged_gaps else calculate_unet_baseline
+            mc = baseline(restoration_model, masked_norm, mask4, n_mc_samples=n_mc_samples, n_components=w_mat.shape[1])
         finally:
             restoration_model.eval()
         w_mc, singular_values = mc['scaled_principal_components'], mc['singular_vals']

@@ -105,8 +105,12 @@ class NPPCModelValidator:
     """Loads a checkpoint written by NPPCAudioInpaintingTrainer.save_checkpoint ({'model_state_dict': ...}) and scores it
     on held-out batches.
 
-    The MC-dropout baseline gathers the gap elements of every item into one [K, B, N_masked] stack, so every item of a
-    batch must have the same number of gap (mask == 0) elements; it raises ValueError otherwise."""
+    The MC-dropout baseline gathers the gap elements of every item into one [K, B, N_masked] stack, so by default every
+    item of a batch must have the same number of gap (mask == 0) elements; it raises ValueError otherwise.
+    `ragged_gaps=True` (validate_batch, validate_dataloader) lifts that: the stack is padded to the largest gap of the
+    batch (mc_baseline.calculate_unet_baseline_ragged), which is what batches of the reference's dataset need (its
+    2048-sample gap covers 17 or 18 frames depending on where it starts).  Everything downstream of the baseline works
+    per item through the mask and is the same in both modes."""
 
     def __init__(self, config: NPPCModelValidatorConfig):
         self.config = config
@@ -119,7 +123,7 @@ class NPPCModelValidator:
         self.model.to(self.device)
         self.model.eval()
 
-    def _run_batch(self, masked_spec, mask, clean_spec, n_mc_samples, n_components):
+    def _run_batch(self, masked_spec, mask, clean_spec, n_mc_samples, n_components, ragged_gaps=False):
         """every device stage of one batch; the Gram matrices stay on the device"""
         H.require_gpu()
         self.model.eval()
@@ -133,9 +137,9 @@ class NPPCModelValidator:
                 raise ValueError(f"n_components = {n_components} but the model has {pc_directions.shape[1]} directions: "
                                  "the metrics compare subspaces of the same dimension")
             restorer = self.model.pretrained_restoration_model
+            baseline = MB.calculate_unet_baseline_ragged if ragged_gaps else MB.calculate_unet_baseline
             try:
-                mc = MB.calculate_unet_baseline(restorer, masked_norm, mask4, n_mc_samples=n_mc_samples,
-                                                n_components=n_components)
+                mc = baseline(restorer, masked_norm, mask4, n_mc_samples=n_mc_samples, n_components=n_components)
             finally:
                 restorer.eval()                                     # enable_dropout left the Dropout modules in train mode
             gram = MB.metrics_gram_batch(pc_directions, mc['scaled_principal_components'], pred, mc['mean_prediction'],
@@ -144,7 +148,7 @@ class NPPCModelValidator:
                 'mask': mask4, 'mean': mean, 'std': std, 'mc_dropout': mc, 'gram': gram, 'clean_spec': clean_spec}
 
     def validate_batch(self, masked_spec, mask, clean_spec, n_mc_samples=50, n_components=5, alphas=None, n_fft=255,
-                       hop_length=128, pitch=False, phase="clean", gl_iters=32):
+                       hop_length=128, pitch=False, phase="clean", gl_iters=32, ragged_gaps=False):
         """validate_sample + _validate_with_baseline (:930-1027) for a uniform batch: masked_spec, clean_spec [B,2,F,T],
         mask [B,T] (1 = known; the same number of gap frames in every item) -> dict with 'pc_directions' [B,K,F,T],
         'pred_spec_mag_norm', 'clean_spec_mag_norm', 'mask' [B,1,F,T], 'mean', 'std', 'mc_dropout' (calculate_unet_baseline's
@@ -159,7 +163,10 @@ class NPPCModelValidator:
         phase="griffin_lim" (needs `alphas`; ValueError otherwise) adds 'audio_variations_blind' [B,K,A,L],
         'restored_audio_blind' [B,L] and 'phase_info' (phase.pc_audio_variations_blind: `gl_iters` iterations of
         gap-constrained Griffin-Lim from the damaged recording's STFT, no clean phase).  The default phase="clean" returns
-        exactly what it returned before; pitch tracking keeps using the clean-phase waveforms."""
+        exactly what it returned before; pitch tracking keeps using the clean-phase waveforms.
+
+        ragged_gaps=True accepts items with different numbers of gap frames (every item needs at least one); the keys
+        and shapes are the same.  The default keeps raising ValueError for such a batch."""
         if phase not in ("clean", "griffin_lim"):
             raise ValueError(f"phase = {phase!r}: 'clean' or 'griffin_lim'")
         if pitch and alphas is None:
@@ -167,7 +174,7 @@ class NPPCModelValidator:
         if phase == "griffin_lim" and alphas is None:
             raise ValueError("phase='griffin_lim' synthesises the PC audio variations: pass `alphas` (e.g. default_alphas())")
         masked_dev = masked_spec.to(self.device) if phase == "griffin_lim" else None
-        out = self._run_batch(masked_spec, mask, clean_spec, n_mc_samples, n_components)
+        out = self._run_batch(masked_spec, mask, clean_spec, n_mc_samples, n_components, ragged_gaps)
         out['metrics'] = MB.metrics_from_gram(out.pop('gram').cpu().numpy(), n_components)
         clean_spec = out.pop('clean_spec')
         if alphas is not None:
@@ -185,14 +192,16 @@ class NPPCModelValidator:
                                                      hop_length=hop_length)
         return out
 
-    def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False):
+    def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False, ragged_gaps=False):
         """every item of every batch ((masked_spec, mask, clean_spec) or utils.collate_fn's five-tuple): the Gram
         matrices stay on the device until the loader is exhausted, then ONE copy to the host and the n x n algebra.
         -> {'per_item': [compute_metrics dicts], 'mean': {'nppc': {...}, 'mc_dropout': {...}, 'principal_angles': [...]},
-            'n_items': int}; save=True also writes validation_metrics/sample_<i>.json under config.save_dir."""
+            'n_items': int}; save=True also writes validation_metrics/sample_<i>.json under config.save_dir.
+        ragged_gaps=True: batches whose items have different numbers of gap frames (one host read of the gap counts per
+        batch on top of the one copy per loader)."""
         grams = []
         for batch in dataloader:
-            grams.append(self._run_batch(*batch[:3], n_mc_samples, n_components)['gram'])
+            grams.append(self._run_batch(*batch[:3], n_mc_samples, n_components, ragged_gaps)['gram'])
         if not grams:
             raise ValueError("the dataloader yielded no batches")
         per_item = MB.metrics_from_gram(torch.cat(grams).cpu().numpy(), n_components)

@@ -692,6 +692,26 @@ int nppc_gl_gap_pc(const float* pred, const float* pc, const float* mean, const 
                    double* target_norm, int* status, void* work, long work_bytes, int B, int K, int A, int T, int nfft, int hop,
                    int L, int n_iter, double momentum, int max_span, void* stream);
 
+/* ---- ragged-gap MC-dropout + PCA baseline (csrc/mc_pca_ragged.hip; specification
+ * tests/mc_ragged_ref.py): the items of a batch may have different numbers of gap (mask == 0) elements ---------------------
+ * mask [B][N] (any mask, N = F T <= 2^31 - 1) -> counts [B] = gap elements per item; then, with Nmax >= max counts,
+ * idx [B][Nmax] = their positions in row-major order (the order of boolean indexing and masked_scatter_), -1 past counts[b].
+ * One workgroup per item, block scan, no atomics. */
+int nppc_gap_count(const float* mask, int* counts, int B, long N, void* stream);
+int nppc_gap_index(const float* mask, int* idx, int B, long N, int Nmax, void* stream);
+/* out [B][Nmax] = src [B][N] through idx, 0 where idx < 0 */
+int nppc_gap_gather(const float* src, const int* idx, float* out, int B, long N, int Nmax, void* stream);
+/* out [B][R][N] = 0, then vals [B][R][Nmax] written through idx (entries < 0 skipped) */
+int nppc_gap_scatter(const float* vals, const int* idx, float* out, int B, int R, long N, int Nmax, void* stream);
+/* nppc_pca_batch for X [K][B][Nmax] where item b owns its first counts[b] (1 <= counts[b] <= Nmax) elements: outputs as
+ * nppc_pca_batch with rows of Nmax, zeros past counts[b].  The Gram is summed without atomics in a fixed order over chunks
+ * of 64 elements that start at the item's element 0, so item b of a batch equals, bit for bit, the same call on that item
+ * alone (B = 1, Nmax = counts[b]), and two runs agree bit for bit.  Same limits: 2 <= K <= 60, n <= min(K, 8).
+ * work = *elems of nppc_pca_ragged_work_elems doubles. */
+int nppc_pca_ragged_work_elems(int K, int B, int Nmax, int n, long* elems);
+int nppc_pca_ragged(const float* X, const int* counts, int K, int B, int Nmax, int n, float* mean, float* comps, float* scaled,
+                    float* svals, float* weights, double* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
