@@ -268,6 +268,8 @@ SIGS = {
     "nppc_gap_scatter": [P, P, P, I, I, L, I, P],
     "nppc_pca_ragged_work_elems": [I, I, I, I, PL],
     "nppc_pca_ragged": [P, P, I, I, I, I, P, P, P, P, P, P, P],
+    "nppc_inpaint_vad_batch": [P, L, P, P, I, P, P, I, I, I, I, I, I, I, L, I, F, D, D, D, D, I, I, P, P, P, P, P, P, P, P],
+    "nppc_inpaint_draw_gaps": [P, P, P, I, I, I, I, I, L, I, P, P, P, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

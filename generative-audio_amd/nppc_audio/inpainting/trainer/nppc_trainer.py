@@ -4,8 +4,10 @@ base_step :338-385, save_checkpoint :604-618, _calculate_final_objective :680-68
 
 Differences, deliberately: the frozen restorer runs once per step (the reference runs it twice on the same input);
 clip_grad_norm_ + Adam run as sum-of-squares + ONE fused kernel over the flat gradient with the clip coefficient
-computed on the device (no host round trip); wandb logging, plotting, the MC-dropout variants (base_step2) and the
-LibriSpeech/VAD dataset are outside the hot path.
+computed on the device (no host round trip); wandb logging and plotting are not built.  Without a
+`dataset=` the trainer builds `data.AudioInpaintingDataset` + `data.InpaintingDeviceLoader` from its data_configuration:
+a wav folder decoded once and minibatches assembled on the device, with the gap placed by an energy voice-activity
+detector (`vad.py`) where the reference uses silero-vad.
 """
 import os
 from datetime import datetime
@@ -24,10 +26,12 @@ from ...pc_ops import NPPCLoss, planes, second_moment_weight
 from ...trainer import FlatAdamStepper, HipAdam, LoopLoader, OptimizerConfig
 from ..nppc.nppc_model import NPPCModel, NPPCModelConfig
 from ..utils import preprocess_data
+from ..vad import EnergyVadConfig
 
 
 class AudioInpaintingConfig(pydantic.BaseModel):
-    """dataset/audio_dataset_inpainting.py:60-83 (the fields; the LibriSpeech loader itself is out of scope)"""
+    """dataset/audio_dataset_inpainting.py:60-83 (the fields).  vad_configuration (not in the reference): the constants of
+    the energy voice-activity detector that use_vad selects here; None = EnergyVadConfig()'s defaults."""
     clean_path: Union[str, Path]
     sample_rate: int = 16000
     missing_length_seconds: float = 0.128
@@ -40,6 +44,22 @@ class AudioInpaintingConfig(pydantic.BaseModel):
     use_vad: bool = False
     seed: Optional[int] = None
     is_random_sub_sample: bool = True
+    vad_configuration: Optional[EnergyVadConfig] = None
+
+
+def build_device_loader(data_configuration, dataloader_configuration, device):
+    """the stock data path of both inpainting trainers: (AudioInpaintingDataset, InpaintingDeviceLoader) from the parsed
+    configuration.  The dataset is built first and raises ValueError (naming the dataset= way in) for a missing or empty
+    folder before anything touches the device.  Of dataloader_configuration only batch_size and shuffle apply (the last
+    batch is kept): num_workers and pin_memory have no meaning for a loader that assembles its batches on the device and
+    are ignored.  Both trainers set up their data before their model, with or without dataset=, so a data error comes
+    before a model or checkpoint error."""
+    from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
+    from ..data import AudioInpaintingDataset, InpaintingDeviceLoader
+    dataset = AudioInpaintingDataset(data_configuration)
+    dl = dataloader_configuration
+    sampler = RandomSampler(dataset) if dl.shuffle else SequentialSampler(dataset)
+    return dataset, InpaintingDeviceLoader(dataset, BatchSampler(sampler, dl.batch_size, drop_last=False), device=device)
 
 
 class NPPCAudioInpaintingTrainerConfig(pydantic.BaseModel):
@@ -90,15 +110,16 @@ class NPPCAudioInpaintingTrainer(nn.Module):
         self.config = config
         if config.use_wandb:
             raise NotImplementedError("wandb logging is outside the MI355X hot path build (no network)")
-        self.nppc_model = NPPCModel(self.config.nppc_model_configuration)
         self.device = self.config.device
-        if dataset is None:
-            raise ValueError("pass a dataset yielding (stft_masked [2,F,T], mask_frames [T], stft_clean [2,F,T]) items; "
-                             "the LibriSpeech/VAD loader of the reference is outside the hot path")
+        if dataset is None:                                          # the wav folder of data_configuration, before the model
+            dataset, self.dataloader = build_device_loader(config.data_configuration, config.dataloader_configuration,
+                                                           self.device)
+        else:
+            dl = config.dataloader_configuration
+            self.dataloader = torch.utils.data.DataLoader(dataset, batch_size=dl.batch_size, shuffle=dl.shuffle,
+                                                          num_workers=dl.num_workers, pin_memory=dl.pin_memory)
         print(f"Total sample pairs in dataset: {len(dataset)}")
-        dl = config.dataloader_configuration
-        self.dataloader = torch.utils.data.DataLoader(dataset, batch_size=dl.batch_size, shuffle=dl.shuffle,
-                                                      num_workers=dl.num_workers, pin_memory=dl.pin_memory)
+        self.nppc_model = NPPCModel(self.config.nppc_model_configuration)
         self.step = 0
         okind = config.optimizer_configuration.type
         if okind == "Adam":

@@ -7,9 +7,11 @@ U-Net runs in train mode (batch-statistics BatchNorm, running-buffer update) wit
 the masked spectral MSE and its gradient are HIP kernels, and with Adam the clip_grad_norm_ + update is the fused
 clipped Adam over the flat parameter buffer (the clip coefficient stays on the device).
 
-Differences, deliberately: wandb logging, matplotlib plotting and the LibriSpeech/VAD dataset are outside the hot path
-(pass `dataset=`; `use_wandb=True` raises NotImplementedError); `max_grad_norm` is a config field (the reference
-hard-codes 5); the step's loss history is kept on the trainer (`loss_history`) and returned by `train`.
+Differences, deliberately: wandb logging and matplotlib plotting are not built (`use_wandb=True` raises
+NotImplementedError); without a `dataset=` the data come from `data.AudioInpaintingDataset` + `data.InpaintingDeviceLoader`
+(a wav folder, minibatches assembled on the device, gaps placed by the energy voice-activity detector of `vad.py` where the
+reference uses silero-vad); `max_grad_norm` is a config field (the reference hard-codes 5); the step's loss history is kept
+on the trainer (`loss_history`) and returned by `train`.
 """
 import json
 import os
@@ -26,7 +28,7 @@ from ...data import DataLoaderConfig
 from ...trainer import FlatAdamStepper, HipAdam, LoopLoader, OptimizerConfig
 from ..networks.unet import RestorationWrapper, UNet, UNetConfig
 from ..utils import preprocess_data
-from .nppc_trainer import AudioInpaintingConfig
+from .nppc_trainer import AudioInpaintingConfig, build_device_loader
 
 __all__ = ["OptimizerConfig", "InpaintingTrainerConfig", "InpaintingTrainer", "MaskedSpectralMSE", "masked_spectral_mse"]
 
@@ -86,9 +88,10 @@ class InpaintingTrainer(nn.Module):
         self.config = config
         if config.use_wandb:
             raise NotImplementedError("wandb logging is outside the MI355X hot path build (no network)")
-        if dataset is None:
-            raise ValueError("pass a dataset yielding (stft_masked [2,F,T], mask_frames [T], stft_clean [2,F,T][, ...]) "
-                             "items; the LibriSpeech/VAD loader of the reference is outside the hot path")
+        self.dataloader = None
+        if dataset is None:                                          # the wav folder of data_configuration, before the model
+            dataset, self.dataloader = build_device_loader(config.data_configuration, config.dataloader_configuration,
+                                                           config.device)
 
         base_network = UNet(self.config.model_configuration)
         self.model = RestorationWrapper(base_network)
@@ -104,9 +107,10 @@ class InpaintingTrainer(nn.Module):
             self.optimizer = getattr(optim, okind)(self.model.parameters(), **config.optimizer_configuration.args)
 
         print(f"Total sample pairs in dataset: {len(dataset)}")
-        dl = config.dataloader_configuration
-        self.dataloader = torch.utils.data.DataLoader(dataset, batch_size=dl.batch_size, shuffle=dl.shuffle,
-                                                      num_workers=dl.num_workers, pin_memory=dl.pin_memory)
+        if self.dataloader is None:
+            dl = config.dataloader_configuration
+            self.dataloader = torch.utils.data.DataLoader(dataset, batch_size=dl.batch_size, shuffle=dl.shuffle,
+                                                          num_workers=dl.num_workers, pin_memory=dl.pin_memory)
         self.step = 0
         self.loss_history: List[float] = []
         self._flat_adam = None

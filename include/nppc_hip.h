@@ -352,6 +352,35 @@ int nppc_time_to_spec_mask(const float* mask_time, float* mask_frames, int B, in
 int nppc_stft_pair(const float* wave, const float* mask_frames /*nullable*/, float* spec, float* masked_spec /*nullable*/,
                    int B, int L, int nfft, int hop, void* stream);
 
+/* ---- inpainting dataset on the device (csrc/inpaint_data.hip; specification tests/vad_ref.py) ------
+ * What AudioInpaintingDataset.__getitem__ (:253-293) does before the STFT, for a batch, from a corpus that stays in HBM:
+ * corpus = every decoded file back to back, file f = corpus[offsets[f], offsets[f + 1]) with the gain gains[f] of its
+ * whole-file _normalize_audio.  Item b is cut from file file_index[b] (at least L samples long):
+ *   crop_start = uniform_int(0, len - L) when random_crop and len > L, else 0;  clean[b] = crop * gain (nullable);
+ *   dbfs_float > 0 multiplies the gain by 10^(d / 20), d uniform in +-dbfs_float (target_dB_FS_floating_value);
+ *   use_vad: an energy voice-activity detector over W = L / win windows (win a multiple of 64; W <= 2048, above that
+ *   NPPC_EUNSUPPORTED): level e_w = 10 log10(mean x^2 + 1e-12), floor = nearest-rank floor_percentile of the levels,
+ *   peak = their maximum, theta_on = max(floor + on_db, peak - range_db), theta_off = theta_on - hysteresis_db, no
+ *   segment when peak - floor < on_db; segments by the state machine of silero's get_speech_timestamps (min_silence in
+ *   samples, minimum length = missing, no padding) -> segments [B][s_max][2] (-1 past n_segments[b]; W <= 2 s_max <= 2048);
+ *   gap (_create_mask :199-221): a uniformly chosen segment, gap_start = its start + uniform_int(0, its length - missing)
+ *   when it is longer than missing; otherwise, and always without use_vad, the fallback (_create_random_mask):
+ *   fixed_start when >= 0, else uniform_int(0, L - missing).  used_fallback [B] = 1 for the fallback (-1: file_index[b]
+ *   does not name a file of at least L samples; nothing was read, clean[b] = 0).
+ * Random numbers: Philox4x32-10, key = seed, counter (item_index[b], epoch, 0, purpose), purpose 0 crop start, 1 segment,
+ * 2 gap offset, 3 level; uniform_int(0, n) = the high 32 bits of word0 * (n + 1).  One workgroup per item, no atomics: an
+ * item's result does not depend on the rest of the batch. */
+int nppc_inpaint_vad_batch(const float* corpus, long corpus_len, const long* offsets, const float* gains, int n_files,
+                           const int* file_index, const int* item_index, int B, int L, int win, int missing, int fixed_start,
+                           int use_vad, int random_crop, long seed, int epoch, float dbfs_float, double on_db, double range_db,
+                           double hysteresis_db, double floor_percentile, int min_silence, int s_max,
+                           float* clean /*nullable*/, int* crop_start /*nullable*/, int* gap_start, int* gap_end, int* segments,
+                           int* n_segments, int* used_fallback, void* stream);
+/* the gap draw of nppc_inpaint_vad_batch alone, on given segments [B][s_max][2] / n_segments [B] */
+int nppc_inpaint_draw_gaps(const int* segments, const int* n_segments, const int* item_index, int B, int L, int missing,
+                           int fixed_start, int s_max, long seed, int epoch, int* gap_start, int* gap_end, int* used_fallback,
+                           void* stream);
+
 /* ---- MC-dropout + PCA baseline (utils.py:334-648) -----------------------------------------------
  * nn.Dropout(p) (tmp_utils.py:28-29) in place on channels [0, C) of a haloed NHWC activation X [rows][ld]:
  * keep bit = Philox4x32-10(seed; row, channel / 4, stream_id) >= p * 2^32, kept values scaled by 1 / (1 - p);
