@@ -270,6 +270,10 @@ SIGS = {
     "nppc_pca_ragged": [P, P, I, I, I, I, P, P, P, P, P, P, P],
     "nppc_inpaint_vad_batch": [P, L, P, P, I, P, P, I, I, I, I, I, I, I, L, I, F, D, D, D, D, I, I, P, P, P, P, P, P, P, P],
     "nppc_inpaint_draw_gaps": [P, P, P, I, I, I, I, I, L, I, P, P, P, P],
+    "nppc_rec_gain": [P, L, P, I, F, P, P, P],
+    "nppc_rec_windows": [P, L, P, I, P, I, I, P, P, P, P],
+    "nppc_rec_splice": [P, L, P, P, I, P, L, L, I, I, I, P, P, P],
+    "nppc_zero_runs": [P, L, L, P, L, P, I, P, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

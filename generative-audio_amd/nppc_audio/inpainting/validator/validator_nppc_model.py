@@ -14,8 +14,8 @@ Griffin-Lim restricted to the gap, the damaged recording's STFT held fixed), whi
 `validate_batch(..., pitch=True)` adds the f0 contours of plot_pitch_comparison (:19-270) for the clean waveform and every
 variation, tracked on the device (nppc_audio/pitch.py), and what each direction does to them.
 
-Outside this build: whisper / phoneme transcription, the plots themselves (pitch and spectrogram), wav files, splicing a
-variation into the full source file (get_with_full_audio), wandb.
+Outside this build: whisper / phoneme transcription, the plots themselves (pitch and spectrogram), wav files, wandb.
+Splicing a restoration or a variation into the full source recording is inpainting/restore.py (RecordingRestorer).
 """
 import json
 from pathlib import Path

@@ -741,6 +741,34 @@ int nppc_pca_ragged_work_elems(int K, int B, int Nmax, int n, long* elems);
 int nppc_pca_ragged(const float* X, const int* counts, int K, int B, int Nmax, int n, float* mean, float* comps, float* scaled,
                     float* svals, float* weights, double* work, void* stream);
 
+/* ---- whole-recording restoration (csrc/restore_rec.hip; specification tests/restore_ref.py) --------
+ * The top layer of the inpainting side: a recording wave [L] with gaps -> windows for the nets -> the window outputs spliced
+ * back.  gaps [G][2] (long): half-open sample intervals [s, e), sorted ascending and disjoint.  Plain vector loads and stores,
+ * no float atomics, sums in a fixed order: two runs give identical bits. */
+#define NPPC_REC_GAIN_WORK 256      /* doubles of nppc_rec_gain's workspace */
+#define NPPC_ZERO_RUN_CHUNK 4096    /* samples per workgroup of nppc_zero_runs' first phase */
+/* gain[0] (fp64) = 10^((target_dbfs - 20 log10(rms + 1e-8)) / 20), rms over the samples outside every gap
+ * (dataset/audio_dataset_inpainting.py:154-168 on the known samples).  G = 0 (gaps nullable): every sample. */
+int nppc_rec_gain(const float* wave, long L, const long* gaps, int G, float target_dbfs, double* work, double* gain,
+                  void* stream);
+/* one workgroup per window w: out [W][win_len] = (float)(wave[win_start[w] + j] * gain[0]) (one fp64 product), 0 inside
+ * every gap and outside [0, L); mask [W][win_len] = 0 there, 1 elsewhere */
+int nppc_rec_windows(const float* wave, long L, const long* gaps, int G, const long* win_start, int W, int win_len,
+                     const double* gain, float* out, float* mask, void* stream);
+/* out [V][L]: out[v] = wave except around gap g, which window g (start win_start[g]) owns; with
+ * y = wout[g * w_stride + v * v_stride + (n - win_start[g])] / gain[0] (fp64):
+ *   n in [s, e): y;  n in [s - xf, s), t = n - (s - xf), and n in [e, e + xf), t = e + xf - 1 - n:
+ *   wave[n] + c (y - wave[n]) with c = 0.5 - 0.5 cos(pi (t + 1) / (xf + 1)), in fp64, rounded to fp32 once;
+ * clipped at the recording's ends and at the window's; every other sample is copied bit for bit.  The regions
+ * [s - xf, e + xf) must not overlap (where they do, the lower gap wins). */
+int nppc_rec_splice(const float* wave, long L, const long* gaps, const long* win_start, int G, const float* wout,
+                    long w_stride, long v_stride, int win_len, int V, int xf, const double* gain, float* out, void* stream);
+/* maximal runs of samples == 0 with at least min_len (>= 1) samples -> runs [cap][2] (start, end) ascending, count[0] = how
+ * many there are (it may exceed cap: nothing is written past the buffer).  work: at least
+ * nchunks (4 + 2 (NPPC_ZERO_RUN_CHUNK / (min_len + 1) + 1)) longs, nchunks = ceil(L / NPPC_ZERO_RUN_CHUNK). */
+int nppc_zero_runs(const float* wave, long L, long min_len, long* work, long work_elems, long* runs, int cap, long* count,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
