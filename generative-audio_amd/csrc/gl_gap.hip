@@ -11,50 +11,20 @@
 //   gl_fill_kernel   copies the known waveform to every variation outside the gap's reach (NaN for an item over the cap)
 //   gl_gap_kernel    one workgroup per (item, variation): all iterations with the gap spectra C, the previous transform P
 //                    (momentum only), the target magnitudes, the span's time segment and the twiddles resident in LDS
+// What this file shares with the tiled path for spans over the cap (gl_gap_long.hip, section 8g: nppc_gl_gap_long_shape,
+// nppc_gl_gap_long, nppc_gl_gap_pc_long) is in gl_gap_common.h; gl_span_kernel, gl_base_kernel and gl_fill_kernel serve both.
 // Both transforms are direct DFTs out of LDS as in inpaint_validator.hip / frontend.hip: twiddles exp(2 pi i j / N) in fp64
 // indexed by (k n) mod N in integers, fp64 accumulation, fp32 state.  Every sum has one writer and a fixed order: no
 // atomics; a waveform does not depend on the batch or on the run.
-#include "common.h"
-#include "nppc_hip.h"
+#include "gl_gap_common.h"
 
-#include <math.h>
+using namespace nppc_gl;
 
 namespace {
 
-constexpr int GL_T = 256;                        // threads of gl_gap_kernel
-constexpr int GL_WAVES = GL_T / 64;
 constexpr size_t GL_LDS_BUDGET = 160 * 1024;     // LDS of one CU
 constexpr int GL_NLIVE = 2 * NPPC_GL_MAX_SPAN_FRAMES;   // byte of the flag area that holds the number of live frames
 static_assert(GL_NLIVE < 256, "the flag area is al256(cap) >= 256 bytes");
-constexpr int GL_INFO = 8;                       // ints per item: t_lo, t_hi, s_lo, s_hi, status, has_gap, o_a, o_b
-
-struct GlGeom {
-  int N, F, hop, T, L;
-  int Lk;        // samples the overlap-add reaches, min(L, N + hop (T - 1) - N / 2); [Lk, L) is zero as in torch.istft
-  int pad, r;    // N / 2; ceil(N / hop) - 1
-  int cap;       // effective span cap (gap bounding range + 2 r)
-  int Gmax;      // cap - 2 r: frame slots of C, P, M
-  int Pmax;      // (cap - 1) hop + N: padded-coordinate samples of the largest span
-  int n_iter, mom;
-  double c;      // momentum / (1 + momentum)
-};
-
-struct GlWork {
-  int* info;       // [B][GL_INFO]
-  float* kspec;    // [B][2][F][T]: known spectrum, gap frames zeroed
-  float* kwave;    // [B][L]
-  double* base;    // [B][Pmax]
-  double* den;     // [B][Pmax]: envelope * N; 0 = the sample is zero (past Lk)
-};
-
-// where the target magnitude of (item, variation) comes from
-struct GlMag {
-  const float* target;                       // [B][V][F][T], or null:
-  const float *pred, *pc, *mean, *stdev, *alphas;
-  int K, A;
-};
-
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 size_t gl_lds_bytes(int N, int F, int hop, int r, int cap, int mom) {
   const size_t G = cap - 2 * r;
@@ -62,8 +32,9 @@ size_t gl_lds_bytes(int N, int F, int hop, int r, int cap, int mom) {
          sizeof(float) * ((size_t)(cap - 1) * hop + N) + al256(cap);
 }
 
-// -> NPPC_OK or an error with *why: 1 F, 2 frame count, 3 overlap / n_fft limit, 4 n_iter or momentum, 5 anything else
-int gl_geom(int B, int V, int F, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span, GlGeom* g,
+}  // namespace
+
+int nppc_gl::gl_geom(int B, int V, int F, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span, GlGeom* g,
             size_t* lds, size_t* work, int* why) {
   *why = 5;
   if (B <= 0 || B > 65535 || V <= 0 || V > 65535 || T <= 0 || nfft < 2 || hop < 1 || hop > nfft || L <= 0 || max_span < 0)
@@ -98,7 +69,7 @@ int gl_geom(int B, int V, int F, int T, int nfft, int hop, int L, int n_iter, do
   return NPPC_OK;
 }
 
-GlWork gl_carve(void* work, const GlGeom& g, int B) {
+GlWork nppc_gl::gl_carve(void* work, const GlGeom& g, int B) {
   char* p = (char*)work;
   GlWork w;
   w.info = (int*)p, p += al256(sizeof(int) * GL_INFO * (size_t)B);
@@ -109,46 +80,12 @@ GlWork gl_carve(void* work, const GlGeom& g, int B) {
   return w;
 }
 
-__device__ __forceinline__ void gl_twiddles(double2* tw, int N, int nthr) {
-  for (int i = threadIdx.x; i < N; i += nthr) {
-    double sn, cs;
-    sincospi(2.0 * i / N, &sn, &cs);
-    tw[i] = make_double2(cs, sn);
-  }
-}
-
-// output sample that padded coordinate p holds under torch's reflect padding (pad < L: one reflection is enough)
-__device__ __forceinline__ int gl_reflect(int p, int pad, int L) {
-  int o = p - pad;
-  if (o < 0) o = -o;
-  if (o >= L) o = 2 * (L - 1) - o;
-  return o;
-}
-
-// sample n of N * irfft(sp): bins 1 .. kmax with their conjugates, bin 0 and the Nyquist bin real, as gather_sample of
-// inpaint_validator.hip
-template <typename Load>
-__device__ __forceinline__ double gl_idft_sample(const double2* tw, int N, int n, Load sp) {
-  const int kmax = (N - 1) / 2;
-  double ar = 0.0, ai = 0.0;
-  int idx = n;
-  for (int k = 1; k <= kmax; ++k) {
-    const double2 w = tw[idx];
-    const float2 x = sp(k);
-    ar += (double)x.x * w.x;
-    ai += (double)x.y * w.y;
-    idx += n;
-    if (idx >= N) idx -= N;
-  }
-  double x = (double)sp(0).x + 2.0 * (ar - ai);
-  if (!(N & 1)) x += (n & 1) ? -(double)sp(N / 2).x : (double)sp(N / 2).x;
-  return x;
-}
+namespace {
 
 // ---------------------------------------------------------------------------------------------------- per-item set-up
 __global__ __launch_bounds__(256) void gl_span_kernel(const float* __restrict__ known, const float* __restrict__ mask,
                                                        int* __restrict__ info, float* __restrict__ kspec,
-                                                       int* __restrict__ status, GlGeom g) {
+                                                       int* __restrict__ status, GlGeom g, int route, int long_cap) {
   __shared__ int lo_s[4], hi_s[4];
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* m = mask + (size_t)b * g.T;
@@ -172,14 +109,16 @@ __global__ __launch_bounds__(256) void gl_span_kernel(const float* __restrict__ 
     }
     int* o = info + b * GL_INFO;
     const int has = hi >= 0;
-    const int bad = has && hi - lo + 1 + 2 * g.r > g.cap;
+    int bad = has && hi - lo + 1 + 2 * g.r > g.cap;           // GL_REFUSED; with a route, GL_TILED where the tiled path takes it
+    if (has && (bad || route == GL_ROUTE_ALL) && route != GL_ROUTE_OFF)
+      bad = hi - lo + 1 + 2 * g.r > long_cap ? GL_REFUSED : GL_TILED;
     const int s_lo = has ? (lo - g.r > 0 ? lo - g.r : 0) : 0;
     const int s_hi = has ? (hi + g.r < g.T - 1 ? hi + g.r : g.T - 1) : 0;
     int oa = lo * g.hop - g.pad, ob = hi * g.hop + g.N - g.pad;
     oa = oa < 0 ? 0 : oa;
     ob = ob > g.L ? g.L : ob;
     o[0] = lo, o[1] = hi, o[2] = s_lo, o[3] = s_hi, o[4] = bad, o[5] = has, o[6] = has ? oa : 0, o[7] = has ? ob : 0;
-    status[b] = bad;
+    status[b] = bad == GL_REFUSED;
   }
   const size_t FT = (size_t)g.F * g.T;
   const float* src = known + (size_t)b * 2 * FT;
@@ -189,11 +128,11 @@ __global__ __launch_bounds__(256) void gl_span_kernel(const float* __restrict__ 
 
 __global__ __launch_bounds__(256) void gl_base_kernel(const float* __restrict__ kspec, const float* __restrict__ mask,
                                                        const int* __restrict__ info, double* __restrict__ base,
-                                                       double* __restrict__ den, GlGeom g) {
+                                                       double* __restrict__ den, GlGeom g, int mine) {
   extern __shared__ double2 gl_lds[];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int* it = info + b * GL_INFO;
-  if (it[4] || !it[5]) return;
+  if (it[4] != mine || !it[5]) return;                         // another path's item: nothing is written
   const int s_lo = it[2], s_hi = it[3];
   const int Lp = (s_hi - s_lo) * g.hop + g.N;
   if ((int)blockIdx.x * 256 >= Lp) return;
@@ -229,23 +168,13 @@ __global__ __launch_bounds__(256) void gl_fill_kernel(const float* __restrict__ 
   if (o >= g.L) return;
   const int* it = info + b * GL_INFO;
   float* row = out + ((size_t)b * V + v) * g.L;
-  if (it[4])
+  if (it[4] == GL_REFUSED)
     row[o] = __builtin_nanf("");
   else if (!it[5] || o < it[6] || o >= it[7])
     row[o] = kwave[(size_t)b * g.L + o];
 }
 
 // ------------------------------------------------------------------------------------------------------ the iterations
-__device__ __forceinline__ double gl_block_sum(double v, double* red) {   // fixed order; every thread gets the sum
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = red[0];
-  for (int w = 1; w < GL_WAVES; ++w) s += red[w];
-  return s;
-}
-
 __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __restrict__ known, const float* __restrict__ mask,
                                                        const float* __restrict__ phase, int phase_per_v,
                                                        const int* __restrict__ info, const double* __restrict__ base,
@@ -453,6 +382,43 @@ __global__ __launch_bounds__(256) void gl_phase_init_kernel(const float* __restr
   phase[(size_t)b * F * T + e] = out;
 }
 
+}  // namespace
+
+int nppc_gl::gl_launch_known(const float* known, const float* mask, const GlWork& w, float* out, int* status, int B, int V,
+                             const GlGeom& g, int route, int long_cap, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(gl_span_kernel, dim3(B), dim3(256), 0, s, known, mask, w.info, w.kspec, status, g, route, long_cap);
+  NPPC_CHECK_LAUNCH();
+  const long FT = (long)g.F * g.T;
+  const int rk = nppc_istft_any(w.kspec, w.kspec + FT, 2 * FT, w.kwave, g.L, B, g.T, g.N, g.hop, g.L, stream);
+  if (rk != NPPC_OK) return rk;
+  hipLaunchKernelGGL(gl_fill_kernel, dim3(ceil_div(g.L, 256), V, B), dim3(256), 0, s, w.kwave, w.info, out, V, g);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_gl::gl_launch_base(const float* kspec, const float* mask, const int* info, double* base, double* den, int B,
+                            const GlGeom& g, int mine, void* stream) {
+  hipLaunchKernelGGL(gl_base_kernel, dim3(ceil_div(g.Pmax, 256), B), dim3(256), sizeof(double2) * g.N, (hipStream_t)stream, kspec,
+                     mask, info, base, den, g, mine);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+int nppc_gl::gl_launch_resident(const GlMag& ms, const float* known, const float* mask, const float* phase, int phase_per_v,
+                                const GlWork& w, float* out, double* dist, double* tnorm, int B, int V, const GlGeom& g,
+                                size_t lds, void* stream) {
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)gl_gap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return NPPC_ELAUNCH;
+  hipLaunchKernelGGL(gl_gap_kernel, dim3(V, B), dim3(GL_T), lds, (hipStream_t)stream, ms, known, mask, phase, phase_per_v, w.info,
+                     w.base, w.den, out, dist, tnorm, V, g);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+namespace {
+
 int gl_run(const GlMag& ms, const float* known, const float* mask, const float* phase, int phase_per_v, float* out, double* dist,
            double* tnorm, int* status, void* work, long work_bytes, int B, int V, int T, int nfft, int hop, int L, int n_iter,
            double momentum, int max_span, void* stream) {
@@ -460,28 +426,15 @@ int gl_run(const GlMag& ms, const float* known, const float* mask, const float* 
   GlGeom g;
   size_t lds, need;
   int why;
-  const int rc = gl_geom(B, V, nfft / 2 + 1, T, nfft, hop, L, n_iter, momentum, max_span, &g, &lds, &need, &why);
+  int rc = gl_geom(B, V, nfft / 2 + 1, T, nfft, hop, L, n_iter, momentum, max_span, &g, &lds, &need, &why);
   if (rc != NPPC_OK) return rc;
   if (work_bytes < (long)need) return NPPC_EBADARG;
   const GlWork w = gl_carve(work, g, B);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(gl_span_kernel, dim3(B), dim3(256), 0, s, known, mask, w.info, w.kspec, status, g);
-  NPPC_CHECK_LAUNCH();
-  const long FT = (long)g.F * T;
-  const int rk = nppc_istft_any(w.kspec, w.kspec + FT, 2 * FT, w.kwave, L, B, T, nfft, hop, L, stream);
-  if (rk != NPPC_OK) return rk;
-  hipLaunchKernelGGL(gl_base_kernel, dim3(ceil_div(g.Pmax, 256), B), dim3(256), sizeof(double2) * nfft, s, w.kspec, mask, w.info,
-                     w.base, w.den, g);
-  NPPC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(gl_fill_kernel, dim3(ceil_div(L, 256), V, B), dim3(256), 0, s, w.kwave, w.info, out, V, g);
-  NPPC_CHECK_LAUNCH();
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)gl_gap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return NPPC_ELAUNCH;
-  hipLaunchKernelGGL(gl_gap_kernel, dim3(V, B), dim3(GL_T), lds, s, ms, known, mask, phase, phase_per_v, w.info, w.base, w.den, out,
-                     dist, tnorm, V, g);
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  // the launch order of before the tiled path existed: span, known waveform, base, fill, iterations (base and fill are
+  // independent of each other)
+  if ((rc = gl_launch_known(known, mask, w, out, status, B, V, g, GL_ROUTE_OFF, 0, stream)) != NPPC_OK) return rc;
+  if ((rc = gl_launch_base(w.kspec, mask, w.info, w.base, w.den, B, g, GL_RESIDENT, stream)) != NPPC_OK) return rc;
+  return gl_launch_resident(ms, known, mask, phase, phase_per_v, w, out, dist, tnorm, B, V, g, lds, stream);
 }
 
 }  // namespace

@@ -262,6 +262,9 @@ SIGS = {
     "nppc_gl_phase_init": [P, P, P, I, I, I, I, P],
     "nppc_gl_gap": [P, P, P, P, I, P, P, P, P, P, L, I, I, I, I, I, I, I, D, I, P],
     "nppc_gl_gap_pc": [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, I, I, D, I, P],
+    "nppc_gl_gap_long_shape": [I, I, I, I, I, I, I, I, D, I, I, PI, PI, PI, PI, PL, PL],
+    "nppc_gl_gap_long": [P, P, P, P, I, P, P, P, P, P, L, I, I, I, I, I, I, I, D, I, I, I, P],
+    "nppc_gl_gap_pc_long": [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, I, I, D, I, I, I, P],
     "nppc_gap_count": [P, P, I, L, P],
     "nppc_gap_index": [P, P, I, L, I, P],
     "nppc_gap_gather": [P, P, P, I, L, I, P],

@@ -52,6 +52,7 @@ class RecordingRestorerConfig(pydantic.BaseModel):
     momentum: float = 0.0
     crossfade_samples: int = 64
     min_gap_samples: int = 160                 # detect_gaps: shorter runs of zeros are signal
+    long_gaps: bool = False                    # gaps over Griffin-Lim's resident span cap run its tiled path (long_spans)
 
 
 def _frame_range(a, b, n_fft, hop, T):
@@ -63,7 +64,7 @@ def _frame_range(a, b, n_fft, hop, T):
     return max(lo, 0), min(hi, T - 1)
 
 
-def plan_windows(length, gaps, window_samples=32704, crossfade_samples=64, n_fft=255, hop_length=128):
+def plan_windows(length, gaps, window_samples=32704, crossfade_samples=64, n_fft=255, hop_length=128, long_gaps=False):
     """The windows that restore `gaps` (half-open sample pairs) of a recording of `length` samples: a list, ascending, of
     {'start': first sample of the window, 'gap': (s, e) the merged gap this window owns and writes back,
      'masked': [(a, b)] every gap's part inside the window in window coordinates, 'frames': (lo, hi) the bounding range of
@@ -71,7 +72,8 @@ def plan_windows(length, gaps, window_samples=32704, crossfade_samples=64, n_fft
     ValueError for a pair that is empty, negative or out of range (it names the pair), a recording shorter than the window,
     a gap with fewer than ceil(n_fft / hop) known frames on either side inside its window, a crossfade that leaves the
     window, and a window whose masked frames (+ the 2 (ceil(n_fft / hop) - 1) neighbours Griffin-Lim keeps with them) exceed
-    phase.gl_gap_shape(...)['span_cap'].  No GPU."""
+    phase.gl_gap_shape(...)['span_cap'].  With long_gaps=True that last refusal is dropped (griffin_lim_gap's long_spans=True
+    takes such windows); every other one stays.  No GPU."""
     length, W, xf, hop = int(length), int(window_samples), int(crossfade_samples), int(hop_length)
     if xf < 0 or W <= 0 or hop <= 0 or n_fft < 2:
         raise ValueError(f"window_samples {W}, crossfade_samples {xf}, n_fft {n_fft}, hop_length {hop}: not a configuration")
@@ -116,7 +118,7 @@ def plan_windows(length, gaps, window_samples=32704, crossfade_samples=64, n_fft
         if (s - xf < ws and ws > 0) or (e + xf > ws + W and ws + W < length):
             raise ValueError(f"the crossfade of {xf} samples around gap ({s}, {e}) leaves its window [{ws}, {ws + W})")
         f_lo, f_hi = known.index(False), T - 1 - known[::-1].index(False)
-        if f_hi - f_lo + 1 + 2 * sh["r"] > sh["span_cap"]:
+        if not long_gaps and f_hi - f_lo + 1 + 2 * sh["r"] > sh["span_cap"]:
             raise ValueError(f"the window [{ws}, {ws + W}) of gap ({s}, {e}) masks frames {f_lo}..{f_hi}: with "
                              f"{2 * sh['r']} neighbours that is more than the span cap of {sh['span_cap']} frames "
                              "(a gap too long, or two gaps inside one window)")
@@ -203,7 +205,7 @@ class RecordingRestorer:
 
     def plan(self, length, gaps):
         c = self.config
-        return plan_windows(length, gaps, c.window_samples, c.crossfade_samples, c.n_fft, c.hop_length)
+        return plan_windows(length, gaps, c.window_samples, c.crossfade_samples, c.n_fft, c.hop_length, c.long_gaps)
 
     def restore(self, wave, gaps, alphas=None, variations="windows"):
         """wave [L] float (host or device), gaps [(start, end)] half-open sample pairs -> dict:
@@ -240,6 +242,8 @@ class RecordingRestorer:
             _, mask4, masked_norm, mean, std = preprocess_data(masked, masked, mask_f, plot_mean_std=True)
             mask4 = mask4.contiguous()
             kw = dict(n_iter=c.gl_iters, momentum=c.momentum, n_fft=c.n_fft, hop_length=c.hop_length, length=Lw)
+            if c.long_gaps:
+                kw["long_spans"] = True
             out = {"windows": plan, "gain": gain}
             if alphas is None:
                 pred = self.model.get_pred_spec_mag_norm(masked_norm, mask4, reuse=False)

@@ -148,7 +148,7 @@ class NPPCModelValidator:
                 'mask': mask4, 'mean': mean, 'std': std, 'mc_dropout': mc, 'gram': gram, 'clean_spec': clean_spec}
 
     def validate_batch(self, masked_spec, mask, clean_spec, n_mc_samples=50, n_components=5, alphas=None, n_fft=255,
-                       hop_length=128, pitch=False, phase="clean", gl_iters=32, ragged_gaps=False):
+                       hop_length=128, pitch=False, phase="clean", gl_iters=32, ragged_gaps=False, long_spans=False):
         """validate_sample + _validate_with_baseline (:930-1027) for a uniform batch: masked_spec, clean_spec [B,2,F,T],
         mask [B,T] (1 = known; the same number of gap frames in every item) -> dict with 'pc_directions' [B,K,F,T],
         'pred_spec_mag_norm', 'clean_spec_mag_norm', 'mask' [B,1,F,T], 'mean', 'std', 'mc_dropout' (calculate_unet_baseline's
@@ -163,7 +163,9 @@ class NPPCModelValidator:
         phase="griffin_lim" (needs `alphas`; ValueError otherwise) adds 'audio_variations_blind' [B,K,A,L],
         'restored_audio_blind' [B,L] and 'phase_info' (phase.pc_audio_variations_blind: `gl_iters` iterations of
         gap-constrained Griffin-Lim from the damaged recording's STFT, no clean phase).  The default phase="clean" returns
-        exactly what it returned before; pitch tracking keeps using the clean-phase waveforms.
+        exactly what it returned before; pitch tracking keeps using the clean-phase waveforms.  `long_spans` is passed to
+        pc_audio_variations_blind: True lets gaps over Griffin-Lim's resident span cap through (the reference yaml's 0.256 s
+        gap is 33 frames at 255 / 128), the default flags them with status 1 and NaN.
 
         ragged_gaps=True accepts items with different numbers of gap frames (every item needs at least one); the keys
         and shapes are the same.  The default keeps raising ValueError for such a batch."""
@@ -189,7 +191,7 @@ class NPPCModelValidator:
                     out['audio_variations_blind'], out['restored_audio_blind'], out['phase_info'] = \
                         PH.pc_audio_variations_blind(out['pred_spec_mag_norm'], out['pc_directions'], masked_dev, out['mask'],
                                                      alphas, out['mean'], out['std'], n_iter=gl_iters, n_fft=n_fft,
-                                                     hop_length=hop_length)
+                                                     hop_length=hop_length, long_spans=long_spans)
         return out
 
     def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False, ragged_gaps=False):

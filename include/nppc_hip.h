@@ -721,6 +721,27 @@ int nppc_gl_gap_pc(const float* pred, const float* pc, const float* mean, const 
                    double* target_norm, int* status, void* work, long work_bytes, int B, int K, int A, int T, int nfft, int hop,
                    int L, int n_iter, double momentum, int max_span, void* stream);
 
+/* ---- Griffin-Lim for spans over the cap: the tiled path (csrc/gl_gap_long.hip) -------------------------
+ * The same algorithm and the same bits per waveform as nppc_gl_gap, with a waveform's state (C, P, M, the span's time
+ * segment) in the workspace and one launch per half-iteration over many workgroups: 2 n_iter + O(1) launches on the caller's
+ * stream, no host read, no atomics, no kernel waits for another workgroup.  mode 1: items whose span is within the resident
+ * cap (max_span, as above) run as nppc_gl_gap runs them, the others run tiled; mode 2: every item runs tiled.
+ * long_max_span: 0 = T + 2 r (no gap of the clip is refused), else the span cap of the tiled path (> 2 r), which sizes the
+ * workspace; an item over it gets NaN and status 1 as above.  dist and target_norm of a tiled item are folded over workgroups
+ * in ascending order: they may differ from the resident kernel's in the last bits, the waveforms may not.
+ * The argument rules without a GPU: as nppc_gl_gap_shape, plus *long_span_cap; *work_bytes covers both paths. */
+int nppc_gl_gap_long_shape(int B, int V, int F, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span,
+                           int long_max_span, int* why, int* r, int* span_cap, int* long_span_cap, long* lds_bytes,
+                           long* work_bytes);
+int nppc_gl_gap_long(const float* target_mag, const float* known_spec, const float* mask, const float* init_phase,
+                     int phase_per_variation, float* out, double* dist, double* target_norm, int* status, void* work,
+                     long work_bytes, int B, int V, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span,
+                     int long_max_span, int mode, void* stream);
+int nppc_gl_gap_pc_long(const float* pred, const float* pc, const float* mean, const float* stdev, const float* alphas,
+                        const float* known_spec, const float* mask, const float* init_phase, float* out, double* dist,
+                        double* target_norm, int* status, void* work, long work_bytes, int B, int K, int A, int T, int nfft,
+                        int hop, int L, int n_iter, double momentum, int max_span, int long_max_span, int mode, void* stream);
+
 /* ---- ragged-gap MC-dropout + PCA baseline (csrc/mc_pca_ragged.hip; specification
  * tests/mc_ragged_ref.py): the items of a batch may have different numbers of gap (mask == 0) elements ---------------------
  * mask [B][N] (any mask, N = F T <= 2^31 - 1) -> counts [B] = gap elements per item; then, with Nmax >= max counts,
