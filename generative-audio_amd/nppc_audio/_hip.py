@@ -277,6 +277,13 @@ SIGS = {
     "nppc_rec_windows": [P, L, P, I, P, I, I, P, P, P, P],
     "nppc_rec_splice": [P, L, P, P, I, P, L, L, I, I, I, P, P, P],
     "nppc_zero_runs": [P, L, L, P, L, P, I, P, P],
+    "nppc_flac_probe": [P, L, P, P],
+    "nppc_flac_decode_host": [P, L, P, L, P, L, P],
+    "nppc_flac_work_elems": [L, PL],
+    "nppc_flac_scan": [P, L, P, I, P, L, P],
+    "nppc_flac_parse": [P, P, I, P, L, P],
+    "nppc_flac_chain": [P, P, I, P, L, P, P],
+    "nppc_flac_decode": [P, P, I, P, L, P, L, P, L, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

@@ -63,12 +63,27 @@ def _decode_wav(path, sample_rate):
         a = a.astype(np.float32)
     if a.ndim > 1:
         a = a.mean(axis=1)
+    return torch.from_numpy(np.ascontiguousarray(_to_rate(a, sr, sample_rate)))
+
+
+def _to_rate(a, sr, sample_rate):
+    """mono float32 [n] at sr -> at sample_rate (scipy's polyphase filter in fp64): the one branch wav and flac share"""
     if sr != sample_rate:
         from math import gcd
         from scipy.signal import resample_poly
         g = gcd(int(sr), int(sample_rate))
         a = resample_poly(a.astype(np.float64), sample_rate // g, sr // g).astype(np.float32)
-    return torch.from_numpy(np.ascontiguousarray(a))
+    return a
+
+
+def _decode_flac(path, sample_rate):
+    """one flac file -> mono float32 [n] at `sample_rate`: the contract of _decode_wav (nppc_audio.flac decodes; the mean
+    over channels is formed as numpy forms it, so the same PCM as wav and as flac gives the same bits)"""
+    from .flac import decode_files
+    (a,), (info,) = decode_files([path], out="mono")
+    if a.numel() == 0:
+        return None
+    return torch.from_numpy(np.ascontiguousarray(_to_rate(a.numpy(), info.sample_rate, sample_rate)))
 
 
 class AudioDataset(torch.utils.data.Dataset):

@@ -72,9 +72,15 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
     """dataset/audio_dataset_inpainting.py:86-333 on pre-decoded clips.
 
     AudioInpaintingDataset(config)                     scans config.clean_path for *.wav and decodes every file ONCE
-                                                       (data._decode_wav).  *.flac files are found but this build has no
-                                                       flac decoder: a folder with only flac files raises a ValueError
-                                                       that says so.
+                                                       (data._decode_wav); flac files next to them stay ignored.  A
+                                                       folder with no wav and some *.flac files (LibriSpeech) is decoded
+                                                       by nppc_audio.flac.decode_files in batches, on the device when
+                                                       there is one; the same PCM as wav and as flac gives the same
+                                                       dataset bit for bit.  When the flac decoder rejects every file it
+                                                       is a ValueError that says so.  No file written by libFLAC or any
+                                                       other encoder was available when the decoder was built: the
+                                                       format is pinned by tests/flac_ref.py, written from the
+                                                       specification.
     AudioInpaintingDataset(config, clean_clips=[...])  tensor-backed: 1-D float tensors already at config.sample_rate
     `config` is the trainer's AudioInpaintingConfig.  No transcriptions, no torch.hub.
 
@@ -115,13 +121,13 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
             how = ("; put *.wav files there, or pass dataset= (items of (stft_masked [2,F,T], mask_frames [T], "
                    "stft_clean [2,F,T])) or clean_clips=")
             wavs = sorted(self.clean_path.rglob("*.wav")) if self.clean_path.is_dir() else []
-            if not wavs:
-                n_flac = len(list(self.clean_path.rglob("*.flac"))) if self.clean_path.is_dir() else 0
-                if n_flac:
-                    raise ValueError(f"{self.clean_path} holds {n_flac} FLAC files and no WAV file: this build has no flac "
-                                     f"decoder, convert them to wav" + how)
+            flacs = sorted(self.clean_path.rglob("*.flac")) if self.clean_path.is_dir() and not wavs else []
+            if flacs:
+                decoded = self._decode_flac_folder(flacs, sr, how)
+            elif not wavs:
                 raise ValueError(f"No WAV files found in clean directory: {self.clean_path}" + how)
-            decoded = [(f, _decode_wav(f, sr)) for f in wavs]
+            else:
+                decoded = [(f, _decode_wav(f, sr)) for f in wavs]
             self.clean_files = [f for f, c in decoded if c is not None]
             clean_clips = [c for _, c in decoded if c is not None]
         self.clean = [torch.as_tensor(c, dtype=torch.float32).reshape(-1) for c in clean_clips]
@@ -144,6 +150,29 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
         else:
             self.seed = (int.from_bytes(os.urandom(8), "little") if seed is None else int(seed)) & V.SEED_MASK
         self._single = None
+
+    def _decode_flac_folder(self, flacs, sr, how):
+        """[(file, mono float32 clip at sr)] of a folder of flac files: every file is probed on the host first (a file the
+        probe rejects is skipped with a warning; when it rejects all of them that is the ValueError), the rest are decoded
+        by flac.decode_files in batches -- on the device when there is one -- and brought to `sr` like a wav"""
+        import warnings
+        import numpy as np
+        from ..data import _to_rate
+        from ..flac import FlacError, decode_files, probe
+        good, first = [], None
+        for f in flacs:
+            try:
+                probe(f)
+                good.append(f)
+            except FlacError as e:
+                first = first or e
+                warnings.warn(f"skipping {e}")
+        if not good:
+            raise ValueError(f"{self.clean_path} holds {len(flacs)} FLAC files and no WAV file, and the flac decoder rejects "
+                             f"every one of them (the first: {first})" + how)
+        clips, infos = decode_files(good, out="mono")
+        return [(f, torch.from_numpy(np.ascontiguousarray(_to_rate(c.numpy(), i.sample_rate, sr))))
+                for f, c, i in zip(good, clips, infos)]
 
     def __len__(self) -> int:
         return len(self.clean)

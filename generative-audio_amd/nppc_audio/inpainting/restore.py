@@ -284,12 +284,14 @@ class RecordingRestorer:
             cap = n
 
     def restore_file(self, path_in, path_out, gaps=None):
-        """wav -> wav: decodes with data._decode_wav (mono, config.sample_rate), detects the gaps when none are given,
-        restores, writes 16-bit PCM.  -> restore's dict"""
+        """wav or flac -> wav: decodes with data._decode_wav, or data._decode_flac for a name ending in .flac (mono,
+        config.sample_rate), detects the gaps when none are given, restores, writes 16-bit PCM wav (there is no flac
+        encoder).  -> restore's dict"""
         import numpy as np
         from scipy.io import wavfile
-        from ..data import _decode_wav
-        wave = _decode_wav(path_in, self.config.sample_rate)
+        from ..data import _decode_flac, _decode_wav
+        decode = _decode_flac if str(path_in).lower().endswith(".flac") else _decode_wav
+        wave = decode(path_in, self.config.sample_rate)
         if wave is None:
             raise ValueError(f"{path_in} holds no samples")
         if gaps is None:

@@ -790,6 +790,50 @@ int nppc_rec_splice(const float* wave, long L, const long* gaps, const long* win
 int nppc_zero_runs(const float* wave, long L, long min_len, long* work, long work_elems, long* runs, int cap, long* count,
                    void* stream);
 
+/* ---- FLAC decoding (csrc/flac_core.h + csrc/flac.hip; specification tests/flac_ref.py) --------------
+ * Every entry point returns NPPC_OK / an NPPC_E* code for its ARGUMENTS; what is wrong with a FILE is a per-file status: */
+#define NPPC_FLAC_OK 0
+#define NPPC_FLAC_BAD_MARKER 1        /* the file does not begin with fLaC */
+#define NPPC_FLAC_TRUNCATED 2         /* the file ends inside its metadata or inside a frame */
+#define NPPC_FLAC_BAD_STREAMINFO 3    /* no STREAMINFO block first, or one that cannot be */
+#define NPPC_FLAC_UNSUPPORTED 4       /* 32-bit (or odd-sized) samples, total_samples == 0, an ID3v2 prefix, an Ogg container */
+#define NPPC_FLAC_BAD_HEADER 5        /* no valid frame header where a frame has to begin */
+#define NPPC_FLAC_RESERVED 6          /* a reserved subframe or residual type, or parameters the format rules out */
+#define NPPC_FLAC_CRC16 7             /* a frame's CRC-16 does not match */
+#define NPPC_FLAC_COUNT_MISMATCH 8    /* a frame's sample position is not the running count, or runs past total_samples */
+#define NPPC_FLAC_INFO 8              /* longs of nppc_flac_probe's info */
+#define NPPC_FLAC_META 12             /* longs per file of the device entry points' meta */
+/* host only.  info[0..6] = sample rate, channels, bits per sample, total samples, min blocksize, max blocksize, byte offset
+ * of the first frame (info[7] = 0); *status as above (info is valid when it is 0).  nbytes >= 2^31: NPPC_EUNSUPPORTED. */
+int nppc_flac_probe(const unsigned char* bytes, long nbytes, long* info, int* status);
+/* host only, the serial decoder: probes, then decodes frame after frame into pcm [C][n] (int32, n = total samples;
+ * pcm_elems >= C n) and, when mono is not null, mono [n] (float; mono_elems >= n) = (sum_c (float)pcm[c] / 2^(bps-1)) / C,
+ * summed left to right in fp32.  A status other than 0 leaves the outputs partly written. */
+int nppc_flac_decode_host(const unsigned char* bytes, long nbytes, int* pcm, long pcm_elems, float* mono, long mono_elems,
+                          int* status);
+/* device, a batch of nfiles files laid back to back in bytes [total_bytes].  meta [nfiles][NPPC_FLAC_META] (long, device):
+ *   0 byte_begin  1 byte_end  2 sample rate  3 channels  4 bits per sample  5 min blocksize  6 max blocksize  7 total samples
+ *   8 first-frame byte offset within the file  9 pcm offset (int32 elements)  10 mono offset (floats)  11 unused
+ * with byte_begin ascending, byte_end[f] == byte_begin[f + 1], values 2..8 from nppc_flac_probe.  work: *elems longs of
+ * nppc_flac_work_elems(cap), cap = how many frame-header candidates fit.  The four calls run in this order on one stream
+ * with no host read between them (a clear and four kernels, whatever nfiles is):
+ *   scan    clears work; tests EVERY byte position for a frame header of its file (flac_parse_header) and appends the
+ *           candidates (an integer counter; nothing depends on the order) and enters them in a hash table by offset
+ *   parse   one lane per candidate: the frame parsed to its end with stores off -> end offset, status (CRC-16 included)
+ *   chain   one lane per file: from the first-frame offset along the end offsets exactly as the serial decoder walks;
+ *           marks the accepted candidates; status [nfiles + 1] (int): per file, then 1 when more than cap candidates were
+ *           found (every status is then void: call again with cap >= total_bytes / 4 + 1, which always suffices)
+ *   decode  one lane per accepted candidate: pcm [pcm_elems] int32 and, when not null, mono [mono_elems] float, at the
+ *           offsets of meta; a file whose range does not fit pcm_elems / mono_elems is skipped
+ * No kernel waits for another workgroup and there are no float atomics: two runs give identical bits, and a file's output
+ * does not depend on its neighbours. */
+int nppc_flac_work_elems(long cap, long* elems);
+int nppc_flac_scan(const unsigned char* bytes, long total_bytes, const long* meta, int nfiles, long* work, long cap, void* stream);
+int nppc_flac_parse(const unsigned char* bytes, const long* meta, int nfiles, long* work, long cap, void* stream);
+int nppc_flac_chain(const unsigned char* bytes, const long* meta, int nfiles, long* work, long cap, int* status, void* stream);
+int nppc_flac_decode(const unsigned char* bytes, const long* meta, int nfiles, long* work, long cap, int* pcm, long pcm_elems,
+                     float* mono, long mono_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
