@@ -284,6 +284,9 @@ SIGS = {
     "nppc_flac_parse": [P, P, I, P, L, P],
     "nppc_flac_chain": [P, P, I, P, L, P, P],
     "nppc_flac_decode": [P, P, I, P, L, P, L, P, L, P],
+    "nppc_flac_stream_md5": [P, L, P, P, P],
+    "nppc_flac_md5_host": [P, L, I, I, P],
+    "nppc_flac_md5": [P, L, P, I, P, P, P, P, P, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

@@ -76,11 +76,12 @@ def _to_rate(a, sr, sample_rate):
     return a
 
 
-def _decode_flac(path, sample_rate):
+def _decode_flac(path, sample_rate, verify_md5=True):
     """one flac file -> mono float32 [n] at `sample_rate`: the contract of _decode_wav (nppc_audio.flac decodes; the mean
-    over channels is formed as numpy forms it, so the same PCM as wav and as flac gives the same bits)"""
+    over channels is formed as numpy forms it, so the same PCM as wav and as flac gives the same bits).  verify_md5: the
+    decoded samples are checked against the MD5 STREAMINFO states, when it states one (FlacError, status 9, when not)"""
     from .flac import decode_files
-    (a,), (info,) = decode_files([path], out="mono")
+    (a,), (info,) = decode_files([path], out="mono", verify_md5=verify_md5)
     if a.numel() == 0:
         return None
     return torch.from_numpy(np.ascontiguousarray(_to_rate(a.numpy(), info.sample_rate, sample_rate)))

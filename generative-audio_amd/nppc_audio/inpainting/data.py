@@ -80,7 +80,11 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
                                                        is a ValueError that says so.  No file written by libFLAC or any
                                                        other encoder was available when the decoder was built: the
                                                        format is pinned by tests/flac_ref.py, written from the
-                                                       specification.
+                                                       specification.  verify_flac_md5 (default True): the decoded
+                                                       samples of every file whose STREAMINFO states an MD5 are hashed
+                                                       (on the device when it decodes there) and a file that decodes to
+                                                       other samples than its encoder saw raises flac.FlacError (status
+                                                       9) with its name; False loads such a file as it decodes.
     AudioInpaintingDataset(config, clean_clips=[...])  tensor-backed: 1-D float tensors already at config.sample_rate
     `config` is the trainer's AudioInpaintingConfig.  No transcriptions, no torch.hub.
 
@@ -94,9 +98,10 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
     dataset[i] = (stft_masked [2,F,T], mask_frames [T], stft_clean [2,F,T], masked_audio [1,L]) device tensors: a batch
     of one through `InpaintingDeviceLoader`."""
 
-    def __init__(self, config, clean_clips=None, seed=None, vad=None):
+    def __init__(self, config, clean_clips=None, seed=None, vad=None, verify_flac_md5=True):
         from ..data import _decode_wav
         self.config = config
+        self.verify_flac_md5 = bool(verify_flac_md5)
         sr = int(config.sample_rate)
         self.sub_sample_length = int(config.sub_sample_length_seconds * sr)            # :81-82
         self.missing_length = int(config.missing_length_seconds * sr)
@@ -170,7 +175,7 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
         if not good:
             raise ValueError(f"{self.clean_path} holds {len(flacs)} FLAC files and no WAV file, and the flac decoder rejects "
                              f"every one of them (the first: {first})" + how)
-        clips, infos = decode_files(good, out="mono")
+        clips, infos = decode_files(good, out="mono", verify_md5=self.verify_flac_md5)
         return [(f, torch.from_numpy(np.ascontiguousarray(_to_rate(c.numpy(), i.sample_rate, sr))))
                 for f, c, i in zip(good, clips, infos)]
 

@@ -283,15 +283,18 @@ class RecordingRestorer:
                 return [(int(s), int(e)) for s, e in host[1:1 + 2 * n].view(-1, 2).tolist()]
             cap = n
 
-    def restore_file(self, path_in, path_out, gaps=None):
+    def restore_file(self, path_in, path_out, gaps=None, verify_flac_md5=True):
         """wav or flac -> wav: decodes with data._decode_wav, or data._decode_flac for a name ending in .flac (mono,
         config.sample_rate), detects the gaps when none are given, restores, writes 16-bit PCM wav (there is no flac
-        encoder).  -> restore's dict"""
+        encoder).  A flac file whose STREAMINFO states an MD5 is checked against it (flac.FlacError, status 9, when the
+        decoded samples differ); verify_flac_md5=False takes it as it decodes.  -> restore's dict"""
         import numpy as np
         from scipy.io import wavfile
         from ..data import _decode_flac, _decode_wav
-        decode = _decode_flac if str(path_in).lower().endswith(".flac") else _decode_wav
-        wave = decode(path_in, self.config.sample_rate)
+        if str(path_in).lower().endswith(".flac"):
+            wave = _decode_flac(path_in, self.config.sample_rate, verify_md5=verify_flac_md5)
+        else:
+            wave = _decode_wav(path_in, self.config.sample_rate)
         if wave is None:
             raise ValueError(f"{path_in} holds no samples")
         if gaps is None:

@@ -801,6 +801,7 @@ int nppc_zero_runs(const float* wave, long L, long min_len, long* work, long wor
 #define NPPC_FLAC_RESERVED 6          /* a reserved subframe or residual type, or parameters the format rules out */
 #define NPPC_FLAC_CRC16 7             /* a frame's CRC-16 does not match */
 #define NPPC_FLAC_COUNT_MISMATCH 8    /* a frame's sample position is not the running count, or runs past total_samples */
+#define NPPC_FLAC_MD5 9               /* the decoded samples do not match STREAMINFO's MD5 (nppc_flac_md5's verdict 2) */
 #define NPPC_FLAC_INFO 8              /* longs of nppc_flac_probe's info */
 #define NPPC_FLAC_META 12             /* longs per file of the device entry points' meta */
 /* host only.  info[0..6] = sample rate, channels, bits per sample, total samples, min blocksize, max blocksize, byte offset
@@ -833,6 +834,31 @@ int nppc_flac_parse(const unsigned char* bytes, const long* meta, int nfiles, lo
 int nppc_flac_chain(const unsigned char* bytes, const long* meta, int nfiles, long* work, long cap, int* status, void* stream);
 int nppc_flac_decode(const unsigned char* bytes, const long* meta, int nfiles, long* work, long cap, int* pcm, long pcm_elems,
                      float* mono, long mono_elems, void* stream);
+/* ---- MD5 of the decoded samples (csrc/md5_core.h + csrc/flac_md5.hip) -------------------------------
+ * STREAMINFO holds the MD5 (RFC 1321) of the unencoded samples, written by the encoder: the one check that does not depend
+ * on how the bitstream is read.  The entry points above ignore the field; these read it and compute what it should be.
+ * The message, as libFLAC forms it: the samples interleaved by channel, sample-major, each a signed little-endian integer
+ * of (bps + 7) / 8 bytes (the low bytes of the sign-extended int32: 12 bits fill 2 bytes, 20 bits 3), n C bytes_per_sample
+ * bytes in all.  It is never materialised; lengths are 64-bit, so 2^31 message bytes and more hash like any other.
+ *
+ * host only.  md5 [16] = bytes 18..34 of STREAMINFO, *present = whether any of them is non-zero (sixteen zero bytes are the
+ * format's "not computed"); *status as nppc_flac_probe gives it (md5 is zeroed and *present 0 when it is not 0). */
+int nppc_flac_stream_md5(const unsigned char* bytes, long nbytes, unsigned char* md5, int* present, int* status);
+/* host only, the serial hash: digest [16] of pcm [channels][n] (int32).  n >= 0 (n = 0: the MD5 of the empty message, pcm
+ * may be null); channels outside 1..8, bps outside 4..32 or n < 0: NPPC_EBADARG. */
+int nppc_flac_md5_host(const int* pcm, long n, int channels, int bps, unsigned char* digest);
+/* device, one launch, one lane per file.  pcm [pcm_elems] and meta [nfiles][NPPC_FLAC_META] are the decode calls' (of meta
+ * only channels 3, bits per sample 4, total samples 7 and the pcm offset 9 are read; total samples may be 0 here).  order
+ * [nfiles] (int, device): a permutation of the files, lane i hashes file order[i]; built on the host by descending message
+ * length so that the lanes of a wave run similar block counts.  No result depends on it.  expected [nfiles][16] or null:
+ * the digests nppc_flac_stream_md5 gave.  status [nfiles] or null: nppc_flac_chain's, read on the same stream.
+ *   digest  [nfiles][16]  the MD5 of each file's samples
+ *   verdict [nfiles] int  0 = nothing to compare (expected null or all zero) or the file was skipped, 1 = match, 2 = mismatch
+ * A file with a non-zero status, channels outside 1..8, bits outside 4..32 or a pcm range outside pcm_elems is skipped:
+ * digest zeroed, verdict 0.  16-bit (9..16) mono and stereo take a path of two samples per message word with 16-byte loads
+ * where the address allows; every other format is formed byte by byte.  Two runs give identical bytes. */
+int nppc_flac_md5(const int* pcm, long pcm_elems, const long* meta, int nfiles, const int* order, const unsigned char* expected,
+                  const int* status, unsigned char* digest, int* verdict, void* stream);
 
 #ifdef __cplusplus
 }

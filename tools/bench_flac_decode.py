@@ -46,6 +46,12 @@ def repeat(fn, runs, warmup):
     return out
 
 
+def corpus_clip(seconds):
+    """the one clip whose bytes every file of the corpus holds (tools/bench_flac_md5.py times the same corpus)"""
+    import flac_cases as C
+    return C.speech(seconds, 1234)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=2048)
@@ -55,10 +61,9 @@ def main():
     ap.add_argument("--host1-files", type=int, default=256)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "flac_decode_bench.json"))
     a = ap.parse_args()
-    import flac_cases as C
     from nppc_audio import _hip as H
     from nppc_audio import flac
-    clip = C.speech(a.seconds, 1234)
+    clip = corpus_clip(a.seconds)
     data = clip.data
     n, nf = clip.pcm.shape[1], a.files
     buf = np.frombuffer(data, np.uint8)
