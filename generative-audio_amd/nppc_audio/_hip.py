@@ -287,6 +287,8 @@ SIGS = {
     "nppc_flac_stream_md5": [P, L, P, P, P],
     "nppc_flac_md5_host": [P, L, I, I, P],
     "nppc_flac_md5": [P, L, P, I, P, P, P, P, P, P],
+    "nppc_resample_sinc_shape": [I, I, I, I, I, PI, PL, PL, PL, PI],
+    "nppc_resample_sinc": [P, L, P, I, P, I, I, I, I, I, P, L, P],
 }
 _bound = set()
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;

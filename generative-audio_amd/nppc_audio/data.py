@@ -47,10 +47,14 @@ class DataConfig(pydantic.BaseModel):
     data_path: str
 
 
-def _decode_wav(path, sample_rate):
+RESAMPLERS = ("scipy", "sinc_hann")
+
+
+def _decode_wav(path, sample_rate, resampler="scipy"):
     """one wav file -> mono float32 [n] at `sample_rate` (dataset/audio_dataset.py:69-90 uses torchaudio.load + mean over
     channels + torchaudio Resample; torchaudio is not part of this build: scipy decodes, and a rate mismatch is resampled
-    with scipy's polyphase filter, which is NOT bit-identical to torchaudio's windowed-sinc kernel)"""
+    with scipy's polyphase filter, which is NOT bit-identical to torchaudio's windowed-sinc kernel; resampler="sinc_hann"
+    is that kernel, nppc_audio.resample)"""
     from scipy.io import wavfile
     sr, a = wavfile.read(str(path))
     if a.size == 0:
@@ -63,12 +67,19 @@ def _decode_wav(path, sample_rate):
         a = a.astype(np.float32)
     if a.ndim > 1:
         a = a.mean(axis=1)
-    return torch.from_numpy(np.ascontiguousarray(_to_rate(a, sr, sample_rate)))
+    return torch.from_numpy(np.ascontiguousarray(_to_rate(a, sr, sample_rate, resampler)))
 
 
-def _to_rate(a, sr, sample_rate):
-    """mono float32 [n] at sr -> at sample_rate (scipy's polyphase filter in fp64): the one branch wav and flac share"""
+def _to_rate(a, sr, sample_rate, resampler="scipy"):
+    """mono float32 [n] at sr -> at sample_rate: the one branch wav and flac share.  resampler="scipy": scipy's polyphase
+    filter in fp64; "sinc_hann": the reference's filter (torchaudio's default Resample) through nppc_audio.resample, on
+    the device when there is one.  Equal rates: `a` as it is, whichever."""
+    if resampler not in RESAMPLERS:
+        raise ValueError(f"resampler = {resampler!r}: one of {RESAMPLERS}")
     if sr != sample_rate:
+        if resampler == "sinc_hann":
+            from .resample import resample
+            return resample(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)), int(sr), int(sample_rate)).cpu().numpy()
         from math import gcd
         from scipy.signal import resample_poly
         g = gcd(int(sr), int(sample_rate))
@@ -76,7 +87,33 @@ def _to_rate(a, sr, sample_rate):
     return a
 
 
-def _decode_flac(path, sample_rate, verify_md5=True):
+def _to_rate_batch(clips, rates, sample_rate, resampler="scipy"):
+    """clips (1-D float32 host tensors) at `rates` -> host tensors at sample_rate.  "sinc_hann" groups the clips by rate and
+    resamples every group as ONE ragged batch (one launch on the device); a group already at sample_rate launches nothing.
+    The kernel's bits of a clip do not depend on its batch, so this gives what _to_rate gives clip by clip."""
+    if resampler != "sinc_hann":
+        return [torch.from_numpy(np.ascontiguousarray(_to_rate(c.numpy(), r, sample_rate, resampler)))
+                for c, r in zip(clips, rates)]
+    from .resample import resample
+    out = [None] * len(clips)
+    for rate in sorted(set(int(r) for r in rates)):
+        idx = [i for i, r in enumerate(rates) if int(r) == rate]
+        if rate == int(sample_rate):
+            for i in idx:
+                out[i] = clips[i]
+            continue
+        lens = [clips[i].numel() for i in idx]
+        x = torch.zeros(len(idx), max(max(lens), 1), dtype=torch.float32)
+        for row, i in enumerate(idx):
+            x[row, :lens[row]] = clips[i]
+        y, out_lens = resample(x, rate, int(sample_rate), lengths=lens)
+        y = y.cpu()
+        for row, i in enumerate(idx):
+            out[i] = y[row, :int(out_lens[row])].clone()
+    return out
+
+
+def _decode_flac(path, sample_rate, verify_md5=True, resampler="scipy"):
     """one flac file -> mono float32 [n] at `sample_rate`: the contract of _decode_wav (nppc_audio.flac decodes; the mean
     over channels is formed as numpy forms it, so the same PCM as wav and as flac gives the same bits).  verify_md5: the
     decoded samples are checked against the MD5 STREAMINFO states, when it states one (FlacError, status 9, when not)"""
@@ -84,7 +121,7 @@ def _decode_flac(path, sample_rate, verify_md5=True):
     (a,), (info,) = decode_files([path], out="mono", verify_md5=verify_md5)
     if a.numel() == 0:
         return None
-    return torch.from_numpy(np.ascontiguousarray(_to_rate(a.numpy(), info.sample_rate, sample_rate)))
+    return torch.from_numpy(np.ascontiguousarray(_to_rate(a.numpy(), info.sample_rate, sample_rate, resampler)))
 
 
 class AudioDataset(torch.utils.data.Dataset):
@@ -94,11 +131,15 @@ class AudioDataset(torch.utils.data.Dataset):
                                                directory holds none, like the reference) and decodes every file ONCE
     AudioDataset(config, clean_clips=[...], noise_clips=[...])   tensor-backed: 1-D float tensors already at sample_rate
     seed: None = entropy-seeded like the reference's global `random`; an int makes the item stream reproducible.
+    resampler: how a file at another rate is brought to config.sample_rate, "scipy" (the default) or "sinc_hann", the
+    reference's torchaudio filter (data._to_rate).
     The random decisions of one item are drawn in the reference's order (crop start, noise files [+ their levels], SNR,
     [clean level]), so a generator in the same state as the reference's `random` yields the same item."""
 
-    def __init__(self, config: AudioDataSetConfig, clean_clips=None, noise_clips=None, seed=None):
+    def __init__(self, config: AudioDataSetConfig, clean_clips=None, noise_clips=None, seed=None, resampler="scipy"):
         import random
+        if resampler not in RESAMPLERS:
+            raise ValueError(f"resampler = {resampler!r}: one of {RESAMPLERS}")
         self.config = config
         if clean_clips is None:
             self.clean_path = Path(config.clean_path).resolve()
@@ -109,8 +150,8 @@ class AudioDataset(torch.utils.data.Dataset):
                 raise ValueError(f"No WAV files found in clean directory: {self.clean_path}")
             if not self.noise_files:
                 raise ValueError(f"No WAV files found in noise directory: {self.noisy_path}")
-            clean_clips = [_decode_wav(f, config.sample_rate) for f in self.clean_files]
-            noise_clips = [_decode_wav(f, config.sample_rate) for f in self.noise_files]
+            clean_clips = [_decode_wav(f, config.sample_rate, resampler) for f in self.clean_files]
+            noise_clips = [_decode_wav(f, config.sample_rate, resampler) for f in self.noise_files]
             clean_clips = [c for c in clean_clips if c is not None]
             noise_clips = [c for c in noise_clips if c is not None]
             if not clean_clips or not noise_clips:

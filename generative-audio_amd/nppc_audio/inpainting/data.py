@@ -85,6 +85,11 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
                                                        (on the device when it decodes there) and a file that decodes to
                                                        other samples than its encoder saw raises flac.FlacError (status
                                                        9) with its name; False loads such a file as it decodes.
+                                                       resampler: how files at another rate reach
+                                                       config.sample_rate, "scipy" (the default, data._to_rate) or
+                                                       "sinc_hann", the reference's torchaudio filter
+                                                       (nppc_audio.resample); a flac folder is then grouped by source
+                                                       rate and every group resampled as one ragged batch.
     AudioInpaintingDataset(config, clean_clips=[...])  tensor-backed: 1-D float tensors already at config.sample_rate
     `config` is the trainer's AudioInpaintingConfig.  No transcriptions, no torch.hub.
 
@@ -98,8 +103,11 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
     dataset[i] = (stft_masked [2,F,T], mask_frames [T], stft_clean [2,F,T], masked_audio [1,L]) device tensors: a batch
     of one through `InpaintingDeviceLoader`."""
 
-    def __init__(self, config, clean_clips=None, seed=None, vad=None, verify_flac_md5=True):
-        from ..data import _decode_wav
+    def __init__(self, config, clean_clips=None, seed=None, vad=None, verify_flac_md5=True, resampler="scipy"):
+        from ..data import RESAMPLERS, _decode_wav
+        if resampler not in RESAMPLERS:
+            raise ValueError(f"resampler = {resampler!r}: one of {RESAMPLERS}")
+        self.resampler = resampler
         self.config = config
         self.verify_flac_md5 = bool(verify_flac_md5)
         sr = int(config.sample_rate)
@@ -132,7 +140,7 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
             elif not wavs:
                 raise ValueError(f"No WAV files found in clean directory: {self.clean_path}" + how)
             else:
-                decoded = [(f, _decode_wav(f, sr)) for f in wavs]
+                decoded = [(f, _decode_wav(f, sr, resampler)) for f in wavs]
             self.clean_files = [f for f, c in decoded if c is not None]
             clean_clips = [c for _, c in decoded if c is not None]
         self.clean = [torch.as_tensor(c, dtype=torch.float32).reshape(-1) for c in clean_clips]
@@ -162,7 +170,7 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
         by flac.decode_files in batches -- on the device when there is one -- and brought to `sr` like a wav"""
         import warnings
         import numpy as np
-        from ..data import _to_rate
+        from ..data import _to_rate, _to_rate_batch
         from ..flac import FlacError, decode_files, probe
         good, first = [], None
         for f in flacs:
@@ -176,6 +184,8 @@ class AudioInpaintingDataset(torch.utils.data.Dataset):
             raise ValueError(f"{self.clean_path} holds {len(flacs)} FLAC files and no WAV file, and the flac decoder rejects "
                              f"every one of them (the first: {first})" + how)
         clips, infos = decode_files(good, out="mono", verify_md5=self.verify_flac_md5)
+        if self.resampler != "scipy":
+            return list(zip(good, _to_rate_batch(clips, [i.sample_rate for i in infos], sr, self.resampler)))
         return [(f, torch.from_numpy(np.ascontiguousarray(_to_rate(c.numpy(), i.sample_rate, sr))))
                 for f, c, i in zip(good, clips, infos)]
 

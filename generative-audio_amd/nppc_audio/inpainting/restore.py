@@ -18,6 +18,9 @@ Normalisation rules
     from the damaged windows' STFT (there is no clean one).  So a gap restored together with other gaps is not bit-equal
     to the same gap restored alone.
   * Samples outside every [s - crossfade, e + crossfade) are the input's, bit for bit: they never pass through the gain.
+    A recording at another rate than the model's keeps this rule at ITS rate: restore(..., sample_rate=44100) resamples
+    down (nppc_audio.resample), restores, resamples up and splices there; inside the gaps nothing above the model's
+    Nyquist frequency is synthesised.
 
 Policy (`plan_windows`, pure Python): gaps are sorted; two gaps closer than 2 x crossfade_samples are merged into their hull
 (the few known samples between them are synthesised too); every merged gap gets one window of `window_samples` centred on it
@@ -33,7 +36,8 @@ from .. import _hip as H
 from . import phase as PH
 from .nppc.nppc_model import NPPCModel, NPPCModelConfig
 
-__all__ = ["RecordingRestorerConfig", "RecordingRestorer", "plan_windows", "REC_GAIN_WORK", "ZERO_RUN_CHUNK"]
+__all__ = ["RecordingRestorerConfig", "RecordingRestorer", "plan_windows", "native_crossfade", "merge_native_gaps",
+           "REC_GAIN_WORK", "ZERO_RUN_CHUNK"]
 
 REC_GAIN_WORK = 256          # NPPC_REC_GAIN_WORK
 ZERO_RUN_CHUNK = 4096        # NPPC_ZERO_RUN_CHUNK
@@ -126,6 +130,24 @@ def plan_windows(length, gaps, window_samples=32704, crossfade_samples=64, n_fft
     return plan
 
 
+def native_crossfade(crossfade_samples, rate, model_rate):
+    """the crossfade of `crossfade_samples` at model_rate, in samples at `rate`, rounded up"""
+    return -(-int(crossfade_samples) * int(rate) // int(model_rate))
+
+
+def merge_native_gaps(gaps, crossfade):
+    """sorted; two gaps closer than 2 x crossfade become their hull (plan_windows' rule, at the recording's own rate), so
+    that the regions [s - crossfade, e + crossfade) nppc_rec_splice blends never overlap"""
+    pairs = sorted((int(s), int(e)) for s, e in gaps)
+    merged = pairs[:1]
+    for s, e in pairs[1:]:
+        if s - merged[-1][1] < 2 * crossfade:
+            merged[-1] = (merged[-1][0], max(merged[-1][1], e))
+        else:
+            merged.append((s, e))
+    return merged
+
+
 def _upload_plan(plan, device):
     """-> gaps [W, 2] and window starts [W], int64 on the device, one copy"""
     host = torch.tensor([[p["gap"][0], p["gap"][1], p["start"]] for p in plan], dtype=torch.int64)
@@ -207,7 +229,7 @@ class RecordingRestorer:
         c = self.config
         return plan_windows(length, gaps, c.window_samples, c.crossfade_samples, c.n_fft, c.hop_length, c.long_gaps)
 
-    def restore(self, wave, gaps, alphas=None, variations="windows"):
+    def restore(self, wave, gaps, alphas=None, variations="windows", sample_rate=None):
         """wave [L] float (host or device), gaps [(start, end)] half-open sample pairs -> dict:
           'restored' [L]; 'windows' (plan_windows' list); 'gain' (fp64 device scalar [1]); 'inconsistency' [W, V, gl_iters],
           'target_norm' [W, V], 'status' [W] as phase.griffin_lim_gap reports them, per window (V = 1, or K A + 1 with the
@@ -216,12 +238,16 @@ class RecordingRestorer:
           ready to be written as wav; with variations='full': 'variations' [K, A, L], the recording with every gap replaced
           by that variation.
         With no gaps the input comes back as it is (the same tensor) and nothing is launched.  One host read per call: the
-        status check at the end."""
+        status check at the end.
+        sample_rate: None or config.sample_rate runs exactly the above.  Another rate: `wave` and `gaps` are at that rate
+        and so are 'restored' and 'variations' (see _restore_native); 'variation_windows' stay at the model's rate."""
         if variations not in ("windows", "full"):
             raise ValueError(f"variations = {variations!r}: 'windows' or 'full'")
         if wave.dim() != 1:
             raise ValueError(f"wave {tuple(wave.shape)}: want one channel, [L]")
         c = self.config
+        if sample_rate is not None and int(sample_rate) != int(c.sample_rate):
+            return self._restore_native(wave, gaps, alphas, variations, int(sample_rate))
         plan = self.plan(wave.numel(), gaps)
         if not plan:
             return {"restored": wave, "windows": [], "gain": None, "inconsistency": None, "target_norm": None, "status": None}
@@ -268,6 +294,71 @@ class RecordingRestorer:
                                "span exceeds the cap (plan_windows should have raised)")
         return out
 
+    def _restore_native(self, wave, gaps, alphas, variations, rate):
+        """restore() for a recording at `rate` != config.sample_rate:
+          the recording is resampled to config.sample_rate (nppc_audio.resample, the reference's windowed sinc); every gap
+          [s, e) becomes resample.map_gap's [a, b), the outputs the gap's samples reach through the filter, so nothing
+          outside the mapped gaps depends on what the gaps hold; restore() runs on that, unchanged; its result is resampled
+          back, cut to len(wave) and spliced AT `rate` (nppc_rec_splice with the upsampled recording as one stride-0
+          window starting at sample 0 and a gain of one): inside each gap (gaps closer than twice the native crossfade
+          ceil(crossfade_samples rate / config.sample_rate) are merged) the upsampled signal, a raised-cosine blend over
+          the native crossfade on both sides, and everywhere else the input's own samples, bit for bit and full band.
+        The model is a config.sample_rate model: inside the gaps nothing above config.sample_rate / 2 is synthesised.
+        Adds 'sample_rate', 'restored_model_rate' [ceil(L model / rate)], 'gaps_model_rate' (the mapped gaps, in the order
+        given) and 'gaps_merged' (the native gaps as spliced).  Still one host read: the inner call's status check."""
+        from .. import resample as RSM
+        c = self.config
+        if rate <= 0:
+            raise ValueError(f"sample_rate = {rate}: not a rate")
+        N = wave.numel()
+        pairs = []
+        for g in gaps:
+            try:
+                s, e = (int(v) for v in g)
+            except (TypeError, ValueError) as err:
+                raise ValueError(f"gap {g!r} is not a (start, end) pair of samples") from err
+            if s < 0 or e <= s or e > N:
+                raise ValueError(f"gap ({s}, {e}) is empty, negative or outside the recording's {N} samples")
+            pairs.append((s, e))
+        extra = {"sample_rate": rate, "restored_model_rate": None, "gaps_model_rate": [], "gaps_merged": []}
+        if not pairs:
+            return {"restored": wave, "windows": [], "gain": None, "inconsistency": None, "target_norm": None,
+                    "status": None, **extra}
+        down_t, up_t = RSM.sinc_table(rate, c.sample_rate), RSM.sinc_table(c.sample_rate, rate)
+        for t, pair in ((down_t, (rate, c.sample_rate)), (up_t, (c.sample_rate, rate))):
+            if t.tile == 0:                                                             # before anything is launched
+                raise RSM._unsupported(t, *pair)
+        H.require_gpu()
+        n_model = RSM.out_length(N, rate, c.sample_rate)
+        mapped = [RSM.map_gap(s, e, down_t, out_len=n_model) for s, e in pairs]
+        for (s, e), (a, b) in zip(pairs, mapped):
+            if b <= a:
+                raise ValueError(f"gap ({s}, {e}) reaches no sample at {c.sample_rate} Hz")
+        xf = native_crossfade(c.crossfade_samples, rate, c.sample_rate)
+        merged = merge_native_gaps(pairs, xf)
+        x = wave.to(self.device).float().contiguous()
+        with torch.no_grad():
+            low = RSM.resample(x, rate, c.sample_rate, backend="hip")
+            out = self.restore(low, mapped, alphas, variations)
+            if "variations" in out:
+                K, A = out["variations"].shape[:2]
+                stack = torch.cat([out["variations"].reshape(K * A, -1), out["restored"][None]])
+            else:
+                stack = out["restored"][None]
+            up = RSM.resample(stack, c.sample_rate, rate, backend="hip")                # [V, >= N], one batched launch
+            gaps_d = torch.tensor(merged, dtype=torch.int64).to(x.device)
+            zeros = torch.zeros(len(merged), dtype=torch.int64, device=x.device)
+            one = torch.ones(1, dtype=torch.float64, device=x.device)
+            V = up.shape[0]
+            full = torch.empty(V, N, dtype=torch.float32, device=x.device)
+            H.call("nppc_rec_splice", x, N, gaps_d, zeros, len(merged), up, 0, up.stride(0), N, V, xf, one, full, H.stream())
+        out["restored_model_rate"] = out["restored"]
+        out["restored"] = full[V - 1]
+        if "variations" in out:
+            out["variations"] = full[:V - 1].view(K, A, N)
+        out.update(sample_rate=rate, gaps_model_rate=mapped, gaps_merged=merged)
+        return out
+
     def detect_gaps(self, wave):
         """the maximal runs of exactly-zero samples at least config.min_gap_samples long, [(start, end)] ascending: how a
         digital dropout looks, and the reference's masked_audio = audio * mask.  On the device (nppc_zero_runs); one host
@@ -283,25 +374,37 @@ class RecordingRestorer:
                 return [(int(s), int(e)) for s, e in host[1:1 + 2 * n].view(-1, 2).tolist()]
             cap = n
 
-    def restore_file(self, path_in, path_out, gaps=None, verify_flac_md5=True):
+    def restore_file(self, path_in, path_out, gaps=None, verify_flac_md5=True, keep_rate=False):
         """wav or flac -> wav: decodes with data._decode_wav, or data._decode_flac for a name ending in .flac (mono,
         config.sample_rate), detects the gaps when none are given, restores, writes 16-bit PCM wav (there is no flac
         encoder).  A flac file whose STREAMINFO states an MD5 is checked against it (flac.FlacError, status 9, when the
-        decoded samples differ); verify_flac_md5=False takes it as it decodes.  -> restore's dict"""
+        decoded samples differ); verify_flac_md5=False takes it as it decodes.  -> restore's dict
+        keep_rate=True: the file is decoded at ITS rate (the wav header's, flac.probe's), the gaps are detected on those
+        samples -- a filter would smear the exact zeros of a dropout -- and given at that rate, restore(...,
+        sample_rate=rate) keeps every sample outside the crossfaded gaps, and the wav written has the file's rate and
+        sample count.  Inside the gaps there is nothing above config.sample_rate / 2."""
         import numpy as np
         from scipy.io import wavfile
         from ..data import _decode_flac, _decode_wav
-        if str(path_in).lower().endswith(".flac"):
-            wave = _decode_flac(path_in, self.config.sample_rate, verify_md5=verify_flac_md5)
+        is_flac = str(path_in).lower().endswith(".flac")
+        rate = self.config.sample_rate
+        if keep_rate:
+            if is_flac:
+                from ..flac import probe
+                rate = int(probe(path_in).sample_rate)
+            else:
+                rate = int(wavfile.read(str(path_in), mmap=True)[0])
+        if is_flac:
+            wave = _decode_flac(path_in, rate, verify_md5=verify_flac_md5)
         else:
-            wave = _decode_wav(path_in, self.config.sample_rate)
+            wave = _decode_wav(path_in, rate)
         if wave is None:
             raise ValueError(f"{path_in} holds no samples")
         if gaps is None:
             gaps = self.detect_gaps(wave)
-        out = self.restore(wave, gaps)
+        out = self.restore(wave, gaps, sample_rate=rate) if keep_rate else self.restore(wave, gaps)
         pcm = np.clip(np.rint(out["restored"].detach().cpu().double().numpy() * 32768.0), -32768, 32767).astype(np.int16)
-        wavfile.write(str(path_out), self.config.sample_rate, pcm)
+        wavfile.write(str(path_out), rate, pcm)
         return out
 
 

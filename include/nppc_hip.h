@@ -860,6 +860,27 @@ int nppc_flac_md5_host(const int* pcm, long n, int channels, int bps, unsigned c
 int nppc_flac_md5(const int* pcm, long pcm_elems, const long* meta, int nfiles, const int* order, const unsigned char* expected,
                   const int* status, unsigned char* digest, int* verdict, void* stream);
 
+/* ---- windowed-sinc resampling of ragged batches (csrc/resample.hip; specification
+ * tests/resample_ref.py): torchaudio's default Resample (Hann window).  With orig / new the two rates reduced by their gcd,
+ * Klen = 2 width + orig and xpad the item padded with `width` zeros on the left and zeros on the right,
+ *   y[i new + p] = sum_k xpad[i orig + k] kern[p][k],  cut to ceil(new len / orig) outputs.
+ * table [new][stride] 32-bit words (device): per phase p (int k0, int count, float taps[maxcount]) = kern[p][k0 .. k0 +
+ * count), every other tap of kern[p] being exactly 0.0f; stride = (2 + maxcount) | 1.  Each output is one fp32 fma chain
+ * over its `count` taps in ascending k, started from 0: no atomics, no workspace, identical bits run to run, and an item's
+ * bits do not depend on the tile or on the rest of the batch. */
+#define NPPC_RESAMPLE_LDS_BUDGET 65536     /* bytes of LDS a workgroup may take: table + the tile's input span */
+#define NPPC_RESAMPLE_TABLE_BUDGET 40960   /* bytes the table may take of that */
+/* host only.  *stride as above; *table_bytes = new stride 4; *span_elems = ((tile - 1) / new + 1) orig + Klen, the most
+ * input samples a tile of `tile` outputs touches; *lds_bytes = table + span; *fits = both budgets hold.  Out pointers
+ * may be null.  Non-positive arguments or maxcount > Klen: NPPC_EBADARG. */
+int nppc_resample_sinc_shape(int orig, int new_, int width, int maxcount, int tile, int* stride, long* table_bytes,
+                             long* span_elems, long* lds_bytes, int* fits);
+/* x [B][ldx] fp32, lengths [B] (long, device; null = every item has ldx samples; clamped to [0, ldx]) -> y [B][ldy]:
+ * columns below ceil(new len / orig) as above, zeros from there to ldy (every column is written).  Samples at or past an
+ * item's length are never read.  grid (ceil(ldy / tile), B).  A (ratio, tile) that does not fit: NPPC_EUNSUPPORTED. */
+int nppc_resample_sinc(const float* x, long ldx, const long* lengths, int B, const int* table, int orig, int new_, int width,
+                       int maxcount, int tile, float* y, long ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
