@@ -21,19 +21,6 @@ constexpr int CORR_CHUNK = 8192;         // samples of m per corr workgroup (8 t
 constexpr int PROJ_CHUNK = 1024;         // output samples per project workgroup (4 per thread)
 constexpr int PROJ_PER_THREAD = PROJ_CHUNK / 256;
 
-// block-wide fp64 sum of NW waves in a fixed order: xor-butterfly inside each wave, then the wave sums in index order;
-// every thread gets the result
-template <int NW> __device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();                                     // red may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double acc = red[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) acc += red[w];
-  return acc;
-}
-
 // ---- correlations ------------------------------------------------------------------------------------------------------
 // grid (chunk, item), 256 threads; thread tid owns lags tid and tid + 256.  Per tile the workgroup stages, as fp64,
 // s[m0 - (P - 1) .. m0 + tile) (zeros before the signal and past its end) and e[m0 .. m0 + tile).  In the inner loop
@@ -217,8 +204,8 @@ __global__ __launch_bounds__(256) void bss_project_kernel(const float* __restric
       den = fma(res, res, den);
     }
   }
-  num = block_sum<4>(num, red);
-  den = block_sum<4>(den, red);
+  num = block_sum_waves<4>(num, red);
+  den = block_sum_waves<4>(den, red);
   if (tid == 0) {
     double* o = part + ((long)b * nchunks + blockIdx.x) * 2;
     o[0] = num;
@@ -273,16 +260,16 @@ __global__ __launch_bounds__(256) void bss_scale_kernel(const float* __restrict_
     sse = fma(a, c, sse);
     srs = fma(d, d, srs);
   }
-  sss = block_sum<4>(sss, red);
-  sse = block_sum<4>(sse, red);
-  srs = block_sum<4>(srs, red);
+  sss = block_sum_waves<4>(sss, red);
+  sse = block_sum_waves<4>(sse, red);
+  srs = block_sum_waves<4>(srs, red);
   const double alpha = sse / sss;
   double ra = 0.0;
   for (long i = threadIdx.x; i < n; i += 256) {
     const double d = (double)e[i] - alpha * (double)s[i];
     ra = fma(d, d, ra);
   }
-  ra = block_sum<4>(ra, red);
+  ra = block_sum_waves<4>(ra, red);
   if (threadIdx.x == 0) {
     if (sums) {
       double* o = sums + 4L * b;

@@ -135,5 +135,38 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The two block-wide fp64 sums.  Their addition orders are what the bit-for-bit tests rest on: do not reorder.
+// NW waves: xor butterfly inside each wave, then the wave sums in index order; every thread gets the result.
+// red: NW doubles.  The leading barrier lets back-to-back calls share red.
+template <int NW> __device__ __forceinline__ double block_sum_waves(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double acc = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) acc += red[w];
+  return acc;
+}
+// 256 threads: halving tree over the 256 values in LDS; every thread gets the result.  red: 256 doubles.
+__device__ __forceinline__ double block_sum_tree256(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// cIRM compression of mask.py:24-54: 10 (1 - e^{-0.1 m}) / (1 + e^{-0.1 m}), m floored at -100
+__device__ __forceinline__ float compress_cirm(float m) {
+  m = m <= -100.f ? -100.f : m;
+  const float e = expf(-0.1f * m);
+  return 10.f * (1.f - e) / (1.f + e);
+}
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }

@@ -8,18 +8,56 @@
 #include "common.h"
 #include "nppc_hip.h"
 
+#include <type_traits>
+
 namespace {
 
+// ---------------------------------------------------------------- radix-2 FFT in LDS, shared by STFT and iSTFT
+// tw[i] = exp(sign 2 pi i / N) and the periodic hann window, generated in fp64 -> fp32 once per workgroup
+template <int LOGN>
+__device__ __forceinline__ void fft_tables(float2* tw, float* win, double sign) {
+  constexpr int N = 1 << LOGN;
+  for (int i = threadIdx.x; i < N / 2; i += 256) {
+    double s, c;
+    sincospi(sign * 2.0 * i / N, &s, &c);
+    tw[i] = make_float2((float)c, (float)s);
+  }
+  for (int i = threadIdx.x; i < N; i += 256) win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / N));
+}
+
+// DIT butterfly stages over nfr rows loaded in bit-reversed order; ends on a barrier
+template <int LOGN>
+__device__ __forceinline__ void fft_stages(float2 (*buf)[(1 << LOGN) + 1], const float2* tw, int nfr) {
+  constexpr int N = 1 << LOGN;
+#pragma unroll 1
+  for (int s = 0; s < LOGN; ++s) {
+    const int half = 1 << s;
+    for (int e = threadIdx.x; e < nfr * (N / 2); e += 256) {
+      const int j = e / (N / 2), k = e % (N / 2);
+      const int grp = k >> s, pos = k & (half - 1);
+      const int i0 = (grp << (s + 1)) + pos, i1 = i0 + half;
+      const float2 w = tw[pos << (LOGN - 1 - s)];
+      const float2 a = buf[j][i0], c = buf[j][i1];
+      const float xr = c.x * w.x - c.y * w.y, xi = c.x * w.y + c.y * w.x;
+      buf[j][i0] = make_float2(a.x + xr, a.y + xi);
+      buf[j][i1] = make_float2(a.x - xr, a.y - xi);
+    }
+    __syncthreads();
+  }
+}
+
 // ---------------------------------------------------------------- STFT
-// One workgroup = FR consecutive frames of one clip.  Radix-2 DIT FFT in LDS (complex N points,
-// imaginary input 0), twiddles/window generated in fp64 -> fp32 once per workgroup.
-// Output layout [B][F][T] (F = N/2+1), written with the FR frames of a bin contiguous.
+// One workgroup = FR consecutive frames of one clip.  Radix-2 DIT FFT in LDS (complex N points, imaginary input 0).
+// wave [B][ld], output layout [B][F][T] (F = N/2+1), written with the FR frames of a bin contiguous.
+// RAGGED: item b is its first L_b = lengths[b] samples / T_b = 1 + L_b / hop frames long; it computes exactly what the
+// uniform form computes for that item run alone, never reads past L_b and writes frames t >= T_b as 0.  Otherwise every
+// item is ld samples long and lengths is not read.
 constexpr int STFT_FR = 8;
 
-template <int LOGN>
-__global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wave, float* __restrict__ out_re,
-                                                   float* __restrict__ out_im, float* __restrict__ out_mag, int L,
-                                                   int hop, int T) {
+template <int LOGN, bool RAGGED>
+__global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wave, long ld, const int* __restrict__ lengths,
+                                                   float* __restrict__ out_re, float* __restrict__ out_im,
+                                                   float* __restrict__ out_mag, int hop, int T) {
   constexpr int N = 1 << LOGN;
   constexpr int F = N / 2 + 1;
   __shared__ float2 buf[STFT_FR][N + 1];
@@ -28,53 +66,51 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wav
   const int tid = threadIdx.x;
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * STFT_FR;
-  for (int i = tid; i < N / 2; i += 256) {
-    double s, c;
-    sincospi(-2.0 * i / N, &s, &c);
-    tw[i] = make_float2((float)c, (float)s);
+  // (the host validates L_b > N/2; the clamp only keeps reads in the row)
+  const int L = RAGGED ? clampi(lengths[b], 1, (int)ld) : (int)ld;
+  const int Tb = RAGGED ? min(1 + L / hop, T) : T;
+  if (RAGGED && t0 >= Tb) {                            // the whole block is past the item's end
+    for (int e = tid; e < F * STFT_FR; e += 256) {
+      const int f = e / STFT_FR, t = t0 + e % STFT_FR;
+      if (t < T) {
+        const size_t o = ((size_t)b * F + f) * T + t;
+        out_re[o] = 0.f;
+        out_im[o] = 0.f;
+        if (out_mag) out_mag[o] = 0.f;
+      }
+    }
+    return;
   }
-  for (int i = tid; i < N; i += 256) win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / N));
+  fft_tables<LOGN>(tw, win, -1.0);
   __syncthreads();
-  const float* wv = wave + (size_t)b * L;
+  const float* wv = wave + (size_t)b * ld;
   // load, window, bit-reverse
   for (int e = tid; e < STFT_FR * N; e += 256) {
     const int j = e / N, n = e % N;
     const int t = t0 + j;
     float v = 0.f;
-    if (t < T) {
+    if (t < Tb) {
       int sidx = t * hop + n - N / 2;
       if (sidx < 0) sidx = -sidx;
-      if (sidx >= L) sidx = 2 * (L - 1) - sidx;
+      if (sidx >= L) sidx = 2 * (L - 1) - sidx;        // reflect at the item's own end
+      if (RAGGED) sidx = clampi(sidx, 0, L - 1);
       v = wv[sidx] * win[n];
     }
     const int r = __brev((unsigned)n) >> (32 - LOGN);
     buf[j][r] = make_float2(v, 0.f);
   }
   __syncthreads();
-#pragma unroll 1
-  for (int s = 0; s < LOGN; ++s) {
-    const int half = 1 << s;
-    for (int e = tid; e < STFT_FR * (N / 2); e += 256) {
-      const int j = e / (N / 2), k = e % (N / 2);
-      const int grp = k >> s, pos = k & (half - 1);
-      const int i0 = (grp << (s + 1)) + pos, i1 = i0 + half;
-      const float2 w = tw[pos << (LOGN - 1 - s)];
-      const float2 a = buf[j][i0], c = buf[j][i1];
-      const float xr = c.x * w.x - c.y * w.y, xi = c.x * w.y + c.y * w.x;
-      buf[j][i0] = make_float2(a.x + xr, a.y + xi);
-      buf[j][i1] = make_float2(a.x - xr, a.y - xi);
-    }
-    __syncthreads();
-  }
+  fft_stages<LOGN>(buf, tw, STFT_FR);
   for (int e = tid; e < F * STFT_FR; e += 256) {
     const int f = e / STFT_FR, j = e % STFT_FR;
     const int t = t0 + j;
     if (t < T) {
-      const float2 v = buf[j][f];
+      const bool live = !RAGGED || t < Tb;
+      const float2 v = live ? buf[j][f] : make_float2(0.f, 0.f);
       const size_t o = ((size_t)b * F + f) * T + t;
       out_re[o] = v.x;
       out_im[o] = v.y;
-      if (out_mag) out_mag[o] = sqrtf(v.x * v.x + v.y * v.y);
+      if (out_mag) out_mag[o] = live ? sqrtf(v.x * v.x + v.y * v.y) : 0.f;
     }
   }
 }
@@ -83,11 +119,14 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wav
 // torch.istft(center=True, periodic hann, onesided input, length=L): y[p] = sum_t w[p - t*hop] x_t[p - t*hop] / sum_t w^2[p - t*hop],
 // x_t = irfft(X_t), p = n + N/2.  One workgroup = ISTFT_FR*hop consecutive output samples of one clip; it inverts the
 // ISTFT_FR + N/hop - 1 frames that overlap them (radix-2 in LDS on the Hermitian-extended spectrum).
+// re / im [B][F][T], out [B][ld].  RAGGED: samples n < L_b = lengths[b] as torch.istft(length=L_b) of the item's own
+// T_b = 1 + L_b / hop frames (window envelope of those frames only), samples L_b <= n < ld written as 0.
 constexpr int ISTFT_FR = 4;
 
-template <int LOGN>
+template <int LOGN, bool RAGGED>
 __global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ re, const float* __restrict__ im,
-                                                    float* __restrict__ out, int T, int hop, int L) {
+                                                    float* __restrict__ out, long ld, const int* __restrict__ lengths, int T,
+                                                    int hop) {
   constexpr int N = 1 << LOGN;
   constexpr int F = N / 2 + 1;
   constexpr int MAXFR = ISTFT_FR + 7;            // supports hop >= N/8
@@ -95,22 +134,26 @@ __global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ re
   __shared__ float2 tw[N / 2];
   __shared__ float win[N];
   const int tid = threadIdx.x, b = blockIdx.y;
+  const int L = RAGGED ? clampi(lengths[b], 0, (int)ld) : (int)ld;
+  const int Tb = RAGGED ? min(1 + L / hop, T) : T;
   const int ov = N / hop;                          // frames overlapping one sample
   const int nfr = ISTFT_FR + ov - 1;
   const int p0 = blockIdx.x * ISTFT_FR * hop;      // first padded-coordinate sample of this block
   const int tfirst = p0 / hop - (ov - 1);          // first frame that can touch [p0, p0 + FR*hop)
-  for (int i = tid; i < N / 2; i += 256) {
-    double s, c;
-    sincospi(2.0 * i / N, &s, &c);                 // inverse transform: +i
-    tw[i] = make_float2((float)c, (float)s);
+  if (RAGGED && p0 - N / 2 >= L) {                 // every sample of the block is past the item's end
+    for (int e = tid; e < ISTFT_FR * hop; e += 256) {
+      const int nidx = p0 + e - N / 2;
+      if (nidx >= 0 && nidx < ld) out[(size_t)b * ld + nidx] = 0.f;
+    }
+    return;
   }
-  for (int i = tid; i < N; i += 256) win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / N));
+  fft_tables<LOGN>(tw, win, 1.0);                  // inverse transform: +i
   __syncthreads();
   for (int e = tid; e < nfr * N; e += 256) {
     const int j = e / N, k = e % N;
     const int t = tfirst + j;
     float2 v = make_float2(0.f, 0.f);
-    if (t >= 0 && t < T) {
+    if (t >= 0 && t < Tb) {
       const int kk = k < F ? k : N - k;
       const size_t o = ((size_t)b * F + kk) * T + t;
       v = make_float2(re[o], k < F ? im[o] : -im[o]);
@@ -119,36 +162,26 @@ __global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ re
     buf[j][__brev((unsigned)k) >> (32 - LOGN)] = v;
   }
   __syncthreads();
-#pragma unroll 1
-  for (int s = 0; s < LOGN; ++s) {
-    const int half = 1 << s;
-    for (int e = tid; e < nfr * (N / 2); e += 256) {
-      const int j = e / (N / 2), k = e % (N / 2);
-      const int grp = k >> s, pos = k & (half - 1);
-      const int i0 = (grp << (s + 1)) + pos, i1 = i0 + half;
-      const float2 w = tw[pos << (LOGN - 1 - s)];
-      const float2 a = buf[j][i0], c = buf[j][i1];
-      const float xr = c.x * w.x - c.y * w.y, xi = c.x * w.y + c.y * w.x;
-      buf[j][i0] = make_float2(a.x + xr, a.y + xi);
-      buf[j][i1] = make_float2(a.x - xr, a.y - xi);
-    }
-    __syncthreads();
-  }
+  fft_stages<LOGN>(buf, tw, nfr);
   for (int e = tid; e < ISTFT_FR * hop; e += 256) {
     const int p = p0 + e;
     const int nidx = p - N / 2;
-    if (nidx < 0 || nidx >= L) continue;
+    if (nidx < 0 || nidx >= ld) continue;
+    if (RAGGED && nidx >= L) {
+      out[(size_t)b * ld + nidx] = 0.f;
+      continue;
+    }
     float num = 0.f, den = 0.f;
     for (int j = 0; j < nfr; ++j) {
       const int t = tfirst + j;
       const int off = p - t * hop;
-      if (t >= 0 && t < T && off >= 0 && off < N) {
+      if (t >= 0 && t < Tb && off >= 0 && off < N) {
         const float w = win[off];
         num += w * buf[j][off].x * (1.0f / N);
         den += w * w;
       }
     }
-    out[(size_t)b * L + nidx] = den > 1e-11f ? num / den : 0.f;
+    out[(size_t)b * ld + nidx] = den > 1e-11f ? num / den : 0.f;
   }
 }
 
@@ -181,12 +214,6 @@ __global__ void dropband_kernel(const float* __restrict__ in, float* __restrict_
     dropband_src(bo, fo, B, G, &bs, &fs);
     out[e] = in[(((size_t)bs * C + c) * F + fs) * T + t];
   }
-}
-
-__device__ __forceinline__ float compress_cirm(float m) {
-  m = m <= -100.f ? -100.f : m;
-  const float e = expf(-0.1f * m);
-  return 10.f * (1.f - e) / (1.f + e);
 }
 
 // gt[bo][{0,1}][fo][t] = compress(cIRM(noisy, clean))[b_src][f_src][t]
@@ -235,16 +262,6 @@ __device__ __forceinline__ void cirm_target(const float* __restrict__ nr, const 
   *o = (((size_t)bo * 2) * Fo + fo) * T + t;
 }
 
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ __launch_bounds__(256) void crm_mse_part_kernel(const float* __restrict__ nr, const float* __restrict__ ni,
                                                            const float* __restrict__ cr, const float* __restrict__ ci,
                                                            const float* __restrict__ crm, float* __restrict__ gt, int B, int F,
@@ -263,14 +280,14 @@ __global__ __launch_bounds__(256) void crm_mse_part_kernel(const float* __restri
       gt[o + FoT] = gi;
     }
   }
-  s = block_sum_d(s, red);
+  s = block_sum_tree256(s, red);
   if (threadIdx.x == 0) work[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void crm_mse_finish_kernel(const double* __restrict__ work, float* __restrict__ loss,
                                                              double n) {
   __shared__ double red[256];
-  const double s = block_sum_d(work[threadIdx.x], red);     // CRM_BLOCKS == 256: one partial per thread
+  const double s = block_sum_tree256(work[threadIdx.x], red);     // CRM_BLOCKS == 256: one partial per thread
   if (threadIdx.x == 0) *loss = (float)(s / n);
 }
 
@@ -504,24 +521,52 @@ __global__ __launch_bounds__(256) void stft_dft_kernel(const float* __restrict__
   }
 }
 
+// runs launch(std::integral_constant<int, log2 nfft>) for the FFT sizes the radix-2 kernels are built for
+template <typename Launch>
+static int launch_by_nfft(int nfft, Launch launch) {
+  switch (nfft) {
+    case 64: launch(std::integral_constant<int, 6>()); break;
+    case 128: launch(std::integral_constant<int, 7>()); break;
+    case 256: launch(std::integral_constant<int, 8>()); break;
+    case 512: launch(std::integral_constant<int, 9>()); break;
+    default: return NPPC_EUNSUPPORTED;
+  }
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+template <bool RAGGED>
+static int launch_stft(const float* wave, long ld, const int* lengths, float* re, float* im, float* mag, int B, int T, int nfft,
+                       int hop, void* stream) {
+  return launch_by_nfft(nfft, [&](auto logn) {
+    hipLaunchKernelGGL((stft_kernel<decltype(logn)::value, RAGGED>), dim3(ceil_div(T, STFT_FR), B), dim3(256), 0,
+                       (hipStream_t)stream, wave, ld, lengths, re, im, mag, hop, T);
+  });
+}
+
+template <bool RAGGED>
+static int launch_istft(const float* re, const float* im, float* out, long ld, const int* lengths, int B, int T, int nfft,
+                        int hop, void* stream) {
+  const long total = ld + nfft / 2;                   // padded samples that can reach the output
+  return launch_by_nfft(nfft, [&](auto logn) {
+    hipLaunchKernelGGL((istft_kernel<decltype(logn)::value, RAGGED>), dim3(ceil_div(total, (long)ISTFT_FR * hop), B),
+                       dim3(256), 0, (hipStream_t)stream, re, im, out, ld, lengths, T, hop);
+  });
+}
+
 }  // namespace
 
 extern "C" {
 
 int nppc_stft(const float* wave, float* re, float* im, float* mag, int B, int L, int nfft, int hop, void* stream) {
   if (!wave || !re || !im || B <= 0 || L <= nfft / 2 || hop <= 0) return NPPC_EBADARG;
-  const int T = 1 + L / hop;
-  dim3 grid(ceil_div(T, STFT_FR), B);
-  hipStream_t s = (hipStream_t)stream;
-  switch (nfft) {
-    case 64: hipLaunchKernelGGL(stft_kernel<6>, grid, dim3(256), 0, s, wave, re, im, mag, L, hop, T); break;
-    case 128: hipLaunchKernelGGL(stft_kernel<7>, grid, dim3(256), 0, s, wave, re, im, mag, L, hop, T); break;
-    case 256: hipLaunchKernelGGL(stft_kernel<8>, grid, dim3(256), 0, s, wave, re, im, mag, L, hop, T); break;
-    case 512: hipLaunchKernelGGL(stft_kernel<9>, grid, dim3(256), 0, s, wave, re, im, mag, L, hop, T); break;
-    default: return NPPC_EUNSUPPORTED;
-  }
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  return launch_stft<false>(wave, L, nullptr, re, im, mag, B, 1 + L / hop, nfft, hop, stream);
+}
+
+int nppc_stft_ragged(const float* wave, long ld, const int* lengths, float* re, float* im, float* mag, int B, int T, int nfft,
+                     int hop, void* stream) {
+  if (!wave || !lengths || !re || !im || B <= 0 || T <= 0 || hop <= 0 || ld <= nfft / 2) return NPPC_EBADARG;
+  return launch_stft<true>(wave, ld, lengths, re, im, mag, B, T, nfft, hop, stream);
 }
 
 int nppc_dropband(const float* in, float* out, int B, int C, int F, int T, int G, void* stream) {
@@ -592,18 +637,14 @@ int nppc_cirm_decompress_apply(const float* crm, const float* nr, const float* n
 
 int nppc_istft(const float* re, const float* im, float* out, int B, int T, int nfft, int hop, int L, void* stream) {
   if (!re || !im || !out || B <= 0 || T <= 0 || hop <= 0 || L <= 0 || nfft % hop || nfft / hop > 8) return NPPC_EBADARG;
-  const int total = L + nfft / 2;                     // padded samples that can reach the output
-  dim3 grid(ceil_div(total, ISTFT_FR * hop), B);
-  hipStream_t s = (hipStream_t)stream;
-  switch (nfft) {
-    case 64: hipLaunchKernelGGL(istft_kernel<6>, grid, dim3(256), 0, s, re, im, out, T, hop, L); break;
-    case 128: hipLaunchKernelGGL(istft_kernel<7>, grid, dim3(256), 0, s, re, im, out, T, hop, L); break;
-    case 256: hipLaunchKernelGGL(istft_kernel<8>, grid, dim3(256), 0, s, re, im, out, T, hop, L); break;
-    case 512: hipLaunchKernelGGL(istft_kernel<9>, grid, dim3(256), 0, s, re, im, out, T, hop, L); break;
-    default: return NPPC_EUNSUPPORTED;
-  }
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  return launch_istft<false>(re, im, out, L, nullptr, B, T, nfft, hop, stream);
+}
+
+int nppc_istft_ragged(const float* re, const float* im, float* out, long ld, const int* lengths, int B, int T, int nfft, int hop,
+                      void* stream) {
+  if (!re || !im || !out || !lengths || B <= 0 || T <= 0 || hop <= 0 || ld <= 0 || nfft % hop || nfft / hop > 8)
+    return NPPC_EBADARG;
+  return launch_istft<true>(re, im, out, ld, lengths, B, T, nfft, hop, stream);
 }
 
 int nppc_mix_snr(const float* clean, const float* noise, const float* snr_db, float target_dbfs, const float* target_item,

@@ -136,11 +136,11 @@ __global__ __launch_bounds__(256) void gl_base_kernel(const float* __restrict__ 
   const int s_lo = it[2], s_hi = it[3];
   const int Lp = (s_hi - s_lo) * g.hop + g.N;
   if ((int)blockIdx.x * 256 >= Lp) return;
-  gl_twiddles(gl_lds, g.N, 256);
+  dft_twiddles(gl_lds, g.N, 256);
   __syncthreads();
   const int i = blockIdx.x * 256 + tid;
   if (i >= Lp) return;
-  const int o = gl_reflect(s_lo * g.hop + i, g.pad, g.L);
+  const int o = reflect_index(s_lo * g.hop + i, g.pad, g.L);
   double num = 0.0, dn = 0.0;
   if (o < g.Lk) {
     const int p = o + g.pad, a = p - g.N + 1;
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void gl_base_kernel(const float* __restrict__ 
       const double w = 0.5 - 0.5 * gl_lds[n].x;
       dn += w * w;
       if (m[t] == 0.f) continue;
-      num += w * gl_idft_sample(gl_lds, g.N, n, [&](int k) { return make_float2(re[(size_t)k * g.T + t], im[(size_t)k * g.T + t]); });
+      num += w * idft_sample(gl_lds, g.N, n, [&](int k) { return make_float2(re[(size_t)k * g.T + t], im[(size_t)k * g.T + t]); });
     }
   }
   base[(size_t)b * g.Pmax + i] = num;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
   const float* m = mask + (size_t)b * g.T;
   const float* kre = known + (size_t)b * 2 * FT;
   const float* kim = kre + FT;
-  gl_twiddles(tw, N, GL_T);
+  dft_twiddles(tw, N, GL_T);
   for (int j = tid; j < ns; j += GL_T) {
     const int t = s_lo + j;
     int f = 1;
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
     M[j * F + k] = mg;
     if (g.mom) P[j * F + k] = make_float2(0.f, 0.f);
   }
-  tn = gl_block_sum(tn, red);                                  // its barriers also publish tw, flag, C, M, P
+  tn = block_sum_waves<GL_WAVES>(tn, red);                                  // its barriers also publish tw, flag, C, M, P
   if (tid == 0) tnorm[(size_t)b * V + v] = sqrt(tn);
 
   const double* bs = base + (size_t)b * g.Pmax;
@@ -269,13 +269,13 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
     for (int i = tid; i < Lp; i += GL_T) {
       const int o = p_lo + i - g.pad;
       if (o < 0 || o >= g.L) {                                 // a reflected sample whose mirror is in the span: copied below
-        const int mi = gl_reflect(p_lo + i, g.pad, g.L) + g.pad - p_lo;
+        const int mi = reflect_index(p_lo + i, g.pad, g.L) + g.pad - p_lo;
         if (mi >= 0 && mi < Lp) continue;
       }
       const double d = dn[i];
       float x = 0.f;
       if (d != 0.0) {
-        const int p = gl_reflect(p_lo + i, g.pad, g.L) + g.pad, a = p - N + 1;
+        const int p = reflect_index(p_lo + i, g.pad, g.L) + g.pad, a = p - N + 1;
         int t0 = a <= 0 ? 0 : (a + hop - 1) / hop, t1 = p / hop;
         t0 = t0 < t_lo ? t_lo : t0;
         t1 = t1 > t_hi ? t_hi : t1;
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
           if (flag[t - s_lo] != 1) continue;
           const int nn = p - t * hop;
           const float2* sp = C + (size_t)(t - t_lo) * F;
-          num += (0.5 - 0.5 * tw[nn].x) * gl_idft_sample(tw, N, nn, [&](int k) { return sp[k]; });
+          num += hann_tw(tw, nn) * idft_sample(tw, N, nn, [&](int k) { return sp[k]; });
         }
         x = (float)(num / d);
       }
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
     for (int i = tid; i < Lp; i += GL_T) {                      // the mirrored head and tail from their in-span originals
       const int o = p_lo + i - g.pad;
       if (o >= 0 && o < g.L) continue;
-      const int mi = gl_reflect(p_lo + i, g.pad, g.L) + g.pad - p_lo;
+      const int mi = reflect_index(p_lo + i, g.pad, g.L) + g.pad - p_lo;
       if (mi >= 0 && mi < Lp) xp[i] = xp[mi];
     }
     __syncthreads();
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
       int idx = 0;
       for (int nn = 0; nn < N; ++nn) {
         const double2 w = tw[idx];
-        const double hw = 0.5 - 0.5 * tw[nn].x;
+        const double hw = hann_tw(tw, nn);
         const double a0 = hw * (double)x0[nn], a1 = hw * (double)x1[nn];
         r0 += a0 * w.x;
         i0 -= a0 * w.y;
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
         }
       }
     }
-    dacc = gl_block_sum(dacc, red);                            // its barriers also publish C and P
+    dacc = block_sum_waves<GL_WAVES>(dacc, red);                            // its barriers also publish C and P
     if (tid == 0) drow[n] = sqrt(dacc);
   }
   float* row = out + ((size_t)b * V + v) * g.L;

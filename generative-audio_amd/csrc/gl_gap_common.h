@@ -1,10 +1,11 @@
 // What the two execution paths of gap-constrained Griffin-Lim share (DESIGN.md sections 8c and 8g): the geometry and
-// workspace of the known part, the per-sample helpers of the two direct DFTs, and the host launchers of the kernels that
-// stay in gl_gap.hip.  gl_gap.hip holds the resident path (one workgroup per waveform, the span in LDS), gl_gap_long.hip
+// workspace of the known part and the host launchers of the kernels that stay in gl_gap.hip (the per-sample helpers of
+// the direct DFTs are in stft_core.h).  gl_gap.hip holds the resident path (one workgroup per waveform, the span in LDS), gl_gap_long.hip
 // the tiled path (the span in a workspace, one launch per half-iteration).
 #pragma once
 #include "common.h"
 #include "nppc_hip.h"
+#include "stft_core.h"
 
 #include <math.h>
 
@@ -45,52 +46,6 @@ struct GlMag {
 };
 
 inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
-__device__ __forceinline__ void gl_twiddles(double2* tw, int N, int nthr) {
-  for (int i = threadIdx.x; i < N; i += nthr) {
-    double sn, cs;
-    sincospi(2.0 * i / N, &sn, &cs);
-    tw[i] = make_double2(cs, sn);
-  }
-}
-
-// output sample that padded coordinate p holds under torch's reflect padding (pad < L: one reflection is enough)
-__device__ __forceinline__ int gl_reflect(int p, int pad, int L) {
-  int o = p - pad;
-  if (o < 0) o = -o;
-  if (o >= L) o = 2 * (L - 1) - o;
-  return o;
-}
-
-// sample n of N * irfft(sp): bins 1 .. kmax with their conjugates, bin 0 and the Nyquist bin real, as gather_sample of
-// inpaint_validator.hip
-template <typename Load>
-__device__ __forceinline__ double gl_idft_sample(const double2* tw, int N, int n, Load sp) {
-  const int kmax = (N - 1) / 2;
-  double ar = 0.0, ai = 0.0;
-  int idx = n;
-  for (int k = 1; k <= kmax; ++k) {
-    const double2 w = tw[idx];
-    const float2 x = sp(k);
-    ar += (double)x.x * w.x;
-    ai += (double)x.y * w.y;
-    idx += n;
-    if (idx >= N) idx -= N;
-  }
-  double x = (double)sp(0).x + 2.0 * (ar - ai);
-  if (!(N & 1)) x += (n & 1) ? -(double)sp(N / 2).x : (double)sp(N / 2).x;
-  return x;
-}
-
-__device__ __forceinline__ double gl_block_sum(double v, double* red) {   // fixed order; every thread gets the sum
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = red[0];
-  for (int w = 1; w < GL_WAVES; ++w) s += red[w];
-  return s;
-}
 
 // ---- host side, defined in gl_gap.hip
 // -> NPPC_OK or an error with *why: 1 F, 2 frame count, 3 overlap / n_fft limit, 4 n_iter or momentum, 5 anything else

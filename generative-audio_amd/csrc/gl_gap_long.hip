@@ -163,7 +163,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_setup_kernel(GlMag ms, const flo
     M[j * F + k] = mg;
     if (g.mom) w.P[bv * GF + j * F + k] = make_float2(0.f, 0.f);
   }
-  tn = gl_block_sum(tn, red);
+  tn = block_sum_waves<GL_WAVES>(tn, red);
   if (tid == 0) w.tpart[bv * q.nS + blockIdx.x] = tn;
 }
 
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_synth_kernel(const float* __rest
   if ((int)blockIdx.x * GL_T >= Lp) return;
   double2* tw = gl_lds;
   float2* Cs = reinterpret_cast<float2*>(tw + N);
-  gl_twiddles(tw, N, GL_T);
+  dft_twiddles(tw, N, GL_T);
   const size_t bv = (size_t)b * V + v;
   const float* m = mask + (size_t)b * g.T;
   const double* bs = w.base + (size_t)b * q.Pmax;
@@ -195,12 +195,12 @@ __global__ __launch_bounds__(GL_T) void gl_long_synth_kernel(const float* __rest
   if (i < Lp) {
     const int o = p_lo + i - g.pad;
     if (o < 0 || o >= g.L) {
-      const int mi = gl_reflect(p_lo + i, g.pad, g.L) + g.pad - p_lo;
+      const int mi = reflect_index(p_lo + i, g.pad, g.L) + g.pad - p_lo;
       if (mi >= 0 && mi < Lp) ii = mi;
     }
     d = dn[ii];
     if (d != 0.0) {
-      p = gl_reflect(p_lo + ii, g.pad, g.L) + g.pad;
+      p = reflect_index(p_lo + ii, g.pad, g.L) + g.pad;
       const int a = p - N + 1;
       t0 = a <= 0 ? 0 : (a + hop - 1) / hop, t1 = p / hop;
       t0 = t0 < t_lo ? t_lo : t0;
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_synth_kernel(const float* __rest
       if (m[t] != 0.f || t > tb) continue;                     // a known frame between two gaps is in `base`
       const int nn = p - t * hop;
       const float2* sp = Cs + (size_t)(t - ta) * F;
-      num += (0.5 - 0.5 * tw[nn].x) * gl_idft_sample(tw, N, nn, [&](int k) { return sp[k]; });
+      num += hann_tw(tw, nn) * idft_sample(tw, N, nn, [&](int k) { return sp[k]; });
     }
     x = (float)(num / d);
   }
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_analysis_kernel(const float* __r
   const int* live = w.live + (size_t)b * q.span;
   const int* flag = w.flag + (size_t)b * q.span;
   const float* xg = w.x + bv * q.Pmax;
-  gl_twiddles(tw, N, GL_T);
+  dft_twiddles(tw, N, GL_T);
   const int pr_a = q0 / F;
   int q1 = q0 + GL_T - 1;
   q1 = q1 > npair * F - 1 ? npair * F - 1 : q1;
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_analysis_kernel(const float* __r
     int idx = 0;
     for (int nn = 0; nn < N; ++nn) {
       const double2 wt = tw[idx];
-      const double hw = 0.5 - 0.5 * tw[nn].x;
+      const double hw = hann_tw(tw, nn);
       const double a0 = hw * (double)x0[nn], a1 = hw * (double)x1[nn];
       r0 += a0 * wt.x;
       i0 -= a0 * wt.y;
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_analysis_kernel(const float* __r
       }
     }
   }
-  dacc = gl_block_sum(dacc, red);
+  dacc = block_sum_waves<GL_WAVES>(dacc, red);
   if (tid == 0) w.dpart[(bv * g.n_iter + n) * q.nA + blockIdx.x] = dacc;
 }
 

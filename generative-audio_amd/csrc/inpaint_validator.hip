@@ -9,6 +9,7 @@
 // it in ascending frame order: no atomics, the same thread does the same sums whatever the batch.
 #include "common.h"
 #include "nppc_hip.h"
+#include "stft_core.h"
 
 #include <math.h>
 #include <vector>
@@ -33,19 +34,10 @@ __device__ __forceinline__ void frame_range(const IstftGeom& g, int p0, int pend
   *t_hi = b < g.T - 1 ? b : g.T - 1;
 }
 
-__device__ __forceinline__ void fill_twiddles(double2* tw, int N) {
-  for (int i = threadIdx.x; i < N; i += IS_S) {
-    double sn, cs;
-    sincospi(2.0 * i / N, &sn, &cs);
-    tw[i] = make_double2(cs, sn);
-  }
-}
-
 // sample p (padded coordinates) of the overlap-add of the staged spectra spec[t - t_lo][F], divided by the envelope
 __device__ __forceinline__ float gather_sample(const IstftGeom& g, const double2* tw, const float2* spec, int t_lo, int t_hi,
                                                int p) {
   const int N = g.N, F = g.F, hop = g.hop;
-  const int kmax = (N - 1) / 2;                               // bins with a conjugate partner: 1 .. kmax
   const int a = p - N + 1;
   int t0 = a <= 0 ? 0 : (a + hop - 1) / hop;
   int t1 = p / hop;
@@ -55,19 +47,8 @@ __device__ __forceinline__ float gather_sample(const IstftGeom& g, const double2
   for (int t = t0; t <= t1; ++t) {
     const int n = p - t * hop;
     const float2* sp = spec + (size_t)(t - t_lo) * F;
-    double ar = 0.0, ai = 0.0;
-    int idx = n;
-    for (int k = 1; k <= kmax; ++k) {
-      const double2 w = tw[idx];
-      const float2 x = sp[k];
-      ar += (double)x.x * w.x;
-      ai += (double)x.y * w.y;
-      idx += n;
-      if (idx >= N) idx -= N;
-    }
-    double x = (double)sp[0].x + 2.0 * (ar - ai);             // imaginary part of bin 0 ignored
-    if (!(N & 1)) x += (n & 1) ? -(double)sp[N / 2].x : (double)sp[N / 2].x;   // Nyquist bin: once, real part only
-    const double w = 0.5 - 0.5 * tw[n].x;                     // periodic hann
+    const double x = idft_sample(tw, N, n, [&](int k) { return sp[k]; });
+    const double w = hann_tw(tw, n);
     num += w * x;
     den += w * w;
   }
@@ -90,7 +71,7 @@ __global__ __launch_bounds__(IS_S) void istft_any_kernel(const float* __restrict
   }
   int t_lo, t_hi;
   frame_range(g, p0, pend, &t_lo, &t_hi);
-  fill_twiddles(tw, g.N);
+  dft_twiddles(tw, g.N, IS_S);
   const int nt = t_hi - t_lo + 1;
   const float* rb = re + (size_t)b * sb;
   const float* ib = im + (size_t)b * sb;
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(IS_S) void pc_variation_kernel(const float* __restr
   }
   int t_lo, t_hi;
   frame_range(g, p0, pend, &t_lo, &t_hi);
-  fill_twiddles(tw, g.N);
+  dft_twiddles(tw, g.N, IS_S);
   const int nt = t_hi - t_lo + 1;
   const size_t FT = (size_t)g.F * g.T;
   const double mean = (double)*mean_p, sd = (double)*std_p;

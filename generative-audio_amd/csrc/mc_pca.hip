@@ -207,10 +207,8 @@ __global__ __launch_bounds__(256) void rows_gram_kernel(const float* __restrict_
   const float* b = Bm + (size_t)j * N;
   double s = 0.0;
   for (long k = (long)blockIdx.x * 256 + tid; k < N; k += (long)gridDim.x * 256) s += (double)a[k] * (double)b[k];
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) atomicAdd(&G[pair], red[0] + red[1] + red[2] + red[3]);
+  s = block_sum_waves<4>(s, red);
+  if (tid == 0) atomicAdd(&G[pair], s);
 }
 
 }  // namespace

@@ -13,8 +13,6 @@
 
 namespace {
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // ---------------------------------------------------------------- raw magnitude staging (spec.hip: scale_transpose_kernel)
 // y[b][t][c] = x[b][c][t] for t < T_b, 0 for T_b <= t < Tp: EVERY row of the buffer is written (it is reused across calls
 // of other lengths); columns F..ld-1 stay as the caller left them (zero)
@@ -169,12 +167,6 @@ __global__ __launch_bounds__(256) void combine_ragged_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------- ground-truth cIRM (frontend.hip: cirm_build_kernel, G = 1)
-__device__ __forceinline__ float compress_cirm_v(float m) {
-  m = m <= -100.f ? -100.f : m;
-  const float e = expf(-0.1f * m);
-  return 10.f * (1.f - e) / (1.f + e);
-}
-
 // gt[b][{0,1}][f][t] = compress(cIRM(noisy, clean)) for t < T_b, 0 for T_b <= t < T (no drop-band)
 __global__ __launch_bounds__(256) void cirm_build_ragged_kernel(const float* __restrict__ nr, const float* __restrict__ ni,
                                                                 const float* __restrict__ cr, const float* __restrict__ ci,
@@ -189,8 +181,8 @@ __global__ __launch_bounds__(256) void cirm_build_ragged_kernel(const float* __r
     if (t < clampi(frames[b], 0, T)) {
       const float a = nr[e], bb = ni[e], c = cr[e], d = ci[e];
       const float den = a * a + bb * bb + eps;
-      gr = compress_cirm_v((a * c + bb * d) / den);
-      gi = compress_cirm_v((a * d - bb * c) / den);
+      gr = compress_cirm((a * c + bb * d) / den);
+      gi = compress_cirm((a * d - bb * c) / den);
     }
     out[o] = gr;
     out[o + FT] = gi;

@@ -1,181 +1,14 @@
 // Ragged (variable-length) inference of the FullSubNet+ restorer (n_maps = 1): a padded batch [B][Lmax] whose item b
 // is L_b samples / T_b = 1 + L_b / hop frames long.  Each kernel here is the per-item form of a uniform kernel
-// (frontend.hip, spec.hip, tcn.hip, subband.hip): it reads an item's own length from a device int[B] and computes
-// exactly what the uniform kernel computes for that item run alone.  Padding past an item's end is never read, and
+// (spec.hip, tcn.hip, subband.hip, frontend.hip's cIRM MSE): it reads an item's own length from a device int[B] and
+// computes exactly what the uniform kernel computes for that item run alone.  (The ragged STFT and iSTFT are the
+// RAGGED instantiations of frontend.hip's own kernels.)  Padding past an item's end is never read, and
 // what these kernels write past it is zero.  No float atomics: every sum has one writer and a fixed order.
 // The uniform GEMMs, the staging and the LSTM run at the batch's longest length.
 #include "common.h"
 #include "nppc_hip.h"
 
 namespace {
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// ---------------------------------------------------------------- STFT (frontend.hip: stft_kernel, per-item length)
-// wave [B][ld] (item b: its first L_b samples), out [B][F][T] with T = 1 + Lmax / hop; frames t >= T_b written as 0.
-constexpr int RSTFT_FR = 8;
-
-template <int LOGN>
-__global__ __launch_bounds__(256) void stft_ragged_kernel(const float* __restrict__ wave, long ld, const int* __restrict__ lengths,
-                                                          float* __restrict__ out_re, float* __restrict__ out_im,
-                                                          float* __restrict__ out_mag, int hop, int T) {
-  constexpr int N = 1 << LOGN;
-  constexpr int F = N / 2 + 1;
-  __shared__ float2 buf[RSTFT_FR][N + 1];
-  __shared__ float2 tw[N / 2];
-  __shared__ float win[N];
-  const int tid = threadIdx.x;
-  const int b = blockIdx.y;
-  const int t0 = blockIdx.x * RSTFT_FR;
-  const int L = clampi(lengths[b], 1, (int)ld);       // (the host validates L_b > N/2; the clamp only keeps reads in the row)
-  const int Tb = min(1 + L / hop, T);
-  if (t0 >= Tb) {                                      // the whole block is past the item's end
-    for (int e = tid; e < F * RSTFT_FR; e += 256) {
-      const int f = e / RSTFT_FR, t = t0 + e % RSTFT_FR;
-      if (t < T) {
-        const size_t o = ((size_t)b * F + f) * T + t;
-        out_re[o] = 0.f;
-        out_im[o] = 0.f;
-        if (out_mag) out_mag[o] = 0.f;
-      }
-    }
-    return;
-  }
-  for (int i = tid; i < N / 2; i += 256) {
-    double s, c;
-    sincospi(-2.0 * i / N, &s, &c);
-    tw[i] = make_float2((float)c, (float)s);
-  }
-  for (int i = tid; i < N; i += 256) win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / N));
-  __syncthreads();
-  const float* wv = wave + (size_t)b * ld;
-  for (int e = tid; e < RSTFT_FR * N; e += 256) {
-    const int j = e / N, n = e % N;
-    const int t = t0 + j;
-    float v = 0.f;
-    if (t < Tb) {
-      int sidx = t * hop + n - N / 2;
-      if (sidx < 0) sidx = -sidx;
-      if (sidx >= L) sidx = 2 * (L - 1) - sidx;       // reflect at the item's own end
-      v = wv[clampi(sidx, 0, L - 1)] * win[n];
-    }
-    const int r = __brev((unsigned)n) >> (32 - LOGN);
-    buf[j][r] = make_float2(v, 0.f);
-  }
-  __syncthreads();
-#pragma unroll 1
-  for (int s = 0; s < LOGN; ++s) {
-    const int half = 1 << s;
-    for (int e = tid; e < RSTFT_FR * (N / 2); e += 256) {
-      const int j = e / (N / 2), k = e % (N / 2);
-      const int grp = k >> s, pos = k & (half - 1);
-      const int i0 = (grp << (s + 1)) + pos, i1 = i0 + half;
-      const float2 w = tw[pos << (LOGN - 1 - s)];
-      const float2 a = buf[j][i0], c = buf[j][i1];
-      const float xr = c.x * w.x - c.y * w.y, xi = c.x * w.y + c.y * w.x;
-      buf[j][i0] = make_float2(a.x + xr, a.y + xi);
-      buf[j][i1] = make_float2(a.x - xr, a.y - xi);
-    }
-    __syncthreads();
-  }
-  for (int e = tid; e < F * RSTFT_FR; e += 256) {
-    const int f = e / RSTFT_FR, j = e % RSTFT_FR;
-    const int t = t0 + j;
-    if (t < T) {
-      const float2 v = t < Tb ? buf[j][f] : make_float2(0.f, 0.f);
-      const size_t o = ((size_t)b * F + f) * T + t;
-      out_re[o] = v.x;
-      out_im[o] = v.y;
-      if (out_mag) out_mag[o] = t < Tb ? sqrtf(v.x * v.x + v.y * v.y) : 0.f;
-    }
-  }
-}
-
-// ---------------------------------------------------------------- iSTFT (frontend.hip: istft_kernel, per-item length)
-// re / im [B][F][T] (item b: frames t < T_b), out [B][ld]: samples n < L_b as torch.istft(length=L_b) of the item's own
-// T_b frames (window envelope of those frames only), samples L_b <= n < ld written as 0.
-constexpr int RISTFT_FR = 4;
-
-template <int LOGN>
-__global__ __launch_bounds__(256) void istft_ragged_kernel(const float* __restrict__ re, const float* __restrict__ im,
-                                                           float* __restrict__ out, long ld, const int* __restrict__ lengths,
-                                                           int T, int hop) {
-  constexpr int N = 1 << LOGN;
-  constexpr int F = N / 2 + 1;
-  constexpr int MAXFR = RISTFT_FR + 7;
-  __shared__ float2 buf[MAXFR][N + 1];
-  __shared__ float2 tw[N / 2];
-  __shared__ float win[N];
-  const int tid = threadIdx.x, b = blockIdx.y;
-  const int L = clampi(lengths[b], 0, (int)ld);
-  const int Tb = min(1 + L / hop, T);
-  const int ov = N / hop;
-  const int nfr = RISTFT_FR + ov - 1;
-  const int p0 = blockIdx.x * RISTFT_FR * hop;
-  const int tfirst = p0 / hop - (ov - 1);
-  if (p0 - N / 2 >= L) {                               // every sample of the block is past the item's end
-    for (int e = tid; e < RISTFT_FR * hop; e += 256) {
-      const int nidx = p0 + e - N / 2;
-      if (nidx >= 0 && nidx < ld) out[(size_t)b * ld + nidx] = 0.f;
-    }
-    return;
-  }
-  for (int i = tid; i < N / 2; i += 256) {
-    double s, c;
-    sincospi(2.0 * i / N, &s, &c);
-    tw[i] = make_float2((float)c, (float)s);
-  }
-  for (int i = tid; i < N; i += 256) win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / N));
-  __syncthreads();
-  for (int e = tid; e < nfr * N; e += 256) {
-    const int j = e / N, k = e % N;
-    const int t = tfirst + j;
-    float2 v = make_float2(0.f, 0.f);
-    if (t >= 0 && t < Tb) {
-      const int kk = k < F ? k : N - k;
-      const size_t o = ((size_t)b * F + kk) * T + t;
-      v = make_float2(re[o], k < F ? im[o] : -im[o]);
-      if (k == 0 || k == N / 2) v.y = 0.f;
-    }
-    buf[j][__brev((unsigned)k) >> (32 - LOGN)] = v;
-  }
-  __syncthreads();
-#pragma unroll 1
-  for (int s = 0; s < LOGN; ++s) {
-    const int half = 1 << s;
-    for (int e = tid; e < nfr * (N / 2); e += 256) {
-      const int j = e / (N / 2), k = e % (N / 2);
-      const int grp = k >> s, pos = k & (half - 1);
-      const int i0 = (grp << (s + 1)) + pos, i1 = i0 + half;
-      const float2 w = tw[pos << (LOGN - 1 - s)];
-      const float2 a = buf[j][i0], c = buf[j][i1];
-      const float xr = c.x * w.x - c.y * w.y, xi = c.x * w.y + c.y * w.x;
-      buf[j][i0] = make_float2(a.x + xr, a.y + xi);
-      buf[j][i1] = make_float2(a.x - xr, a.y - xi);
-    }
-    __syncthreads();
-  }
-  for (int e = tid; e < RISTFT_FR * hop; e += 256) {
-    const int p = p0 + e;
-    const int nidx = p - N / 2;
-    if (nidx < 0 || nidx >= ld) continue;
-    if (nidx >= L) {
-      out[(size_t)b * ld + nidx] = 0.f;
-      continue;
-    }
-    float num = 0.f, den = 0.f;
-    for (int j = 0; j < nfr; ++j) {
-      const int t = tfirst + j;
-      const int off = p - t * hop;
-      if (t >= 0 && t < Tb && off >= 0 && off < N) {
-        const float w = win[off];
-        num += w * buf[j][off].x * (1.0f / N);
-        den += w * w;
-      }
-    }
-    out[(size_t)b * ld + nidx] = den > 1e-11f ? num / den : 0.f;
-  }
-}
 
 // ---------------------------------------------------------------- TSSE front (spec.hip, inference form, per-item frames)
 struct MapSet { const float* x[6]; };
@@ -428,12 +261,8 @@ __global__ __launch_bounds__(1024) void subband_mean_ragged_kernel(const TT* __r
     v += to_f32<TT>(fb[row * ldF + f]) + to_f32<TT>(fb[strideFb + row * ldF + f]) + to_f32<TT>(fb[2 * strideFb + row * ldF + f]);
     s += (double)v;
   }
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
+  const double tot = block_sum_waves<16>(s, red);
   if (tid == 0) {
-    double tot = 0.0;
-    for (int w = 0; w < 16; ++w) tot += red[w];
     const float mu = (float)(tot / ((double)F * nfeat * Tvb));
     scale[b] = 1.0f / (mu + 1e-5f);
   }
@@ -451,12 +280,6 @@ __global__ __launch_bounds__(256) void crop_frames_kernel(float* __restrict__ x,
 }
 
 // ---------------------------------------------------------------- per-item cIRM MSE (frontend.hip: crm_mse, G = 1)
-__device__ __forceinline__ float compress_cirm_r(float m) {
-  m = m <= -100.f ? -100.f : m;
-  const float e = expf(-0.1f * m);
-  return 10.f * (1.f - e) / (1.f + e);
-}
-
 // loss[b] = mean over [2][F][T_b] of (gt - crm)^2, gt = compress(cIRM(noisy, clean)) with crm_mse's formula; one workgroup
 // per item, fixed-order fp64 reduction
 __global__ __launch_bounds__(1024) void crm_mse_ragged_kernel(const float* __restrict__ nr, const float* __restrict__ ni,
@@ -473,18 +296,14 @@ __global__ __launch_bounds__(1024) void crm_mse_ragged_kernel(const float* __res
     const size_t i = ((size_t)b * F + f) * T + t;
     const float a = nr[i], bb = ni[i], c = cr[i], d = ci[i];
     const float den = a * a + bb * bb + eps;
-    const float gr = compress_cirm_r((a * c + bb * d) / den);
-    const float gi = compress_cirm_r((a * d - bb * c) / den);
+    const float gr = compress_cirm((a * c + bb * d) / den);
+    const float gi = compress_cirm((a * d - bb * c) / den);
     const size_t o = (size_t)b * 2 * FT + (size_t)f * T + t;
     const double dr = (double)gr - (double)crm[o], di = (double)gi - (double)crm[o + FT];
     s += dr * dr + di * di;
   }
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
+  const double tot = block_sum_waves<16>(s, red);
   if (tid == 0) {
-    double tot = 0.0;
-    for (int w = 0; w < 16; ++w) tot += red[w];
     loss[b] = tot / (2.0 * F * Tb);
   }
 }
@@ -492,40 +311,6 @@ __global__ __launch_bounds__(1024) void crm_mse_ragged_kernel(const float* __res
 }  // namespace
 
 extern "C" {
-
-int nppc_stft_ragged(const float* wave, long ld, const int* lengths, float* re, float* im, float* mag, int B, int T, int nfft,
-                     int hop, void* stream) {
-  if (!wave || !lengths || !re || !im || B <= 0 || T <= 0 || hop <= 0 || ld <= nfft / 2) return NPPC_EBADARG;
-  dim3 grid(ceil_div(T, RSTFT_FR), B);
-  hipStream_t s = (hipStream_t)stream;
-  switch (nfft) {
-    case 64: hipLaunchKernelGGL(stft_ragged_kernel<6>, grid, dim3(256), 0, s, wave, ld, lengths, re, im, mag, hop, T); break;
-    case 128: hipLaunchKernelGGL(stft_ragged_kernel<7>, grid, dim3(256), 0, s, wave, ld, lengths, re, im, mag, hop, T); break;
-    case 256: hipLaunchKernelGGL(stft_ragged_kernel<8>, grid, dim3(256), 0, s, wave, ld, lengths, re, im, mag, hop, T); break;
-    case 512: hipLaunchKernelGGL(stft_ragged_kernel<9>, grid, dim3(256), 0, s, wave, ld, lengths, re, im, mag, hop, T); break;
-    default: return NPPC_EUNSUPPORTED;
-  }
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
-}
-
-int nppc_istft_ragged(const float* re, const float* im, float* out, long ld, const int* lengths, int B, int T, int nfft, int hop,
-                      void* stream) {
-  if (!re || !im || !out || !lengths || B <= 0 || T <= 0 || hop <= 0 || ld <= 0 || nfft % hop || nfft / hop > 8)
-    return NPPC_EBADARG;
-  const long total = ld + nfft / 2;
-  dim3 grid(ceil_div(total, (long)RISTFT_FR * hop), B);
-  hipStream_t s = (hipStream_t)stream;
-  switch (nfft) {
-    case 64: hipLaunchKernelGGL(istft_ragged_kernel<6>, grid, dim3(256), 0, s, re, im, out, ld, lengths, T, hop); break;
-    case 128: hipLaunchKernelGGL(istft_ragged_kernel<7>, grid, dim3(256), 0, s, re, im, out, ld, lengths, T, hop); break;
-    case 256: hipLaunchKernelGGL(istft_ragged_kernel<8>, grid, dim3(256), 0, s, re, im, out, ld, lengths, T, hop); break;
-    case 512: hipLaunchKernelGGL(istft_ragged_kernel<9>, grid, dim3(256), 0, s, re, im, out, ld, lengths, T, hop); break;
-    default: return NPPC_EUNSUPPORTED;
-  }
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
-}
 
 int nppc_tsse_fwd_maps_ragged(int prec, const float* const* maps, int nmaps, double* rowsum, const float* cw0, const float* cb0,
                               const float* cw1, const float* cb1, const float* cw2, const float* cb2, int ks0, int ks1, int ks2,

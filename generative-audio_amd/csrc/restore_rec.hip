@@ -33,16 +33,6 @@ __device__ __forceinline__ bool in_gap(const long* __restrict__ iv, int G, long 
   return g < G && iv[2 * g] <= n;
 }
 
-__device__ __forceinline__ double block_sum(double a, double* red) {
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // ---------------------------------------------------------------------------------------------------------------- gain
 __global__ __launch_bounds__(256) void rec_gain_part_kernel(const float* __restrict__ wave, long L,
                                                             const long* __restrict__ gaps, int G, double* __restrict__ work) {
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(256) void rec_gain_part_kernel(const float* __restr
     const long n = nvec * 4 + threadIdx.x;
     if (threadIdx.x < 4 && n < L && !in_gap(gaps, G, n)) acc += (double)wave[n] * (double)wave[n];
   }
-  acc = block_sum(acc, red);
+  acc = block_sum_tree256(acc, red);
   if (threadIdx.x == 0) work[blockIdx.x] = acc;
 }
 
@@ -85,7 +75,7 @@ __global__ __launch_bounds__(256) void rec_gain_finish_kernel(const double* __re
                                                               const long* __restrict__ gaps, int G, float target_dbfs,
                                                               double* __restrict__ gain) {
   __shared__ double red[256];
-  const double sum = block_sum(work[threadIdx.x], red);
+  const double sum = block_sum_tree256(work[threadIdx.x], red);
   if (threadIdx.x == 0) {
     long known = L;
     for (int g = 0; g < G; ++g) known -= gaps[2 * g + 1] - gaps[2 * g];

@@ -24,16 +24,6 @@ constexpr int MAX_TAPS = 4096;                         // resampler taps held in
 // third-octave band k covers bins [kEdge[k], kEdge[k + 1]) (pystoi thirdoct(10000, 512, 15, 150))
 __device__ __constant__ int kEdge[NBAND + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
 
-// block-wide fp64 sum of 256 threads in a fixed order: xor-butterfly inside each wave, then the four wave sums in index
-// order; every thread gets the result
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();                                     // red may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // np.hanning(258)[1:-1] in numpy's form: 0.5 + 0.5 cos(pi n / 257), n = 2 (m + 1) - 257
 __device__ __forceinline__ double hann256(int m) { return 0.5 + 0.5 * cospi((double)(2 * (m + 1) - 257) / 257.0); }
 
@@ -60,11 +50,11 @@ __global__ __launch_bounds__(256) void sisdr_kernel(const float* __restrict__ re
     see += c * c;
     sse += a * c;
   }
-  ss = block_sum(ss, red);
-  se = block_sum(se, red);
-  sss = block_sum(sss, red);
-  see = block_sum(see, red);
-  sse = block_sum(sse, red);
+  ss = block_sum_waves<4>(ss, red);
+  se = block_sum_waves<4>(se, red);
+  sss = block_sum_waves<4>(sss, red);
+  see = block_sum_waves<4>(see, red);
+  sse = block_sum_waves<4>(sse, red);
   const double ms = ss / (double)n, me = se / (double)n, a1 = sse / sss;
   double zss = 0.0, zes = 0.0, r1 = 0.0;
   for (long i = threadIdx.x; i < n; i += 256) {
@@ -74,16 +64,16 @@ __global__ __launch_bounds__(256) void sisdr_kernel(const float* __restrict__ re
     zes += zc * za;
     r1 += d * d;
   }
-  zss = block_sum(zss, red);
-  zes = block_sum(zes, red);
-  r1 = block_sum(r1, red);
+  zss = block_sum_waves<4>(zss, red);
+  zes = block_sum_waves<4>(zes, red);
+  r1 = block_sum_waves<4>(r1, red);
   const double a2 = zes / (zss + 1e-6);
   double r2 = 0.0;
   for (long i = threadIdx.x; i < n; i += 256) {
     const double d = a2 * ((double)s[i] - ms) - ((double)e[i] - me);
     r2 += d * d;
   }
-  r2 = block_sum(r2, red);
+  r2 = block_sum_waves<4>(r2, red);
   if (threadIdx.x == 0) {
     if (sums) {
       double* o = sums + (long)b * SISDR_SUMS;
@@ -300,7 +290,7 @@ __global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict
     }
     acc += dxy / ((sqrt(dyy) + EPS64) * (sqrt(dxx) + EPS64));
   }
-  acc = block_sum(acc, red);
+  acc = block_sum_waves<4>(acc, red);
   if (threadIdx.x == 0) out[b] = acc / ((double)NBAND * J);
 }
 

@@ -43,11 +43,9 @@ __global__ __launch_bounds__(256) void subband_mean_kernel(const T* __restrict__
     v += to_f32<T>(fb[row * ldF + f]) + to_f32<T>(fb[strideFb + row * ldF + f]) + to_f32<T>(fb[2 * strideFb + row * ldF + f]);
     s += (double)v;
   }
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
+  s = block_sum_waves<4>(s, red);
   if (tid == 0) {
-    atomicAdd(&g_sm_acc[b], red[0] + red[1] + red[2] + red[3]);
+    atomicAdd(&g_sm_acc[b], s);
     __threadfence();
     if (atomicAdd(&g_sm_cnt[2 * b], 1u) == gridDim.x - 1) {
       const double tot = atomicAdd(&g_sm_acc[b], 0.0);

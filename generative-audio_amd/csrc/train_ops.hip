@@ -280,10 +280,8 @@ __global__ __launch_bounds__(256) void sb_bwd_reduce_kernel(const T* __restrict_
         dpre[(size_t)m * strideFb + orow + (size_t)r * G + g] = from_f32<T>(v);
       }
   }
-  const double d = wave_sum((double)s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(D + bo, red[0] + red[1] + red[2] + red[3]);
+  const double d = block_sum_waves<4>((double)s, red);
+  if (threadIdx.x == 0) atomicAdd(D + bo, d);
 }
 
 // in place: dpre[m][b][t][f] = (fb[m][b][t][f] > 0) * ( sc_b * (kept ? raw : 0) - sc_b * D[bo] / Nn ),  raw = dx[t][n][W+m] as

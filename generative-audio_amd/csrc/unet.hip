@@ -1308,10 +1308,8 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
   __shared__ double red[4];
   double s = 0.0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += (double)g[i] * (double)g[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
+  s = block_sum_waves<4>(s, red);
+  if (threadIdx.x == 0) atomicAdd(out, s);
 }
 
 // rows per workgroup of the BatchNorm column reductions: every workgroup ends with 2*C fp64 atomics on the same

@@ -80,9 +80,8 @@ def test_stft_istft_ragged_match_single_clips():
         m1, r1, i1 = ops.stft(w[None].cuda(), c["nfft"], c["hop"])
         om, orr, oi = R.stft_parts(w.double(), c["nfft"], c["hop"], c["nfft"])
         for got, alone, ref in ((re, r1, orr), (im, i1, oi), (mag, m1, om)):
-            g = got[b, :, :Tb].cpu().numpy()
-            assert rel(g, alone[0].cpu().numpy()) < 2e-6
-            assert rel(g, ref[0, 0].numpy()) < 2e-6
+            assert torch.equal(got[b, :, :Tb], alone[0])          # one kernel body: the same bits
+            assert rel(got[b, :, :Tb].cpu().numpy(), ref[0, 0].numpy()) < 2e-6
             assert bool((got[b, :, Tb:] == 0).all()), (b, Tb, T)
     # padding is never read: NaN / 3e38 padding gives the same bits as zero padding
     for fill in (float("nan"), 3e38):
@@ -96,9 +95,8 @@ def test_stft_istft_ragged_match_single_clips():
         one = ops.istft(re[b:b + 1, :, :Tb], im[b:b + 1, :, :Tb], c["nfft"], c["hop"], LENGTHS[b])
         ref = torch.istft(torch.complex(re[b, :, :Tb].double().cpu(), im[b, :, :Tb].double().cpu()), c["nfft"], c["hop"],
                           c["nfft"], torch.hann_window(c["nfft"], dtype=torch.float64), center=True, length=LENGTHS[b])
-        g = out[b, :LENGTHS[b]].cpu().numpy()
-        assert rel(g, one[0].cpu().numpy()) < 2e-6
-        assert rel(g, ref.numpy()) < 2e-6
+        assert torch.equal(out[b, :LENGTHS[b]], one[0])
+        assert rel(out[b, :LENGTHS[b]].cpu().numpy(), ref.numpy()) < 2e-6
         assert bool((out[b, LENGTHS[b]:] == 0).all())
     # NaN / huge values in the spectra past an item's frames are not read either
     re2, im2 = re.clone(), im.clone()
@@ -107,6 +105,54 @@ def test_stft_istft_ragged_match_single_clips():
         re2[b, :, Tb:] = float("nan")
         im2[b, :, Tb:] = 3e38
     assert torch.equal(out, ops.istft(re2, im2, c["nfft"], c["hop"], max(LENGTHS), lengths=lengths))
+
+
+# (nfft, hop) -> limits of the error against torch.stft / torch.istft in fp64.  64 / 32: the test above; 512 / 256:
+# test_forward_gpu.py (test_stft_matches_reference, test_istft_roundtrip_and_enhanced_waveform).  No test bounded the two
+# overlap-8 shapes: twice the worst error, on this test's inputs, of the separate uniform and ragged kernels that the one
+# template replaced (128 / 16: 1.155e-7 / 1.029e-7, 512 / 64: 1.301e-7 / 1.339e-7, the same for both)
+FFT_SHAPES = {(64, 32): (2e-6, 2e-6), (128, 16): (2 * 1.155e-7, 2 * 1.029e-7), (512, 256): (2e-6, 2e-6),
+              (512, 64): (2 * 1.301e-7, 2 * 1.339e-7)}
+
+
+@pytest.mark.parametrize("short", [True, False])
+@pytest.mark.parametrize("nfft,hop", list(FFT_SHAPES))
+def test_equal_lengths_ragged_stft_istft_equal_uniform(nfft, hop, short, record_err):
+    """a padded batch whose items all have the same length gives the bits of the uniform call: the shortest legal clip, and
+    9 frames (a second, partial STFT workgroup; an iSTFT workgroup that straddles the item's end).  hop = nfft / 8 fills
+    every frame slot of the iSTFT kernel, 512 / 64 at its largest LDS footprint."""
+    from nppc_audio import ops
+    B, L = 3, nfft // 2 + 1 if short else 8 * hop + 3
+    Tb, pad = 1 + L // hop, 2 * hop + 5
+    x = torch.stack([w for w, _ in clips([L] * B, first=130)])
+    xp = torch.full((B, L + pad), float("nan"))
+    xp[:, :L] = x
+    uni = ops.stft(x.cuda(), nfft, hop)
+    for wave in (x, xp):                                   # ld == L, and NaN padding past it
+        rag = ops.stft(wave.cuda(), nfft, hop, lengths=[L] * B)
+        for u, r in zip(uni, rag):
+            assert r.shape[-1] == 1 + wave.shape[1] // hop
+            assert torch.equal(r[:, :, :Tb], u) and bool((r[:, :, Tb:] == 0).all())
+    win = torch.hann_window(nfft, dtype=torch.float64)
+    ref = torch.stft(x.double(), nfft, hop, nfft, win, center=True, pad_mode="reflect", return_complex=True)
+    lim_stft, lim_istft = FFT_SHAPES[(nfft, hop)]
+    mag, re, im = uni
+    # every part against the spectrum's largest magnitude: the shortest clip at hop = nfft / 2 is two frames that the
+    # reflection makes symmetric, so its imaginary part is zero and has no scale of its own
+    err = max(float((got.cpu().double() - want).abs().max()) for got, want in ((re, ref.real), (im, ref.imag), (mag, ref.abs())))
+    err /= float(ref.abs().max())
+    print(f"stft {nfft}/{hop} L={L}: rel {err:.3e}")
+    record_err("stft_vs_fp64", err, lim_stft)
+    back = ops.istft(re, im, nfft, hop, L)
+    rp, ip = (torch.full((B, nfft // 2 + 1, Tb + 3), fill, device="cuda") for fill in (float("nan"), 3e38))
+    rp[:, :, :Tb], ip[:, :, :Tb] = re, im
+    for r_, i_, ld in ((re, im, L), (rp, ip, L + pad)):
+        rag = ops.istft(r_, i_, nfft, hop, ld, lengths=[L] * B)
+        assert torch.equal(rag[:, :L], back) and bool((rag[:, L:] == 0).all())
+    ref = torch.istft(torch.complex(re.double().cpu(), im.double().cpu()), nfft, hop, nfft, win, center=True, length=L)
+    err = rel(back.cpu().numpy(), ref.numpy())
+    print(f"istft {nfft}/{hop} L={L}: rel {err:.3e}")
+    record_err("istft_vs_fp64", err, lim_istft)
 
 
 # ---------------------------------------------------------------------------------------------------- forward
