@@ -12,7 +12,8 @@
 //   gl_gap_kernel    one workgroup per (item, variation): all iterations with the gap spectra C, the previous transform P
 //                    (momentum only), the target magnitudes, the span's time segment and the twiddles resident in LDS
 // What this file shares with the tiled path for spans over the cap (gl_gap_long.hip, section 8g: nppc_gl_gap_long_shape,
-// nppc_gl_gap_long, nppc_gl_gap_pc_long) is in gl_gap_common.h; gl_span_kernel, gl_base_kernel and gl_fill_kernel serve both.
+// nppc_gl_gap_long, nppc_gl_gap_pc_long) is in gl_gap_common.h, the per-element expressions of gl_gap_kernel included;
+// gl_span_kernel, gl_base_kernel and gl_fill_kernel serve both.
 // Both transforms are direct DFTs out of LDS as in inpaint_validator.hip / frontend.hip: twiddles exp(2 pi i j / N) in fp64
 // indexed by (k n) mod N in integers, fp64 accumulation, fp32 state.  Every sum has one writer and a fixed order: no
 // atomics; a waveform does not depend on the batch or on the run.
@@ -208,16 +209,7 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
   const float* kre = known + (size_t)b * 2 * FT;
   const float* kim = kre + FT;
   dft_twiddles(tw, N, GL_T);
-  for (int j = tid; j < ns; j += GL_T) {
-    const int t = s_lo + j;
-    int f = 1;
-    if (m[t] != 0.f) {
-      f = 0;
-      const int a = t - g.r < 0 ? 0 : t - g.r, e = t + g.r > g.T - 1 ? g.T - 1 : t + g.r;
-      for (int u = a; u <= e; ++u) f = m[u] == 0.f ? 2 : f;
-    }
-    flag[j] = (unsigned char)f;
-  }
+  for (int j = tid; j < ns; j += GL_T) flag[j] = (unsigned char)gl_frame_flag(m, s_lo + j, g.r, g.T);
   __syncthreads();
   if (tid == 0) {                                              // the frames the forward transform visits, in ascending order
     int nl = 0;
@@ -226,35 +218,13 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
     flag[GL_NLIVE] = (unsigned char)nl;
   }
   // C_0 = M exp(i phi0) on the gap frames
-  const float* ph = phase + (phase_per_v ? ((size_t)b * V + v) * FT : (size_t)b * FT);
-  const float* tm = nullptr;
-  const float* dir = nullptr;
-  double alpha = 0.0, mean = 0.0, sd = 1.0;
-  if (ms.target)
-    tm = ms.target + ((size_t)b * V + v) * FT;
-  else {
-    tm = ms.pred + (size_t)b * FT;
-    mean = (double)*ms.mean, sd = (double)*ms.stdev;
-    if (v < ms.K * ms.A) {
-      dir = ms.pc + ((size_t)b * ms.K + v / ms.A) * FT;
-      alpha = (double)ms.alphas[v % ms.A];
-    }
-  }
+  const GlMagRow src = gl_mag_row(ms, phase, phase_per_v, b, v, V, FT);
   double tn = 0.0;
   for (int e = tid; e < G * F; e += GL_T) {
-    const int k = e / G, j = e % G, t = t_lo + j;
-    float2 c0 = make_float2(0.f, 0.f);
-    float mg = 0.f;
-    if (m[t] == 0.f) {
-      const size_t o = (size_t)k * g.T + t;
-      double mag = (double)tm[o];
-      if (!ms.target) mag = exp((mag + (dir ? alpha * (double)dir[o] : 0.0)) * sd + mean);
-      mg = (float)mag;
-      double sn, cs;
-      sincos((double)ph[o], &sn, &cs);
-      c0 = make_float2((float)((double)mg * cs), (float)((double)mg * sn));
-      tn += (double)mg * (double)mg;
-    }
+    const int k = e / G, j = e % G;
+    float2 c0;
+    float mg;
+    tn = gl_init_bin(tn, src, m, k, t_lo + j, g.T, c0, mg);
     C[j * F + k] = c0;
     M[j * F + k] = mg;
     if (g.mom) P[j * F + k] = make_float2(0.f, 0.f);
@@ -275,18 +245,12 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
       const double d = dn[i];
       float x = 0.f;
       if (d != 0.0) {
-        const int p = reflect_index(p_lo + i, g.pad, g.L) + g.pad, a = p - N + 1;
-        int t0 = a <= 0 ? 0 : (a + hop - 1) / hop, t1 = p / hop;
-        t0 = t0 < t_lo ? t_lo : t0;
-        t1 = t1 > t_hi ? t_hi : t1;
-        double num = bs[i];
-        for (int t = t0; t <= t1; ++t) {
-          if (flag[t - s_lo] != 1) continue;
-          const int nn = p - t * hop;
-          const float2* sp = C + (size_t)(t - t_lo) * F;
-          num += hann_tw(tw, nn) * idft_sample(tw, N, nn, [&](int k) { return sp[k]; });
-        }
-        x = (float)(num / d);
+        const int p = reflect_index(p_lo + i, g.pad, g.L) + g.pad;
+        int t0, t1;
+        gl_reach(p, N, hop, t_lo, t_hi, t0, t1);
+        x = gl_synth_sample(
+            tw, N, hop, p, t0, t1, bs[i], d, [&](int t) { return flag[t - s_lo] == 1; },
+            [&](int t) { return C + (size_t)(t - t_lo) * F; });
       }
       xp[i] = x;
     }
@@ -306,44 +270,12 @@ __global__ __launch_bounds__(GL_T) void gl_gap_kernel(GlMag ms, const float* __r
       const int k = q % F, pr = 2 * (q / F);
       const int j0 = live[pr], j1 = pr + 1 < nlive ? live[pr + 1] : j0;
       const int f0 = flag[j0], f1 = pr + 1 < nlive ? flag[j1] : 0;
-      const float* x0 = xp + (size_t)j0 * hop;
-      const float* x1 = xp + (size_t)j1 * hop;
-      double r0 = 0.0, i0 = 0.0, r1 = 0.0, i1 = 0.0;
-      int idx = 0;
-      for (int nn = 0; nn < N; ++nn) {
-        const double2 w = tw[idx];
-        const double hw = hann_tw(tw, nn);
-        const double a0 = hw * (double)x0[nn], a1 = hw * (double)x1[nn];
-        r0 += a0 * w.x;
-        i0 -= a0 * w.y;
-        r1 += a1 * w.x;
-        i1 -= a1 * w.y;
-        idx += k;
-        if (idx >= N) idx -= N;
-      }
+      const GlBinPair R = gl_dft_pair(tw, N, k, xp + (size_t)j0 * hop, xp + (size_t)j1 * hop);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const int f = h ? f1 : f0, t = s_lo + (h ? j1 : j0);
-        const double rr = h ? r1 : r0, ri = h ? i1 : i0;
-        if (f == 1) {
-          const int s = (t - t_lo) * F + k;
-          const double mg = (double)M[s];
-          const double e = sqrt(rr * rr + ri * ri) - mg;
-          dacc += e * e;
-          double ar = rr, ai = ri;
-          if (g.mom) {
-            const float2 pv = P[s];
-            ar -= g.c * (double)pv.x;
-            ai -= g.c * (double)pv.y;
-            P[s] = make_float2((float)rr, (float)ri);
-          }
-          const double sc = mg / (sqrt(ar * ar + ai * ai) + 1e-16);
-          C[s] = make_float2((float)(ar * sc), (float)(ai * sc));
-        } else if (f == 2) {
-          const size_t o = (size_t)k * g.T + t;
-          const double er = rr - (double)kre[o], ei = ri - (double)kim[o];
-          dacc += er * er + ei * ei;
-        }
+        const int t = s_lo + (h ? j1 : j0);
+        dacc = gl_project(dacc, h ? f1 : f0, h ? R.r1 : R.r0, h ? R.i1 : R.i0, (t - t_lo) * F + k, (size_t)k * g.T + t, C, P, M, kre,
+                          kim, g.mom, g.c);
       }
     }
     dacc = block_sum_waves<GL_WAVES>(dacc, red);                            // its barriers also publish C and P
@@ -470,9 +402,8 @@ int nppc_gl_gap(const float* target_mag, const float* known_spec, const float* m
                 int phase_per_variation, float* out, double* dist, double* target_norm, int* status, void* work,
                 long work_bytes, int B, int V, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span,
                 void* stream) {
-  if (!target_mag) return NPPC_EBADARG;
-  GlMag ms = {};
-  ms.target = target_mag;
+  GlMag ms;
+  if (gl_mag_target(target_mag, &ms) != NPPC_OK) return NPPC_EBADARG;
   return gl_run(ms, known_spec, mask, init_phase, phase_per_variation != 0, out, dist, target_norm, status, work, work_bytes, B, V,
                 T, nfft, hop, L, n_iter, momentum, max_span, stream);
 }
@@ -481,9 +412,8 @@ int nppc_gl_gap_pc(const float* pred, const float* pc, const float* mean, const 
                    const float* known_spec, const float* mask, const float* init_phase, float* out, double* dist,
                    double* target_norm, int* status, void* work, long work_bytes, int B, int K, int A, int T, int nfft, int hop,
                    int L, int n_iter, double momentum, int max_span, void* stream) {
-  if (!pred || !pc || !mean || !stdev || !alphas || K <= 0 || A <= 0 || (long)K * A + 1 > 65535) return NPPC_EBADARG;
-  GlMag ms = {};
-  ms.pred = pred, ms.pc = pc, ms.mean = mean, ms.stdev = stdev, ms.alphas = alphas, ms.K = K, ms.A = A;
+  GlMag ms;
+  if (gl_mag_pc(pred, pc, mean, stdev, alphas, K, A, &ms) != NPPC_OK) return NPPC_EBADARG;
   return gl_run(ms, known_spec, mask, init_phase, 0, out, dist, target_norm, status, work, work_bytes, B, K * A + 1, T, nfft, hop,
                 L, n_iter, momentum, max_span, stream);
 }

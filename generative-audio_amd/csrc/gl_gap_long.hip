@@ -1,5 +1,5 @@
 // Gap-constrained Griffin-Lim for spans longer than the resident kernel's cap: the same algorithm as
-// gl_gap.hip, expression for expression, with the span's state (C, P for momentum, M, the time segment x) in a workspace in
+// gl_gap.hip, through the same per-element helpers (gl_gap_common.h), with the span's state (C, P for momentum, M, the time segment x) in a workspace in
 // HBM / L2 instead of one workgroup's LDS, and one launch per half-iteration over many workgroups.
 //   nppc_gl_gap_long_shape   argument rules, both caps and the workspace size; runs without a GPU
 //   nppc_gl_gap_long         target magnitudes [B][V][F][T]
@@ -94,16 +94,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_live_kernel(const float* __restr
   const int s_lo = it[2], ns = it[3] - s_lo + 1;               // ns <= q.span: t_hi - t_lo + 1 + 2 r <= q.cap, and ns <= T
   const float* m = mask + (size_t)b * g.T;
   int* fl = flag + (size_t)b * q.span;
-  for (int j = tid; j < ns; j += GL_T) {
-    const int t = s_lo + j;
-    int f = 1;
-    if (m[t] != 0.f) {
-      f = 0;
-      const int a = t - g.r < 0 ? 0 : t - g.r, e = t + g.r > g.T - 1 ? g.T - 1 : t + g.r;
-      for (int u = a; u <= e; ++u) f = m[u] == 0.f ? 2 : f;
-    }
-    fl[j] = f;
-  }
+  for (int j = tid; j < ns; j += GL_T) fl[j] = gl_frame_flag(m, s_lo + j, g.r, g.T);
   __syncthreads();
   if (tid == 0) {                                              // the frames the forward transform visits, in ascending order
     int* lv = live + (size_t)b * q.span;
@@ -129,36 +120,14 @@ __global__ __launch_bounds__(GL_T) void gl_long_setup_kernel(GlMag ms, const flo
   const float* m = mask + (size_t)b * g.T;
   float2* C = w.C + bv * GF;
   float* M = w.M + bv * GF;
-  const float* ph = phase + (phase_per_v ? bv * FT : (size_t)b * FT);
-  const float* tm = nullptr;
-  const float* dir = nullptr;
-  double alpha = 0.0, mean = 0.0, sd = 1.0;
-  if (ms.target)
-    tm = ms.target + bv * FT;
-  else {
-    tm = ms.pred + (size_t)b * FT;
-    mean = (double)*ms.mean, sd = (double)*ms.stdev;
-    if (v < ms.K * ms.A) {
-      dir = ms.pc + ((size_t)b * ms.K + v / ms.A) * FT;
-      alpha = (double)ms.alphas[v % ms.A];
-    }
-  }
+  const GlMagRow src = gl_mag_row(ms, phase, phase_per_v, b, v, V, FT);
   double tn = 0.0;
   const int e = blockIdx.x * GL_T + tid;
   if (e < G * F) {
-    const int k = e / G, j = e % G, t = t_lo + j;
-    float2 c0 = make_float2(0.f, 0.f);
-    float mg = 0.f;
-    if (m[t] == 0.f) {
-      const size_t o = (size_t)k * g.T + t;
-      double mag = (double)tm[o];
-      if (!ms.target) mag = exp((mag + (dir ? alpha * (double)dir[o] : 0.0)) * sd + mean);
-      mg = (float)mag;
-      double sn, cs;
-      sincos((double)ph[o], &sn, &cs);
-      c0 = make_float2((float)((double)mg * cs), (float)((double)mg * sn));
-      tn += (double)mg * (double)mg;
-    }
+    const int k = e / G, j = e % G;
+    float2 c0;
+    float mg;
+    tn = gl_init_bin(tn, src, m, k, t_lo + j, g.T, c0, mg);
     C[j * F + k] = c0;
     M[j * F + k] = mg;
     if (g.mom) w.P[bv * GF + j * F + k] = make_float2(0.f, 0.f);
@@ -168,7 +137,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_setup_kernel(GlMag ms, const flo
 }
 
 // ------------------------------------------------------------------------------------------------------- x = istft(C)
-// One thread per padded-coordinate sample of the span, the expression of gl_gap_kernel.  A mirrored head or tail sample
+// One thread per padded-coordinate sample of the span, gl_gap_kernel's gl_synth_sample.  A mirrored head or tail sample
 // whose original lies in the span is that original: gl_gap_kernel copies it after a barrier, here the thread evaluates the
 // original's expression itself (the same bits), because the original may belong to another workgroup.
 __global__ __launch_bounds__(GL_T) void gl_long_synth_kernel(const float* __restrict__ mask, const int* __restrict__ info,
@@ -201,10 +170,7 @@ __global__ __launch_bounds__(GL_T) void gl_long_synth_kernel(const float* __rest
     d = dn[ii];
     if (d != 0.0) {
       p = reflect_index(p_lo + ii, g.pad, g.L) + g.pad;
-      const int a = p - N + 1;
-      t0 = a <= 0 ? 0 : (a + hop - 1) / hop, t1 = p / hop;
-      t0 = t0 < t_lo ? t_lo : t0;
-      t1 = t1 > t_hi ? t_hi : t1;
+      gl_reach(p, N, hop, t_lo, t_hi, t0, t1);
     }
   }
   // the gap frames this tile reads: [ta, tb]
@@ -227,16 +193,10 @@ __global__ __launch_bounds__(GL_T) void gl_long_synth_kernel(const float* __rest
   __syncthreads();
   if (i >= Lp) return;
   float x = 0.f;
-  if (d != 0.0) {
-    double num = bs[ii];
-    for (int t = t0; t <= t1; ++t) {
-      if (m[t] != 0.f || t > tb) continue;                     // a known frame between two gaps is in `base`
-      const int nn = p - t * hop;
-      const float2* sp = Cs + (size_t)(t - ta) * F;
-      num += hann_tw(tw, nn) * idft_sample(tw, N, nn, [&](int k) { return sp[k]; });
-    }
-    x = (float)(num / d);
-  }
+  if (d != 0.0)                                                // a known frame between two gaps is in `base`
+    x = gl_synth_sample(
+        tw, N, hop, p, t0, t1, bs[ii], d, [&](int t) { return m[t] == 0.f && t <= tb; },
+        [&](int t) { return Cs + (size_t)(t - ta) * F; });
   w.x[bv * q.Pmax + i] = x;
 }
 
@@ -282,43 +242,12 @@ __global__ __launch_bounds__(GL_T) void gl_long_analysis_kernel(const float* __r
     const int j0 = live[pr], j1 = pr + 1 < nlive ? live[pr + 1] : j0;
     const int f0 = flag[j0], f1 = pr + 1 < nlive ? flag[j1] : 0;
     const float* x0 = xs + (size_t)(qq / F - pr_a) * 2 * N;
-    const float* x1 = x0 + N;
-    double r0 = 0.0, i0 = 0.0, r1 = 0.0, i1 = 0.0;
-    int idx = 0;
-    for (int nn = 0; nn < N; ++nn) {
-      const double2 wt = tw[idx];
-      const double hw = hann_tw(tw, nn);
-      const double a0 = hw * (double)x0[nn], a1 = hw * (double)x1[nn];
-      r0 += a0 * wt.x;
-      i0 -= a0 * wt.y;
-      r1 += a1 * wt.x;
-      i1 -= a1 * wt.y;
-      idx += k;
-      if (idx >= N) idx -= N;
-    }
+    const GlBinPair R = gl_dft_pair(tw, N, k, x0, x0 + N);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int f = h ? f1 : f0, t = s_lo + (h ? j1 : j0);
-      const double rr = h ? r1 : r0, ri = h ? i1 : i0;
-      if (f == 1) {
-        const int s = (t - t_lo) * F + k;
-        const double mg = (double)M[s];
-        const double e = sqrt(rr * rr + ri * ri) - mg;
-        dacc += e * e;
-        double ar = rr, ai = ri;
-        if (g.mom) {
-          const float2 pv = P[s];
-          ar -= g.c * (double)pv.x;
-          ai -= g.c * (double)pv.y;
-          P[s] = make_float2((float)rr, (float)ri);
-        }
-        const double sc = mg / (sqrt(ar * ar + ai * ai) + 1e-16);
-        C[s] = make_float2((float)(ar * sc), (float)(ai * sc));
-      } else if (f == 2) {
-        const size_t o = (size_t)k * g.T + t;
-        const double er = rr - (double)kre[o], ei = ri - (double)kim[o];
-        dacc += er * er + ei * ei;
-      }
+      const int t = s_lo + (h ? j1 : j0);
+      dacc = gl_project(dacc, h ? f1 : f0, h ? R.r1 : R.r0, h ? R.i1 : R.i0, (t - t_lo) * F + k, (size_t)k * g.T + t, C, P, M, kre,
+                        kim, g.mom, g.c);
     }
   }
   dacc = block_sum_waves<GL_WAVES>(dacc, red);
@@ -430,9 +359,8 @@ int nppc_gl_gap_long(const float* target_mag, const float* known_spec, const flo
                      int phase_per_variation, float* out, double* dist, double* target_norm, int* status, void* work,
                      long work_bytes, int B, int V, int T, int nfft, int hop, int L, int n_iter, double momentum, int max_span,
                      int long_max_span, int mode, void* stream) {
-  if (!target_mag) return NPPC_EBADARG;
-  GlMag ms = {};
-  ms.target = target_mag;
+  GlMag ms;
+  if (gl_mag_target(target_mag, &ms) != NPPC_OK) return NPPC_EBADARG;
   return gl_long_run(ms, known_spec, mask, init_phase, phase_per_variation != 0, out, dist, target_norm, status, work, work_bytes,
                      B, V, T, nfft, hop, L, n_iter, momentum, max_span, long_max_span, mode, stream);
 }
@@ -441,9 +369,8 @@ int nppc_gl_gap_pc_long(const float* pred, const float* pc, const float* mean, c
                         const float* known_spec, const float* mask, const float* init_phase, float* out, double* dist,
                         double* target_norm, int* status, void* work, long work_bytes, int B, int K, int A, int T, int nfft,
                         int hop, int L, int n_iter, double momentum, int max_span, int long_max_span, int mode, void* stream) {
-  if (!pred || !pc || !mean || !stdev || !alphas || K <= 0 || A <= 0 || (long)K * A + 1 > 65535) return NPPC_EBADARG;
-  GlMag ms = {};
-  ms.pred = pred, ms.pc = pc, ms.mean = mean, ms.stdev = stdev, ms.alphas = alphas, ms.K = K, ms.A = A;
+  GlMag ms;
+  if (gl_mag_pc(pred, pc, mean, stdev, alphas, K, A, &ms) != NPPC_OK) return NPPC_EBADARG;
   return gl_long_run(ms, known_spec, mask, init_phase, 0, out, dist, target_norm, status, work, work_bytes, B, K * A + 1, T, nfft,
                      hop, L, n_iter, momentum, max_span, long_max_span, mode, stream);
 }

@@ -1,146 +1,15 @@
 // Ragged (variable-length) inference of the FullSubNet+ restorer (n_maps = 1): a padded batch [B][Lmax] whose item b
 // is L_b samples / T_b = 1 + L_b / hop frames long.  Each kernel here is the per-item form of a uniform kernel
-// (spec.hip, tcn.hip, subband.hip, frontend.hip's cIRM MSE): it reads an item's own length from a device int[B] and
-// computes exactly what the uniform kernel computes for that item run alone.  (The ragged STFT and iSTFT are the
-// RAGGED instantiations of frontend.hip's own kernels.)  Padding past an item's end is never read, and
+// (tcn.hip, subband.hip, frontend.hip's cIRM MSE) whose work decomposition differs from its twin's: it reads an item's
+// own length from a device int[B] and computes exactly what the uniform kernel computes for that item run alone.  (The
+// ragged STFT / iSTFT and the ragged TSSE front are the RAGGED instantiations of frontend.hip's and spec.hip's own
+// kernels.)  Padding past an item's end is never read, and
 // what these kernels write past it is zero.  No float atomics: every sum has one writer and a fixed order.
 // The uniform GEMMs, the staging and the LSTM run at the batch's longest length.
 #include "common.h"
 #include "nppc_hip.h"
 
 namespace {
-
-// ---------------------------------------------------------------- TSSE front (spec.hip, inference form, per-item frames)
-struct MapSet { const float* x[6]; };
-
-struct TsseW {
-  const float* cw[3];
-  const float* cb[3];
-  int ks[3];
-  const float* fcw;
-  const float* fcb;
-  const float* w1;
-  const float* b1;
-  const float* w2;
-  const float* b2;
-};
-
-constexpr int TSSE_MAXC = 1024;
-
-// sums[j][b][c] = sum_{t < T_b} x_j[b][c][t]  (map rows of stride T = the padded frame count)
-__global__ __launch_bounds__(256) void rowsum_ragged_kernel(MapSet ms, double* __restrict__ sums, const int* __restrict__ frames,
-                                                            int B, int C, int T) {
-  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= (long)B * C) return;
-  const int lane = threadIdx.x & 63;
-  const int Tb = clampi(frames[r / C], 1, T);
-  const float* p = ms.x[blockIdx.y] + (size_t)r * T;
-  double s = 0.0;
-  for (int t = lane; t < Tb; t += 64) s += (double)p[t];
-  s = wave_sum(s);
-  if (lane == 0) sums[(size_t)blockIdx.y * B * C + r] = s;
-}
-
-// tsse_fwd_kernel of spec.hip without the saved tensors, item b over its own T_b frames (+ la look-ahead zeros)
-__global__ __launch_bounds__(1024) void tsse_fwd_ragged_kernel(MapSet ms, const double* __restrict__ rowsum, TsseW w, long sW,
-                                                               int nm, float* __restrict__ scale, const int* __restrict__ frames,
-                                                               int C, int C2, int T, int la) {
-  __shared__ double red[16];
-  __shared__ float sq[TSSE_MAXC];
-  __shared__ float h1[TSSE_MAXC / 2];
-  __shared__ float ns_s;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  {
-    const int j = blockIdx.y, z = j % 3, m = j / 3, B = gridDim.x;
-    for (int i = 0; i < 3; ++i) { w.cw[i] += (long)z * sW; w.cb[i] += (long)z * sW; }
-    w.fcw += (long)z * sW; w.fcb += (long)z * sW;
-    w.w1 += (long)z * sW; w.b1 += (long)z * sW;
-    w.w2 += (long)z * sW; w.b2 += (long)z * sW;
-    rowsum += (size_t)j * B * C;
-    scale += ((size_t)z * nm + m) * B * C;
-  }
-  const float* __restrict__ x = ms.x[blockIdx.y];
-  const int Tn = clampi(frames[b], 1, T);
-  const int Tp = Tn + la;
-  double part = 0.0;
-  for (int c = tid; c < C; c += blockDim.x) part += rowsum[(size_t)b * C + c];
-  part = wave_sum(part);
-  if ((tid & 63) == 0) red[tid >> 6] = part;
-  __syncthreads();
-  if (tid == 0) {
-    double tot_all = 0.0;
-    for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) tot_all += red[wv];
-    const float mu = (float)(tot_all / ((double)C * Tp));
-    ns_s = 1.0f / (mu + 1e-5f);
-  }
-  __syncthreads();
-  const float ns = ns_s;
-  for (int c = tid; c < C; c += blockDim.x) {
-    const float* xr = x + ((size_t)b * C + c) * T;
-    const double tot = rowsum[(size_t)b * C + c];
-    float acc = w.fcb[0];
-    for (int i = 0; i < 3; ++i) {
-      const int ks = w.ks[i];
-      const int Lout = Tp - ks + 1;
-      double conv = 0.0;
-      for (int k = 0; k < ks; ++k) {
-        double pre = 0.0, suf = 0.0;
-        for (int t = 0; t < k; ++t) pre += (t < Tn) ? (double)xr[t] : 0.0;
-        for (int m = 0; m < ks - 1 - k; ++m) {
-          const int t = Tp - 1 - m;
-          suf += (t < Tn && t >= 0) ? (double)xr[t] : 0.0;
-        }
-        conv += (double)w.cw[i][c * ks + k] * (tot - pre - suf);
-      }
-      const float pv = w.cb[i][c] + ns * (float)(conv / Lout);
-      acc += w.fcw[i] * fmaxf(pv, 0.f);
-    }
-    sq[c] = acc;
-  }
-  __syncthreads();
-  for (int j = tid; j < C2; j += blockDim.x) {
-    float a = w.b1[j];
-    const float* wr = w.w1 + (size_t)j * C;
-    for (int c = 0; c < C; ++c) a += wr[c] * sq[c];
-    h1[j] = fmaxf(a, 0.f);
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += blockDim.x) {
-    float a = w.b2[c];
-    const float* wr = w.w2 + (size_t)c * C2;
-    for (int j = 0; j < C2; ++j) a += wr[j] * h1[j];
-    const float sg = 1.0f / (1.0f + expf(-a));
-    scale[(size_t)b * C + c] = ns * sg;
-  }
-}
-
-// y[z][b][t][m*C + c] = x_j[b][c][t] * scale[z][m][b][c] for t < T_b, 0 for T_b <= t < Tp: EVERY row of the buffer is
-// written (it is reused across calls of other lengths)
-template <typename TT>
-__global__ __launch_bounds__(256) void scale_transpose_ragged_kernel(MapSet ms, const float* __restrict__ scale,
-                                                                     TT* __restrict__ y, const int* __restrict__ frames, int B,
-                                                                     int nm, long sY, int C, int Tn, int Tp, int ld) {
-  __shared__ float tile[32][33];
-  const int j = blockIdx.z / B, b = blockIdx.z % B, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
-  const float* __restrict__ x = ms.x[j];
-  const int z = j % 3, m = j / 3;
-  scale += ((size_t)z * nm + m) * B * C;
-  y += (size_t)z * sY;
-  const int coff = m * C;
-  const int Tb = clampi(frames[b], 1, Tn);
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int i = ty; i < 32; i += 8) {
-    const int c = c0 + i, t = t0 + tx;
-    float v = 0.f;
-    if (c < C && t < Tb) v = x[((size_t)b * C + c) * Tn + t] * scale[(size_t)b * C + c];
-    tile[i][tx] = v;
-  }
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8) {
-    const int t = t0 + i, c = c0 + tx;
-    if (t < Tp && c < C) y[((size_t)b * Tp + t) * ld + coff + c] = from_f32<TT>(tile[tx][i]);
-  }
-}
 
 // ---------------------------------------------------------------- TCN depthwise stage (tcn.hip: dwconv_kernel)
 // The depthwise conv is CENTRED (padding = dilation): frame t reads t + dil, so the frames of a longer item would leak
@@ -311,38 +180,6 @@ __global__ __launch_bounds__(1024) void crm_mse_ragged_kernel(const float* __res
 }  // namespace
 
 extern "C" {
-
-int nppc_tsse_fwd_maps_ragged(int prec, const float* const* maps, int nmaps, double* rowsum, const float* cw0, const float* cb0,
-                              const float* cw1, const float* cb1, const float* cw2, const float* cb2, int ks0, int ks1, int ks2,
-                              const float* fcw, const float* fcb, const float* w1, const float* b1, const float* w2,
-                              const float* b2, long sW, float* scale, void* X0, long sY, const int* frames, int B, int C, int T,
-                              int look_ahead, int Tp, int ld, void* stream) {
-  if (!maps || !rowsum || !scale || !X0 || !frames || B <= 0 || C <= 0 || C > TSSE_MAXC || (nmaps != 3 && nmaps != 6))
-    return NPPC_EBADARG;
-  if (!cw0 || !cb0 || !cw1 || !cb1 || !cw2 || !cb2 || !fcw || !fcb || !w1 || !b1 || !w2 || !b2) return NPPC_EBADARG;
-  if (ks0 > T || ks1 > T || ks2 > T) return NPPC_EUNSUPPORTED;
-  const int nm = nmaps / 3;
-  if (nm * C > ld || T > Tp) return NPPC_EBADARG;
-  hipStream_t s = (hipStream_t)stream;
-  MapSet ms{};
-  for (int j = 0; j < nmaps; ++j) { if (!maps[j]) return NPPC_EBADARG; ms.x[j] = maps[j]; }
-  hipLaunchKernelGGL(rowsum_ragged_kernel, dim3(ceil_div((long)B * C, 4), nmaps), dim3(256), 0, s, ms, rowsum, frames, B, C, T);
-  TsseW w{{cw0, cw1, cw2}, {cb0, cb1, cb2}, {ks0, ks1, ks2}, fcw, fcb, w1, b1, w2, b2};
-  const int nt = round_up(C, 64) > 1024 ? 1024 : round_up(C, 64);
-  hipLaunchKernelGGL(tsse_fwd_ragged_kernel, dim3(B, nmaps), dim3(nt), 0, s, ms, rowsum, w, sW, nm, scale, frames, C, C / 2, T,
-                     look_ahead);
-  dim3 grid(ceil_div(Tp, 32), ceil_div(C, 32), B * nmaps);
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(scale_transpose_ragged_kernel<bf16_t>, grid, dim3(256), 0, s, ms, scale, (bf16_t*)X0, frames, B, nm, sY, C,
-                       T, Tp, ld);
-  else if (prec == NPPC_PREC_F32)
-    hipLaunchKernelGGL(scale_transpose_ragged_kernel<float>, grid, dim3(256), 0, s, ms, scale, (float*)X0, frames, B, nm, sY, C, T,
-                       Tp, ld);
-  else
-    return NPPC_EBADARG;
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
-}
 
 int nppc_tcn_dwconv_ragged(int prec, const void* in, void* out, const double* st1, const float* gamma, const float* beta,
                            const float* wd, const float* bd, const float* slope2, const int* frames, int la, int B, int Cc, int ld,

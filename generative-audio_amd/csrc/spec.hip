@@ -1,5 +1,7 @@
 // Full-band front: offline laplace norm (per-sample mean), TSSE channel attention, and the
 // scale + transpose into the time-major activation layout the TCN GEMMs consume.
+// RAGGED instantiations (nppc_tsse_fwd_maps_ragged): item b is T_b = frames[b] frames long in maps whose
+// rows keep the padded stride T, and gets exactly what the uniform kernels compute for that item run alone.
 // Reference: audio_zen/model/base_model.py:210-224 (offline_laplace_norm),
 //            audio_zen/model/module/attention_model.py:43-98 (ChannelTimeSenseSELayer),
 //            fullsubnet_plus.py:158-185 / nppc_audio/networks.py:80-112 (pad look_ahead, norm, attention, concat).
@@ -10,17 +12,21 @@ namespace {
 
 // one wave per row: sums[r] = sum_t x[r][t]   (fp64 accumulate: the real/imag maps have |mean| << |x|)
 // blockIdx.y = map j of a set of equally shaped maps (the 3 or 6 input maps of a net: one launch for all of them)
+// RAGGED: row r of R = B C rows belongs to item r / C and is summed over its first T_b frames
 struct MapSet { const float* x[6]; };
 
-__global__ __launch_bounds__(256) void rowsum_kernel(MapSet ms, double* __restrict__ sums, long R, int T) {
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void rowsum_kernel(MapSet ms, double* __restrict__ sums, const int* __restrict__ frames, long R,
+                                                     int C, int T) {
   const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   const int lane = threadIdx.x & 63;
+  const int Tb = RAGGED ? clampi(frames[r / C], 1, T) : T;
   const float* x = ms.x[blockIdx.y];
   sums += (size_t)blockIdx.y * R;
   const float* p = x + (size_t)r * T;
   double s = 0.0;
-  for (int t = lane; t < T; t += 64) s += (double)p[t];
+  for (int t = lane; t < Tb; t += 64) s += (double)p[t];
   s = wave_sum(s);
   if (lane == 0) sums[r] = s;
 }
@@ -39,7 +45,8 @@ struct TsseW {
 
 // One workgroup per sample.  x [B][C][T] is the UNPADDED map; the padded length is Tp = T + la (zeros).
 // mean_t(conv_ks(norm x))[c] = bias + ns/(Tp-ks+1) * sum_k w[c][k] * (rowsum - prefix(k) - suffix(ks-1-k)).
-// Outputs: scale[b][c] = ns_b * s[b][c];  saved for backward: ns[B], pre[B][C][3], sq[B][C], h1[B][C2], sg[B][C].
+// Outputs: scale[b][c] = ns_b * s[b][c];  saved for backward (each nullable): ns[B], pre[B][C][3], sq[B][C], h1[B][C2], sg[B][C].
+// RAGGED: item b over its own T_b frames (+ la look-ahead zeros) of rows of stride T.
 constexpr int TSSE_MAXC = 1024;
 // blockDim = C rounded up to 64 (<= 1024): with 256 threads a C = 257 map took two trips through every per-channel loop,
 // the second for ONE channel
@@ -53,11 +60,12 @@ __device__ __forceinline__ TsseW tsse_branch(TsseW w, long off) {
   return w;
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(1024) void tsse_fwd_kernel(MapSet ms, const double* __restrict__ rowsum,
                                                        TsseW w, long sW, int nm, float* __restrict__ scale, float* __restrict__ ns_out,
                                                        float* __restrict__ pre_out, float* __restrict__ sq_out,
-                                                       float* __restrict__ h1_out, float* __restrict__ sg_out, int C, int C2,
-                                                       int T, int la) {
+                                                       float* __restrict__ h1_out, float* __restrict__ sg_out,
+                                                       const int* __restrict__ frames, int C, int C2, int T, int la) {
   __shared__ double red[16];
   __shared__ float sq[TSSE_MAXC];
   __shared__ float h1[TSSE_MAXC / 2];
@@ -76,7 +84,8 @@ __global__ __launch_bounds__(1024) void tsse_fwd_kernel(MapSet ms, const double*
     if (sg_out) sg_out += slot * B * C;
   }
   const float* __restrict__ x = ms.x[blockIdx.y];
-  const int Tp = T + la;
+  const int Tn = RAGGED ? clampi(frames[b], 1, T) : T;
+  const int Tp = Tn + la;
   double part = 0.0;
   for (int c = tid; c < C; c += blockDim.x) part += rowsum[(size_t)b * C + c];
   part = wave_sum(part);
@@ -101,10 +110,10 @@ __global__ __launch_bounds__(1024) void tsse_fwd_kernel(MapSet ms, const double*
       double conv = 0.0;
       for (int k = 0; k < ks; ++k) {
         double pre = 0.0, suf = 0.0;
-        for (int t = 0; t < k; ++t) pre += (t < T) ? (double)xr[t] : 0.0;
+        for (int t = 0; t < k; ++t) pre += (t < Tn) ? (double)xr[t] : 0.0;
         for (int m = 0; m < ks - 1 - k; ++m) {
           const int t = Tp - 1 - m;
-          suf += (t < T && t >= 0) ? (double)xr[t] : 0.0;
+          suf += (t < Tn && t >= 0) ? (double)xr[t] : 0.0;
         }
         conv += (double)w.cw[i][c * ks + k] * (tot - pre - suf);
       }
@@ -136,12 +145,13 @@ __global__ __launch_bounds__(1024) void tsse_fwd_kernel(MapSet ms, const double*
 }
 
 // y[b][t][coff + c] = x[b][c][t] * scale[b][c]   for t < T  (rows T..Tp-1 and pad columns stay as the caller left them: zero)
+// RAGGED: t < T_b, and 0 for T_b <= t < Tp: EVERY row of the buffer is written (it is reused across calls of other lengths)
 // batched over the maps of a net: blockIdx.z = b + B * j, j = m*3 + z: source map j, scale [3][nm][B][C], destination
 // branch z (stride sY elements) at column offset m * C
-template <typename T>
+template <typename T, bool RAGGED>
 __global__ __launch_bounds__(256) void scale_transpose_kernel(MapSet ms, const float* __restrict__ scale,
-                                                              T* __restrict__ y, int B, int nm, long sY, int C, int Tn, int Tp,
-                                                              int ld, int coff) {
+                                                              T* __restrict__ y, const int* __restrict__ frames, int B, int nm,
+                                                              long sY, int C, int Tn, int Tp, int ld, int coff) {
   __shared__ float tile[32][33];
   const int j = blockIdx.z / B, b = blockIdx.z % B, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
   const float* __restrict__ x = ms.x[j];
@@ -151,11 +161,13 @@ __global__ __launch_bounds__(256) void scale_transpose_kernel(MapSet ms, const f
     y += (size_t)z * sY;
     coff += m * C;
   }
+  const int Tb = RAGGED ? clampi(frames[b], 1, Tn) : Tn;   // frames read
+  const int Tw = RAGGED ? Tp : Tn;                         // rows written
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
   for (int i = ty; i < 32; i += 8) {
     const int c = c0 + i, t = t0 + tx;
     float v = 0.f;
-    if (c < C && t < Tn) {
+    if (c < C && t < Tb) {
       v = x[((size_t)b * C + c) * Tn + t];
       if (scale) v *= scale[(size_t)b * C + c];
     }
@@ -164,7 +176,7 @@ __global__ __launch_bounds__(256) void scale_transpose_kernel(MapSet ms, const f
   __syncthreads();
   for (int i = ty; i < 32; i += 8) {
     const int t = t0 + i, c = c0 + tx;
-    if (t < Tn && c < C) y[((size_t)b * Tp + t) * ld + coff + c] = from_f32<T>(tile[tx][i]);
+    if (t < Tw && c < C) y[((size_t)b * Tp + t) * ld + coff + c] = from_f32<T>(tile[tx][i]);
   }
 }
 
@@ -393,6 +405,37 @@ __global__ __launch_bounds__(256) void tsse_bwd_outer_kernel(const float* __rest
   *dst = acc;
 }
 
+// the three launches of nppc_tsse_fwd_maps / nppc_tsse_fwd_maps_ragged (RAGGED: frames is a device int[B], the grid of the
+// transpose covers all Tp rows)
+template <bool RAGGED>
+int tsse_fwd_maps(int prec, const float* const* maps, int nmaps, double* rowsum, const TsseW& w, long sW, float* scale, float* ns,
+                  float* pre, float* sq, float* h1, float* sg, void* X0, long sY, const int* frames, int B, int C, int T,
+                  int look_ahead, int Tp, int ld, void* stream) {
+  if (!maps || !rowsum || !scale || !X0 || B <= 0 || C <= 0 || C > TSSE_MAXC || (nmaps != 3 && nmaps != 6)) return NPPC_EBADARG;
+  if (w.ks[0] > T || w.ks[1] > T || w.ks[2] > T) return NPPC_EUNSUPPORTED;
+  const int nm = nmaps / 3;
+  if (nm * C > ld || T > Tp) return NPPC_EBADARG;
+  hipStream_t s = (hipStream_t)stream;
+  MapSet ms{};
+  for (int j = 0; j < nmaps; ++j) { if (!maps[j]) return NPPC_EBADARG; ms.x[j] = maps[j]; }
+  hipLaunchKernelGGL(rowsum_kernel<RAGGED>, dim3(ceil_div((long)B * C, 4), nmaps), dim3(256), 0, s, ms, rowsum, frames,
+                     (long)B * C, C, T);
+  const int nt = round_up(C, 64) > 1024 ? 1024 : round_up(C, 64);
+  hipLaunchKernelGGL(tsse_fwd_kernel<RAGGED>, dim3(B, nmaps), dim3(nt), 0, s, ms, rowsum, w, sW, nm, scale, ns, pre, sq, h1, sg,
+                     frames, C, C / 2, T, look_ahead);
+  dim3 grid(ceil_div(RAGGED ? Tp : T, 32), ceil_div(C, 32), B * nmaps);
+  if (prec == NPPC_PREC_BF16)
+    hipLaunchKernelGGL((scale_transpose_kernel<bf16_t, RAGGED>), grid, dim3(256), 0, s, ms, scale, (bf16_t*)X0, frames, B, nm, sY, C,
+                       T, Tp, ld, 0);
+  else if (prec == NPPC_PREC_F32)
+    hipLaunchKernelGGL((scale_transpose_kernel<float, RAGGED>), grid, dim3(256), 0, s, ms, scale, (float*)X0, frames, B, nm, sY, C, T,
+                       Tp, ld, 0);
+  else
+    return NPPC_EBADARG;
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -437,29 +480,23 @@ int nppc_tsse_fwd_maps(int prec, const float* const* maps, int nmaps, double* ro
                        const float* fcw, const float* fcb, const float* w1, const float* b1, const float* w2, const float* b2, long sW,
                        float* scale, float* ns, float* pre, float* sq, float* h1, float* sg, void* X0, long sY, int B, int C, int T,
                        int look_ahead, int Tp, int ld, void* stream) {
-  if (!maps || !rowsum || !scale || !X0 || B <= 0 || C <= 0 || C > TSSE_MAXC || (nmaps != 3 && nmaps != 6)) return NPPC_EBADARG;
-  if (ks0 > T || ks1 > T || ks2 > T) return NPPC_EUNSUPPORTED;
-  const int nm = nmaps / 3;
-  if (nm * C > ld || T > Tp) return NPPC_EBADARG;
-  hipStream_t s = (hipStream_t)stream;
-  MapSet ms{};
-  for (int j = 0; j < nmaps; ++j) { if (!maps[j]) return NPPC_EBADARG; ms.x[j] = maps[j]; }
-  hipLaunchKernelGGL(rowsum_kernel, dim3(ceil_div((long)B * C, 4), nmaps), dim3(256), 0, s, ms, rowsum, (long)B * C, T);
-  TsseW w{{cw0, cw1, cw2}, {cb0, cb1, cb2}, {ks0, ks1, ks2}, fcw, fcb, w1, b1, w2, b2};
-  const int nt = round_up(C, 64) > 1024 ? 1024 : round_up(C, 64);
-  hipLaunchKernelGGL(tsse_fwd_kernel, dim3(B, nmaps), dim3(nt), 0, s, ms, rowsum, w, sW, nm, scale, ns, pre, sq, h1, sg, C, C / 2, T,
-                     look_ahead);
-  dim3 grid(ceil_div(T, 32), ceil_div(C, 32), B * nmaps);
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(scale_transpose_kernel<bf16_t>, grid, dim3(256), 0, s, ms, scale, (bf16_t*)X0, B, nm, sY, C, T, Tp, ld, 0);
-  else if (prec == NPPC_PREC_F32)
-    hipLaunchKernelGGL(scale_transpose_kernel<float>, grid, dim3(256), 0, s, ms, scale, (float*)X0, B, nm, sY, C, T, Tp, ld, 0);
-  else
-    return NPPC_EBADARG;
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  const TsseW w{{cw0, cw1, cw2}, {cb0, cb1, cb2}, {ks0, ks1, ks2}, fcw, fcb, w1, b1, w2, b2};
+  return tsse_fwd_maps<false>(prec, maps, nmaps, rowsum, w, sW, scale, ns, pre, sq, h1, sg, X0, sY, nullptr, B, C, T, look_ahead,
+                              Tp, ld, stream);
 }
 
+/* the same for a padded batch whose item b is frames[b] (device int[B]) frames long: inference form, no saved tensors; every
+ * row t < Tp of X0 is written, zeros past the item's end */
+int nppc_tsse_fwd_maps_ragged(int prec, const float* const* maps, int nmaps, double* rowsum, const float* cw0, const float* cb0,
+                              const float* cw1, const float* cb1, const float* cw2, const float* cb2, int ks0, int ks1, int ks2,
+                              const float* fcw, const float* fcb, const float* w1, const float* b1, const float* w2,
+                              const float* b2, long sW, float* scale, void* X0, long sY, const int* frames, int B, int C, int T,
+                              int look_ahead, int Tp, int ld, void* stream) {
+  if (!frames || !cw0 || !cb0 || !cw1 || !cb1 || !cw2 || !cb2 || !fcw || !fcb || !w1 || !b1 || !w2 || !b2) return NPPC_EBADARG;
+  const TsseW w{{cw0, cw1, cw2}, {cb0, cb1, cb2}, {ks0, ks1, ks2}, fcw, fcb, w1, b1, w2, b2};
+  return tsse_fwd_maps<true>(prec, maps, nmaps, rowsum, w, sW, scale, nullptr, nullptr, nullptr, nullptr, nullptr, X0, sY, frames,
+                             B, C, T, look_ahead, Tp, ld, stream);
+}
 
 int nppc_tsse_bwd(int prec, const void* dX0, const float* x, const double* rowsum, const float* cw0, const float* cw1,
                   const float* cw2, int ks0, int ks1, int ks2, const float* fcw, const float* w1, const float* w2,
@@ -501,7 +538,7 @@ int nppc_rowsum(const float* x, double* sums, long R, int T, void* stream) {
   if (!x || !sums || R <= 0 || T <= 0) return NPPC_EBADARG;
   MapSet ms{};
   ms.x[0] = x;
-  hipLaunchKernelGGL(rowsum_kernel, dim3(ceil_div(R, 4), 1), dim3(256), 0, (hipStream_t)stream, ms, sums, R, T);
+  hipLaunchKernelGGL(rowsum_kernel<false>, dim3(ceil_div(R, 4), 1), dim3(256), 0, (hipStream_t)stream, ms, sums, nullptr, R, 0, T);
   NPPC_CHECK_LAUNCH();
   return NPPC_OK;
 }
@@ -517,8 +554,8 @@ int nppc_tsse_fwd(const float* x, const double* rowsum, const float* cw0, const 
   const int nt = round_up(C, 64) > 1024 ? 1024 : round_up(C, 64);
   MapSet ms{};
   ms.x[0] = x;
-  hipLaunchKernelGGL(tsse_fwd_kernel, dim3(B, 1), dim3(nt), 0, (hipStream_t)stream, ms, rowsum, w, 0L, 1, scale, ns, pre, sq, h1, sg,
-                     C, C / 2, T, look_ahead);
+  hipLaunchKernelGGL(tsse_fwd_kernel<false>, dim3(B, 1), dim3(nt), 0, (hipStream_t)stream, ms, rowsum, w, 0L, 1, scale, ns, pre, sq, h1,
+                     sg, nullptr, C, C / 2, T, look_ahead);
   NPPC_CHECK_LAUNCH();
   return NPPC_OK;
 }
@@ -530,11 +567,11 @@ int nppc_scale_transpose(int prec, const float* x, const float* scale, void* y, 
   MapSet ms{};
   ms.x[0] = x;
   if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(scale_transpose_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, ms, scale, (bf16_t*)y, B, 1, 0L, C, T,
-                       Tp, ld, coff);
+    hipLaunchKernelGGL((scale_transpose_kernel<bf16_t, false>), grid, dim3(256), 0, (hipStream_t)stream, ms, scale, (bf16_t*)y,
+                       nullptr, B, 1, 0L, C, T, Tp, ld, coff);
   else if (prec == NPPC_PREC_F32)
-    hipLaunchKernelGGL(scale_transpose_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, ms, scale, (float*)y, B, 1, 0L, C, T, Tp,
-                       ld, coff);
+    hipLaunchKernelGGL((scale_transpose_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, ms, scale, (float*)y,
+                       nullptr, B, 1, 0L, C, T, Tp, ld, coff);
   else
     return NPPC_EBADARG;
   NPPC_CHECK_LAUNCH();

@@ -93,9 +93,10 @@ def calculate_unet_baseline(model, masked_spec, mask, n_mc_samples=50, n_compone
 
 
 # ------------------------------------------------------------------------------------------------ ragged gaps
-# The same baseline for batches whose items have DIFFERENT numbers of gap elements (csrc/mc_pca_ragged.hip, DESIGN.md
-# section 8d): the reference's dataset cuts 2048 samples at a random start, which zeroes 17 or 18 frames (fewer at the
-# ends of a clip), so its batches are rarely uniform.  Everything is padded to Nmax = the largest count of the batch.
+# The same baseline for batches whose items have DIFFERENT numbers of gap elements (csrc/mc_pca_ragged.hip and the ragged
+# PCA of csrc/mc_pca.hip): the reference's dataset cuts 2048 samples at a random start, which zeroes
+# 17 or 18 frames (fewer at the ends of a clip), so its batches are rarely uniform.  Everything is padded to Nmax = the
+# largest count of the batch.
 def _hole_counts_host(mask, B):
     return (mask.reshape(B, -1) == 0).sum(dim=1).tolist()
 

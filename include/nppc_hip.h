@@ -563,7 +563,8 @@ int nppc_bss_scale(const float* ref, const float* est, const int* lengths, int B
                    double* out, void* stream);
 
 
-/* ---- ragged inference of the FullSubNet+ restorer (csrc/ragged.hip) -----------------------------------
+/* ---- ragged inference of the FullSubNet+ restorer (csrc/ragged.hip; STFT / iSTFT in csrc/frontend.hip, TSSE front in
+ * csrc/spec.hip) ---------------------------------------------------------------------------------------
  * A padded batch: item b is L_b = lengths[b] samples (device int[B]) and T_b = 1 + L_b / hop frames; frames[b] (device
  * int[B]) = T_b.  Item b's results equal the uniform entry point's for that item alone; nothing past an item's end is
  * read, and what is written past it is 0.  No float atomics (bit-identical on repeat).
@@ -742,7 +743,7 @@ int nppc_gl_gap_pc_long(const float* pred, const float* pc, const float* mean, c
                         double* target_norm, int* status, void* work, long work_bytes, int B, int K, int A, int T, int nfft,
                         int hop, int L, int n_iter, double momentum, int max_span, int long_max_span, int mode, void* stream);
 
-/* ---- ragged-gap MC-dropout + PCA baseline (csrc/mc_pca_ragged.hip; specification
+/* ---- ragged-gap MC-dropout + PCA baseline (csrc/mc_pca_ragged.hip, the PCA in csrc/mc_pca.hip; specification
  * tests/mc_ragged_ref.py): the items of a batch may have different numbers of gap (mask == 0) elements ---------------------
  * mask [B][N] (any mask, N = F T <= 2^31 - 1) -> counts [B] = gap elements per item; then, with Nmax >= max counts,
  * idx [B][Nmax] = their positions in row-major order (the order of boolean indexing and masked_scatter_), -1 past counts[b].

@@ -1,4 +1,4 @@
-"""fp64 NumPy restatement of the ragged-gap MC-dropout + PCA baseline (csrc/mc_pca_ragged.hip): the
+"""fp64 NumPy restatement of the ragged-gap MC-dropout + PCA baseline (csrc/mc_pca_ragged.hip, csrc/mc_pca.hip): the
 yardstick of tests/test_mc_ragged_cpu.py and tests/test_mc_ragged_gpu.py.  Straight loops over the items, no chunking."""
 import numpy as np
 

@@ -1,4 +1,5 @@
-"""GPU: the TSSE channel attention of the full-band front (csrc/spec.hip) against fp64 references built from the oracle.
+"""GPU: the TSSE channel attention of the full-band front (csrc/spec.hip) against fp64 references built from the oracle, and
+its ragged entry (nppc_tsse_fwd_maps_ragged, the same kernels with per-item frame counts) against the uniform one bit for bit.
 
 nppc_tsse_fwd_maps: per map, pad the look-ahead with zeros -> laplace_norm -> oracle.nppc_ref.tsse (attention_model.py:78-98),
 its scale and saved intermediates, and the scaled map transposed into the TCN input X0 [3][B][Tp][ld] (map j = m*3 + z lands
@@ -177,6 +178,65 @@ def test_tsse_forward_argument_guards():
         _, offs, sW, flat, maps = _setup(1, 1, C, T, seed=3)
         with pytest.raises(RuntimeError, match=msg):
             _launch_fwd(1, [m.cuda() for m in maps], flat.float().cuda(), 1, 1, C, T, 2, T + 2, C, sW, offs)
+
+
+def _launch_fwd_ragged(prec, maps_d, flat_d, nm, B, C, T, la, Tp, ld, sW, offs, frames):
+    """nppc_tsse_fwd_maps_ragged into NaN-filled buffers; frames: the items' frame counts (None: a null pointer)"""
+    from nppc_audio import _hip as H
+    P = lambda k: flat_d[offs[k]:]
+    rs = torch.full((3 * nm, B, C), NAN, dtype=torch.float64, device="cuda")
+    scale = torch.full((3, nm, B, C), NAN, device="cuda")
+    X0 = torch.full((3, B, Tp, ld), NAN, dtype=H.dtype_of(prec), device="cuda")
+    fr = None if frames is None else torch.tensor(frames, dtype=torch.int32, device="cuda")
+    H.call("nppc_tsse_fwd_maps_ragged", prec, H.ptr_array(maps_d), 3 * nm, rs, P("cw0"), P("cb0"), P("cw1"), P("cb1"), P("cw2"),
+           P("cb2"), *KS, P("fcw"), P("fcb"), P("w1"), P("b1"), P("w2"), P("b2"), sW, scale, X0, B * Tp * ld, fr, B, C, T, la, Tp,
+           ld, H.stream())
+    return rs, scale, X0
+
+
+# (prec, nm, B, C, T, la, frames): 10 = the largest kernel size is the shortest legal item; C at the 64-thread rounding (2, 65)
+# and at TSSE_MAXC
+RAGGED_CASES = [
+    (0, 2, 3, 65, 70, 2, [70, 10, 37]),
+    (1, 2, 3, 65, 70, 2, [70, 10, 37]),
+    (1, 1, 3, 2, 11, 0, [11, 10, 10]),
+    (0, 1, 3, 1024, 12, 2, [12, 10, 11]),
+]
+
+
+@pytest.mark.parametrize("prec,nm,B,C,T,la,frames", RAGGED_CASES)
+def test_tsse_forward_ragged_is_the_uniform_entry_per_item(prec, nm, B, C, T, la, frames):
+    """The ragged entry (the RAGGED instantiations of the uniform kernels) against the uniform entry, bit for bit: with every
+    item full length it is the uniform call; item b of a ragged batch is the uniform call on that item alone with its maps
+    cropped to T_b frames; X0 rows T_b <= t < Tp are written as zero."""
+    _, offs, sW, flat, maps = _setup(nm, B, C, T, seed=C + T + la)
+    Tp, ld, W = T + la + 3, nm * C + 5, nm * C
+    maps_d = [m.cuda() for m in maps]
+    flat_d = flat.float().cuda()
+    # 1: all frames = T
+    rs_u, scale_u, _, X0_u = _launch_fwd(prec, maps_d, flat_d, nm, B, C, T, la, Tp, ld, sW, offs)
+    rs_f, scale_f, X0_f = _launch_fwd_ragged(prec, maps_d, flat_d, nm, B, C, T, la, Tp, ld, sW, offs, [T] * B)
+    assert torch.equal(rs_f, rs_u) and torch.equal(scale_f, scale_u)
+    assert torch.equal(X0_f[:, :, :T, :W], X0_u[:, :, :T, :W]) and not bool(X0_u[:, :, :T, :W].isnan().any())
+    assert float(X0_f[:, :, T:, :W].float().abs().max()) == 0.0
+    # 2, 3: a ragged batch, item by item
+    rs, scale, X0 = _launch_fwd_ragged(prec, maps_d, flat_d, nm, B, C, T, la, Tp, ld, sW, offs, frames)
+    assert bool(X0[..., W:].isnan().all())                              # the pad columns are the caller's
+    for b, Tb in enumerate(frames):
+        alone = [m[b:b + 1, :, :Tb].contiguous() for m in maps_d]
+        rs_a, scale_a, _, X0_a = _launch_fwd(prec, alone, flat_d, nm, 1, C, Tb, la, Tp, ld, sW, offs)
+        assert torch.equal(rs[:, b], rs_a[:, 0]), b
+        assert torch.equal(scale[:, :, b], scale_a[:, :, 0]), b
+        assert torch.equal(X0[:, b, :Tb, :W], X0_a[:, 0, :Tb, :W]) and not bool(X0_a[:, 0, :Tb, :W].isnan().any()), b
+        assert bool((X0[:, b, Tb:, :W] == 0).all()), b
+
+
+def test_tsse_forward_ragged_argument_guards():
+    """the uniform entry's guards, and a null frames pointer"""
+    for C, T, frames, msg in ((33, 9, [9], "unsupported"), (1025, 11, [11], "bad argument"), (33, 11, None, "bad argument")):
+        _, offs, sW, flat, maps = _setup(1, 1, C, T, seed=3)
+        with pytest.raises(RuntimeError, match=msg):
+            _launch_fwd_ragged(1, [m.cuda() for m in maps], flat.float().cuda(), 1, 1, C, T, 2, T + 2, C, sW, offs, frames)
 
 
 @pytest.mark.parametrize("prec,nm,B,C,T,la", ATT_CASES)

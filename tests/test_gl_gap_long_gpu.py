@@ -103,19 +103,19 @@ def test_long_spans_against_the_restatement(i, n_iter, mu, record_err):
 @pytest.mark.parametrize("i", range(len(R.CASES)), ids=IDS)
 def test_tiled_path_gives_the_resident_path_its_bits(i):
     z = short_case(i)
-    mu = 0.99 if i % 2 else 0.0
-    w0, i0 = device_run(z, 4, mu)
-    w1, i1 = device_run(z, 4, mu, long_spans="always")
-    assert i0["status"].cpu().tolist() == [0] * B and i1["status"].cpu().tolist() == [0] * B
-    diff = (w0 != w1)
-    assert torch.equal(w0, w1), (int(diff.sum()), float((w0 - w1).abs().max()))
-    # folded across workgroups in another order: fewer than 2^17 non-negative fp64 terms, reordering error <= about 1.5e-11
-    for k in ("inconsistency", "target_norm"):
-        rel = float(((i0[k] - i1[k]).abs() / i0[k]).max())
-        print(f"{IDS[i]} {k}: tiled vs resident {rel:.3e}")
-        assert rel <= 1e-10, (k, rel)
-    # and through the router nothing here is long: the resident kernel's own results, info included
-    assert same((w0, i0), device_run(z, 4, mu, long_spans=True))
+    for mu in (0.0, 0.99):                                        # every case through the shared momentum branch and without it
+        w0, i0 = device_run(z, 4, mu)
+        w1, i1 = device_run(z, 4, mu, long_spans="always")
+        assert i0["status"].cpu().tolist() == [0] * B and i1["status"].cpu().tolist() == [0] * B
+        diff = (w0 != w1)
+        assert torch.equal(w0, w1), (mu, int(diff.sum()), float((w0 - w1).abs().max()))
+        # folded across workgroups in another order: fewer than 2^17 non-negative fp64 terms, reordering error <= about 1.5e-11
+        for k in ("inconsistency", "target_norm"):
+            rel = float(((i0[k] - i1[k]).abs() / i0[k]).max())
+            print(f"{IDS[i]} mu {mu} {k}: tiled vs resident {rel:.3e}")
+            assert rel <= 1e-10, (mu, k, rel)
+        # and through the router nothing here is long: the resident kernel's own results, info included
+        assert same((w0, i0), device_run(z, 4, mu, long_spans=True)), mu
 
 
 # ---- 3: one batch, both paths -------------------------------------------------------------------------------------------------

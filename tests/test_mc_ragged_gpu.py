@@ -1,4 +1,4 @@
-"""GPU: the ragged-gap MC-dropout + PCA baseline (csrc/mc_pca_ragged.hip through nppc_audio.inpainting.mc_baseline) against
+"""GPU: the ragged-gap MC-dropout + PCA baseline (csrc/mc_pca_ragged.hip, csrc/mc_pca.hip through nppc_audio.inpainting.mc_baseline) against
 torch's own indexing, the fp64 restatement (tests/mc_ragged_ref.py), its bit-for-bit contract (an item in a batch == the
 item alone; two runs agree), the uniform path, and through NPPCModelValidator / NPPCAudioInpaintingTrainer.base_step2 with
 `ragged_gaps=True` on a batch of 5-, 6- and 6-frame gaps, which the uniform path refuses."""

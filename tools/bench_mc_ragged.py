@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the MC-dropout + PCA baseline of the inpainting validator on ragged-gap batches (csrc/mc_pca_ragged.hip,
+"""Times the MC-dropout + PCA baseline of the inpainting validator on ragged-gap batches (csrc/mc_pca_ragged.hip, csrc/mc_pca.hip,
 mc_baseline.calculate_unet_baseline_ragged) against the uniform path (mc_baseline.calculate_unet_baseline) at the C3 shape
 (F = 128, T = 256: a 32704-sample clip at STFT 255/128), B = 16, 50 passes, n = 5 components:
 
