@@ -287,6 +287,12 @@ SIGS = {
     "nppc_flac_stream_md5": [P, L, P, P, P],
     "nppc_flac_md5_host": [P, L, I, I, P],
     "nppc_flac_md5": [P, L, P, I, P, P, P, P, P, P],
+    "nppc_flac_enc_bound": [L, I, I, I, PL, PL],
+    "nppc_flac_encode_host": [P, L, I, I, I, I, P, L, PL],
+    "nppc_pcm_quantize": [P, L, P, I, I, P, P, L, P],
+    "nppc_flac_enc_plan": [P, L, P, I, P, L, I, I, P, P],
+    "nppc_flac_enc_scan": [P, P, L, I, P, P, P],
+    "nppc_flac_enc_write": [P, L, P, I, P, L, I, I, I, P, P, P, P, P, L, P],
     "nppc_resample_sinc_shape": [I, I, I, I, I, PI, PL, PL, PL, PI],
     "nppc_resample_sinc": [P, L, P, I, P, I, I, I, I, I, P, L, P],
 }

@@ -12,7 +12,14 @@ the field, `pcm_md5` hashes int32 PCM where it lies.
 
 No file written by libFLAC or any other encoder was available when this was built: the format is pinned by
 tests/flac_ref.py, written from the published specification; the MD5 of the first LibriSpeech file decides whether libFLAC
-reads it the same way.  Not built: 32-bit samples, streams of unknown length, ID3v2 / Ogg wrappers, any encoder.
+reads it the same way.  Not built: 32-bit samples, streams of unknown length, ID3v2 / Ogg wrappers.
+
+Encoding (csrc/flac_enc_core.h + csrc/flac_enc.hip; specification tests/flac_enc_ref.py):
+`encode_pcm` turns int32 PCM into FLAC streams, `encode_waves` quantises fp32 waveforms first, `write_files` stores them.
+Lossless, fixed predictors with exact Rice-parameter search, one stated decision rule: the bytes are a function of the
+samples alone, the same from the serial host encoder and from the device (plan, scan, MD5, write: four launches, one small
+host read and one copy of exactly the encoded bytes per batch).  Not built: LPC subframes, escape partitions, wasted bits,
+variable block sizes, seek tables and comments, more than two channels on the device.
 """
 import ctypes
 import os
@@ -243,6 +250,8 @@ def _decode_batch_device(bufs, names, infos, out, device, verify_md5=False):
 
 
 def _use_device(backend):
+    if backend == "hip":                                              # the encoder's name for the device
+        backend = "device"
     if backend not in ("auto", "device", "host"):
         raise ValueError(f"backend must be 'auto', 'device' or 'host', got {backend!r}")
     if backend == "device":
@@ -289,3 +298,186 @@ def decode_files(paths, out="mono", backend="auto", device="cuda", max_batch_byt
         used += buf.nbytes
     flush()
     return tensors, infos
+
+
+# ---- encoding --------------------------------------------------------------------------------------------------------
+ENC_BITS = (8, 12, 16, 20, 24)
+ENC_MIN_BLOCK, ENC_MAX_BLOCK = 16, 4608
+
+
+def _enc_args(bits_per_sample, sample_rate, block_size):
+    if bits_per_sample not in ENC_BITS:
+        raise ValueError(f"bits_per_sample must be one of {ENC_BITS}, got {bits_per_sample!r}")
+    if not isinstance(block_size, int) or not ENC_MIN_BLOCK <= block_size <= ENC_MAX_BLOCK:
+        raise ValueError(f"block_size must be an int in {ENC_MIN_BLOCK}..{ENC_MAX_BLOCK}, got {block_size!r}")
+    if not 1 <= int(sample_rate) < 1 << 20:
+        raise ValueError(f"sample_rate must be in 1..{(1 << 20) - 1}, got {sample_rate!r}")
+
+
+def _enc_bound(n, channels, bps, block_size):
+    nbytes, frames = ctypes.c_long(), ctypes.c_long()
+    H.call("nppc_flac_enc_bound", n, channels, bps, block_size, ctypes.byref(nbytes), ctypes.byref(frames))
+    return nbytes.value, frames.value
+
+
+def _encode_host(a, bps, rate, block_size):
+    """nppc_flac_encode_host of a C-contiguous int32 array [C, n]"""
+    cap, _ = _enc_bound(a.shape[1], a.shape[0], bps, block_size)
+    out = np.empty(cap, np.uint8)
+    nbytes = ctypes.c_long()
+    H.call("nppc_flac_encode_host", a.ctypes.data, a.shape[1], a.shape[0], bps, rate, block_size, out.ctypes.data, cap,
+           ctypes.byref(nbytes))
+    return out[:nbytes.value].tobytes()
+
+
+def _encode_host_pool(arrays, bps, rate, block_size):
+    with ThreadPoolExecutor(max_workers=max(1, min(HOST_THREADS, os.cpu_count() or 1, len(arrays) or 1))) as ex:
+        return list(ex.map(lambda a: _encode_host(a, bps, rate, block_size), arrays))   # ctypes releases the GIL
+
+
+def _encode_device(flat, channels, lengths, bps, rate, block_size):
+    """flat: int32 device tensor, the files' planar [C, n] blocks back to back -> list of bytes.  Four launches, one small
+    host read (per-file begin / end / min / max frame size, the batch's byte count, the digests), one copy of the bytes."""
+    dev = flat.device
+    nf = len(lengths)
+    channels, lengths = np.asarray(channels, np.int64), np.asarray(lengths, np.int64)
+    off = np.concatenate([[0], np.cumsum(channels * lengths)])
+    frames = -(-lengths // block_size)
+    meta = np.zeros((nf, META), np.int64)
+    meta[:, 2], meta[:, 3], meta[:, 4], meta[:, 5], meta[:, 6] = rate, channels, bps, block_size, block_size
+    meta[:, 7], meta[:, 9] = lengths, off[:-1]
+    ftab = np.empty((int(frames.sum()), 2), np.int32)
+    ftab[:, 0] = np.repeat(np.arange(nf), frames)
+    ftab[:, 1] = np.arange(len(ftab)) - np.repeat(np.cumsum(frames) - frames, frames)
+    shapes = {(int(n), int(c)) for n, c in zip(lengths, channels)}   # the shape query, once per distinct file shape
+    bound = {k: _enc_bound(k[0], k[1], bps, block_size)[0] for k in shapes}
+    cap = sum(bound[(int(n), int(c))] for n, c in zip(lengths, channels))
+    nfr = len(ftab)
+    d_meta, d_ftab = torch.from_numpy(meta).to(dev), torch.from_numpy(ftab).to(dev)
+    d_order = torch.from_numpy(_md5_order(meta[:, 3], meta[:, 4], meta[:, 7])).to(dev)
+    small = torch.empty(4 * (nf + 1) + 2 * nf, dtype=torch.int64, device=dev)
+    stats, digest = small[:4 * (nf + 1)], small[4 * (nf + 1):].view(torch.uint8)
+    verdict = torch.empty(nf, dtype=torch.int32, device=dev)
+    plan = torch.empty(nfr * 8, dtype=torch.int32, device=dev)
+    goff = torch.empty(nfr, dtype=torch.int64, device=dev)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        s = H.stream()
+        H.call("nppc_flac_enc_plan", flat, flat.numel(), d_meta, nf, d_ftab, nfr, bps, block_size, plan, s)
+        H.call("nppc_flac_enc_scan", plan, d_ftab, nfr, nf, goff, stats, s)
+        H.call("nppc_flac_md5", flat, flat.numel(), d_meta, nf, d_order, None, None, digest, verdict, s)
+        H.call("nppc_flac_enc_write", flat, flat.numel(), d_meta, nf, d_ftab, nfr, bps, rate, block_size, plan, goff, stats,
+               digest, out, cap, s)
+        host = small.cpu().numpy()[:4 * (nf + 1)].reshape(nf + 1, 4)  # the small read
+        total = int(host[nf, 0])
+        data = out[:total].cpu().numpy()                              # exactly the encoded bytes
+    return [data[int(host[f, 0]):int(host[f, 1])].tobytes() for f in range(nf)]
+
+
+def _enc_backend(backend):
+    if backend not in ("auto", "hip", "device", "host"):
+        raise ValueError(f"backend must be 'auto', 'hip' or 'host', got {backend!r}")
+    return _use_device("device" if backend == "hip" else backend)
+
+
+def encode_pcm(pcm, bits_per_sample, sample_rate=16000, block_size=4096, backend="auto", device="cuda"):
+    """int32 PCM -> FLAC streams: a list of [C, n] tensors (host or device) -> a list of bytes.  One call has one sample
+    size, rate and block size; every file has its own length and channel count.  backend "host" runs the serial encoder on
+    a pool of 16 threads (1..8 channels), "hip" the device kernels (1 or 2 channels) and "auto" the device when there is
+    one; both give the same bytes.  ValueError, before anything is launched, for an empty file, an unsupported
+    bits_per_sample or block_size, more than 2 channels on the device, or a sample outside bits_per_sample bits."""
+    _enc_args(bits_per_sample, sample_rate, block_size)
+    tensors = [pcm] if isinstance(pcm, torch.Tensor) else list(pcm)
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or not 1 <= t.shape[0] <= 8:
+            raise ValueError("encode_pcm takes int32 tensors [C, n] with 1 <= C <= 8")
+        if t.shape[1] == 0:
+            raise ValueError("encode_pcm: a file with no samples")
+    on_device = _enc_backend(backend)
+    if on_device and any(t.shape[0] > 2 for t in tensors):
+        raise ValueError("encode_pcm: the device encoder takes 1 or 2 channels")
+    if not tensors:
+        return []
+    lo, hi = -(1 << (bits_per_sample - 1)), (1 << (bits_per_sample - 1)) - 1
+    if not on_device:
+        arrays = [np.ascontiguousarray(t.cpu().numpy()) for t in tensors]
+        if any(a.min() < lo or a.max() > hi for a in arrays):
+            raise ValueError(f"encode_pcm: a sample lies outside {bits_per_sample} bits")
+        return _encode_host_pool(arrays, bits_per_sample, int(sample_rate), block_size)
+    tensors = [t if t.is_cuda else t.to(device) for t in tensors]
+    flat = tensors[0].contiguous().view(-1) if len(tensors) == 1 else torch.cat([t.reshape(-1) for t in tensors])
+    mn, mx = torch.aminmax(flat)
+    if int(mn) < lo or int(mx) > hi:
+        raise ValueError(f"encode_pcm: a sample lies outside {bits_per_sample} bits")
+    return _encode_device(flat, [t.shape[0] for t in tensors], [t.shape[1] for t in tensors], bits_per_sample, int(sample_rate),
+                          block_size)
+
+
+def quantize_waves_host(waves, bits_per_sample=16):
+    """clip(rint(x 2^(bits-1)), -2^(bits-1), 2^(bits-1) - 1) in fp32, halves to even: what nppc_pcm_quantize computes"""
+    full = np.float32(1 << (bits_per_sample - 1))
+    y = np.rint(np.asarray(waves, np.float32) * full)
+    return np.clip(np.nan_to_num(y, nan=0.0, posinf=np.inf, neginf=-np.inf), -full, full - 1).astype(np.int32)
+
+
+def encode_waves(waves, lengths=None, sample_rate=16000, bits_per_sample=16, block_size=4096, backend="auto", device="cuda"):
+    """fp32 waveforms [V, L] (or [L]) in [-1, 1) -> V mono FLAC streams of lengths[v] samples each (default L): quantised as
+    clip(rint(x 2^(bits-1))) (on the device by nppc_pcm_quantize, straight into the encoder's layout), then encoded."""
+    _enc_args(bits_per_sample, sample_rate, block_size)
+    if not isinstance(waves, torch.Tensor) or waves.dtype != torch.float32 or waves.dim() not in (1, 2):
+        raise ValueError("encode_waves takes a float32 tensor [V, L] or [L]")
+    waves = waves.reshape(-1, waves.shape[-1])
+    V, L = waves.shape
+    lens = np.full(V, L, np.int64) if lengths is None else np.asarray(torch.as_tensor(lengths).cpu(), np.int64).reshape(-1)
+    if len(lens) != V or (V and (lens.min() < 1 or lens.max() > L)):
+        raise ValueError("encode_waves: lengths must be V values in 1..L")
+    if not V:
+        return []
+    if not _enc_backend(backend):
+        q = quantize_waves_host(waves.cpu().numpy(), bits_per_sample)
+        return _encode_host_pool([np.ascontiguousarray(q[v:v + 1, :lens[v]]) for v in range(V)], bits_per_sample,
+                                 int(sample_rate), block_size)
+    waves = (waves if waves.is_cuda else waves.to(device)).contiguous()
+    off = np.concatenate([[0], np.cumsum(lens)])
+    flat = torch.empty(int(off[-1]), dtype=torch.int32, device=waves.device)
+    d_len, d_off = torch.from_numpy(lens).to(waves.device), torch.from_numpy(off[:-1].copy()).to(waves.device)
+    for v0 in range(0, V, 65535):                                     # the launch's grid limit
+        v1 = min(V, v0 + 65535)
+        with torch.cuda.device(waves.device):
+            H.call("nppc_pcm_quantize", waves[v0:v1], L, d_len[v0:v1], v1 - v0, bits_per_sample, flat, d_off[v0:v1],
+                   flat.numel(), H.stream())
+    return _encode_device(flat, np.ones(V, np.int64), lens, bits_per_sample, int(sample_rate), block_size)
+
+
+def write_files(paths, streams):
+    """streams (what encode_pcm / encode_waves return) -> files; directories are made as needed"""
+    paths = [str(p) for p in paths]
+    if len(paths) != len(streams):
+        raise ValueError(f"{len(paths)} paths for {len(streams)} streams")
+    for p, b in zip(paths, streams):
+        d = os.path.dirname(p)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with open(p, "wb") as f:
+            f.write(b)
+
+
+def write_waves(paths, waves, sample_rate=16000, fmt="flac", lengths=None, backend="auto"):
+    """fp32 waveforms [V, L] -> V 16-bit mono files: fmt "flac" (encode_waves: the whole batch in one device call) or "wav"
+    (the same samples, through scipy)"""
+    if fmt not in ("flac", "wav"):
+        raise ValueError(f"fmt must be 'flac' or 'wav', got {fmt!r}")
+    waves = waves.detach().reshape(-1, waves.shape[-1])
+    if fmt == "flac":
+        write_files(paths, encode_waves(waves.float(), lengths, sample_rate, 16, backend=backend))
+        return
+    from scipy.io import wavfile
+    paths = [str(p) for p in paths]
+    if len(paths) != waves.shape[0]:
+        raise ValueError(f"{len(paths)} paths for {waves.shape[0]} waveforms")
+    pcm = quantize_waves_host(waves.float().cpu().numpy(), 16).astype(np.int16)
+    for v, p in enumerate(paths):
+        d = os.path.dirname(p)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        wavfile.write(p, int(sample_rate), pcm[v, :None if lengths is None else int(lengths[v])])

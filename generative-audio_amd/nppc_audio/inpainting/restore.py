@@ -271,6 +271,8 @@ class RecordingRestorer:
             if c.long_gaps:
                 kw["long_spans"] = True
             out = {"windows": plan, "gain": gain}
+            if alphas is not None:
+                out["alphas"] = [float(a) for a in torch.as_tensor(alphas).reshape(-1).tolist()]
             if alphas is None:
                 pred = self.model.get_pred_spec_mag_norm(masked_norm, mask4, reuse=False)
                 waves, info = PH.griffin_lim_gap(torch.exp(pred[:, 0] * std + mean), masked, mask_f, **kw)
@@ -374,11 +376,12 @@ class RecordingRestorer:
                 return [(int(s), int(e)) for s, e in host[1:1 + 2 * n].view(-1, 2).tolist()]
             cap = n
 
-    def restore_file(self, path_in, path_out, gaps=None, verify_flac_md5=True, keep_rate=False):
-        """wav or flac -> wav: decodes with data._decode_wav, or data._decode_flac for a name ending in .flac (mono,
-        config.sample_rate), detects the gaps when none are given, restores, writes 16-bit PCM wav (there is no flac
-        encoder).  A flac file whose STREAMINFO states an MD5 is checked against it (flac.FlacError, status 9, when the
-        decoded samples differ); verify_flac_md5=False takes it as it decodes.  -> restore's dict
+    def restore_file(self, path_in, path_out, gaps=None, verify_flac_md5=True, keep_rate=False, out_format="wav"):
+        """wav or flac -> wav or flac: decodes with data._decode_wav, or data._decode_flac for a name ending in .flac (mono,
+        config.sample_rate), detects the gaps when none are given, restores, writes 16-bit PCM: out_format "wav" (the
+        default), "flac" (flac.encode_waves: the same samples, at the rate the wav would have had) or "auto" (flac when
+        path_out ends in .flac).  A flac file whose STREAMINFO states an MD5 is checked against it (flac.FlacError, status
+        9, when the decoded samples differ); verify_flac_md5=False takes it as it decodes.  -> restore's dict
         keep_rate=True: the file is decoded at ITS rate (the wav header's, flac.probe's), the gaps are detected on those
         samples -- a filter would smear the exact zeros of a dropout -- and given at that rate, restore(...,
         sample_rate=rate) keeps every sample outside the crossfaded gaps, and the wav written has the file's rate and
@@ -386,6 +389,10 @@ class RecordingRestorer:
         import numpy as np
         from scipy.io import wavfile
         from ..data import _decode_flac, _decode_wav
+        if out_format not in ("wav", "flac", "auto"):
+            raise ValueError(f"out_format = {out_format!r}: 'wav', 'flac' or 'auto'")
+        if out_format == "auto":
+            out_format = "flac" if str(path_out).lower().endswith(".flac") else "wav"
         is_flac = str(path_in).lower().endswith(".flac")
         rate = self.config.sample_rate
         if keep_rate:
@@ -403,9 +410,35 @@ class RecordingRestorer:
         if gaps is None:
             gaps = self.detect_gaps(wave)
         out = self.restore(wave, gaps, sample_rate=rate) if keep_rate else self.restore(wave, gaps)
+        if out_format == "flac":
+            from ..flac import write_waves
+            write_waves([path_out], out["restored"][None], rate, "flac")
+            return out
         pcm = np.clip(np.rint(out["restored"].detach().cpu().double().numpy() * 32768.0), -32768, 32767).astype(np.int16)
         wavfile.write(str(path_out), rate, pcm)
         return out
+
+    def save_variations(self, out, directory, fmt="flac", alphas=None):
+        """restore's dict -> <directory>/restored.<ext> and, when it holds 'variations' [K, A, L] (restore(..., alphas,
+        variations="full")), <directory>/pc_<k+1>/alpha_<a:.1f>.<ext>: 16-bit mono at the rate of the dict.  fmt "flac"
+        encodes every waveform in one device call (flac.encode_waves), "wav" writes the same samples.  alphas: the sweep,
+        when the dict does not carry it ('alphas', which restore adds).  -> the paths written"""
+        import os
+        from ..flac import write_waves
+        rate = int(out.get("sample_rate", self.config.sample_rate))
+        paths, waves = [os.path.join(str(directory), f"restored.{fmt}")], [out["restored"].reshape(1, -1)]
+        if "variations" in out:
+            var = out["variations"]
+            K, A, L = var.shape
+            alphas = out.get("alphas") if alphas is None else alphas
+            alphas = [float(a) for a in (alphas.tolist() if hasattr(alphas, "tolist") else alphas or [])]
+            if len(alphas) != A:
+                raise ValueError(f"{len(alphas)} alphas for {A} variations per direction")
+            paths += [os.path.join(str(directory), f"pc_{k + 1}", f"alpha_{a:.1f}.{fmt}") for k in range(K) for a in alphas]
+            waves.append(var.reshape(K * A, L))
+        write_waves(paths, torch.cat([w.to(self.device).float() for w in waves]) if fmt == "flac"
+                    else torch.cat([w.float().cpu() for w in waves]), rate, fmt)
+        return paths
 
 
 def _stacked(variations, restored):

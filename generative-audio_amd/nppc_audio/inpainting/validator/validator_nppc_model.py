@@ -14,7 +14,10 @@ Griffin-Lim restricted to the gap, the damaged recording's STFT held fixed), whi
 `validate_batch(..., pitch=True)` adds the f0 contours of plot_pitch_comparison (:19-270) for the clean waveform and every
 variation, tracked on the device (nppc_audio/pitch.py), and what each direction does to them.
 
-Outside this build: whisper / phoneme transcription, the plots themselves (pitch and spectrogram), wav files, wandb.
+`save_pc_audio_variations` writes what validate_batch(..., alphas=) synthesised in the reference's layout, as FLAC encoded
+on the device (nppc_audio/flac.py) or as wav.
+
+Outside this build: whisper / phoneme transcription, the plots themselves (pitch and spectrogram), wandb.
 Splicing a restoration or a variation into the full source recording is inpainting/restore.py (RecordingRestorer).
 """
 import json
@@ -34,7 +37,7 @@ from ..nppc.nppc_model import NPPCModel, NPPCModelConfig
 from ..utils import preprocess_data
 
 __all__ = ["NPPCModelValidatorConfig", "NPPCModelValidator", "pc_audio_variations", "compute_metrics",
-           "compute_metrics_batch", "save_metrics_to_json", "default_alphas"]
+           "compute_metrics_batch", "save_metrics_to_json", "default_alphas", "save_pc_audio_variations"]
 
 compute_metrics = MB.compute_metrics
 compute_metrics_batch = MB.compute_metrics_batch
@@ -76,6 +79,38 @@ def pc_audio_variations(clean_spec_mag_norm_log, pred_spec_mag, pc_directions_ma
         H.call("nppc_pc_variation_waves", pred, pc, cn, cs, as_scalar(mean), as_scalar(std), alphas, out, clean_wave, B, K, A,
                T, n_fft, hop_length, L, H.stream())
     return out, clean_wave
+
+
+def save_pc_audio_variations(out, save_dir, alphas, first_index=0, fmt="flac", sample_rate=16000, backend="auto"):
+    """save_pc_audio_variations (:579-634), the audio files, for a whole batch: from validate_batch's dict (called with
+    `alphas`) writes, for sample b of the batch, under <save_dir>/sample_<first_index + b>/
+        clean.<ext>                            'clean_audio'[b]
+        pc_<k+1>/alpha_<a:.1f>.<ext>           'audio_variations'[b, k, a]
+        pc_<k+1>/alpha_<a:.1f>_blind.<ext>     'audio_variations_blind'[b, k, a], when the dict holds them
+    16-bit mono at sample_rate.  fmt "flac": all B (1 + K A [+ K A]) waveforms are quantised and encoded in ONE device call
+    (flac.encode_waves) and cross to the host as FLAC bytes; fmt "wav": the same samples as wav.  The reference's *_full
+    files (the variation spliced into the source recording) are RecordingRestorer.save_variations; transcriptions,
+    phonemes and pitch plots are outside this build.  -> the paths written"""
+    from ... import flac as FL
+    var, clean = out["audio_variations"], out["clean_audio"]
+    B, K, A, L = var.shape
+    alphas = [float(a) for a in torch.as_tensor(alphas).reshape(-1).tolist()]
+    if len(alphas) != A:
+        raise ValueError(f"{len(alphas)} alphas for {A} variations per direction")
+    blind = out.get("audio_variations_blind")
+    root = Path(save_dir)
+    paths, waves = [], [clean.reshape(B, L), var.reshape(B * K * A, L)]
+    paths += [root / f"sample_{first_index + b}" / f"clean.{fmt}" for b in range(B)]
+    paths += [root / f"sample_{first_index + b}" / f"pc_{k + 1}" / f"alpha_{a:.1f}.{fmt}"
+              for b in range(B) for k in range(K) for a in alphas]
+    if blind is not None:
+        if blind.shape != var.shape:
+            raise ValueError(f"blind variations {tuple(blind.shape)} do not fit {tuple(var.shape)}")
+        waves.append(blind.reshape(B * K * A, L))
+        paths += [root / f"sample_{first_index + b}" / f"pc_{k + 1}" / f"alpha_{a:.1f}_blind.{fmt}"
+                  for b in range(B) for k in range(K) for a in alphas]
+    FL.write_waves(paths, torch.cat([w.float() for w in waves]), sample_rate, fmt, backend=backend)
+    return paths
 
 
 def save_metrics_to_json(metrics, save_dir, sample_idx):

@@ -861,6 +861,43 @@ int nppc_flac_md5_host(const int* pcm, long n, int channels, int bps, unsigned c
 int nppc_flac_md5(const int* pcm, long pcm_elems, const long* meta, int nfiles, const int* order, const unsigned char* expected,
                   const int* status, unsigned char* digest, int* verdict, void* stream);
 
+/* ---- FLAC encoding (csrc/flac_enc_core.h + csrc/flac_enc.hip; specification tests/flac_enc_ref.py) ----
+ * Lossless, fixed predictors only, one stated decision rule (csrc/flac_enc_core.h): the bytes are a function of the samples,
+ * bits per sample (8, 12, 16, 20 or 24), rate (1 .. 2^20 - 1) and block size (16 .. 4608) alone.  The stream is fLaC, one
+ * STREAMINFO (min = max blocksize = block_size, min / max frame size, total samples, MD5 of the samples) and frames of
+ * block_size samples, the last one shorter.  An unsupported bps or block size: NPPC_EUNSUPPORTED. */
+#define NPPC_FLAC_ENC_PLAN 8          /* ints per frame of the plan: bytes, assignment, (type, order, partition order) x 2 */
+/* host only.  *bytes = the most bytes the stream of n samples per channel can take (every subframe verbatim, plus headers);
+ * *frames = ceil(n / block_size).  Either may be null.  n < 1 or channels outside 1..8: NPPC_EBADARG. */
+int nppc_flac_enc_bound(long n, int channels, int bps, int block_size, long* bytes, long* frames);
+/* host only, the serial encoder: pcm [channels][n] int32 -> out [cap], cap >= the bound; *nbytes = the stream's length.
+ * 1..8 channels (stereo tries the four assignments, channels 3..8 are independent).  A sample outside bps bits, n < 1, a
+ * rate outside 1 .. 2^20 - 1 or cap below the bound: NPPC_EBADARG. */
+int nppc_flac_encode_host(const int* pcm, long n, int channels, int bps, int rate, int block_size, unsigned char* out, long cap,
+                          long* nbytes);
+/* x [V][ldx] fp32, lengths [V] (long, device; null = ldx each; clamped to [0, ldx]) -> pcm[pcm_off[v] + i] =
+ * clip(rint(x 2^(bits-1)), -2^(bits-1), 2^(bits-1) - 1), halves to even, NaN -> 0.  pcm_off [V] (long, device); an item
+ * whose range leaves pcm_elems is skipped. */
+int nppc_pcm_quantize(const float* x, long ldx, const long* lengths, int V, int bits, int* pcm, const long* pcm_off, long pcm_elems,
+                      void* stream);
+/* device, a ragged batch of nfiles files of one bps, rate and block size.  pcm [pcm_elems] int32, planar per file; meta
+ * [nfiles][NPPC_FLAC_META] (long, device) as for decoding, of which 3 channels (1 or 2), 4 bits per sample, 7 samples and 9 the
+ * pcm offset are read; ftab [nframes][2] (int, device) = (file, frame number) of every frame, files ascending and each
+ * file's frames ascending.  The calls run in this order on one stream with nppc_flac_md5 (digest [nfiles][16]) anywhere
+ * before write, and no host read between them:
+ *   plan    plan [nframes][NPPC_FLAC_ENC_PLAN] int: one workgroup per frame
+ *   scan    goff [nframes] long: where every frame begins in out, the files back to back, each behind its 42-byte stream
+ *           header; stats [nfiles + 1][4] long: per file begin, end, min and max frame size; stats[nfiles][0] = all bytes
+ *   write   out [out_cap] bytes, out_cap >= the sum of the files' bounds; a frame that would leave it is not written
+ * Integer atomics only, no waiting between workgroups: two runs give identical bytes and a file's bytes do not depend on
+ * the rest of the batch. */
+int nppc_flac_enc_plan(const int* pcm, long pcm_elems, const long* meta, int nfiles, const int* ftab, long nframes, int bps,
+                       int block_size, int* plan, void* stream);
+int nppc_flac_enc_scan(const int* plan, const int* ftab, long nframes, int nfiles, long* goff, long* stats, void* stream);
+int nppc_flac_enc_write(const int* pcm, long pcm_elems, const long* meta, int nfiles, const int* ftab, long nframes, int bps,
+                        int rate, int block_size, const int* plan, const long* goff, const long* stats,
+                        const unsigned char* digest, unsigned char* out, long out_cap, void* stream);
+
 /* ---- windowed-sinc resampling of ragged batches (csrc/resample.hip; specification
  * tests/resample_ref.py): torchaudio's default Resample (Hann window).  With orig / new the two rates reduced by their gcd,
  * Klen = 2 width + orig and xpad the item padded with `width` zeros on the left and zeros on the right,
