@@ -10,6 +10,7 @@
 //     (1 KiB fully coalesced per wave-load); nothing but h/c/gates (train) goes to HBM
 // Layout of every [Tn][N][...] tensor is time-major so one (step, tile) block is contiguous.
 #include "common.h"
+#include "lstm_cell.h"
 #include "nppc_hip.h"
 
 namespace {
@@ -79,17 +80,6 @@ template <> __device__ __forceinline__ void store_pair<float>(float* p, float a,
 }
 template <> __device__ __forceinline__ void store_pair<bf16_t>(bf16_t* p, float a, float b) {
   *reinterpret_cast<uint32_t*>(p) = (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
-}
-
-template <typename T> __device__ __forceinline__ void store_gates(T* p, float a, float b, float c, float d);
-template <> __device__ __forceinline__ void store_gates<float>(float* p, float a, float b, float c, float d) {
-  *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
-}
-template <> __device__ __forceinline__ void store_gates<bf16_t>(bf16_t* p, float a, float b, float c, float d) {
-  uint2 v;
-  v.x = (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
-  v.y = (uint32_t)f2bf(c) | ((uint32_t)f2bf(d) << 16);
-  *reinterpret_cast<uint2*>(p) = v;
 }
 
 // One LSTM layer step for this wave's 16*UB units x M rows.  Two passes over K keep only two gate
@@ -564,13 +554,7 @@ __global__ __launch_bounds__(NW * 64) void lstm2_bwd_kernel(LstmBwdArgs a) {
         const float cp = t > 0 ? to_f32<T>(sv.cp[i]) : 0.f;
         float dh = dh_lds[prow * HP + u0 + i];
         if (has_ext) dh += to_f32<T>(sv.dh[i]);
-        const float tc = tanh_f(ct);
-        const float dct = dh * ov * (1.f - tc * tc) + dc[i];
-        dO = dh * tc * ov * (1.f - ov);
-        di = dct * gv * iv * (1.f - iv);
-        dg = dct * iv * (1.f - gv * gv);
-        df = dct * cp * fv * (1.f - fv);
-        dc[i] = dct * fv;
+        lstm_cell_bwd(iv, gv, fv, ov, ct, cp, dh, dc[i], di, dg, df, dO);
       }
       T* ap = Abuf + prow * RSA + (u0 + i) * 4;
       store_gates<T>(ap, di, dg, df, dO);

@@ -17,6 +17,7 @@
 #include <type_traits>
 #include <utility>
 #include "common.h"
+#include "lstm_cell.h"
 #include "nppc_hip.h"
 
 namespace {
@@ -63,6 +64,34 @@ constexpr bool CF_POLL = false;                      // diagnostic: never wait f
 #else
 constexpr bool CF_POLL = true;
 #endif
+
+// The bounded spin of the hand-off protocol, once per loop shape.  On time-out the caller's counting lane(s) add 1 to the
+// sticky time-out word `tmo` and the wave carries on.  Which lanes poll and which lane counts is the call site's choice.
+// Shape 1 -- load, compare, sleep, count: the calling lane waits until *flag >= ep; every calling lane counts its own time-out.
+__device__ __forceinline__ void spin_until(const gu32* flag, unsigned ep, gu32* tmo) {
+  unsigned spins = 0;
+  while (CF_POLL && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ep) {
+    __builtin_amdgcn_s_sleep(1);
+    if (++spins > SPIN_LIMIT) {
+      __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+  }
+}
+// Shape 2 -- value already in a register (requested earlier, behind a counted wait), compare, count, sleep, reload: used inside
+// the fragment streams, where the loop must not be left with a request still pending (the compiler would wait for it).
+// `counts`: this lane records the time-out.
+__device__ __forceinline__ void spin_reload(unsigned& fl, const gu32* flag, unsigned ep, gu32* tmo, bool counts) {
+  unsigned spins = 0;
+  while (CF_POLL && fl < ep) {
+    if (++spins > SPIN_LIMIT) {
+      if (counts) __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+    fl = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
 
 __device__ __forceinline__ void store_sc1_b128(__amdgpu_buffer_rsrc_t r, int off, u32x4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 16);   // aux 16 = sc1 (write-through)
@@ -212,17 +241,6 @@ __device__ __forceinline__ void coop_gemm(f32x4 (&acc)[2][MT], const T* a_lane /
       if (kk + d < n) compute(b[d], k0 + kk + d);
     }
   }
-}
-
-template <typename T> __device__ __forceinline__ void store4(T* p, float a, float b, float c, float d);
-template <> __device__ __forceinline__ void store4<float>(float* p, float a, float b, float c, float d) {
-  *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
-}
-template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, float a, float b, float c, float d) {
-  uint2 v;
-  v.x = (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
-  v.y = (uint32_t)f2bf(c) | ((uint32_t)f2bf(d) << 16);
-  *reinterpret_cast<uint2*>(p) = v;
 }
 
 // saved state / outputs are written once and read by a LATER kernel: non-temporal stores keep them out of the L2 that
@@ -396,16 +414,7 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
   // wait for the partners' slices of (layer, epoch) and copy them into LDS
   auto consume = [&](int layer, int hoff, int ep) {
     if (wave == 0) {
-      if (lane < G && lane != cu) {
-        unsigned spins = 0;
-        while (CF_POLL && __hip_atomic_load(flags + layer * G + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)ep) {
-          __builtin_amdgcn_s_sleep(1);
-          if (++spins > SPIN_LIMIT) {
-            __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
-      }
+      if (lane < G && lane != cu) spin_until(flags + layer * G + lane, (unsigned)ep, tmo);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");     // compiler ordering only: payload loads are sc1
     }
     CF_BARRIER();
@@ -428,16 +437,7 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
   // used for the h2 hand-off, whose LDS region nobody reads during layer 1, so the transfer hides behind its GEMMs
   constexpr int HXC = (SLICE_CH * (G - 1) + NT - 1) / NT;
   auto wave_poll = [&](int layer, int ep) {
-    if (lane < G && lane != cu) {
-      unsigned spins = 0;
-      while (CF_POLL && __hip_atomic_load(flags + layer * G + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)ep) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > SPIN_LIMIT) {
-          __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-      }
-    }
+    if (lane < G && lane != cu) spin_until(flags + layer * G + lane, (unsigned)ep, tmo);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   };
   auto slice_addr = [&](int idx, int& partner, int& ch) {      // idx-th chunk over the G-1 partner slices
@@ -663,7 +663,7 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
 // What crosses CUs per layer and step is the other half of the dgates tile [32][768] (48 KB), the MFMA A operand.
 struct CoopBwdArgs {
   const void* g1; const void* g2; const void* c1; const void* c2; const void* dh2;
-  const void* wb1; const void* wb2;   // packed by lstm_coop_pack_bwd_kernel
+  const void* wb1; const void* wb2;   // packed by lstm_coop_pack_bwd_kernel<PackOutSplit>
   void* dx; void* dg1; void* dg2;     // dg [Tn][N][4H]
   void* xch;                          // [clusters][2 layers][2 parities][2 CUs][32][768]
   unsigned* flags;                    // [clusters][2 layers][2] epochs + timeout word
@@ -780,15 +780,9 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd_kernel(CoopBwdArgs a) {
         const float cp = t > 0 ? bf2f(sv.cp[i]) : 0.f;
         float dh = dh_lds[prow * HC + ul0 + i];
         if (has_ext) dh += bf2f(sv.dh[i]);
-        const float tc = tanh_f(ct);
-        const float dct = dh * ov * (1.f - tc * tc) + dc[i];
-        dO = dh * tc * ov * (1.f - ov);
-        di = dct * gv * iv * (1.f - iv);
-        dg = dct * iv * (1.f - gv * gv);
-        df = dct * cp * fv * (1.f - fv);
-        dc[i] = dct * fv;
+        lstm_cell_bwd(iv, gv, fv, ov, ct, cp, dh, dc[i], di, dg, df, dO);
       }
-      store4<T>(Abuf + prow * RSA + (u0 + i) * 4, di, dg, df, dO);   // 8-byte LDS stores (16-byte ones measured slower)
+      store_gates<T>(Abuf + prow * RSA + (u0 + i) * 4, di, dg, df, dO);   // 8-byte LDS stores (16-byte ones measured slower)
     }
   };
   // own half of the dgates tile: columns [cu*768, +768) of Abuf -> partner (write-through, drained, flagged).  Read back
@@ -817,16 +811,7 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd_kernel(CoopBwdArgs a) {
   };
   auto consume = [&](int layer, int ep) {
     if (wave == 0) {
-      if (lane == 0) {
-        unsigned spins = 0;
-        while (CF_POLL && __hip_atomic_load(flags + layer * CB_G + pcu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)ep) {
-          __builtin_amdgcn_s_sleep(1);
-          if (++spins > SPIN_LIMIT) {
-            __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
-      }
+      if (lane == 0) spin_until(flags + layer * CB_G + pcu, (unsigned)ep, tmo);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     __syncthreads();
@@ -900,39 +885,6 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd_kernel(CoopBwdArgs a) {
   }
 }
 
-// packed backward weights for the cooperative kernel: element (cu, wave, kk, slot, lane l, j)
-//   k = 32*kk + 8*(l>>4) + j = u*4 + g'  (g' in i,g,f,o -> torch block {0,2,1,3}[g'])
-//   layer 2: slot 0 -> input feature h1 unit cu*192 + 16*wave + (l&15);  slot 1 -> h2 unit (same index)
-//   layer 1: slot 0 -> h1 unit (W_hh);  slot 1 -> x column cu*32 + 16*wave + (l&15) for wave < 2 (W_ih, col < I), else 0
-__global__ void lstm_coop_pack_bwd_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, bf16_t* __restrict__ out,
-                                          int I, int layer) {
-  const size_t total = (size_t)CB_G * CB_NW * CB_NK * 2 * 512;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int j = e & 7, l = (e >> 3) & 63;
-    size_t f = e >> 9;
-    const int slot = f & 1; f >>= 1;
-    const int kk = f % CB_NK; f /= CB_NK;
-    const int wave = f % CB_NW;
-    const int cu = (int)(f / CB_NW);
-    const int k = 32 * kk + 8 * (l >> 4) + j;
-    const int u = k >> 2, gp = k & 3;
-    const int tg = gp == 0 ? 0 : (gp == 1 ? 2 : (gp == 2 ? 1 : 3));
-    const int row = tg * CB_H + u;
-    const int unit = cu * CB_HC + 16 * wave + (l & 15);
-    float v = 0.f;
-    if (layer == 2) {
-      v = slot == 0 ? w_ih[(size_t)row * CB_H + unit] : w_hh[(size_t)row * CB_H + unit];
-    } else {
-      if (slot == 0) v = w_hh[(size_t)row * CB_H + unit];
-      else if (wave < 2) {
-        const int col = cu * 32 + 16 * wave + (l & 15);
-        if (col < I) v = w_ih[(size_t)row * I + col];
-      }
-    }
-    out[e] = f2bf(v);
-  }
-}
-
 // =====================================================================================================
 // Cooperative backward, K-split variant.  Same CU pair / 32-sequence tile / unit ownership as above, but the two
 // backward GEMMs are split along K (the gate columns) instead of along their outputs:
@@ -947,7 +899,7 @@ __global__ void lstm_coop_pack_bwd_kernel(const float* __restrict__ w_ih, const 
 // (h tiles: tau % 24 / 12, x tiles: columns 0-31 -> cu 0, 32-63 -> cu 1).
 struct CoopBwd2Args {
   const void* g1; const void* g2; const void* c1; const void* c2; const void* dh2;
-  const void* wb1; const void* wb2;   // packed by lstm_coop_pack_bwd2_kernel
+  const void* wb1; const void* wb2;   // packed by lstm_coop_pack_bwd_kernel<PackKSplit2> (four-CU kernel: <PackKSplit4>)
   void* dx; void* dg1; void* dg2;     // dg [Tn][N][4H]
   void* xch;                          // [clusters][2 layers][2 parities][2 CUs][32][384] bf16 partial sums
   unsigned* flags;                    // [clusters][2 layers][2 CUs][12 waves] epochs + 4 timeout words
@@ -1059,6 +1011,189 @@ __device__ __forceinline__ void c4_lds_dma16(const void* src_lane, unsigned lds_
                : "=&s"(keep) : "v"(src_lane), "s"(lb) : "memory");
 }
 
+// ---- front end of the K-split backward kernels ------------------------------------------------------------------------
+// What lstm2_coop_bwd2_kernel (CU pairs: 32 rows per cluster, 192 units per CU) and lstm2_coop_bwd4_kernel (four-CU clusters:
+// 64 rows, 96 units) share: the LDS layout, the saved state of a thread and its fetches, the cell backward and the bf16
+// packing of shipped partial sums.  Everything follows from the cluster geometry (MC rows per cluster, HC units per CU); the
+// fragment streams, their schedules and the scatter of their results stay with the kernels.  HEAD (the kernel's own
+// parameter: fused output head) changes no size; it is a parameter here so that every kernel instantiation has its own
+// copies of fetch / fetch_part / cell_bwd, as it had of the lambdas these were: the optimiser then sees the constant
+// arguments of that kernel's calls before it inlines them (the same instruction streams as before the code was shared).
+template <int MC_, int HC_, bool HEAD>
+struct KSplit {
+  typedef bf16_t T;
+  static constexpr int MC = MC_, HC = HC_, H = CB_H, NT = CB_NT;
+  static constexpr int G = H / HC, KC = 4 * HC, XC = CB_KX / G;   // CUs per cluster; own gate columns; own d x columns
+  static constexpr int RSA = KC + COOP_APAD;                      // A tile row stride (elements): own gate columns only
+  static constexpr int TPR = NT / MC;                             // threads per row (24 / 12), 8 units per thread
+  static constexpr size_t SMEM = (size_t)MC * RSA * sizeof(T) + (size_t)(4 * MC * HC + MC * XC) * sizeof(float) +
+                                 (size_t)(HC + MC) * 16 * sizeof(T);
+  static_assert(SMEM <= 160 * 1024 && SMEM > 80 * 1024, "one workgroup per CU");
+
+  T* Abuf;         // [MC][RSA]   own dgates
+  float* dh1buf;   // [MC][HC]    d h1 (own units)
+  float* dhrec2;   // [MC][HC]    d h2 recurrent
+  float* dxbuf;    // [MC][XC]    own d x columns
+  // (d c of the thread's 8 units per layer lives in LDS, not in 16 registers: both layers' saved state is in flight at
+  // the end of a GEMM pass since round 3, and the registers are what that costs)
+  float* dc1;      // [MC][HC]    d c carried from step to step, layer 1
+  float* dc2;      // [MC][HC]    ... layer 2
+  T* whs;          // HEAD: [HC][16] own units' head weights
+  T* dys;          // HEAD: [MC][16] dY rows of one step
+  long N, row0, prow_c;
+  int cu, prow, tc_;
+  bool prow_ok;
+
+  // carves up the workgroup's LDS, zeroes it (HEAD: loads the own units' head weights, whT [H][32]) and finds the thread's row.
+  // Thread -> data: TPR threads per row; thread (prow, tc) owns the four 16-byte chunks c_j = tc + TPR j (j = 0..3) of the
+  // row's own-unit gate block, i.e. units 2 c_j, 2 c_j + 1.  Consecutive lanes then touch consecutive 16-byte chunks in
+  // LDS and in HBM, so the gate gradients go to dg straight from the registers of the cell backward (coalesced,
+  // non-temporal) and their write acknowledgements return while the rest of the cell phase computes -- issued around
+  // the GEMMs they stalled the weight-fragment ring, because stores and loads share the in-order vmcnt counter.
+  // The caller's __syncthreads() completes it; map_thread() follows that barrier.
+  __device__ __forceinline__ void init(unsigned char* smem, long N_, int cluster, int cu_, const void* whT_) {
+    Abuf = reinterpret_cast<T*>(smem);
+    dh1buf = reinterpret_cast<float*>(smem + (size_t)MC * RSA * sizeof(T));
+    dhrec2 = dh1buf + MC * HC;
+    dxbuf = dhrec2 + MC * HC;
+    dc1 = dxbuf + MC * XC;
+    dc2 = dc1 + MC * HC;
+    whs = reinterpret_cast<T*>(dc2 + MC * HC);
+    dys = whs + HC * 16;
+    const int tid = threadIdx.x;
+    N = N_;
+    cu = cu_;
+    row0 = (long)cluster * MC;
+    for (int i = tid; i < 4 * MC * HC + MC * XC; i += NT) dh1buf[i] = 0.f;      // d h1, d h2 rec, d x, d c (both layers)
+    for (int i = tid; i < MC * RSA; i += NT) Abuf[i] = 0;
+    if constexpr (HEAD) {
+      const T* whT = reinterpret_cast<const T*>(whT_);
+      for (int i = tid; i < HC * 16; i += NT) whs[i] = whT[(size_t)(cu * HC + i / 16) * 32 + (i % 16)];
+    }
+    prow = tid / TPR;
+    prow_ok = row0 + prow < N;
+  }
+  // the thread's chunk column and its row clamped into the tensors (fetch_part), computed behind the barrier: in front of
+  // it they are live across the barrier's wait and the prologue is scheduled differently
+  __device__ __forceinline__ void map_thread() {
+    tc_ = threadIdx.x % TPR;
+    prow_c = row0 + prow < N ? row0 + prow : N - 1;
+  }
+
+  struct Saved { u32x4 g[4]; unsigned ct[4], cp[4], dh[4]; };     // packed bf16 pairs: 28 VGPRs
+  static __device__ __forceinline__ unsigned ld_nt4(const T* p) { return __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(p)); }
+  static __device__ __forceinline__ float lo16(unsigned w) { return __uint_as_float(w << 16); }
+  static __device__ __forceinline__ float hi16(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+
+  // carry: sv still holds the (consumed) state of step t + 1, whose "previous cell" c_t is this step's cell state:
+  // moved in registers instead of being read from HBM a second time
+  __device__ void fetch(Saved& sv, const T* gs, const T* cs, const T* dh_ext, int t, bool carry) const {
+    if (!prow_ok || t < 0) return;
+#ifdef C2_NO_FETCH
+    return;                               // diagnostic: timing without the saved-state loads (results are garbage)
+#endif
+    int tc = tc_;
+    asm volatile("" : "+v"(tc));          // keep the per-chunk addresses out of the loop-invariant (spilled) set
+    const size_t e = ((size_t)t * N + row0 + prow) * H + cu * HC;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = tc + TPR * j;
+      sv.g[j] = ld_nt16(gs + e * 4 + 8 * c);
+      if (carry) sv.ct[j] = sv.cp[j];
+      else sv.ct[j] = ld_nt4(cs + e + 2 * c);
+      if (t > 0) sv.cp[j] = ld_nt4(cs + e - (size_t)N * H + 2 * c);
+      if (dh_ext) sv.dh[j] = ld_nt4(dh_ext + e + 2 * c);
+    }
+  }
+  // The same for the chunks j0 <= j < j1 only, always with carry, and UNCONDITIONAL (time and row indices are clamped into
+  // the tensors; what a clamped request returns is never used): this is the form used inside the time loop, from the
+  // `post` hooks of the GEMM passes -- a load that only some paths issue makes hipcc's (path-insensitive) wait-count
+  // insertion drain the whole queue in front of the next fragment use.
+  template <typename WithDh>
+  __device__ void fetch_part(WithDh, Saved& sv, const T* gs, const T* cs, const T* dh_ext, int t, int j0, int j1) const {
+#ifdef C2_NO_FETCH
+    return;
+#endif
+    int tc = tc_;
+    asm volatile("" : "+v"(tc));
+    const int tcl = t > 0 ? t : 0, tpl = t > 1 ? t - 1 : 0;
+    const size_t e = ((size_t)tcl * N + prow_c) * H + cu * HC, ep = ((size_t)tpl * N + prow_c) * H + cu * HC;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < j0 || j >= j1) continue;
+      const int c = tc + TPR * j;
+      sv.g[j] = ld_nt16(gs + e * 4 + 8 * c);
+      sv.ct[j] = sv.cp[j];
+      sv.cp[j] = ld_nt4(cs + ep + 2 * c);
+      if constexpr (WithDh::value) sv.dh[j] = ld_nt4(dh_ext + e + 2 * c);
+    }
+  }
+  // cell backward -> gate gradients (bf16, local k = unit*4 + gate): LDS A operand + dg [t*N + row][4H] (own KC columns)
+  // The phase has NO branch on the row being valid: rows past N compute on clamped (finite) saved state, their gate
+  // gradients are forced to zero for the LDS operand and their dg stores are dropped by the range check of the step's
+  // buffer descriptor (base = row 0 of time t, num_records = one time step).  A store that only some paths issue made
+  // hipcc wait for vmcnt(0) -- i.e. for the acknowledgement of the previous chunk's HBM store -- before every chunk.
+  __device__ void cell_bwd(const Saved& sv, const float* dh_lds, bool has_ext, float* dcl, int t, T* dg) const {
+    int tc = tc_;
+    asm volatile("" : "+v"(tc));
+    const __amdgpu_buffer_rsrc_t dgr = make_rsrc(dg + (size_t)t * N * CB_K4, (unsigned)((size_t)N * CB_K4 * sizeof(T)));
+    const int rowoff = (int)(((row0 + prow) * CB_K4 + cu * KC) * sizeof(T));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = tc + TPR * j;
+      u32x4 out;
+      float2 dcv = *reinterpret_cast<const float2*>(dcl + prow * HC + 2 * c);
+      const float2 dhv = *reinterpret_cast<const float2*>(dh_lds + prow * HC + 2 * c);
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const unsigned w0 = sv.g[j][2 * e], w1 = sv.g[j][2 * e + 1];   // (i, g), (f, o) of unit 2c + e
+        const float iv = lo16(w0), gv = hi16(w0), fv = lo16(w1), ov = hi16(w1);
+        const float ct = e ? hi16(sv.ct[j]) : lo16(sv.ct[j]);
+        const float cp = t > 0 ? (e ? hi16(sv.cp[j]) : lo16(sv.cp[j])) : 0.f;
+        float dh = e ? dhv.y : dhv.x;
+        if (has_ext) dh += e ? hi16(sv.dh[j]) : lo16(sv.dh[j]);
+        float di, dgg, df, dO, dc = e ? dcv.y : dcv.x;   // (a copy, not a reference into dcv: that form was scheduled differently)
+        lstm_cell_bwd(iv, gv, fv, ov, ct, cp, dh, dc, di, dgg, df, dO);
+        if (e) dcv.y = dc; else dcv.x = dc;
+        out[2 * e] = (uint32_t)f2bf(di) | ((uint32_t)f2bf(dgg) << 16);
+        out[2 * e + 1] = (uint32_t)f2bf(df) | ((uint32_t)f2bf(dO) << 16);
+      }
+      if (!prow_ok) { out = u32x4{0u, 0u, 0u, 0u}; dcv = float2{0.f, 0.f}; }
+      *reinterpret_cast<float2*>(dcl + prow * HC + 2 * c) = dcv;
+#ifndef C2_NO_DG
+      __builtin_amdgcn_raw_buffer_store_b128(out, dgr, rowoff + 16 * c, 0, 2);       // aux 2 = nt
+#endif
+      *reinterpret_cast<u32x4*>(Abuf + prow * RSA + 8 * c) = out;
+    }
+  }
+
+  // Partial sums travel accumulator to accumulator as bf16: two 16-row tiles of a lane (2 x f32x4) are 16 bytes
+  static __device__ __forceinline__ u32x4 pack2(const f32x4& a0, const f32x4& a1) {
+    u32x4 o;
+    o[0] = (uint32_t)f2bf(a0[0]) | ((uint32_t)f2bf(a0[1]) << 16);
+    o[1] = (uint32_t)f2bf(a0[2]) | ((uint32_t)f2bf(a0[3]) << 16);
+    o[2] = (uint32_t)f2bf(a1[0]) | ((uint32_t)f2bf(a1[1]) << 16);
+    o[3] = (uint32_t)f2bf(a1[2]) | ((uint32_t)f2bf(a1[3]) << 16);
+    return o;
+  }
+  // acc += the partner's packed partials: NV * 16 bytes hold 2 * NV row tiles
+  template <int NV>
+  static __device__ __forceinline__ void add_packed(f32x4 (&acc)[2 * NV], const u32x4 (&v)[NV]) {
+#pragma unroll
+    for (int mt = 0; mt < 2 * NV; ++mt) {
+      const unsigned w0 = v[mt >> 1][2 * (mt & 1)], w1 = v[mt >> 1][2 * (mt & 1) + 1];
+      acc[mt][0] += lo16(w0);
+      acc[mt][1] += hi16(w0);
+      acc[mt][2] += lo16(w1);
+      acc[mt][3] += hi16(w1);
+    }
+  }
+  static __device__ __forceinline__ void add_packed(f32x4 (&acc)[2], const u32x4 v) {
+    const u32x4 vv[1] = {v};
+    add_packed<1>(acc, vv);
+  }
+};
+
 // Compile-time operation schedule of ONE fragment stream over both passes of a layer of the CU-pair kernel (48 k-steps: 24 on
 // the partner's tiles, 24 on the own ones; the ring never restarts between them and nothing is drained).  Per position g:
 //   side(g)   g = 32: raise the epoch of the shipment (1 store, behind a counted wait for its stores);  g = 36: request the
@@ -1093,18 +1228,11 @@ struct C2Sched {
 
 template <bool HEAD>
 __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) {
-  typedef bf16_t T;
-  constexpr int MC = CB_MC, H = CB_H, HC = CB_HC, KX = CB_KX, NT = CB_NT;
-  constexpr int RSA = CB_KC + COOP_APAD;                            // A tile row stride (elements): own gate columns only
-  constexpr int TPR = NT / MC, UPT = HC / TPR;              // 24 threads per row, 8 units per thread
+  typedef KSplit<CB_MC, CB_HC, HEAD> KS;
+  typedef typename KS::T T;
+  typedef typename KS::Saved Saved;
+  constexpr int MC = KS::MC, HC = KS::HC, KX = CB_KX, NT = CB_NT, RSA = KS::RSA;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  T* Abuf = reinterpret_cast<T*>(smem_raw);                                          // [32][RSA]   own dgates
-  float* dh1buf = reinterpret_cast<float*>(smem_raw + (size_t)MC * RSA * sizeof(T));  // [32][HC]    d h1 (own units)
-  float* dhrec2 = dh1buf + MC * HC;                                                   // [32][HC]    d h2 recurrent
-  float* dxbuf = dhrec2 + MC * HC;                                                    // [32][32]    own d x partial
-  float* dcbuf = dxbuf + MC * 32;                                                     // [2][32][HC] d c carried from step to step
-  T* whs = reinterpret_cast<T*>(dcbuf + 2 * MC * HC);                                 // HEAD: [HC][16] own units' head weights
-  T* dys = whs + HC * 16;                                                             // HEAD: [32][16]  dY rows of one step
 
 #ifdef C2_STAMP
   C2_STAMP_INIT
@@ -1118,21 +1246,18 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
   if (wave >= 9) asm volatile("s_setprio 3"); else if (wave >= 6) asm volatile("s_setprio 2"); else if (wave >= 3) asm volatile("s_setprio 1");
 #endif
   const int pcu = 1 - cu;
-  const long row0 = (long)cluster * MC;
   const long N = a.N;
-  for (int i = tid; i < 4 * MC * HC + MC * 32; i += NT) dh1buf[i] = 0.f;      // d h1, d h2 rec, d x, d c (both layers)
-  for (int i = tid; i < MC * RSA; i += NT) Abuf[i] = 0;
-  if constexpr (HEAD) {
-    const T* whT = reinterpret_cast<const T*>(a.whT);
-    for (int i = tid; i < HC * 16; i += NT) whs[i] = whT[(size_t)(cu * HC + i / 16) * 32 + (i % 16)];
-  }
-
-  const int prow = tid / TPR;
-  const bool prow_ok = row0 + prow < N;
-  // (d c of the thread's 8 units per layer lives in LDS, not in 16 registers: both layers' saved state is in flight at
-  // the end of a GEMM pass since round 3, and the registers are what that costs)
-  float* dc1 = dcbuf;
-  float* dc2 = dcbuf + MC * HC;
+  KS ks;
+  ks.init(smem_raw, N, cluster, cu, a.whT);
+  const long row0 = ks.row0;
+  T* const Abuf = ks.Abuf;
+  float* const dh1buf = ks.dh1buf;
+  float* const dhrec2 = ks.dhrec2;
+  float* const dxbuf = ks.dxbuf;
+  float* const dc1 = ks.dc1;
+  float* const dc2 = ks.dc2;
+  T* const whs = ks.whs;
+  T* const dys = ks.dys;
 
   const T* g1 = reinterpret_cast<const T*>(a.g1);
   const T* g2 = reinterpret_cast<const T*>(a.g2);
@@ -1142,8 +1267,6 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
   T* dx = reinterpret_cast<T*>(a.dx);
   T* dg1T = reinterpret_cast<T*>(a.dg1);
   T* dg2T = reinterpret_cast<T*>(a.dg2);
-  constexpr unsigned WB = CB_G * CB_NW * C2_NKK * C2_SLOTS * 512 * 2;
-  const __amdgpu_buffer_rsrc_t wr1 = make_rsrc(a.wb1, WB), wr2 = make_rsrc(a.wb2, WB);
   constexpr int XSL = MC * C2_XW;                                                   // elements of one partial slab
   const __amdgpu_buffer_rsrc_t xr = make_rsrc(reinterpret_cast<const T*>(a.xch) + (size_t)cluster * 2 * 2 * 2 * XSL,
                                               (unsigned)(2 * 2 * 2 * XSL * sizeof(T)));
@@ -1151,102 +1274,8 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
   gu32* tmo = (gu32*)(a.flags + (size_t)a.clusters * C2_FPC);
   const T* a_lane = Abuf + n * RSA + 8 * q;
   __syncthreads();
+  ks.map_thread();
 
-  // Thread -> data: 24 threads per row; thread (prow, tc) owns the four 16-byte chunks c_j = tc + 24 j (j = 0..3) of the
-  // row's own-unit gate block, i.e. units 2 c_j, 2 c_j + 1.  Consecutive lanes then touch consecutive 16-byte chunks in
-  // LDS and in HBM, so the gate gradients go to dg straight from the registers of the cell backward (coalesced,
-  // non-temporal) and their write acknowledgements return while the rest of the cell phase computes -- issued around
-  // the GEMMs they stalled the weight-fragment ring, because stores and loads share the in-order vmcnt counter.
-  const int tc_ = tid % TPR;
-  struct Saved { u32x4 g[4]; unsigned ct[4], cp[4], dh[4]; };     // packed bf16 pairs: 28 VGPRs
-  auto ld_nt4 = [](const T* p) { return __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(p)); };
-  // carry: sv still holds the (consumed) state of step t + 1, whose "previous cell" c_t is this step's cell state:
-  // moved in registers instead of being read from HBM a second time
-  auto fetch = [&](Saved& sv, const T* gs, const T* cs, const T* dh_ext, int t, bool carry) {
-    if (!prow_ok || t < 0) return;
-#ifdef C2_NO_FETCH
-    return;                               // diagnostic: timing without the saved-state loads (results are garbage)
-#endif
-    int tc = tc_;
-    asm volatile("" : "+v"(tc));          // keep the per-chunk addresses out of the loop-invariant (spilled) set
-    const size_t e = ((size_t)t * N + row0 + prow) * H + cu * HC;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = tc + TPR * j;
-      sv.g[j] = ld_nt16(gs + e * 4 + 8 * c);
-      if (carry) sv.ct[j] = sv.cp[j];
-      else sv.ct[j] = ld_nt4(cs + e + 2 * c);
-      if (t > 0) sv.cp[j] = ld_nt4(cs + e - (size_t)N * H + 2 * c);
-      if (dh_ext) sv.dh[j] = ld_nt4(dh_ext + e + 2 * c);
-    }
-  };
-  // The same for the chunks j0 <= j < j1 only, always with carry, and UNCONDITIONAL (time and row indices are clamped into
-  // the tensors; what a clamped request returns is never used): this is the form used inside the time loop, from the
-  // `post` hooks of the GEMM passes -- a load that only some paths issue makes hipcc's (path-insensitive) wait-count
-  // insertion drain the whole queue in front of the next fragment use.
-  const long prow_c = row0 + prow < N ? row0 + prow : N - 1;
-  auto fetch_part = [&](auto with_dh, Saved& sv, const T* gs, const T* cs, const T* dh_ext, int t, int j0, int j1) {
-#ifdef C2_NO_FETCH
-    return;
-#endif
-    int tc = tc_;
-    asm volatile("" : "+v"(tc));
-    const int tcl = t > 0 ? t : 0, tpl = t > 1 ? t - 1 : 0;
-    const size_t e = ((size_t)tcl * N + prow_c) * H + cu * HC, ep = ((size_t)tpl * N + prow_c) * H + cu * HC;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (j < j0 || j >= j1) continue;
-      const int c = tc + TPR * j;
-      sv.g[j] = ld_nt16(gs + e * 4 + 8 * c);
-      sv.ct[j] = sv.cp[j];
-      sv.cp[j] = ld_nt4(cs + ep + 2 * c);
-      if constexpr (decltype(with_dh)::value) sv.dh[j] = ld_nt4(dh_ext + e + 2 * c);
-    }
-  };
-  auto lo16 = [](unsigned w) { return __uint_as_float(w << 16); };
-  auto hi16 = [](unsigned w) { return __uint_as_float(w & 0xffff0000u); };
-  // cell backward -> gate gradients (bf16, local k = unit*4 + gate): LDS A operand + dg [t*N + row][4H] (own 768 columns)
-  // The phase has NO branch on the row being valid: rows past N compute on clamped (finite) saved state, their gate
-  // gradients are forced to zero for the LDS operand and their dg stores are dropped by the range check of the step's
-  // buffer descriptor (base = row 0 of time t, num_records = one time step).  A store that only some paths issue made
-  // hipcc wait for vmcnt(0) -- i.e. for the acknowledgement of the previous chunk's HBM store -- before every chunk.
-  auto cell_bwd = [&](const Saved& sv, const float* dh_lds, bool has_ext, float* dcl, int t, T* dg) {
-    int tc = tc_;
-    asm volatile("" : "+v"(tc));
-    const __amdgpu_buffer_rsrc_t dgr = make_rsrc(dg + (size_t)t * N * CB_K4, (unsigned)((size_t)N * CB_K4 * sizeof(T)));
-    const int rowoff = (int)(((row0 + prow) * CB_K4 + cu * CB_KC) * sizeof(T));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = tc + TPR * j;
-      u32x4 out;
-      float2 dcv = *reinterpret_cast<const float2*>(dcl + prow * HC + 2 * c);
-      const float2 dhv = *reinterpret_cast<const float2*>(dh_lds + prow * HC + 2 * c);
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const unsigned w0 = sv.g[j][2 * e], w1 = sv.g[j][2 * e + 1];   // (i, g), (f, o) of unit 2c + e
-        const float iv = lo16(w0), gv = hi16(w0), fv = lo16(w1), ov = hi16(w1);
-        const float ct = e ? hi16(sv.ct[j]) : lo16(sv.ct[j]);
-        const float cp = t > 0 ? (e ? hi16(sv.cp[j]) : lo16(sv.cp[j])) : 0.f;
-        float dh = e ? dhv.y : dhv.x;
-        if (has_ext) dh += e ? hi16(sv.dh[j]) : lo16(sv.dh[j]);
-        const float tch = tanh_f(ct);
-        const float dct = dh * ov * (1.f - tch * tch) + (e ? dcv.y : dcv.x);
-        const float dO = dh * tch * ov * (1.f - ov);
-        const float di = dct * gv * iv * (1.f - iv);
-        const float dgg = dct * iv * (1.f - gv * gv);
-        const float df = dct * cp * fv * (1.f - fv);
-        if (e) dcv.y = dct * fv; else dcv.x = dct * fv;
-        out[2 * e] = (uint32_t)f2bf(di) | ((uint32_t)f2bf(dgg) << 16);
-        out[2 * e + 1] = (uint32_t)f2bf(df) | ((uint32_t)f2bf(dO) << 16);
-      }
-      if (!prow_ok) { out = u32x4{0u, 0u, 0u, 0u}; dcv = float2{0.f, 0.f}; }
-      *reinterpret_cast<float2*>(dcl + prow * HC + 2 * c) = dcv;
-#ifndef C2_NO_DG
-      __builtin_amdgcn_raw_buffer_store_b128(out, dgr, rowoff + 16 * c, 0, 2);       // aux 2 = nt
-#endif
-      *reinterpret_cast<u32x4*>(Abuf + prow * RSA + 8 * c) = out;
-    }
-  };
   // Exchange of partial sums, accumulator to accumulator.  Column tile tau = wave + 12 * slot is computed by the SAME wave
   // index on both CUs (pass 0 on the CU that does not own it, pass 1 on the owner), so the non-owner's wave ships its
   // accumulators as they lie in registers -- per lane and tile 2 x f32x4 -> 16 bytes of bf16, lane-contiguous = coalesced
@@ -1255,23 +1284,8 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
   // (Round 2 staged the partials row-major in LDS, published the slab, and added the partner's slab into the fp32 LDS
   // buffers in a phase of its own: poll + barrier + exposed load latency + LDS read-modify-write + barrier = 8 % of a
   // layer-step, twice per step.)  Slab (layer, parity, producing cu): [wave 12][tile-of-pass 2][lane 64][16 B] = 24 KB.
-  auto pack_acc = [](const f32x4 (&acc)[2]) {
-    u32x4 o;
-    o[0] = (uint32_t)f2bf(acc[0][0]) | ((uint32_t)f2bf(acc[0][1]) << 16);
-    o[1] = (uint32_t)f2bf(acc[0][2]) | ((uint32_t)f2bf(acc[0][3]) << 16);
-    o[2] = (uint32_t)f2bf(acc[1][0]) | ((uint32_t)f2bf(acc[1][1]) << 16);
-    o[3] = (uint32_t)f2bf(acc[1][2]) | ((uint32_t)f2bf(acc[1][3]) << 16);
-    return o;
-  };
-  auto add_packed = [](f32x4 (&acc)[2], const u32x4 v) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      acc[mt][0] += __uint_as_float(v[2 * mt] << 16);
-      acc[mt][1] += __uint_as_float(v[2 * mt] & 0xffff0000u);
-      acc[mt][2] += __uint_as_float(v[2 * mt + 1] << 16);
-      acc[mt][3] += __uint_as_float(v[2 * mt + 1] & 0xffff0000u);
-    }
-  };
+  // (KS::pack2 / KS::add_packed)
+  //
   // one 16-column tile of accumulators (slot sl of this wave: column tile tau = wave + 12*sl, owned by this CU) -> the
   // fp32 LDS buffer of the outputs
   auto scatter = [&](const f32x4 (&acc)[2], int sl, int layer) {
@@ -1382,21 +1396,13 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
         if constexpr (g == 36) asm volatile("global_load_dword %0, %1, %2 sc1" : "=v"(fl) : "v"(zoff), "s"(pflag) : "memory");
         if constexpr (g == 40) {
           c4_wait_reg(sch.wait_flag(), fl);
-          unsigned spins = 0;
-          while (CF_POLL && fl < (unsigned)ep) {        // (no exit with a request still pending: the compiler would wait for it)
-            if (++spins > SPIN_LIMIT) {
-              if (lane == 0) __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-            fl = __hip_atomic_load(pflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
+          spin_reload(fl, pflag, (unsigned)ep, tmo, lane == 0);
           p0 = load_sc1_b128(xr, slab + pcu * XSL * 2 + my);
           if constexpr (NS1 == 2) p1 = load_sc1_b128(xr, slab + pcu * XSL * 2 + my + 1024);
         }
         // ---- request, post, wait, MFMAs
         if constexpr (g + RD < 48) request(std::integral_constant<int, (g + RD < 48 ? g + RD : 0)>{});
-        if constexpr (g == 47 - RD) fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);
+        if constexpr (g == 47 - RD) ks.fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);
         if constexpr (C2_KBAR > 0 && g > 0 && g % C2_KBAR == 0) asm volatile("s_barrier" ::: "memory");   // keeps the twelve waves in step
         if constexpr (ns == 2) c2_wait(sch.wait_frag(g), b[g % C2_DEPTH][0], b[g % C2_DEPTH][1]);
         else c2_wait(sch.wait_frag(g), b[g % C2_DEPTH][0]);
@@ -1414,14 +1420,14 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
         // ---- tail of pass 0: ship the partner's tiles straight from the accumulators
         if constexpr (g == 23) {
           if constexpr (l2) dy_dma(nt);                 // HEAD: the dY rows of the next (earlier) step
-          store_sc1_b128(xr, slab + cu * XSL * 2 + my, pack_acc(acc[0]));
-          if constexpr (NS0 == 2) store_sc1_b128(xr, slab + cu * XSL * 2 + my + 1024, pack_acc(acc[1]));
+          store_sc1_b128(xr, slab + cu * XSL * 2 + my, KS::pack2(acc[0][0], acc[0][1]));
+          if constexpr (NS0 == 2) store_sc1_b128(xr, slab + cu * XSL * 2 + my + 1024, KS::pack2(acc[1][0], acc[1][1]));
         }
       });
-      add_packed(acc[0], p0);
+      KS::add_packed(acc[0], p0);
       scatter(acc[0], b0, layer);
       if constexpr (NS1 == 2) {
-        add_packed(acc[1], p1);
+        KS::add_packed(acc[1], p1);
         scatter(acc[1], b1, layer);
       }
     };
@@ -1453,8 +1459,8 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
   const T* dh2_src = HEAD ? nullptr : dh2;
 
   Saved sv2, sv1;
-  fetch(sv2, g2, c2, dh2_src, a.Tn - 1, false);
-  fetch(sv1, g1, c1, nullptr, a.Tn - 1, false);
+  ks.fetch(sv2, g2, c2, dh2_src, a.Tn - 1, false);
+  ks.fetch(sv1, g1, c1, nullptr, a.Tn - 1, false);
   if constexpr (HEAD) {
     dy_dma(a.Tn - 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1475,7 +1481,7 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
     // occupies a CU's memory queue for ~12k cycles -- per-CU miss parallelism, not chip-wide HBM contention: starting the
     // clusters an eighth of a step apart changed nothing.)
     // ---------------- LSTM layer 2 (exchange layer index 1)
-    cell_bwd(sv2, dhrec2, !HEAD, dc2, t, dg2T);
+    ks.cell_bwd(sv2, dhrec2, !HEAD, dc2, t, dg2T);
     C2T(0)
 #ifdef C2_RAWBAR
     lds_barrier();                                     // own dgates complete in LDS; everyone done reading dhrec2
@@ -1487,7 +1493,7 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
     layer_gemm(std::integral_constant<int, 1>{}, a.wb2, ep, sv2, g2, c2, dh2_src, t - 1);   // d h1_t (both contributions) and d h2_{t-1} final
     if (t > 0) head_add();                             // HEAD: + dY_{t-1} . Wh (read by the next step's cell phase, barriers between)
     // ---------------- LSTM layer 1 (exchange layer index 0)
-    cell_bwd(sv1, dh1buf, false, dc1, t, dg1T);
+    ks.cell_bwd(sv1, dh1buf, false, dc1, t, dg1T);
     C2T(9)
 #ifdef C2_RAWBAR
     lds_barrier();
@@ -1565,39 +1571,29 @@ struct C4Sched {
 
 template <bool HEAD>
 __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) {
-  typedef bf16_t T;
-  constexpr int MC = C4_MC, H = CB_H, HC = C4_HC, KX = CB_KX, NT = CB_NT;
-  constexpr int RSA = C4_KC + COOP_APAD;                            // A tile row stride (elements): own gate columns only
-  constexpr int TPR = NT / MC, UPT = HC / TPR;              // 12 threads per row, 8 units per thread
+  typedef KSplit<C4_MC, C4_HC, HEAD> KS;
+  typedef typename KS::T T;
+  typedef typename KS::Saved Saved;
+  constexpr int MC = KS::MC, HC = KS::HC, KX = CB_KX, NT = CB_NT, RSA = KS::RSA;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  T* Abuf = reinterpret_cast<T*>(smem_raw);                                          // [64][RSA]   own dgates
-  float* dh1buf = reinterpret_cast<float*>(smem_raw + (size_t)MC * RSA * sizeof(T));  // [64][HC]    d h1 (own units)
-  float* dhrec2 = dh1buf + MC * HC;                                                   // [64][HC]    d h2 recurrent
-  float* dxbuf = dhrec2 + MC * HC;                                                    // [64][16]    own d x columns
-  float* dcbuf = dxbuf + MC * 16;                                                     // [2][64][HC] d c carried from step to step
-  T* whs = reinterpret_cast<T*>(dcbuf + 2 * MC * HC);                                 // HEAD: [HC][16] own units' head weights
-  T* dys = whs + HC * 16;                                                             // HEAD: [64][16]  dY rows of one step
 
   const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, q = lane >> 4, n_ = n, q_ = q;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int cluster, cu;
   coop_ids(C4_G, cluster, cu);
   if (cluster >= a.clusters) return;
-  const long row0 = (long)cluster * MC;
   const long N = a.N;
-  for (int i = tid; i < 4 * MC * HC + MC * 16; i += NT) dh1buf[i] = 0.f;      // d h1, d h2 rec, d x, d c (both layers)
-  for (int i = tid; i < MC * RSA; i += NT) Abuf[i] = 0;
-  if constexpr (HEAD) {
-    const T* whT = reinterpret_cast<const T*>(a.whT);
-    for (int i = tid; i < HC * 16; i += NT) whs[i] = whT[(size_t)(cu * HC + i / 16) * 32 + (i % 16)];
-  }
-
-  const int prow = tid / TPR;
-  const bool prow_ok = row0 + prow < N;
-  // (d c of the thread's 8 units per layer lives in LDS, not in 16 registers: both layers' saved state is in flight at
-  // the end of a GEMM pass since round 3, and the registers are what that costs)
-  float* dc1 = dcbuf;
-  float* dc2 = dcbuf + MC * HC;
+  KS ks;
+  ks.init(smem_raw, N, cluster, cu, a.whT);
+  const long row0 = ks.row0;
+  T* const Abuf = ks.Abuf;
+  float* const dh1buf = ks.dh1buf;
+  float* const dhrec2 = ks.dhrec2;
+  float* const dxbuf = ks.dxbuf;
+  float* const dc1 = ks.dc1;
+  float* const dc2 = ks.dc2;
+  T* const whs = ks.whs;
+  T* const dys = ks.dys;
 
   const T* g1 = reinterpret_cast<const T*>(a.g1);
   const T* g2 = reinterpret_cast<const T*>(a.g2);
@@ -1613,120 +1609,8 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
   gu32* tmo = (gu32*)(a.flags + (size_t)a.clusters * C4_FPC);
   const T* a_lane = Abuf + n * RSA + 8 * q;
   __syncthreads();
+  ks.map_thread();
 
-  // Thread -> data: 12 threads per row; thread (prow, tc) owns the four 16-byte chunks c_j = tc + 12 j (j = 0..3) of the
-  // row's own-unit gate block, i.e. units 2 c_j, 2 c_j + 1.  Consecutive lanes then touch consecutive 16-byte chunks in
-  // LDS and in HBM, so the gate gradients go to dg straight from the registers of the cell backward (coalesced,
-  // non-temporal) and their write acknowledgements return while the rest of the cell phase computes -- issued around
-  // the GEMMs they stalled the weight-fragment ring, because stores and loads share the in-order vmcnt counter.
-  const int tc_ = tid % TPR;
-  struct Saved { u32x4 g[4]; unsigned ct[4], cp[4], dh[4]; };     // packed bf16 pairs: 28 VGPRs
-  auto ld_nt4 = [](const T* p) { return __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(p)); };
-  // carry: sv still holds the (consumed) state of step t + 1, whose "previous cell" c_t is this step's cell state:
-  // moved in registers instead of being read from HBM a second time
-  auto fetch = [&](Saved& sv, const T* gs, const T* cs, const T* dh_ext, int t, bool carry) {
-    if (!prow_ok || t < 0) return;
-#ifdef C2_NO_FETCH
-    return;                               // diagnostic: timing without the saved-state loads (results are garbage)
-#endif
-    int tc = tc_;
-    asm volatile("" : "+v"(tc));          // keep the per-chunk addresses out of the loop-invariant (spilled) set
-    const size_t e = ((size_t)t * N + row0 + prow) * H + cu * HC;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = tc + TPR * j;
-      sv.g[j] = ld_nt16(gs + e * 4 + 8 * c);
-      if (carry) sv.ct[j] = sv.cp[j];
-      else sv.ct[j] = ld_nt4(cs + e + 2 * c);
-      if (t > 0) sv.cp[j] = ld_nt4(cs + e - (size_t)N * H + 2 * c);
-      if (dh_ext) sv.dh[j] = ld_nt4(dh_ext + e + 2 * c);
-    }
-  };
-  // The same for the chunks j0 <= j < j1 only, always with carry, and UNCONDITIONAL (time and row indices are clamped into
-  // the tensors; what a clamped request returns is never used): this is the form used inside the time loop, from the
-  // `post` hooks of the GEMM passes -- a load that only some paths issue makes hipcc's (path-insensitive) wait-count
-  // insertion drain the whole queue in front of the next fragment use.
-  const long prow_c = row0 + prow < N ? row0 + prow : N - 1;
-  auto fetch_part = [&](auto with_dh, Saved& sv, const T* gs, const T* cs, const T* dh_ext, int t, int j0, int j1) {
-#ifdef C2_NO_FETCH
-    return;
-#endif
-    int tc = tc_;
-    asm volatile("" : "+v"(tc));
-    const int tcl = t > 0 ? t : 0, tpl = t > 1 ? t - 1 : 0;
-    const size_t e = ((size_t)tcl * N + prow_c) * H + cu * HC, ep = ((size_t)tpl * N + prow_c) * H + cu * HC;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (j < j0 || j >= j1) continue;
-      const int c = tc + TPR * j;
-      sv.g[j] = ld_nt16(gs + e * 4 + 8 * c);
-      sv.ct[j] = sv.cp[j];
-      sv.cp[j] = ld_nt4(cs + ep + 2 * c);
-      if constexpr (decltype(with_dh)::value) sv.dh[j] = ld_nt4(dh_ext + e + 2 * c);
-    }
-  };
-  auto lo16 = [](unsigned w) { return __uint_as_float(w << 16); };
-  auto hi16 = [](unsigned w) { return __uint_as_float(w & 0xffff0000u); };
-  // cell backward -> gate gradients (bf16, local k = unit*4 + gate): LDS A operand + dg [t*N + row][4H] (own 768 columns)
-  // The phase has NO branch on the row being valid: rows past N compute on clamped (finite) saved state, their gate
-  // gradients are forced to zero for the LDS operand and their dg stores are dropped by the range check of the step's
-  // buffer descriptor (base = row 0 of time t, num_records = one time step).  A store that only some paths issue made
-  // hipcc wait for vmcnt(0) -- i.e. for the acknowledgement of the previous chunk's HBM store -- before every chunk.
-  auto cell_bwd = [&](const Saved& sv, const float* dh_lds, bool has_ext, float* dcl, int t, T* dg) {
-    int tc = tc_;
-    asm volatile("" : "+v"(tc));
-    const __amdgpu_buffer_rsrc_t dgr = make_rsrc(dg + (size_t)t * N * CB_K4, (unsigned)((size_t)N * CB_K4 * sizeof(T)));
-    const int rowoff = (int)(((row0 + prow) * CB_K4 + cu * C4_KC) * sizeof(T));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = tc + TPR * j;
-      u32x4 out;
-      float2 dcv = *reinterpret_cast<const float2*>(dcl + prow * HC + 2 * c);
-      const float2 dhv = *reinterpret_cast<const float2*>(dh_lds + prow * HC + 2 * c);
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const unsigned w0 = sv.g[j][2 * e], w1 = sv.g[j][2 * e + 1];   // (i, g), (f, o) of unit 2c + e
-        const float iv = lo16(w0), gv = hi16(w0), fv = lo16(w1), ov = hi16(w1);
-        const float ct = e ? hi16(sv.ct[j]) : lo16(sv.ct[j]);
-        const float cp = t > 0 ? (e ? hi16(sv.cp[j]) : lo16(sv.cp[j])) : 0.f;
-        float dh = e ? dhv.y : dhv.x;
-        if (has_ext) dh += e ? hi16(sv.dh[j]) : lo16(sv.dh[j]);
-        const float tch = tanh_f(ct);
-        const float dct = dh * ov * (1.f - tch * tch) + (e ? dcv.y : dcv.x);
-        const float dO = dh * tch * ov * (1.f - ov);
-        const float di = dct * gv * iv * (1.f - iv);
-        const float dgg = dct * iv * (1.f - gv * gv);
-        const float df = dct * cp * fv * (1.f - fv);
-        if (e) dcv.y = dct * fv; else dcv.x = dct * fv;
-        out[2 * e] = (uint32_t)f2bf(di) | ((uint32_t)f2bf(dgg) << 16);
-        out[2 * e + 1] = (uint32_t)f2bf(df) | ((uint32_t)f2bf(dO) << 16);
-      }
-      if (!prow_ok) { out = u32x4{0u, 0u, 0u, 0u}; dcv = float2{0.f, 0.f}; }
-      *reinterpret_cast<float2*>(dcl + prow * HC + 2 * c) = dcv;
-#ifndef C2_NO_DG
-      __builtin_amdgcn_raw_buffer_store_b128(out, dgr, rowoff + 16 * c, 0, 2);       // aux 2 = nt
-#endif
-      *reinterpret_cast<u32x4*>(Abuf + prow * RSA + 8 * c) = out;
-    }
-  };
-  auto pack4 = [](const f32x4 (&acc)[4], int half) {
-    u32x4 o;
-    o[0] = (uint32_t)f2bf(acc[2 * half][0]) | ((uint32_t)f2bf(acc[2 * half][1]) << 16);
-    o[1] = (uint32_t)f2bf(acc[2 * half][2]) | ((uint32_t)f2bf(acc[2 * half][3]) << 16);
-    o[2] = (uint32_t)f2bf(acc[2 * half + 1][0]) | ((uint32_t)f2bf(acc[2 * half + 1][1]) << 16);
-    o[3] = (uint32_t)f2bf(acc[2 * half + 1][2]) | ((uint32_t)f2bf(acc[2 * half + 1][3]) << 16);
-    return o;
-  };
-  auto add4 = [](f32x4 (&acc)[4], const u32x4 (&v)[2]) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const unsigned w0 = v[mt >> 1][2 * (mt & 1)], w1 = v[mt >> 1][2 * (mt & 1) + 1];
-      acc[mt][0] += __uint_as_float(w0 << 16);
-      acc[mt][1] += __uint_as_float(w0 & 0xffff0000u);
-      acc[mt][2] += __uint_as_float(w1 << 16);
-      acc[mt][3] += __uint_as_float(w1 & 0xffff0000u);
-    }
-  };
   // this wave's own output tile (accumulators with all partials added) -> the fp32 LDS buffer of the outputs
   auto scatter = [&](const f32x4 (&acc)[4], int layer) {
     int n = n_, q = q_;
@@ -1775,7 +1659,7 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
     constexpr C4Sched<(l2 && HEAD) ? 2 : 0, RD> sch{};
     const bool active = l2 || wave < 7;                // layer 1 has 7 output tiles per owner: waves 7-11 only fetch their saved state
     if (!active) {
-      fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);
+      ks.fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);
     } else {
       const unsigned char* wbase = reinterpret_cast<const unsigned char*>(wpacked) + (size_t)(cu * CB_NW + wave) * C4_WFRAG;
       int ln = lane;
@@ -1800,19 +1684,11 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
                 offc = slabs + (((cu + 1) & 3) * 3 + 2) * C4_SLAB + my;
       unsigned fla = 0, flb = 0;
       u32x4 pa[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}}, pb[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-      auto poll = [&](unsigned& fl, const gu32* pf) {   // (no exit with a request pending)
+      auto poll = [&](unsigned& fl, const gu32* pf) {
 #ifdef C4_DIAG_NOPOLL
         return;                                         // diagnostic: never wait for a partner (garbage results, timing only)
 #endif
-        unsigned spins = 0;
-        while (CF_POLL && fl < (unsigned)ep) {
-          if (++spins > SPIN_LIMIT) {
-            if (lane == 0) __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-          fl = __hip_atomic_load(pf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        spin_reload(fl, pf, (unsigned)ep, tmo, lane == 0);
       };
       bf16x8 b[C4_DEPTH];
       f32x4 acc[4];
@@ -1848,7 +1724,7 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
         if constexpr (k == 0) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if constexpr (p == 3) add4(acc, pa);          // the own tile starts from cu - 1's partials
+          if constexpr (p == 3) KS::add_packed(acc, pa);          // the own tile starts from cu - 1's partials
         }
         bf16x8 af[4];
 #pragma unroll
@@ -1858,23 +1734,23 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
         // ---- tail: ship the finished partner tile
         if constexpr (k == 11 && p < 3) {
           if constexpr (p == 0 && l2) dy_dma(nt);
-          store_sc1_b128(xr, slabs + (cu * 3 + p) * C4_SLAB + my, pack4(acc, 0));
-          store_sc1_b128(xr, slabs + (cu * 3 + p) * C4_SLAB + my + 16, pack4(acc, 1));
+          store_sc1_b128(xr, slabs + (cu * 3 + p) * C4_SLAB + my, KS::pack2(acc[0], acc[1]));
+          store_sc1_b128(xr, slabs + (cu * 3 + p) * C4_SLAB + my + 16, KS::pack2(acc[2], acc[3]));
         }
       });
-      add4(acc, pb);
+      KS::add_packed(acc, pb);
       // cu + 1 shipped these tiles in its pass 2 and raised the epoch two thirds into its own pass: normally there by now.  Its
       // two loads go out FIRST, then the saved state of this layer's next step (younger: the wait for the partials leaves it in flight)
 #ifdef C4_DIAG_NOFINAL
-      fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);      // diagnostic: the last partner's partials are not fetched (garbage results)
+      ks.fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);      // diagnostic: the last partner's partials are not fetched (garbage results)
 #else
       unsigned flc = __hip_atomic_load(pfc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       poll(flc, pfc);
       u32x4 pc[2];
       pc[0] = load_sc1_b128(xr, offc);
       pc[1] = load_sc1_b128(xr, offc + 16);
-      fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);
-      add4(acc, pc);
+      ks.fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);
+      KS::add_packed(acc, pc);
 #endif
       scatter(acc, layer);
     }
@@ -1904,8 +1780,8 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
   const T* dh2_src = HEAD ? nullptr : dh2;
 
   Saved sv2, sv1;
-  fetch(sv2, g2, c2, dh2_src, a.Tn - 1, false);
-  fetch(sv1, g1, c1, nullptr, a.Tn - 1, false);
+  ks.fetch(sv2, g2, c2, dh2_src, a.Tn - 1, false);
+  ks.fetch(sv1, g1, c1, nullptr, a.Tn - 1, false);
   if constexpr (HEAD) {
     dy_dma(a.Tn - 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1918,12 +1794,12 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
   for (int t = a.Tn - 1; t >= 0; --t) {
     const int ep = a.Tn - t;
     // ---------------- LSTM layer 2 (exchange layer index 1)
-    cell_bwd(sv2, dhrec2, !HEAD, dc2, t, dg2T);
+    ks.cell_bwd(sv2, dhrec2, !HEAD, dc2, t, dg2T);
     __syncthreads();                                   // own dgates complete in LDS; everyone done reading dhrec2
     layer_gemm(std::integral_constant<int, 1>{}, a.wb2, ep, sv2, g2, c2, dh2_src, t - 1);
     if (t > 0) head_add();
     // ---------------- LSTM layer 1 (exchange layer index 0)
-    cell_bwd(sv1, dh1buf, false, dc1, t, dg1T);
+    ks.cell_bwd(sv1, dh1buf, false, dc1, t, dg1T);
     __syncthreads();
     layer_gemm(std::integral_constant<int, 0>{}, a.wb1, ep, sv1, g1, c1, nullptr, t - 1);
     int ti = tid;
@@ -1935,70 +1811,84 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
   }
 }
 
-// packed weights of the four-CU backward: element (cu, wave, kk, owner, lane l, j)
-//   local k = 32*kk + 8*(l>>4) + j = ul*4 + g'  (unit u = cu*96 + ul, g' in i,g,f,o -> torch block {0,2,1,3}[g'])
-//   column of (owner O, wave w, n = l&15):
-//   LSTM layer 2: w < 6 -> W_ih[row][96 O + 16 w + n] (input feature h1);  w >= 6 -> W_hh[row][96 O + 16 (w-6) + n]
-//   LSTM layer 1: w < 6 -> W_hh[row][96 O + 16 w + n];  w == 6 -> W_ih[row][16 O + n] (0 for 16 O + n >= I);  w > 6 -> 0
-__global__ void lstm_coop_pack_bwd4_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, bf16_t* __restrict__ out,
-                                           int I, int layer) {
-  const size_t total = (size_t)C4_G * CB_NW * C4_NKK * C4_G * 512;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int j = (int)(e % 8), l = (int)((e / 8) % 64);
-    size_t f = e / 512;
-    const int owner = (int)(f % C4_G); f /= C4_G;
-    const int kk = (int)(f % C4_NKK); f /= C4_NKK;
-    const int wave = (int)(f % CB_NW);
-    const int cu = (int)(f / CB_NW);
-    const int k = 32 * kk + 8 * (l >> 4) + j, ul = k / 4, gp = k % 4;
-    const int tg = gp == 0 ? 0 : (gp == 1 ? 2 : (gp == 2 ? 1 : 3));
-    const int row = tg * CB_H + cu * C4_HC + ul;
-    const int n = l & 15;
-    float v = 0.f;
-    if (layer == 2) {
-      const int c = owner * C4_HC + 16 * (wave % 6) + n;
-      v = wave < 6 ? w_ih[(size_t)row * CB_H + c] : w_hh[(size_t)row * CB_H + c];
-    } else if (wave < 6) {
-      v = w_hh[(size_t)row * CB_H + owner * C4_HC + 16 * wave + n];
-    } else if (wave == 6) {
-      const int xc = owner * 16 + n;
-      v = xc < I ? w_ih[(size_t)row * I + xc] : 0.f;
-    }
-    out[e] = f2bf(v);
-  }
-}
+// Packed weights of the three cooperative backward kernels: MFMA B fragments [cu][wave 12][kk][slot][lane l][j = 8] of
+//   k = 32*kk + 8*(l>>4) + j = ul*4 + g'  (g' in i,g,f,o -> torch block tg = {0,2,1,3}[g']), weight row tg*H + unit(cu, ul).
+// A layout says how many k-steps and slots a (cu, wave) has, which units the k of a CU run over, and which weight column
+// (cu, wave, slot, n = l&15) multiplies: a column of W_ih, of W_hh, or nothing (zero).  W_ih columns >= I are zero.
+struct PackCol { enum Mat { ZERO, IH, HH } mat; int col; };
 
-// packed weights of the K-split backward: element (cu, wave, kk, slot, lane l, j)
-//   local k = 32*kk + 8*(l>>4) + j = ul*4 + g'  (unit u = cu*192 + ul, g' in i,g,f,o -> torch block {0,2,1,3}[g'])
-//   column tile tau = wave + 12*slot, column c = 16*tau + (l&15)
+// output split (lstm2_coop_bwd_kernel): k runs over ALL units, a CU owns output columns
+//   layer 2: slot 0 -> input feature h1 unit cu*192 + 16*wave + n;  slot 1 -> h2 unit (same index)
+//   layer 1: slot 0 -> h1 unit (W_hh);  slot 1 -> x column cu*32 + 16*wave + n for wave < 2 (W_ih), else 0
+struct PackOutSplit {
+  static constexpr int G = CB_G, NKK = CB_NK, SLOTS = 2, UNITS = 0;
+  static __device__ PackCol column(int layer, int cu, int wave, int slot, int n) {
+    const int unit = cu * CB_HC + 16 * wave + n;
+    if (layer == 2) return {slot == 0 ? PackCol::IH : PackCol::HH, unit};
+    if (slot == 0) return {PackCol::HH, unit};
+    if (wave < 2) return {PackCol::IH, cu * 32 + 16 * wave + n};
+    return {PackCol::ZERO, 0};
+  }
+};
+// K-split on CU pairs (lstm2_coop_bwd2_kernel): unit = cu*192 + ul; column tile tau = wave + 12*slot, column c = 16*tau + n
 //   LSTM layer 2: c < 384 -> W_ih[row][c] (input feature h1 unit c); else W_hh[row][c-384]
-//   LSTM layer 1: c < 384 -> W_hh[row][c];  384 <= c < 448 -> W_ih[row][c-384] (0 for c-384 >= I);  tau >= 28 -> 0
-__global__ void lstm_coop_pack_bwd2_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, bf16_t* __restrict__ out,
-                                           int I, int layer) {
-  const size_t total = (size_t)CB_G * CB_NW * C2_NKK * C2_SLOTS * 512;
+//   LSTM layer 1: c < 384 -> W_hh[row][c];  384 <= c < 448 -> W_ih[row][c-384];  tau >= 28 -> 0
+struct PackKSplit2 {
+  static constexpr int G = CB_G, NKK = C2_NKK, SLOTS = C2_SLOTS, UNITS = CB_HC;
+  static __device__ PackCol column(int layer, int cu, int wave, int slot, int n) {
+    const int c = 16 * (wave + CB_NW * slot) + n;
+    if (layer == 2) return c < CB_H ? PackCol{PackCol::IH, c} : PackCol{PackCol::HH, c - CB_H};
+    if (c < CB_H) return {PackCol::HH, c};
+    if (c < CB_H + CB_KX) return {PackCol::IH, c - CB_H};
+    return {PackCol::ZERO, 0};
+  }
+};
+// K-split on four-CU clusters (lstm2_coop_bwd4_kernel): unit = cu*96 + ul; slot = owner O of the output tile
+//   LSTM layer 2: w < 6 -> W_ih[row][96 O + 16 w + n] (input feature h1);  w >= 6 -> W_hh[row][96 O + 16 (w-6) + n]
+//   LSTM layer 1: w < 6 -> W_hh[row][96 O + 16 w + n];  w == 6 -> W_ih[row][16 O + n];  w > 6 -> 0
+struct PackKSplit4 {
+  static constexpr int G = C4_G, NKK = C4_NKK, SLOTS = C4_G, UNITS = C4_HC;
+  static __device__ PackCol column(int layer, int cu, int wave, int owner, int n) {
+    if (layer == 2) return {wave < 6 ? PackCol::IH : PackCol::HH, owner * C4_HC + 16 * (wave % 6) + n};
+    if (wave < 6) return {PackCol::HH, owner * C4_HC + 16 * wave + n};
+    if (wave == 6) return {PackCol::IH, owner * 16 + n};
+    return {PackCol::ZERO, 0};
+  }
+};
+
+// I: columns of w_ih (layer 1: the input features; layer 2: H)
+template <typename L>
+__global__ void lstm_coop_pack_bwd_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, bf16_t* __restrict__ out,
+                                          int I, int layer) {
+  const size_t total = (size_t)L::G * CB_NW * L::NKK * L::SLOTS * 512;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
     const int j = e & 7, l = (e >> 3) & 63;
     size_t f = e >> 9;
-    const int slot = f % C2_SLOTS; f /= C2_SLOTS;
-    const int kk = f % C2_NKK; f /= C2_NKK;
+    const int slot = f % L::SLOTS; f /= L::SLOTS;
+    const int kk = f % L::NKK; f /= L::NKK;
     const int wave = f % CB_NW;
     const int cu = (int)(f / CB_NW);
     const int k = 32 * kk + 8 * (l >> 4) + j;
     const int ul = k >> 2, gp = k & 3;
     const int tg = gp == 0 ? 0 : (gp == 1 ? 2 : (gp == 2 ? 1 : 3));
-    const int row = tg * CB_H + cu * CB_HC + ul;
-    const int c = 16 * (wave + CB_NW * slot) + (l & 15);
+    const int row = tg * CB_H + cu * L::UNITS + ul;
+    const PackCol pc = L::column(layer, cu, wave, slot, l & 15);
     float v = 0.f;
-    if (layer == 2) {
-      v = c < CB_H ? w_ih[(size_t)row * CB_H + c] : w_hh[(size_t)row * CB_H + (c - CB_H)];
-    } else if (c < CB_H) {
-      v = w_hh[(size_t)row * CB_H + c];
-    } else if (c < CB_H + CB_KX) {
-      const int xc = c - CB_H;
-      v = xc < I ? w_ih[(size_t)row * I + xc] : 0.f;
-    }
+    if (pc.mat == PackCol::HH) v = w_hh[(size_t)row * CB_H + pc.col];
+    else if (pc.mat == PackCol::IH && pc.col < I) v = w_ih[(size_t)row * I + pc.col];
     out[e] = f2bf(v);
   }
+}
+
+template <typename L>
+static int pack_bwd(const float* w_ih0, const float* w_hh0, const float* w_ih1, const float* w_hh1, int I, void* wb1, void* wb2,
+                    void* stream) {
+  if (!w_ih0 || !w_hh0 || !w_ih1 || !w_hh1 || !wb1 || !wb2 || I > CB_KX) return NPPC_EBADARG;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(lstm_coop_pack_bwd_kernel<L>, dim3(512), dim3(256), 0, s, w_ih0, w_hh0, (bf16_t*)wb1, I, 1);
+  hipLaunchKernelGGL(lstm_coop_pack_bwd_kernel<L>, dim3(512), dim3(256), 0, s, w_ih1, w_hh1, (bf16_t*)wb2, CB_H, 2);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
 }
 
 // All workgroups of a cooperative launch must be resident at once (partners spin on each other's flags).  The launchers
@@ -2021,6 +1911,23 @@ static int coop_fits(const void* kernel, int threads, size_t smem, int grid, int
   return NPPC_OK;
 }
 
+// The steps every cooperative launch takes: LDS attribute, residency check (coop_fits), epoch words zeroed (the sticky
+// time-out words behind them are not touched), launch.  workgroups = clusters x G; xcd_grid: the grid is rounded up to a
+// multiple of 8 for the XCD-aware placement (coop_ids), spare workgroups exit at once.  per_cu: the caller's cache of
+// the occupancy query, one per kernel instantiation.
+template <typename Args>
+static int coop_launch(void (*kernel)(Args), int threads, size_t smem, int workgroups, bool xcd_grid, unsigned* flags,
+                       size_t flag_words, int& per_cu, hipStream_t s, const Args& a) {
+  const void* k = reinterpret_cast<const void*>(kernel);
+  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return NPPC_ELAUNCH;
+  const int fits = coop_fits(k, threads, smem, workgroups, per_cu);
+  if (fits != NPPC_OK) return fits;
+  if (hipMemsetAsync(flags, 0, flag_words * sizeof(unsigned), s) != hipSuccess) return NPPC_ELAUNCH;
+  hipLaunchKernelGGL(kernel, dim3(xcd_grid ? round_up(workgroups, 8) : workgroups), dim3(threads), smem, s, a);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
 template <typename T, int G, int MT, bool TRAIN, bool HEAD = false>
 static int launch_coop(CoopArgs a, size_t xch_bytes, hipStream_t s) {
   constexpr int KX = 64, H = 384, MC = 16 * MT;
@@ -2031,20 +1938,37 @@ static int launch_coop(CoopArgs a, size_t xch_bytes, hipStream_t s) {
   if (smem > 160 * 1024) return NPPC_EUNSUPPORTED;
   const long need = (long)a.clusters * 2 * 2 * G * MC * (H / G) * sizeof(T);
   if ((long)xch_bytes < need) return NPPC_EBADARG;
-  auto k = lstm2_coop_fwd_kernel<T, G, MT, KX, TRAIN, HEAD>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
-      hipSuccess)
-    return NPPC_ELAUNCH;
-  if (hipMemsetAsync(a.flags, 0, (size_t)a.clusters * 2 * G * sizeof(unsigned), s) != hipSuccess) return NPPC_ELAUNCH;
-  // G = 2: grid rounded up to a multiple of 8 for the XCD-aware placement (coop_ids); spare workgroups exit at once
-  const int grid = G == 2 ? round_up(a.clusters * G, 8) : a.clusters * G;
   static int per_cu = -1;
-  const int fits = coop_fits(reinterpret_cast<const void*>(k), (H / G / 16) * 64, smem, a.clusters * G, per_cu);
-  if (fits != NPPC_OK) return fits;
-  hipLaunchKernelGGL(k, dim3(grid), dim3((H / G / 16) * 64), smem, s, a);
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  return coop_launch(lstm2_coop_fwd_kernel<T, G, MT, KX, TRAIN, HEAD>, (H / G / 16) * 64, smem, a.clusters * G, G == 2, a.flags,
+                     (size_t)a.clusters * 2 * G, per_cu, s, a);
 }
+
+// The cooperative backward kernels share their tensor contract; the K-split ones take the fused head instead of dh2
+static bool bwd_args_ok(const void* g1, const void* g2, const void* c1, const void* c2, const void* dh2, const void* dyt,
+                        const void* whT, const void* wb1, const void* wb2, void* dx, void* dg1, void* dg2, void* xch,
+                        unsigned* flags, long N, int Tn) {
+  return g1 && g2 && c1 && c2 && (dh2 || (dyt && whT)) && wb1 && wb2 && dx && dg1 && dg2 && xch && flags && N > 0 && Tn > 0;
+}
+
+// K-split backward on CU pairs (KS = KSplit<32, 192>, lstm2_coop_bwd2_kernel) or four-CU clusters (KSplit<64, 96>, bwd4)
+template <typename KS>
+static int bwd_ksplit(void (*plain)(CoopBwd2Args), void (*fused)(CoopBwd2Args), long xch_per_cluster, int flags_per_cluster,
+                      const void* g1, const void* g2, const void* c1, const void* c2, const void* dh2, const void* dyt,
+                      const void* whT, const void* wb1, const void* wb2, void* dx, void* dg1, void* dg2, void* xch, long xch_bytes,
+                      unsigned* flags, long N, int Tn, int n_cu, void* stream) {
+  if (!bwd_args_ok(g1, g2, c1, c2, dh2, dyt, whT, wb1, wb2, dx, dg1, dg2, xch, flags, N, Tn)) return NPPC_EBADARG;
+  const int clusters = (int)((N + KS::MC - 1) / KS::MC);
+  if (clusters * KS::G > n_cu) return NPPC_EUNSUPPORTED;     // every workgroup of a cluster must be resident
+  if (xch_bytes < clusters * xch_per_cluster) return NPPC_EBADARG;
+  const bool head = !dh2;
+  CoopBwd2Args a{g1, g2, c1, c2, dh2, wb1, wb2, dx, dg1, dg2, xch, flags, N, Tn, clusters, head ? dyt : nullptr, head ? whT : nullptr};
+  static int per_cu[2] = {-1, -1};                           // (per KS: one static per instantiation of this template)
+  return coop_launch(head ? fused : plain, CB_NT, KS::SMEM, clusters * KS::G, true, flags, (size_t)clusters * flags_per_cluster,
+                     per_cu[head ? 1 : 0], (hipStream_t)stream, a);
+}
+typedef KSplit<CB_MC, CB_HC, false> KSplitPair;   // (host side: the geometry, which the fused head does not change)
+typedef KSplit<C4_MC, C4_HC, false> KSplitQuad;
+constexpr long C2_XCH = 2L * 2 * 2 * CB_MC * C2_XW * 2;     // bytes per cluster: [layer][parity][cu][32][384] bf16
 
 }  // namespace
 
@@ -2142,37 +2066,26 @@ int nppc_lstm2_coop_bwd_packed_elems(long* n) {
 
 int nppc_lstm2_coop_bwd_pack(const float* w_ih0, const float* w_hh0, const float* w_ih1, const float* w_hh1, int I, void* wb1,
                              void* wb2, void* stream) {
-  if (!w_ih0 || !w_hh0 || !w_ih1 || !w_hh1 || !wb1 || !wb2 || I > CB_KX) return NPPC_EBADARG;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(lstm_coop_pack_bwd_kernel, dim3(512), dim3(256), 0, s, w_ih0, w_hh0, (bf16_t*)wb1, I, 1);
-  hipLaunchKernelGGL(lstm_coop_pack_bwd_kernel, dim3(512), dim3(256), 0, s, w_ih1, w_hh1, (bf16_t*)wb2, CB_H, 2);
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  return pack_bwd<PackOutSplit>(w_ih0, w_hh0, w_ih1, w_hh1, I, wb1, wb2, stream);
 }
 
 int nppc_lstm2_bwd_coop(const void* g1, const void* g2, const void* c1, const void* c2, const void* dh2, const void* wb1,
                         const void* wb2, void* dx, void* dg1, void* dg2, void* xch, long xch_bytes, unsigned* flags, long N,
                         int Tn, int n_cu, void* stream) {
-  if (!g1 || !g2 || !c1 || !c2 || !dh2 || !wb1 || !wb2 || !dx || !dg1 || !dg2 || !xch || !flags || N <= 0 || Tn <= 0)
-    return NPPC_EBADARG;
+  if (!dh2 || !bwd_args_ok(g1, g2, c1, c2, dh2, nullptr, nullptr, wb1, wb2, dx, dg1, dg2, xch, flags, N, Tn)) return NPPC_EBADARG;
   const int clusters = (int)((N + CB_MC - 1) / CB_MC);
   if (clusters * CB_G > n_cu) return NPPC_EUNSUPPORTED;      // every workgroup of a cluster must be resident
   if (xch_bytes < (long)clusters * 2 * 2 * 2 * CB_MC * CB_KC * 2) return NPPC_EBADARG;
   CoopBwdArgs a{g1, g2, c1, c2, dh2, wb1, wb2, dx, dg1, dg2, xch, flags, N, Tn, clusters};
-  hipStream_t s = (hipStream_t)stream;
   constexpr size_t smem = (size_t)CB_MC * (CB_K4 + COOP_APAD) * 2 + (size_t)2 * CB_MC * CB_HC * 4;
   static_assert(smem <= 160 * 1024 && smem > 80 * 1024, "one workgroup per CU");
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(lstm2_coop_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)smem) != hipSuccess)
-    return NPPC_ELAUNCH;
-  if (hipMemsetAsync(flags, 0, (size_t)clusters * 2 * CB_G * sizeof(unsigned), s) != hipSuccess) return NPPC_ELAUNCH;
-  hipLaunchKernelGGL(lstm2_coop_bwd_kernel, dim3(round_up(clusters * CB_G, 8)), dim3(CB_NT), smem, s, a);
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  static int per_cu = -1;
+  return coop_launch(lstm2_coop_bwd_kernel, CB_NT, smem, clusters * CB_G, true, flags, (size_t)clusters * 2 * CB_G, per_cu,
+                     (hipStream_t)stream, a);
 }
 
 // K-split cooperative backward (lstm2_coop_bwd2_kernel): same tensor contract as nppc_lstm2_bwd_coop; xch holds
-// clusters*2*2*2*32*384 bf16 partial sums, flags clusters*4 + 4 u32 (zeroed by the launcher)
+// clusters*2*2*2*32*384 bf16 partial sums, flags clusters*48 + 4 u32 (zeroed by the launcher)
 int nppc_lstm2_coop_bwd2_packed_elems(long* n) {
   *n = (long)CB_G * CB_NW * C2_NKK * C2_SLOTS * 512;
   return NPPC_OK;
@@ -2180,41 +2093,23 @@ int nppc_lstm2_coop_bwd2_packed_elems(long* n) {
 
 int nppc_lstm2_coop_bwd2_pack(const float* w_ih0, const float* w_hh0, const float* w_ih1, const float* w_hh1, int I, void* wb1,
                               void* wb2, void* stream) {
-  if (!w_ih0 || !w_hh0 || !w_ih1 || !w_hh1 || !wb1 || !wb2 || I > CB_KX) return NPPC_EBADARG;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(lstm_coop_pack_bwd2_kernel, dim3(512), dim3(256), 0, s, w_ih0, w_hh0, (bf16_t*)wb1, I, 1);
-  hipLaunchKernelGGL(lstm_coop_pack_bwd2_kernel, dim3(512), dim3(256), 0, s, w_ih1, w_hh1, (bf16_t*)wb2, CB_H, 2);
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  return pack_bwd<PackKSplit2>(w_ih0, w_hh0, w_ih1, w_hh1, I, wb1, wb2, stream);
 }
 
-static int bwd_coop2_impl(const void* g1, const void* g2, const void* c1, const void* c2, const void* dh2, const void* dyt,
-                          const void* whT, const void* wb1, const void* wb2, void* dx, void* dg1, void* dg2, void* xch,
-                          long xch_bytes, unsigned* flags, long N, int Tn, int n_cu, void* stream) {
-  if (!g1 || !g2 || !c1 || !c2 || (!dh2 && !(dyt && whT)) || !wb1 || !wb2 || !dx || !dg1 || !dg2 || !xch || !flags || N <= 0 ||
-      Tn <= 0)
-    return NPPC_EBADARG;
-  const int clusters = (int)((N + CB_MC - 1) / CB_MC);
-  if (clusters * CB_G > n_cu) return NPPC_EUNSUPPORTED;      // every workgroup of a cluster must be resident
-  if (xch_bytes < (long)clusters * 2 * 2 * 2 * CB_MC * C2_XW * 2) return NPPC_EBADARG;
-  CoopBwd2Args a{g1, g2, c1, c2, dh2, wb1, wb2, dx, dg1, dg2, xch, flags, N, Tn, clusters, dyt, whT};
-  hipStream_t s = (hipStream_t)stream;
-  constexpr size_t smem = (size_t)CB_MC * (CB_KC + COOP_APAD) * 2 + (size_t)4 * CB_MC * CB_HC * 4 + (size_t)CB_MC * 32 * 4 +
-                          (size_t)(CB_HC + CB_MC) * 16 * 2;
-  static_assert(smem <= 160 * 1024 && smem > 80 * 1024, "one workgroup per CU");
-  const void* k = dyt ? reinterpret_cast<const void*>(lstm2_coop_bwd2_kernel<true>)
-                      : reinterpret_cast<const void*>(lstm2_coop_bwd2_kernel<false>);
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return NPPC_ELAUNCH;
-  static int per_cu[2] = {-1, -1};
-  const int fits = coop_fits(k, CB_NT, smem, clusters * CB_G, per_cu[dyt ? 1 : 0]);
-  if (fits != NPPC_OK) return fits;
-  if (hipMemsetAsync(flags, 0, (size_t)clusters * C2_FPC * sizeof(unsigned), s) != hipSuccess) return NPPC_ELAUNCH;
-  if (dyt)
-    hipLaunchKernelGGL(lstm2_coop_bwd2_kernel<true>, dim3(round_up(clusters * CB_G, 8)), dim3(CB_NT), smem, s, a);
-  else
-    hipLaunchKernelGGL(lstm2_coop_bwd2_kernel<false>, dim3(round_up(clusters * CB_G, 8)), dim3(CB_NT), smem, s, a);
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+int nppc_lstm2_bwd_coop2(const void* g1, const void* g2, const void* c1, const void* c2, const void* dh2, const void* wb1,
+                         const void* wb2, void* dx, void* dg1, void* dg2, void* xch, long xch_bytes, unsigned* flags, long N,
+                         int Tn, int n_cu, void* stream) {
+  if (!dh2) return NPPC_EBADARG;
+  return bwd_ksplit<KSplitPair>(lstm2_coop_bwd2_kernel<false>, lstm2_coop_bwd2_kernel<true>, C2_XCH, C2_FPC, g1, g2, c1, c2, dh2,
+                                nullptr, nullptr, wb1, wb2, dx, dg1, dg2, xch, xch_bytes, flags, N, Tn, n_cu, stream);
+}
+
+int nppc_lstm2_bwd_coop2_head(const void* g1, const void* g2, const void* c1, const void* c2, const void* dyt, const void* whT,
+                              const void* wb1, const void* wb2, void* dx, void* dg1, void* dg2, void* xch, long xch_bytes,
+                              unsigned* flags, long N, int Tn, int n_cu, void* stream) {
+  if (!dyt || !whT) return NPPC_EBADARG;
+  return bwd_ksplit<KSplitPair>(lstm2_coop_bwd2_kernel<false>, lstm2_coop_bwd2_kernel<true>, C2_XCH, C2_FPC, g1, g2, c1, c2,
+                                nullptr, dyt, whT, wb1, wb2, dx, dg1, dg2, xch, xch_bytes, flags, N, Tn, n_cu, stream);
 }
 
 // four-CU K-split backward (lstm2_coop_bwd4_kernel): same tensor contract as nppc_lstm2_bwd_coop2 / _head (dh2 == null
@@ -2230,57 +2125,15 @@ int nppc_lstm2_coop_bwd4_sizes(long N, long* packed_elems, long* xch_bytes, long
 
 int nppc_lstm2_coop_bwd4_pack(const float* w_ih0, const float* w_hh0, const float* w_ih1, const float* w_hh1, int I, void* wb1,
                               void* wb2, void* stream) {
-  if (!w_ih0 || !w_hh0 || !w_ih1 || !w_hh1 || !wb1 || !wb2 || I > CB_KX) return NPPC_EBADARG;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(lstm_coop_pack_bwd4_kernel, dim3(512), dim3(256), 0, s, w_ih0, w_hh0, (bf16_t*)wb1, I, 1);
-  hipLaunchKernelGGL(lstm_coop_pack_bwd4_kernel, dim3(512), dim3(256), 0, s, w_ih1, w_hh1, (bf16_t*)wb2, CB_H, 2);
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  return pack_bwd<PackKSplit4>(w_ih0, w_hh0, w_ih1, w_hh1, I, wb1, wb2, stream);
 }
 
 int nppc_lstm2_bwd_coop4(const void* g1, const void* g2, const void* c1, const void* c2, const void* dh2, const void* dyt,
                          const void* whT, const void* wb1, const void* wb2, void* dx, void* dg1, void* dg2, void* xch,
                          long xch_bytes, unsigned* flags, long N, int Tn, int n_cu, void* stream) {
-  if (!g1 || !g2 || !c1 || !c2 || (!dh2 && !(dyt && whT)) || !wb1 || !wb2 || !dx || !dg1 || !dg2 || !xch || !flags || N <= 0 ||
-      Tn <= 0)
-    return NPPC_EBADARG;
-  const int clusters = (int)((N + C4_MC - 1) / C4_MC);
-  if (clusters * C4_G > n_cu) return NPPC_EUNSUPPORTED;      // every workgroup of a cluster must be resident
-  if (xch_bytes < (long)clusters * C4_XCH) return NPPC_EBADARG;
-  CoopBwd2Args a{g1, g2, c1, c2, dh2, wb1, wb2, dx, dg1, dg2, xch, flags, N, Tn, clusters, dh2 ? nullptr : dyt, dh2 ? nullptr : whT};
-  hipStream_t s = (hipStream_t)stream;
-  constexpr size_t smem = (size_t)C4_MC * (C4_KC + COOP_APAD) * 2 + (size_t)4 * C4_MC * C4_HC * 4 + (size_t)C4_MC * 16 * 4 +
-                          (size_t)(C4_HC + C4_MC) * 16 * 2;
-  static_assert(smem <= 160 * 1024 && smem > 80 * 1024, "one workgroup per CU");
-  const bool head = !dh2;
-  const void* k = head ? reinterpret_cast<const void*>(lstm2_coop_bwd4_kernel<true>)
-                       : reinterpret_cast<const void*>(lstm2_coop_bwd4_kernel<false>);
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return NPPC_ELAUNCH;
-  static int per_cu[2] = {-1, -1};
-  const int fits = coop_fits(k, CB_NT, smem, clusters * C4_G, per_cu[head ? 1 : 0]);
-  if (fits != NPPC_OK) return fits;
-  if (hipMemsetAsync(flags, 0, (size_t)clusters * C4_FPC * sizeof(unsigned), s) != hipSuccess) return NPPC_ELAUNCH;
-  if (head)
-    hipLaunchKernelGGL(lstm2_coop_bwd4_kernel<true>, dim3(round_up(clusters * C4_G, 8)), dim3(CB_NT), smem, s, a);
-  else
-    hipLaunchKernelGGL(lstm2_coop_bwd4_kernel<false>, dim3(round_up(clusters * C4_G, 8)), dim3(CB_NT), smem, s, a);
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
-}
-
-int nppc_lstm2_bwd_coop2(const void* g1, const void* g2, const void* c1, const void* c2, const void* dh2, const void* wb1,
-                         const void* wb2, void* dx, void* dg1, void* dg2, void* xch, long xch_bytes, unsigned* flags, long N,
-                         int Tn, int n_cu, void* stream) {
-  if (!dh2) return NPPC_EBADARG;
-  return bwd_coop2_impl(g1, g2, c1, c2, dh2, nullptr, nullptr, wb1, wb2, dx, dg1, dg2, xch, xch_bytes, flags, N, Tn, n_cu,
-                        stream);
-}
-
-int nppc_lstm2_bwd_coop2_head(const void* g1, const void* g2, const void* c1, const void* c2, const void* dyt, const void* whT,
-                              const void* wb1, const void* wb2, void* dx, void* dg1, void* dg2, void* xch, long xch_bytes,
-                              unsigned* flags, long N, int Tn, int n_cu, void* stream) {
-  if (!dyt || !whT) return NPPC_EBADARG;
-  return bwd_coop2_impl(g1, g2, c1, c2, nullptr, dyt, whT, wb1, wb2, dx, dg1, dg2, xch, xch_bytes, flags, N, Tn, n_cu, stream);
+  return bwd_ksplit<KSplitQuad>(lstm2_coop_bwd4_kernel<false>, lstm2_coop_bwd4_kernel<true>, C4_XCH, C4_FPC, g1, g2, c1, c2, dh2,
+                                dyt, whT, wb1, wb2, dx, dg1, dg2, xch, xch_bytes, flags, N, Tn, n_cu, stream);
 }
 
 }  // extern "C"
+

@@ -183,6 +183,14 @@ def rows_view(flat, Tn, N):
 FUSED_HEAD_MAX_O = 16    # one MFMA column tile
 
 
+def _coop_plan(N, packed, train):
+    """(G, mtile, clusters) of the streaming cooperative forward for N sequences; clusters == 0: no cooperative plan"""
+    G, cmt, ncl = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    H.call("nppc_lstm2_coop_plan", packed.prec, int(train), N, packed.Hd, _n_cu(), ctypes.byref(G), ctypes.byref(cmt),
+           ctypes.byref(ncl))
+    return G.value, cmt.value, ncl.value
+
+
 def lstm2_forward(x_tm, packed, train, mtile=None, head=None):
     """x_tm [Tn][N][kx] (time-major, zero padded to kx) -> dict(h2[, h1, g1, g2, c1, c2]) time-major.
     In train mode h1/h2 are prefixes of zero-padded row buffers (`h1_rows`, `h2_rows`: [Rpad][H]) that the
@@ -220,16 +228,13 @@ def lstm2_forward(x_tm, packed, train, mtile=None, head=None):
         assert mtile != "ws", "the weight-stationary plan does not apply to this shape"
         mtile = None
     if (COOP and mtile is None) or isinstance(mtile, tuple):
-        G, cmt, ncl = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         if isinstance(mtile, tuple):               # (G, mtile) forced by a test / benchmark
-            G.value, cmt.value = mtile
-            ncl.value = (N + 16 * cmt.value - 1) // (16 * cmt.value)
-            assert ncl.value * G.value <= _n_cu(), "cooperative launch needs one CU per workgroup"
+            G, cmt = mtile
+            ncl = (N + 16 * cmt - 1) // (16 * cmt)
+            assert ncl * G <= _n_cu(), "cooperative launch needs one CU per workgroup"
         else:
-            H.call("nppc_lstm2_coop_plan", packed.prec, int(train), N, Hd, _n_cu(), ctypes.byref(G), ctypes.byref(cmt),
-                   ctypes.byref(ncl))
-        if ncl.value > 0:
-            G, cmt, ncl = G.value, cmt.value, ncl.value
+            G, cmt, ncl = _coop_plan(N, packed, train)
+        if ncl > 0:
             xch = workspace(tag + ("coop_xch",), (ncl * 2 * 2 * 16 * cmt * Hd,), dt, dev)
             flags = workspace(tag + ("coop_flags",), (ncl * 2 * G + 4,), torch.int32, dev, zero=True)
             if head is not None and G == 2 and head[1] <= FUSED_HEAD_MAX_O and (not train or cmt == 2):
@@ -273,18 +278,16 @@ def forward_x_ld(N, packed, train, head):
         return packed.kx
     if WS and _ws_wanted(N, packed, train) and ws_plan(N, packed) is not None:
         return packed.kx
-    G, cmt, ncl = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    H.call("nppc_lstm2_coop_plan", packed.prec, 0, N, packed.Hd, _n_cu(), ctypes.byref(G), ctypes.byref(cmt), ctypes.byref(ncl))
-    return 40 if (ncl.value > 0 and G.value == 2) else packed.kx
+    G, _, ncl = _coop_plan(N, packed, False)
+    return 40 if (ncl > 0 and G == 2) else packed.kx
 
 
 def _ws_wanted(N, packed, train):
     """NPPC_LSTM_WS=1|2: whenever the plan applies; "auto": only where the streaming plan would not be CU pairs"""
     if WS_MODE != "auto":
         return True
-    G, cmt, ncl = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    H.call("nppc_lstm2_coop_plan", packed.prec, int(train), N, packed.Hd, _n_cu(), ctypes.byref(G), ctypes.byref(cmt), ctypes.byref(ncl))
-    return ncl.value > 0 and G.value >= 4
+    G, _, ncl = _coop_plan(N, packed, train)
+    return ncl > 0 and G >= 4
 
 
 def ws_plan(N, packed):
@@ -379,39 +382,31 @@ def lstm2_backward(saved, dh2, packed_bwd, kx, coop=None, head=None):
     dg1 = workspace(tag + ("dg1",), (Rp, 4 * Hd), dt, dev, zero=True)
     dg2 = workspace(tag + ("dg2",), (Rp, 4 * Hd), dt, dev, zero=True)
     use_coop = (COOP if coop is None else coop) and packed_bwd.coop and ((N + 31) // 32) * 2 <= _n_cu()
+    st = (saved["g1"], saved["g2"], saved["c1"], saved["c2"])
+
+    def launch(label, G, fn, grads, wb, xch_key, xch_elems, flag_key, flag_words, xch_dt=dt):
+        """what the cooperative launches share: exchange workspace, flag block (epoch words + 4 for the sticky time-outs), timed call"""
+        xch = workspace(tag + xch_key, (xch_elems,), xch_dt, dev)
+        flags = workspace(tag + flag_key, (flag_words,), torch.int32, dev, zero=True)
+        _timed((label, 1, N, Tn, G), lambda: H.call(fn, *st, *grads, *wb, dx, dg1, dg2, xch, xch.numel() * xch.element_size(),
+                                                   flags, N, Tn, _n_cu(), H.stream()))
+        return dx, dg1, dg2
+
+    ncl = (N + 31) // 32
     if use_coop and COOP_BWD_KSPLIT and BWD_G4 != "0" and ((N + 63) // 64) * 4 <= _n_cu():
         npk, nx, nf = ctypes.c_long(), ctypes.c_long(), ctypes.c_long()
         H.call("nppc_lstm2_coop_bwd4_sizes", N, ctypes.byref(npk), ctypes.byref(nx), ctypes.byref(nf))
-        xch = workspace(tag + ("coop_xch4",), (nx.value,), torch.uint8, dev)
-        flags = workspace(tag + ("g4", "coop_flags"), (nf.value,), torch.int32, dev, zero=True)
-        dyt, whT = head if head is not None else (None, None)
-        _timed(("lstm2_bwd_coop_ksplit_g4", 1, N, Tn, 4), lambda: H.call(
-            "nppc_lstm2_bwd_coop4", saved["g1"], saved["g2"], saved["c1"], saved["c2"], dh2 if head is None else None, dyt, whT,
-            packed_bwd.k4wb1, packed_bwd.k4wb2, dx, dg1, dg2, xch, nx.value, flags, N, Tn, _n_cu(), H.stream()))
-        return dx, dg1, dg2
-    if use_coop and COOP_BWD_KSPLIT:
-        ncl = (N + 31) // 32
-        xch = workspace(tag + ("coop_xch",), (ncl * 2 * 2 * 2 * 32 * 384,), dt, dev)
-        flags = workspace(tag + ("coop_flags",), (ncl * 48 + 4,), torch.int32, dev, zero=True)   # [cluster][layer][cu][wave] epochs + time-out words
-        if head is not None:
-            dyt, whT = head
-            _timed(("lstm2_bwd_coop_ksplit", 1, N, Tn, 2), lambda: H.call(
-                "nppc_lstm2_bwd_coop2_head", saved["g1"], saved["g2"], saved["c1"], saved["c2"], dyt, whT, packed_bwd.kwb1,
-                packed_bwd.kwb2, dx, dg1, dg2, xch, xch.numel() * xch.element_size(), flags, N, Tn, _n_cu(), H.stream()))
-            return dx, dg1, dg2
-        _timed(("lstm2_bwd_coop_ksplit", 1, N, Tn, 2), lambda: H.call(
-            "nppc_lstm2_bwd_coop2", saved["g1"], saved["g2"], saved["c1"], saved["c2"], dh2, packed_bwd.kwb1, packed_bwd.kwb2,
-            dx, dg1, dg2, xch, xch.numel() * xch.element_size(), flags, N, Tn, _n_cu(), H.stream()))
-        return dx, dg1, dg2
+        grads = (dh2, None, None) if head is None else (None,) + tuple(head)
+        return launch("lstm2_bwd_coop_ksplit_g4", 4, "nppc_lstm2_bwd_coop4", grads, (packed_bwd.k4wb1, packed_bwd.k4wb2),
+                      ("coop_xch4",), nx.value, ("g4", "coop_flags"), nf.value, xch_dt=torch.uint8)
+    if use_coop and COOP_BWD_KSPLIT:      # partial sums [cluster][layer][parity][cu][32][384]; epochs [cluster][layer][cu][wave]
+        fn, grads = ("nppc_lstm2_bwd_coop2", (dh2,)) if head is None else ("nppc_lstm2_bwd_coop2_head", tuple(head))
+        return launch("lstm2_bwd_coop_ksplit", 2, fn, grads, (packed_bwd.kwb1, packed_bwd.kwb2),
+                      ("coop_xch",), ncl * 2 * 2 * 2 * 32 * 384, ("coop_flags",), ncl * 48 + 4)
     assert head is None, "the fused head backward needs the K-split cooperative kernel"
-    if use_coop:
-        ncl = (N + 31) // 32
-        xch = workspace(tag + ("coop_xch",), (ncl * 2 * 2 * 2 * 32 * 768,), dt, dev)
-        flags = workspace(tag + ("coop_flags",), (ncl * 4 + 4,), torch.int32, dev, zero=True)
-        _timed(("lstm2_bwd_coop_g2", 1, N, Tn, 2), lambda: H.call(
-            "nppc_lstm2_bwd_coop", saved["g1"], saved["g2"], saved["c1"], saved["c2"], dh2, packed_bwd.cwb1, packed_bwd.cwb2,
-            dx, dg1, dg2, xch, xch.numel() * xch.element_size(), flags, N, Tn, _n_cu(), H.stream()))
-        return dx, dg1, dg2
+    if use_coop:                          # gate gradients [cluster][layer][parity][cu][32][768]; epochs [cluster][layer][cu]
+        return launch("lstm2_bwd_coop_g2", 2, "nppc_lstm2_bwd_coop", (dh2,), (packed_bwd.cwb1, packed_bwd.cwb2),
+                      ("coop_xch",), ncl * 2 * 2 * 2 * 32 * 768, ("coop_flags",), ncl * 4 + 4)
     _timed(("lstm2_bwd", 1, N, Tn, 1), lambda: H.call(
         "nppc_lstm2_bwd", packed_bwd.prec, saved["g1"], saved["g2"], saved["c1"], saved["c2"], dh2, packed_bwd.wb1,
         packed_bwd.wb2, dx, dg1, dg2, N, Tn, packed_bwd.I, Hd, H.stream()))
