@@ -22,6 +22,23 @@ typedef __attribute__((ext_vector_type(8))) float f32x8;
     if (e__ != hipSuccess) return NPPC_ELAUNCH;              \
   } while (0)
 
+// typed launch: KERNEL<bf16_t> or KERNEL<float> with the void* operands cast by the ARGS expression (uses `TT`); the
+// enclosing function has a `stream` and returns NPPC_EBADARG for any other precision, NPPC_ELAUNCH if the launch failed
+#define LAUNCH_TS(prec, KERNEL, GRID, BLOCK, SMEM, ...)                                           \
+  do {                                                                                            \
+    if ((prec) == NPPC_PREC_BF16) {                                                               \
+      typedef bf16_t TT;                                                                          \
+      hipLaunchKernelGGL(KERNEL<TT>, GRID, BLOCK, SMEM, (hipStream_t)stream, __VA_ARGS__);        \
+    } else if ((prec) == NPPC_PREC_F32) {                                                         \
+      typedef float TT;                                                                           \
+      hipLaunchKernelGGL(KERNEL<TT>, GRID, BLOCK, SMEM, (hipStream_t)stream, __VA_ARGS__);        \
+    } else {                                                                                      \
+      return NPPC_EBADARG;                                                                        \
+    }                                                                                             \
+    NPPC_CHECK_LAUNCH();                                                                          \
+  } while (0)
+#define LAUNCH_T(prec, KERNEL, GRID, ...) LAUNCH_TS(prec, KERNEL, GRID, dim3(256), 0, __VA_ARGS__)
+
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {
   __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32: round-to-nearest-even, NaN stays NaN
@@ -119,6 +136,16 @@ template <> __device__ __forceinline__ void store8<float>(float* p, const float 
 // once-read streams, never on slices every CU re-reads).
 __device__ __forceinline__ u32x4 ld_nt16(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
 __device__ __forceinline__ void st_nt16(void* p, u32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p)); }
+
+// LDS-DMA: 16 bytes per lane global -> LDS (lds_addr + 16 * lane; lds_addr wave-uniform, carried in M0, which is saved and
+// restored).  Through inline asm: issued with the builtin, hipcc treats every later ds_read as a possible reader of the pending
+// LDS write and puts s_waitcnt vmcnt(0) in front of it, which drains a ring of such requests.  Hidden from the compiler, the
+// completion is counted by hand by the caller (an LDS-DMA has no VGPR destination, so it is register-safe).
+__device__ __forceinline__ void lds_dma16(const void* src_lane, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(src_lane), "s"(lds_addr) : "memory");
+}
 
 // v_exp_f32 / v_rcp_f32 based (1 ulp each): absolute error ~1e-7, saturate cleanly for |x| large
 __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }

@@ -1005,10 +1005,7 @@ __device__ __forceinline__ void c4_wait_reg(int m, unsigned& x) {
 // 16 bytes per lane global -> LDS (lds_base + 16 * lane), through inline asm: invisible to the compiler's wait insertion, which
 // would otherwise drain the fragment ring in front of the next LDS read; completion is covered by a later counted wait
 __device__ __forceinline__ void c4_lds_dma16(const void* src_lane, unsigned lds_base /* wave-uniform */) {
-  unsigned keep;
-  const unsigned lb = __builtin_amdgcn_readfirstlane(lds_base);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src_lane), "s"(lb) : "memory");
+  lds_dma16(src_lane, __builtin_amdgcn_readfirstlane(lds_base));
 }
 
 // ---- front end of the K-split backward kernels ------------------------------------------------------------------------

@@ -8,155 +8,41 @@
 // on bf16 (or exact-f32) MFMA 16x16 tiles, with bias / PReLU / GroupNorm statistics / residual fused in the epilogue.
 #include <cstdlib>
 #include "common.h"
+#include "mfma_tile.h"
 #include "nppc_hip.h"
 
 namespace {
 
-enum { EPI_PLAIN = 0, EPI_PRELU_STATS = 1, EPI_RESIDUAL = 2, EPI_RELU = 3, EPI_PLAIN_F32 = 4, EPI_MASK_POS = 5, EPI_RESIDUAL_GN = 6 };
-// EPI_RESIDUAL_GN: the GroupNorm in front of the product is folded into it.  With a = (y - mean_b) * rstd_b * gamma + beta,
-//   a W^T = rstd_b * (y Wg^T) - mean_b * rstd_b * v + u,   Wg[n][k] = gamma[k] W[n][k],  v[n] = sum_k Wg[n][k],  u[n] = sum_k beta[k] W[n][k] + bias[n]
-// so the GEMM reads the un-normalised y (B operand = Wg, `bias` = u, `gnv` = v, `stats` = the per-sample (sum, sumsq) of y)
-// and the normalised activation is never written (nppc_tcn_pack_sconv builds Wg, u, v).
+// (GemmArgs, the EPI_* epilogues, the main loops and the per-element epilogue: mfma_tile.h)
 
-struct GemmArgs {
-  const void* A; long lda; long strideA;   // [R][lda]   (strides in elements, per batch z)
-  const void* B; long ldb; long strideB;   // [N][ldb]
-  void* C; long ldc; long strideC;         // [R][ldc]
-  const float* bias; long strideBias;      // [N] or null
-  const void* res; long ldres; long strideRes;  // residual [R][ldres] (EPI_RESIDUAL)
-  const float* slope; long strideSlope;    // PReLU slope (1 value)
-  double* stats; long strideStats;         // [R/Tp][2] (sum, sumsq) (EPI_PRELU_STATS)
-  int R, N, K;                             // R % 128 == 0, N % 64 == 0, K % 32 == 0
-  int Tp, Tv;                              // rows with (row % Tp) >= Tv are padding: forced to zero
-  int Nv;                                  // columns >= Nv are padding: forced to zero
-  int relu_in;                             // apply ReLU to A on load (TCN trailing nn.ReLU before the Linear)
-  int ksplit;                              // >1: blockIdx.z = batch*ksplit + s; slice s covers K elements [s*K, (s+1)*K)
-  const float* gnv; long strideGnv;        // EPI_RESIDUAL_GN: v[N]; `stats` then holds the GroupNorm (sum, sumsq) per sample
-  double gcnt; float geps;                 // ... elements per sample, epsilon
-  int staged;                              // LDS kernels, residual / mask epilogues: coalesced epilogue through LDS (ldc, ldres % 8 == 0)
-  float* colpart; long strideColpart;      // optional (LDS kernels, EPI_RESIDUAL / EPI_MASK_POS): column sums of each 128-row tile of
-                                           // the OUTPUT, [z][R/128][N] fp32 -- the bias gradient of the layer that consumes C as its
-                                           // upstream gradient, without a pass of its own over C
-};
-
-template <typename T> __device__ __forceinline__ typename Frag<T>::type relu_frag(typename Frag<T>::type f);
-template <> __device__ __forceinline__ bf16x8 relu_frag<bf16_t>(bf16x8 f) {
-  u32x4 v = __builtin_bit_cast(u32x4, f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    unsigned x = v[i];
-    if (x & 0x8000u) x &= 0xffff0000u;
-    if (x & 0x80000000u) x &= 0x0000ffffu;
-    v[i] = x;
-  }
-  return __builtin_bit_cast(bf16x8, v);
-}
-template <> __device__ __forceinline__ f32x8 relu_frag<float>(f32x8 f) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = fmaxf(f[i], 0.f);
-  return f;
-}
-
-// 256 threads = 4 waves stacked over rows; wave tile 32 x 64, block tile 128 x 64.
+// 256 threads = 4 waves stacked over rows; wave tile 32 x 64, block tile 128 x 64 (nt_reg_mainloop).
 template <typename T, int EPI>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs g) {
-  typedef typename Frag<T>::type frag;
   const int ks = g.ksplit > 1 ? g.ksplit : 1;
   const int z = blockIdx.z / ks, ksl = blockIdx.z % ks;
   const T* A = reinterpret_cast<const T*>(g.A) + (size_t)z * g.strideA + (size_t)ksl * g.K;
   const T* B = reinterpret_cast<const T*>(g.B) + (size_t)z * g.strideB + (size_t)ksl * g.K;
-  T* C = reinterpret_cast<T*>(g.C) + (size_t)blockIdx.z * g.strideC;
-  float* Cf = reinterpret_cast<float*>(g.C) + (size_t)blockIdx.z * g.strideC;   // EPI_PLAIN_F32: fp32 output (split-K slabs)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, q = lane >> 4;
   const int r0 = blockIdx.x * 128 + wave * 32, c0 = blockIdx.y * 64;
   const T* ap = A + (size_t)(r0 + n) * g.lda + 8 * q;
   const T* bp = B + (size_t)(c0 + n) * g.ldb + 8 * q;
   f32x4 acc[2][4];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nk = g.K / 32;
-  frag a0[2], b0[4], a1[2], b1[4];
-  auto ld = [&](frag(&a)[2], frag(&b)[4], int kk) {
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) a[mi] = load_frag<T>(ap + (size_t)16 * mi * g.lda + 32 * kk);
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) b[ni] = load_frag<T>(bp + (size_t)16 * ni * g.ldb + 32 * kk);
-  };
-  auto mm = [&](frag(&a)[2], frag(&b)[4]) {
-    if (g.relu_in) {
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) a[mi] = relu_frag<T>(a[mi]);
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mma16(a[mi], b[ni], acc[mi][ni]);
-  };
-  ld(a0, b0, 0);
-  int kk = 0;
-#pragma unroll 1
-  for (; kk + 2 < nk; kk += 2) {
-    ld(a1, b1, kk + 1);
-    mm(a0, b0);
-    ld(a0, b0, kk + 2);
-    mm(a1, b1);
-  }
-  if (kk + 1 < nk) {
-    ld(a1, b1, kk + 1);
-    mm(a0, b0);
-    mm(a1, b1);
-  } else {
-    mm(a0, b0);
-  }
+  nt_reg_mainloop<T>(acc, g.K / 32, g.lda, g.ldb, [&](int kk) { return ap + 32 * kk; }, [&](int kk) { return bp + 32 * kk; },
+                     g.relu_in);
 
   // ---- epilogue: element (row r0+16mi+4q+j, col c0+16ni+n)
-  const float* bias = g.bias ? g.bias + (size_t)z * g.strideBias : nullptr;
-  float slope = 0.f;
-  if (EPI == EPI_PRELU_STATS) slope = g.slope[(size_t)z * g.strideSlope];
-  float gn_rstd = 1.f, gn_mr = 0.f;        // EPI_RESIDUAL_GN: one sample per 128-row tile (Tp % 128 == 0)
-  const float* gnv = nullptr;
-  if (EPI == EPI_RESIDUAL_GN) {
-    const double* st = g.stats + (size_t)z * g.strideStats + (size_t)((blockIdx.x * 128) / g.Tp) * 2;
-    const double m = st[0] / g.gcnt, var = st[1] / g.gcnt - m * m;
-    gn_rstd = (float)(1.0 / sqrt((var > 0 ? var : 0) + (double)g.geps));
-    gn_mr = (float)m * gn_rstd;
-    gnv = g.gnv + (size_t)z * g.strideGnv;
-  }
+  const NtEpilogue<T, EPI> ep(g, z, blockIdx.x * 128);
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) {
     const int col = c0 + 16 * ni + n;
-    const bool cvalid = col < g.Nv;
-    float bv = (bias && cvalid) ? bias[col] : 0.f;
-    if (EPI == EPI_RESIDUAL_GN && cvalid) bv -= gn_mr * gnv[col];
+    const float bv = ep.col_bias(col);
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int row = r0 + 16 * mi + 4 * q + j;
-        const bool valid = cvalid && (row % g.Tp) < g.Tv;
-        float v = (EPI == EPI_RESIDUAL_GN ? gn_rstd * acc[mi][ni][j] : acc[mi][ni][j]) + bv;
-        if (EPI == EPI_PRELU_STATS) v = v > 0.f ? v : slope * v;
-        if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-        if (EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_GN) {
-          const T* res = reinterpret_cast<const T*>(g.res) + (size_t)z * g.strideRes;
-          v += to_f32<T>(res[(size_t)row * g.ldres + col]);
-        }
-        if (EPI == EPI_MASK_POS) {
-          const T* res = reinterpret_cast<const T*>(g.res) + (size_t)z * g.strideRes;
-          if (!(to_f32<T>(res[(size_t)row * g.ldres + col]) > 0.f)) v = 0.f;
-        }
-        if (!valid) v = 0.f;
-        if (EPI == EPI_PLAIN_F32) {
-          Cf[(size_t)row * g.ldc + col] = v;
-          continue;
-        }
-        const T o = from_f32<T>(v);
-        C[(size_t)row * g.ldc + col] = o;
-        if (EPI == EPI_PRELU_STATS) {
-          const float vo = to_f32<T>(o);   // statistics of the STORED (rounded) activations
+        const float vo = ep.put(acc[mi][ni][j], bv, r0 + 16 * mi + 4 * q + j, col);
+        if (EPI == EPI_PRELU_STATS) {        // statistics of the STORED (rounded) activations
           s1 += vo;
           s2 += vo * vo;
         }
@@ -173,14 +59,11 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs g) {
 }
 
 // LDS-staged variant of gemm_nt_kernel (same arguments and epilogues) for K-slices that are multiples of the 128-byte
-// stage (64 bf16 / 32 f32): 256 threads = 2 x 2 waves, block tile 128 x BN, double-buffered XOR-swizzled LDS with register
-// staging, one barrier per stage.  Operand tiles are read from HBM/L2 once per workgroup instead of once per wave.
+// stage (64 bf16 / 32 f32): 256 threads = 2 x 2 waves, block tile 128 x BN (nt_lds_mainloop).
 template <typename T, int EPI, int BN>
 __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
-  typedef typename Frag<T>::type frag;
   constexpr int EPC = 16 / (int)sizeof(T);
   constexpr int BK = 8 * EPC;
-  constexpr int KS = BK / 32;
   constexpr int NJ = BN / 32;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2][(128 + BN) * 128];
   __shared__ double red[2][4];
@@ -192,7 +75,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
   const int srow = tid >> 3, sc = tid & 7;
   const T* ga = reinterpret_cast<const T*>(g.A) + (size_t)z * g.strideA + (size_t)ksl * g.K + (long)(m0 + srow) * g.lda + sc * EPC;
   const T* gb = reinterpret_cast<const T*>(g.B) + (size_t)z * g.strideB + (size_t)ksl * g.K + (long)(n0 + srow) * g.ldb + sc * EPC;
-  const int soff = srow * 128 + ((sc ^ (srow & 7)) << 4);
   // diagnostic builds (tools/diag/nt_variants.py; timing only): NT_DIAG_NOLOOP = one K stage instead of K / BK (what the launch,
   // the first stage's latency and the epilogue cost without the main loop), NT_DIAG_NOEPI = no epilogue (one store per lane).
   // Measured at the TCN shapes (profiles/r04_nt_variants.txt): 38 us = 12 us launch + first stage, 14 us for the other eight
@@ -205,77 +87,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
 #else
   const int nstage = g.K / BK;
 #endif
-  uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-#define NGLOAD(k0)                                                            \
-  {                                                                           \
-    ra0 = *reinterpret_cast<const uint4*>(ga + (k0));                         \
-    ra1 = *reinterpret_cast<const uint4*>(ga + 32 * g.lda + (k0));            \
-    ra2 = *reinterpret_cast<const uint4*>(ga + 64 * g.lda + (k0));            \
-    ra3 = *reinterpret_cast<const uint4*>(ga + 96 * g.lda + (k0));            \
-    rb0 = *reinterpret_cast<const uint4*>(gb + (k0));                         \
-    rb1 = *reinterpret_cast<const uint4*>(gb + 32 * g.ldb + (k0));            \
-    if constexpr (NJ == 4) {                                                  \
-      rb2 = *reinterpret_cast<const uint4*>(gb + 64 * g.ldb + (k0));          \
-      rb3 = *reinterpret_cast<const uint4*>(gb + 96 * g.ldb + (k0));          \
-    }                                                                         \
-  }
-#define NLSTORE(buf)                                                          \
-  {                                                                           \
-    *reinterpret_cast<uint4*>(&lds[buf][soff]) = ra0;                         \
-    *reinterpret_cast<uint4*>(&lds[buf][soff + 32 * 128]) = ra1;              \
-    *reinterpret_cast<uint4*>(&lds[buf][soff + 64 * 128]) = ra2;              \
-    *reinterpret_cast<uint4*>(&lds[buf][soff + 96 * 128]) = ra3;              \
-    *reinterpret_cast<uint4*>(&lds[buf][128 * 128 + soff]) = rb0;             \
-    *reinterpret_cast<uint4*>(&lds[buf][128 * 128 + soff + 32 * 128]) = rb1;  \
-    if constexpr (NJ == 4) {                                                  \
-      *reinterpret_cast<uint4*>(&lds[buf][128 * 128 + soff + 64 * 128]) = rb2; \
-      *reinterpret_cast<uint4*>(&lds[buf][128 * 128 + soff + 96 * 128]) = rb3; \
-    }                                                                         \
-  }
-  auto lfrag = [&](const unsigned char* base, int row, int ks) -> frag {
-    if constexpr (sizeof(T) == 2) {
-      const int c = 4 * ks + q;
-      return *reinterpret_cast<const frag*>(base + row * 128 + ((c ^ (row & 7)) << 4));
-    } else {
-      const int c0 = 2 * q, c1 = 2 * q + 1;
-      const float4 lo = *reinterpret_cast<const float4*>(base + row * 128 + ((c0 ^ (row & 7)) << 4));
-      const float4 hi = *reinterpret_cast<const float4*>(base + row * 128 + ((c1 ^ (row & 7)) << 4));
-      frag f;
-      f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
-      return f;
-    }
-  };
   f32x4 acc[4][NJ];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  NGLOAD(0)
-  NLSTORE(0)
-  __syncthreads();
-  for (int s = 0; s < nstage; ++s) {
-    const int buf = s & 1;
-    if (s + 1 < nstage) NGLOAD((s + 1) * BK)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      frag af[4], bf[NJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        af[i] = lfrag(lds[buf], wm * 64 + 16 * i + n, ks);
-        if (g.relu_in) af[i] = relu_frag<T>(af[i]);
-      }
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bf[j] = lfrag(lds[buf] + 128 * 128, wn * (BN / 2) + 16 * j + n, ks);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = mma16(af[i], bf[j], acc[i][j]);
-    }
-    if (s + 1 < nstage) NLSTORE(buf ^ 1)
-    __syncthreads();
-  }
-#undef NGLOAD
-#undef NLSTORE
+  nt_lds_mainloop<T, BN>(acc, &lds[0][0], nstage, g.lda, g.ldb, [&](int s) { return ga + s * BK; }, [&](int s) { return gb + s * BK; },
+                         g.relu_in);
 #ifdef NT_DIAG_NOEPI
   {
     float v = 0.f;
@@ -288,20 +102,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
   }
 #endif
   // ---- epilogue (identical to gemm_nt_kernel): element (row m0 + wm*64 + 16 i + 4 q + r, col n0 + wn*BN/2 + 16 j + n)
-  T* C = reinterpret_cast<T*>(g.C) + (size_t)blockIdx.z * g.strideC;
-  float* Cf = reinterpret_cast<float*>(g.C) + (size_t)blockIdx.z * g.strideC;
-  const float* bias = g.bias ? g.bias + (size_t)z * g.strideBias : nullptr;
-  float slope = 0.f;
-  if (EPI == EPI_PRELU_STATS) slope = g.slope[(size_t)z * g.strideSlope];
-  float gn_rstd = 1.f, gn_mr = 0.f;        // EPI_RESIDUAL_GN: one sample per 128-row tile (Tp % 128 == 0)
-  const float* gnv = nullptr;
-  if (EPI == EPI_RESIDUAL_GN) {
-    const double* st = g.stats + (size_t)z * g.strideStats + (size_t)(m0 / g.Tp) * 2;
-    const double m = st[0] / g.gcnt, var = st[1] / g.gcnt - m * m;
-    gn_rstd = (float)(1.0 / sqrt((var > 0 ? var : 0) + (double)g.geps));
-    gn_mr = (float)m * gn_rstd;
-    gnv = g.gnv + (size_t)z * g.strideGnv;
-  }
+  const NtEpilogue<T, EPI> ep(g, z, m0);
   constexpr bool HAS_RES = EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_GN || EPI == EPI_MASK_POS;
   // round 4: the plain / PReLU + statistics / ReLU epilogues take the same coalesced route (conv1x1 forward, dA2 of the backward,
   // the fc layer: 64 two-byte stores per lane were 12-15 of a launch's 38 us, profiles/r04_nt_variants.txt)
@@ -319,7 +120,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
       constexpr int HALVES = (128 * LD * 4 <= (int)sizeof(lds)) ? 1 : 2;   // BN = 128: two passes of 64 rows
       constexpr int ROWS = 128 / HALVES;
       float* ot = reinterpret_cast<float*>(&lds[0][0]);
-      [[maybe_unused]] const T* res = HAS_RES ? reinterpret_cast<const T*>(g.res) + (size_t)z * g.strideRes : nullptr;
       float csum[VE];
       float t1 = 0.f, t2 = 0.f;                 // EPI_PRELU_STATS: sums of the stored (rounded) activations
 #pragma unroll
@@ -330,15 +130,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
           for (int j = 0; j < NJ; ++j) {
             const int col = n0 + wn * (BN / 2) + 16 * j + n;
             const bool cvalid = col < g.Nv;
-            float bv = (bias && cvalid) ? bias[col] : 0.f;
-            if (EPI == EPI_RESIDUAL_GN && cvalid) bv -= gn_mr * gnv[col];
+            const float bv = ep.col_bias(col);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
-                float pv = (EPI == EPI_RESIDUAL_GN ? gn_rstd * acc[i][j][r] : acc[i][j][r]) + bv;
-                if (EPI == EPI_PRELU_STATS) pv = pv > 0.f ? pv : slope * pv;
-                if (EPI == EPI_RELU) pv = fmaxf(pv, 0.f);
+                const float pv = ep.act(acc[i][j][r], bv);
                 ot[((HALVES == 1 ? wm * 64 : 0) + 16 * i + 4 * q + r) * LD + wn * (BN / 2) + 16 * j + n] = pv;
                 if (EPI == EPI_PRELU_STATS) {
                   // statistics of the stored (rounded, masked) activations, summed per lane in the accumulator layout and in
@@ -359,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
           float v[VE], rv[VE];
           const float4 lo = *reinterpret_cast<const float4*>(ot + rl * LD + cc), hi = *reinterpret_cast<const float4*>(ot + rl * LD + cc + 4);
           v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-          if constexpr (HAS_RES) load8<T>(res + (size_t)row * g.ldres + col, rv);
+          if constexpr (HAS_RES) load8<T>(ep.res + (size_t)row * g.ldres + col, rv);
 #pragma unroll
           for (int e = 0; e < VE; ++e) {
             float x = v[e];
@@ -411,36 +208,14 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
   for (int j = 0; j < NJ; ++j) {
     cs[j] = 0.f;
     const int col = n0 + wn * (BN / 2) + 16 * j + n;
-    const bool cvalid = col < g.Nv;
-    float bv = (bias && cvalid) ? bias[col] : 0.f;
-    if (EPI == EPI_RESIDUAL_GN && cvalid) bv -= gn_mr * gnv[col];
+    const float bv = ep.col_bias(col);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm * 64 + 16 * i + 4 * q + r;
-        const bool valid = cvalid && (row % g.Tp) < g.Tv;
-        float v = (EPI == EPI_RESIDUAL_GN ? gn_rstd * acc[i][j][r] : acc[i][j][r]) + bv;
-        if (EPI == EPI_PRELU_STATS) v = v > 0.f ? v : slope * v;
-        if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-        if (EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_GN) {
-          const T* res = reinterpret_cast<const T*>(g.res) + (size_t)z * g.strideRes;
-          v += to_f32<T>(res[(size_t)row * g.ldres + col]);
-        }
-        if (EPI == EPI_MASK_POS) {
-          const T* res = reinterpret_cast<const T*>(g.res) + (size_t)z * g.strideRes;
-          if (!(to_f32<T>(res[(size_t)row * g.ldres + col]) > 0.f)) v = 0.f;
-        }
-        if (!valid) v = 0.f;
-        if (EPI == EPI_PLAIN_F32) {
-          Cf[(size_t)row * g.ldc + col] = v;
-          continue;
-        }
-        const T o = from_f32<T>(v);
-        C[(size_t)row * g.ldc + col] = o;
-        if (EPI == EPI_RESIDUAL || EPI == EPI_MASK_POS) cs[j] += to_f32<T>(o);
+        const float vo = ep.put(acc[i][j][r], bv, m0 + wm * 64 + 16 * i + 4 * q + r, col);
+        if (EPI == EPI_RESIDUAL || EPI == EPI_MASK_POS) cs[j] += vo;
         if (EPI == EPI_PRELU_STATS) {
-          const float vo = to_f32<T>(o);
           s1 += vo;
           s2 += vo * vo;
         }
@@ -648,6 +423,31 @@ static int nt_staged_plain() {                       // (read per call: tests/te
   return (e && e[0] == '0') ? 0 : 1;
 }
 
+// The one dispatch of the NT GEMM entry points over (T, EPI, path).  lds_path: 128 / 64 = gemm_nt_lds_kernel with that tile
+// width (the K slice is a multiple of the 128-byte stage), 0 = gemm_nt_kernel.
+template <typename T, int EPI> static void launch_nt_path(int lds_path, int nz, const GemmArgs& g, hipStream_t s) {
+  dim3 grid(g.R / 128, lds_path == 128 ? g.N / 128 : g.N / 64, nz);
+  if (lds_path == 128) hipLaunchKernelGGL((gemm_nt_lds_kernel<T, EPI, 128>), grid, dim3(256), 0, s, g);
+  else if (lds_path == 64) hipLaunchKernelGGL((gemm_nt_lds_kernel<T, EPI, 64>), grid, dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm_nt_kernel<T, EPI>), grid, dim3(256), 0, s, g);
+}
+template <typename T> static int dispatch_nt_epi(int epi, int lds_path, int nz, const GemmArgs& g, hipStream_t s) {
+  switch (epi) {
+#define NT_CASE(E) case E: launch_nt_path<T, E>(lds_path, nz, g, s); break;
+    NT_CASE(EPI_PLAIN) NT_CASE(EPI_PRELU_STATS) NT_CASE(EPI_RESIDUAL) NT_CASE(EPI_RELU) NT_CASE(EPI_PLAIN_F32) NT_CASE(EPI_MASK_POS)
+    NT_CASE(EPI_RESIDUAL_GN)
+#undef NT_CASE
+    default: return NPPC_EBADARG;
+  }
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+static int dispatch_nt(int prec, int epi, int lds_path, int nz, const GemmArgs& g, hipStream_t s) {
+  if (prec == NPPC_PREC_BF16) return dispatch_nt_epi<bf16_t>(epi, lds_path, nz, g, s);
+  if (prec == NPPC_PREC_F32) return dispatch_nt_epi<float>(epi, lds_path, nz, g, s);
+  return NPPC_EBADARG;
+}
+
 static int launch_nt(int prec, int epi, const void* A, long lda, long sA, const void* B, long ldb, long sB, void* C, long ldc,
                      long sC, const float* bias, long sBias, const void* res, long ldres, long sRes, const float* slope,
                      long sSlope, double* stats, long sStats, int R, int N, int K, int Tp, int Tv, int Nv, int relu_in,
@@ -668,44 +468,11 @@ static int launch_nt(int prec, int epi, const void* A, long lda, long sA, const 
                    : ((epi == EPI_PLAIN || epi == EPI_PRELU_STATS || epi == EPI_RELU) && ksplit == 1 && nt_staged_plain())) &&
               ldc % 8 == 0) ? 1 : 0,
              colpart, (long)(R / 128) * N};
-  hipStream_t s = (hipStream_t)stream;
   const int bk = prec == NPPC_PREC_BF16 ? 64 : 32;
   const int lds_path = ((K / ksplit) % bk == 0) ? (N % 128 == 0 ? 128 : 64) : 0;
   // the tile column sums come out of the LDS kernels' epilogue for the two epilogues that produce an upstream gradient
   if (colpart && (lds_path == 0 || ksplit != 1 || (epi != EPI_RESIDUAL && epi != EPI_MASK_POS))) return NPPC_EUNSUPPORTED;
-  dim3 grid(R / 128, lds_path == 128 ? N / 128 : N / 64, batch * ksplit);
-#define LAUNCH(TT, E)                                                                              \
-  do {                                                                                             \
-    if (lds_path == 128) hipLaunchKernelGGL((gemm_nt_lds_kernel<TT, E, 128>), grid, dim3(256), 0, s, g); \
-    else if (lds_path == 64) hipLaunchKernelGGL((gemm_nt_lds_kernel<TT, E, 64>), grid, dim3(256), 0, s, g); \
-    else hipLaunchKernelGGL((gemm_nt_kernel<TT, E>), grid, dim3(256), 0, s, g);                    \
-  } while (0)
-  if (prec == NPPC_PREC_BF16) {
-    switch (epi) {
-      case EPI_PLAIN: LAUNCH(bf16_t, EPI_PLAIN); break;
-      case EPI_PRELU_STATS: LAUNCH(bf16_t, EPI_PRELU_STATS); break;
-      case EPI_RESIDUAL: LAUNCH(bf16_t, EPI_RESIDUAL); break;
-      case EPI_RELU: LAUNCH(bf16_t, EPI_RELU); break;
-      case EPI_PLAIN_F32: LAUNCH(bf16_t, EPI_PLAIN_F32); break;
-      case EPI_MASK_POS: LAUNCH(bf16_t, EPI_MASK_POS); break;
-      default: return NPPC_EBADARG;
-    }
-  } else if (prec == NPPC_PREC_F32) {
-    switch (epi) {
-      case EPI_PLAIN: LAUNCH(float, EPI_PLAIN); break;
-      case EPI_PRELU_STATS: LAUNCH(float, EPI_PRELU_STATS); break;
-      case EPI_RESIDUAL: LAUNCH(float, EPI_RESIDUAL); break;
-      case EPI_RELU: LAUNCH(float, EPI_RELU); break;
-      case EPI_PLAIN_F32: LAUNCH(float, EPI_PLAIN_F32); break;
-      case EPI_MASK_POS: LAUNCH(float, EPI_MASK_POS); break;
-      default: return NPPC_EBADARG;
-    }
-  } else {
-    return NPPC_EBADARG;
-  }
-#undef LAUNCH
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  return dispatch_nt(prec, epi, lds_path, batch * ksplit, g, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -739,22 +506,9 @@ int nppc_gemm_nt_gn(int prec, const void* A, long lda, long sA, const void* Wg, 
   if (R % 128 || N % 64 || K % 32 || Tp <= 0 || (Tp % 128) || lda % 8 || ldb % 8) return NPPC_EUNSUPPORTED;
   GemmArgs g{A, lda, sA, Wg, ldb, sB, C, ldc, sC, u, sUV, res, ldres, sRes, nullptr, 0, const_cast<double*>(stats), sStats,
              R, N, K, Tp, Tv, Nv, 0, 1, v, sUV, cnt, eps, (ldc % 8 == 0 && ldres % 8 == 0 && nt_staged()) ? 1 : 0, nullptr, 0};
-  hipStream_t s = (hipStream_t)stream;
   const int bk = prec == NPPC_PREC_BF16 ? 64 : 32;
   const int lds_path = (K % bk == 0) ? (N % 128 == 0 ? 128 : 64) : 0;
-  dim3 grid(R / 128, lds_path == 128 ? N / 128 : N / 64, batch);
-#define LAUNCH_GN(TT)                                                                                             \
-  do {                                                                                                            \
-    if (lds_path == 128) hipLaunchKernelGGL((gemm_nt_lds_kernel<TT, EPI_RESIDUAL_GN, 128>), grid, dim3(256), 0, s, g);   \
-    else if (lds_path == 64) hipLaunchKernelGGL((gemm_nt_lds_kernel<TT, EPI_RESIDUAL_GN, 64>), grid, dim3(256), 0, s, g); \
-    else hipLaunchKernelGGL((gemm_nt_kernel<TT, EPI_RESIDUAL_GN>), grid, dim3(256), 0, s, g);                      \
-  } while (0)
-  if (prec == NPPC_PREC_BF16) LAUNCH_GN(bf16_t);
-  else if (prec == NPPC_PREC_F32) LAUNCH_GN(float);
-  else return NPPC_EBADARG;
-#undef LAUNCH_GN
-  NPPC_CHECK_LAUNCH();
-  return NPPC_OK;
+  return dispatch_nt(prec, EPI_RESIDUAL_GN, lds_path, batch, g, (hipStream_t)stream);
 }
 
 int nppc_tcn_pack_sconv(int prec, const float* W, const float* gamma, const float* beta, const float* bias, void* Wg, float* u,
@@ -762,14 +516,8 @@ int nppc_tcn_pack_sconv(int prec, const float* W, const float* gamma, const floa
                         long dst_stride_a, long dst_stride_b, void* stream) {
   if (!W || !gamma || !beta || !bias || !Wg || !u || !v || N > Npad || K > ldd || n_a <= 0 || n_b <= 0 || (long)n_a * n_b > 65535)
     return NPPC_EBADARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(pack_sconv_kernel<bf16_t>, dim3(Npad, n_a * n_b), dim3(64), 0, s, W, gamma, beta, bias, (bf16_t*)Wg, u, v, N,
-                       K, Npad, ldd, n_b, src_stride_a, src_stride_b, dst_stride_a, dst_stride_b);
-  else
-    hipLaunchKernelGGL(pack_sconv_kernel<float>, dim3(Npad, n_a * n_b), dim3(64), 0, s, W, gamma, beta, bias, (float*)Wg, u, v, N, K,
-                       Npad, ldd, n_b, src_stride_a, src_stride_b, dst_stride_a, dst_stride_b);
-  NPPC_CHECK_LAUNCH();
+  LAUNCH_TS(prec, pack_sconv_kernel, dim3(Npad, n_a * n_b), dim3(64), 0, W, gamma, beta, bias, (TT*)Wg, u, v, N, K, Npad, ldd, n_b,
+            src_stride_a, src_stride_b, dst_stride_a, dst_stride_b);
   return NPPC_OK;
 }
 
@@ -777,30 +525,16 @@ int nppc_tcn_dwconv(int prec, const void* in, void* out, const double* st1, doub
                     const float* beta, const float* wd, const float* bd, const float* slope2, int B, int Cc, int ld, int Tp,
                     int Tv, int dil, float eps, long sAct, long sSt, long sP, int batch, void* stream) {
   if (!in || !out || !st1 || !st2 || Cc % 8 || Cc / 8 > 256) return NPPC_EBADARG;
-  dim3 grid(ceil_div(Tp, DW_FRAMES), B, batch);
-  hipStream_t s = (hipStream_t)stream;
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(dwconv_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, st1, st2, gamma, beta,
-                       wd, bd, slope2, Cc, ld, Tp, Tv, dil, eps, sAct, sSt, sP);
-  else
-    hipLaunchKernelGGL(dwconv_kernel<float>, grid, dim3(256), 0, s, (const float*)in, (float*)out, st1, st2, gamma, beta, wd,
-                       bd, slope2, Cc, ld, Tp, Tv, dil, eps, sAct, sSt, sP);
-  NPPC_CHECK_LAUNCH();
+  LAUNCH_T(prec, dwconv_kernel, dim3(ceil_div(Tp, DW_FRAMES), B, batch), (const TT*)in, (TT*)out, st1, st2, gamma, beta, wd, bd,
+           slope2, Cc, ld, Tp, Tv, dil, eps, sAct, sSt, sP);
   return NPPC_OK;
 }
 
 int nppc_tcn_gn_apply(int prec, const void* in, void* out, const double* st, const float* gamma, const float* beta, int B,
                       int Cc, int ld, int Tp, int Tv, float eps, long sAct, long sSt, long sP, int batch, void* stream) {
   if (!in || !out || !st || Cc % 8) return NPPC_EBADARG;
-  dim3 grid(ceil_div((long)Tv * (Cc / 8), 256), B, batch);
-  hipStream_t s = (hipStream_t)stream;
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, st, gamma, beta, Cc,
-                       ld, Tp, Tv, eps, sAct, sSt, sP);
-  else
-    hipLaunchKernelGGL(gn_apply_kernel<float>, grid, dim3(256), 0, s, (const float*)in, (float*)out, st, gamma, beta, Cc, ld,
-                       Tp, Tv, eps, sAct, sSt, sP);
-  NPPC_CHECK_LAUNCH();
+  LAUNCH_T(prec, gn_apply_kernel, dim3(ceil_div((long)Tv * (Cc / 8), 256), B, batch), (const TT*)in, (TT*)out, st, gamma, beta, Cc,
+           ld, Tp, Tv, eps, sAct, sSt, sP);
   return NPPC_OK;
 }
 
@@ -808,14 +542,7 @@ int nppc_pack_matrix(int prec, const float* src, void* dst, int N, int K, int Np
   if (!src || !dst || N > Npad || K > ldd) return NPPC_EBADARG;
   const long total = (long)Npad * ldd;
   const int grid = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-  hipStream_t s = (hipStream_t)stream;
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(pack_matrix_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, src, (bf16_t*)dst, N, K, Npad, ldd, transpose, 1,
-                       0L, 0L, 0L, 0L);
-  else
-    hipLaunchKernelGGL(pack_matrix_kernel<float>, dim3(grid), dim3(256), 0, s, src, (float*)dst, N, K, Npad, ldd, transpose, 1, 0L,
-                       0L, 0L, 0L);
-  NPPC_CHECK_LAUNCH();
+  LAUNCH_T(prec, pack_matrix_kernel, dim3(grid), src, (TT*)dst, N, K, Npad, ldd, transpose, 1, 0L, 0L, 0L, 0L);
   return NPPC_OK;
 }
 
@@ -824,14 +551,8 @@ int nppc_pack_matrix_batched(int prec, const float* src, void* dst, int N, int K
   if (!src || !dst || N > Npad || K > ldd || n_a <= 0 || n_b <= 0 || (long)n_a * n_b > 65535) return NPPC_EBADARG;
   const long total = (long)Npad * ldd;
   const int gx = (int)((total + 255) / 256 > 256 ? 256 : (total + 255) / 256);
-  hipStream_t s = (hipStream_t)stream;
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(pack_matrix_kernel<bf16_t>, dim3(gx, n_a * n_b), dim3(256), 0, s, src, (bf16_t*)dst, N, K, Npad, ldd,
-                       transpose, n_b, src_stride_a, src_stride_b, dst_stride_a, dst_stride_b);
-  else
-    hipLaunchKernelGGL(pack_matrix_kernel<float>, dim3(gx, n_a * n_b), dim3(256), 0, s, src, (float*)dst, N, K, Npad, ldd,
-                       transpose, n_b, src_stride_a, src_stride_b, dst_stride_a, dst_stride_b);
-  NPPC_CHECK_LAUNCH();
+  LAUNCH_T(prec, pack_matrix_kernel, dim3(gx, n_a * n_b), src, (TT*)dst, N, K, Npad, ldd, transpose, n_b, src_stride_a,
+           src_stride_b, dst_stride_a, dst_stride_b);
   return NPPC_OK;
 }
 
@@ -840,21 +561,17 @@ int nppc_pack_matrix_batched(int prec, const float* src, void* dst, int N, int K
 // =====================================================================================================
 // LDS-staged NT GEMM for the long-K weight-gradient products (K = T'*N ~ 1e6, split over blockIdx.z):
 //   C_slab[z][M][N] (fp32) = A[M][Kz] * B[N][Kz]^T,   A, B K-contiguous.
-// 256 threads = 2x2 waves, block tile 128x128, 128-byte K slices per stage (64 bf16 / 32 f32), double-buffered LDS,
-// register staging (issue the next stage's global loads before the MFMAs, write them to LDS after), one barrier
-// per stage.  LDS rows are 128 B = 8 chunks of 16 B stored at slot (chunk ^ (row & 7)): both the staging
-// ds_write_b128 and the fragment ds_read_b128 are bank-conflict free.
+// 256 threads = 2x2 waves, block tile 128x128, 128-byte K slices per stage (64 bf16 / 32 f32): nt_lds_mainloop at BN = 128
+// (mfma_tile.h: double-buffered swizzled LDS, register staging, one barrier per stage).
 namespace {
 
 template <typename T>
 __global__ __launch_bounds__(256, 2) void gemm_nt_tiled_kernel(const T* __restrict__ A, long lda, const T* __restrict__ B,
                                                                long ldb, float* __restrict__ C, long ldc, long slab_stride,
                                                                long Kz) {
-  typedef typename Frag<T>::type frag;
   constexpr int EPC = 16 / (int)sizeof(T);      // elements per 16-byte chunk
   constexpr int BK = 8 * EPC;                   // elements per 128-byte stage row
-  constexpr int KS = BK / 32;                   // 32-wide MFMA k-steps per stage
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][128 * 128];   // [buffer][A|B][row*128 B]
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * (128 + 128) * 128];   // [buffer][A rows | B rows][128 B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, q = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
   const long m0 = (long)blockIdx.x * 128, n0 = (long)blockIdx.y * 128;
@@ -867,70 +584,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tiled_kernel(const T* __restri
   const int srow = tid >> 3, sc = tid & 7;                       // rows srow + 32*i
   const T* ga = Ab + (long)srow * lda + sc * EPC;
   const T* gb = Bb + (long)srow * ldb + sc * EPC;
-  const int soff = srow * 128 + ((sc ^ (srow & 7)) << 4);        // (srow + 32*i) & 7 == srow & 7
-  uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-#define GLOAD(k0)                                                              \
-  ra0 = *reinterpret_cast<const uint4*>(ga + (k0));                            \
-  ra1 = *reinterpret_cast<const uint4*>(ga + 32 * lda + (k0));                 \
-  ra2 = *reinterpret_cast<const uint4*>(ga + 64 * lda + (k0));                 \
-  ra3 = *reinterpret_cast<const uint4*>(ga + 96 * lda + (k0));                 \
-  rb0 = *reinterpret_cast<const uint4*>(gb + (k0));                            \
-  rb1 = *reinterpret_cast<const uint4*>(gb + 32 * ldb + (k0));                 \
-  rb2 = *reinterpret_cast<const uint4*>(gb + 64 * ldb + (k0));                 \
-  rb3 = *reinterpret_cast<const uint4*>(gb + 96 * ldb + (k0));
-#define LSTORE(buf)                                                            \
-  *reinterpret_cast<uint4*>(&lds[buf][0][soff]) = ra0;                         \
-  *reinterpret_cast<uint4*>(&lds[buf][0][soff + 32 * 128]) = ra1;              \
-  *reinterpret_cast<uint4*>(&lds[buf][0][soff + 64 * 128]) = ra2;              \
-  *reinterpret_cast<uint4*>(&lds[buf][0][soff + 96 * 128]) = ra3;              \
-  *reinterpret_cast<uint4*>(&lds[buf][1][soff]) = rb0;                         \
-  *reinterpret_cast<uint4*>(&lds[buf][1][soff + 32 * 128]) = rb1;              \
-  *reinterpret_cast<uint4*>(&lds[buf][1][soff + 64 * 128]) = rb2;              \
-  *reinterpret_cast<uint4*>(&lds[buf][1][soff + 96 * 128]) = rb3;
-  auto lfrag = [&](const unsigned char* base, int row, int ks) -> frag {
-    if constexpr (sizeof(T) == 2) {
-      const int c = 4 * ks + q;
-      return *reinterpret_cast<const frag*>(base + row * 128 + ((c ^ (row & 7)) << 4));
-    } else {
-      const int c0 = 2 * q, c1 = 2 * q + 1;   // KS == 1: the 32-float row is the whole k-step
-      const float4 lo = *reinterpret_cast<const float4*>(base + row * 128 + ((c0 ^ (row & 7)) << 4));
-      const float4 hi = *reinterpret_cast<const float4*>(base + row * 128 + ((c1 ^ (row & 7)) << 4));
-      frag f;
-      f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
-      return f;
-    }
-  };
-
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const long nstage = Kz / BK;
-  GLOAD(0)
-  LSTORE(0)
-  __syncthreads();
-  for (long s = 0; s < nstage; ++s) {
-    const int buf = (int)(s & 1);
-    if (s + 1 < nstage) { GLOAD((s + 1) * BK) }
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      frag af[4], bf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = lfrag(lds[buf][0], wm * 64 + 16 * i + n, ks);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = lfrag(lds[buf][1], wn * 64 + 16 * j + n, ks);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mma16(af[i], bf[j], acc[i][j]);
-    }
-    if (s + 1 < nstage) { LSTORE(buf ^ 1) }
-    __syncthreads();
-  }
-#undef GLOAD
-#undef LSTORE
+  nt_lds_mainloop<T, 128>(acc, lds, Kz / BK, lda, ldb, [&](long s) { return ga + s * BK; }, [&](long s) { return gb + s * BK; }, 0);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -951,16 +606,7 @@ extern "C" int nppc_gemm_nt_splitk(int prec, const void* A, long lda, const void
   const int bk = prec == NPPC_PREC_BF16 ? 64 : 32;
   if (M % 128 || N % 128 || K % ((long)bk * ksplit) || lda % 8 || ldb % 8) return NPPC_EUNSUPPORTED;
   dim3 grid(M / 128, N / 128, ksplit);
-  hipStream_t s = (hipStream_t)stream;
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(gemm_nt_tiled_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc,
-                       (long)M * ldc, K / ksplit);
-  else if (prec == NPPC_PREC_F32)
-    hipLaunchKernelGGL(gemm_nt_tiled_kernel<float>, grid, dim3(256), 0, s, (const float*)A, lda, (const float*)B, ldb, C, ldc,
-                       (long)M * ldc, K / ksplit);
-  else
-    return NPPC_EBADARG;
-  NPPC_CHECK_LAUNCH();
+  LAUNCH_T(prec, gemm_nt_tiled_kernel, grid, (const TT*)A, lda, (const TT*)B, ldb, C, ldc, (long)M * ldc, K / ksplit);
   return NPPC_OK;
 }
 
@@ -1199,26 +845,20 @@ __device__ __forceinline__ void dma_tile(const bf16_t* __restrict__ A, long lda,
     srcB[h] = reinterpret_cast<const unsigned char*>(B + (rbaseB + row) * ldb + n0) + p;
   }
   const long strA = (long)BR * lda * 2, strB = (long)BR * ldb * 2;        // bytes per stage
-  // The DMAs go out through inline asm: issued with the builtin, hipcc treats every later ds_read as a possible reader of
-  // the pending LDS write and puts s_waitcnt vmcnt(0) in front of each stage's first fragment read, which drains the ring
-  // (the stage issued a moment earlier included) -- the pipeline this kernel exists for.  Hidden from the compiler, their
-  // completion is counted by hand below (cdna_hip_programming.md section 5.7 item 1: an LDS-DMA has no VGPR destination,
-  // so it is register-safe).  M0 carries the wave-uniform LDS byte address of each piece.
+  // The DMAs go out through inline asm (lds_dma16, common.h): issued with the builtin, hipcc puts s_waitcnt vmcnt(0) in front
+  // of each stage's first fragment read, which drains the ring (the stage issued a moment earlier included) -- the pipeline
+  // this kernel exists for.  Hidden from the compiler, their completion is counted by hand below (cdna_hip_programming.md
+  // section 5.7 item 1).  M0 carries the wave-uniform LDS byte address of each piece.
   const unsigned lds_base = (unsigned)(unsigned long)(lds_void*)dr_lds;
-  auto dma = [&](const unsigned char* src, unsigned ldst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(ldst) : "memory");
-  };
   auto fill = [&](int slot, long st) {
     if (!producer) return;
     const unsigned l = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)slot * STAGE_BYTES);
 #pragma unroll
-    for (int h = 0; h < NA; ++h) dma(srcA[h] + st * strA, l + (NA * pwv + h) * 1024);
+    for (int h = 0; h < NA; ++h) lds_dma16(srcA[h] + st * strA, l + (NA * pwv + h) * 1024);
 #pragma unroll
-    for (int h = 0; h < NBF; ++h) dma(srcB[h] + st * strB, l + A_BYTES + pwv * BW + h * 1024);
+    for (int h = 0; h < NBF; ++h) lds_dma16(srcB[h] + st * strB, l + A_BYTES + pwv * BW + h * 1024);
     if constexpr (NBH != 0) {
-      if (lane < 32) dma(srcB[NBF] + st * strB, l + A_BYTES + pwv * BW + NBF * 1024);
+      if (lane < 32) lds_dma16(srcB[NBF] + st * strB, l + A_BYTES + pwv * BW + NBF * 1024);
     }
   };
   // transposed fragment of k-rows [32 ks + 8 qq, + 8) x 16 columns starting at col0 (ds_read_b64_tr_b16, two 4-row halves)

@@ -642,18 +642,10 @@ int nppc_tcn_gn_bwd(int prec, const void* dA, const void* y, const double* st, c
   const int RPB = tcn_rpb(), noatom = diag_noatom();
   dim3 g1(ceil_div(Tv, RPB), B, batch), g2(ceil_div(Tp, RPB), B, batch);
   const size_t smem = (size_t)2 * Cc * sizeof(float);
-  if (prec == NPPC_PREC_BF16) {
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel<bf16_t>, g1, dim3(256), smem, s, (const bf16_t*)dA, (const bf16_t*)y, st, gamma, S,
-                       dgamma, dbeta, Cc, Tp, Tv, eps, sAct, sSt, sP, RPB, noatom);
-    hipLaunchKernelGGL(gn_prelu_bwd_kernel<bf16_t>, g2, dim3(256), 0, s, (const bf16_t*)dA, (const bf16_t*)y, st, gamma, S,
-                       slope, (bf16_t*)dpre, dslope, Cc, Tp, Tv, eps, sAct, sSt, sP, RPB, noatom);
-  } else {
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel<float>, g1, dim3(256), smem, s, (const float*)dA, (const float*)y, st, gamma, S,
-                       dgamma, dbeta, Cc, Tp, Tv, eps, sAct, sSt, sP, RPB, noatom);
-    hipLaunchKernelGGL(gn_prelu_bwd_kernel<float>, g2, dim3(256), 0, s, (const float*)dA, (const float*)y, st, gamma, S, slope,
-                       (float*)dpre, dslope, Cc, Tp, Tv, eps, sAct, sSt, sP, RPB, noatom);
-  }
-  NPPC_CHECK_LAUNCH();
+  LAUNCH_TS(prec, gn_bwd_reduce_kernel, g1, dim3(256), smem, (const TT*)dA, (const TT*)y, st, gamma, S, dgamma, dbeta, Cc, Tp, Tv,
+            eps, sAct, sSt, sP, RPB, noatom);
+  LAUNCH_T(prec, gn_prelu_bwd_kernel, g2, (const TT*)dA, (const TT*)y, st, gamma, S, slope, (TT*)dpre, dslope, Cc, Tp, Tv, eps, sAct,
+           sSt, sP, RPB, noatom);
   return NPPC_OK;
 }
 
@@ -661,17 +653,11 @@ int nppc_tcn_dwconv_bwd(int prec, const void* du, const void* y1, const double* 
                         const float* wd, void* dz, float* dwd, float* dbd, int B, int Cc, int Tp, int Tv, int dil, float eps,
                         long sAct, long sSt, long sP, int batch, void* stream) {
   if (!du || !y1 || !st1 || !gamma || !beta || !wd || !dz || !dwd || !dbd || Cc % 8 || Cc / 8 > 256) return NPPC_EBADARG;
-  hipStream_t s = (hipStream_t)stream;
   const int RPB = tcn_rpb(), noatom = diag_noatom();
   dim3 g(ceil_div(Tp, RPB), B, batch);
   const size_t smem = (size_t)4 * Cc * sizeof(float);
-  if (prec == NPPC_PREC_BF16)
-    hipLaunchKernelGGL(dwconv_bwd_kernel<bf16_t>, g, dim3(256), smem, s, (const bf16_t*)du, (const bf16_t*)y1, st1, gamma, beta,
-                       wd, (bf16_t*)dz, dwd, dbd, Cc, Tp, Tv, dil, eps, sAct, sSt, sP, RPB, noatom);
-  else
-    hipLaunchKernelGGL(dwconv_bwd_kernel<float>, g, dim3(256), smem, s, (const float*)du, (const float*)y1, st1, gamma, beta, wd,
-                       (float*)dz, dwd, dbd, Cc, Tp, Tv, dil, eps, sAct, sSt, sP, RPB, noatom);
-  NPPC_CHECK_LAUNCH();
+  LAUNCH_TS(prec, dwconv_bwd_kernel, g, dim3(256), smem, (const TT*)du, (const TT*)y1, st1, gamma, beta, wd, (TT*)dz, dwd, dbd, Cc,
+            Tp, Tv, dil, eps, sAct, sSt, sP, RPB, noatom);
   return NPPC_OK;
 }
 

@@ -13,262 +13,70 @@
 // The concatenations are channel slices of one buffer (producers write with a channel offset).
 #include <algorithm>
 #include "common.h"
+#include "mfma_tile.h"
 #include "nppc_hip.h"
 #include "philox.h"
 
 namespace {
 
-// 32-bit arithmetic: the host entry points reject P >= 2^31 (64-bit integer division has no hardware support)
-__device__ __forceinline__ bool interior(long p, long P, int H, int W) {
-  if (p >= P) return false;
-  const unsigned Wp = W + 2, Hp = H + 2, pu = (unsigned)p;
-  const unsigned row = pu / Wp;
-  const unsigned x = pu - row * Wp;
-  const unsigned y = row % Hp;
-  return x >= 1 && x <= (unsigned)W && y >= 1 && y <= (unsigned)H;
-}
-
 // ------------------------------------------------------------------------------------------------ convolution
-struct ConvArgs {
-  const void* A; long lda;            // haloed NHWC input, pointer at pixel row 0 (guard rows exist before it)
-  const void* Wp;                     // packed weights [Np][ntap*Cin], K contiguous
-  void* C; long ldc;                  // haloed NHWC output; interior rows, columns < Cout are written
-  const float* bias;                  // [Cout] or null
-  const float* scale;                 // optional folded BatchNorm (eval mode): v = leaky(v * scale[c] + shift[c])
-  const float* shift;
-  float slope;
-  long P;                             // haloed pixel rows B*(H+2)*(W+2)
-  int H, W, Cin, Cout, ntap;          // Cin % 32 == 0
-  // optional (conv_tiled_kernel): per-tile column sums of the STORED output, [tile = row / 128][2: sum, sum of squares][ldp]
-  // fp32 -- the batch statistics of the train-mode BatchNorm that follows, without a pass of its own over the tensor
-  float* stat_part; int ldp;
-};
+// (ConvArgs, the interior test, the tap offsets, the main loops and the epilogue: mfma_tile.h)
 
-// row offset of tap t: (dy, dx) = (t/3 - 1, t%3 - 1) for a 3x3 kernel, 0 for 1x1 (arithmetic on a uniform value:
-// a dynamically indexed array in the by-value argument struct would be copied to scratch / LDS)
-__device__ __forceinline__ int tap_offset(const ConvArgs& g, int t) {
-  return g.ntap == 9 ? (t / 3 - 1) * (g.W + 2) + (t % 3 - 1) : 0;
-}
-
-// 256 threads = 4 waves stacked over rows; wave tile 32 x 64, block tile 128 rows x 64 output channels.
+// 256 threads = 4 waves stacked over rows; wave tile 32 x 64, block tile 128 rows x 64 output channels, one 32-deep K slice of
+// ONE tap per k-step (nt_reg_mainloop).  The A fragments of a k-step are the pixel rows shifted by that tap's offset.
 template <typename T>
 __global__ __launch_bounds__(256) void conv_kernel(ConvArgs g) {
-  typedef typename Frag<T>::type frag;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, q = lane >> 4;
   const long r0 = (long)blockIdx.x * 128 + wave * 32;
   const int c0 = blockIdx.y * 64;
-  const int kc = g.Cin / 32, nk = g.ntap * kc;
+  const int kc = g.Cin / 32;
   const long ldw = (long)g.ntap * g.Cin;
   const T* ap = reinterpret_cast<const T*>(g.A) + (r0 + n) * g.lda + 8 * q;
   const T* bp = reinterpret_cast<const T*>(g.Wp) + (long)(c0 + n) * ldw + 8 * q;
-  f32x4 acc[2][4];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-  frag a0[2], b0[4], a1[2], b1[4];
   int tap = 0, cc = 0;   // position of the NEXT k-step to load
-  auto ld = [&](frag(&a)[2], frag(&b)[4], int kk) {
-    const long aoff = (long)tap_offset(g, tap) * g.lda + 32 * cc;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) a[mi] = load_frag<T>(ap + (long)16 * mi * g.lda + aoff);
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) b[ni] = load_frag<T>(bp + (long)16 * ni * ldw + 32 * kk);
+  auto a_of = [&](int) {
+    const T* pa = ap + (long)tap_offset(g, tap) * g.lda + 32 * cc;
     if (++cc == kc) { cc = 0; ++tap; }
+    return pa;
   };
-  auto mm = [&](frag(&a)[2], frag(&b)[4]) {
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mma16(a[mi], b[ni], acc[mi][ni]);
-  };
-  ld(a0, b0, 0);
-  int kk = 0;
-#pragma unroll 1
-  for (; kk + 2 < nk; kk += 2) {
-    ld(a1, b1, kk + 1);
-    mm(a0, b0);
-    ld(a0, b0, kk + 2);
-    mm(a1, b1);
-  }
-  if (kk + 1 < nk) {
-    ld(a1, b1, kk + 1);
-    mm(a0, b0);
-    mm(a1, b1);
-  } else {
-    mm(a0, b0);
-  }
-  // epilogue: element (row r0 + 16 mi + 4 q + j, col c0 + 16 ni + n)
-  T* C = reinterpret_cast<T*>(g.C);
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long row = r0 + 16 * mi + 4 * q + j;
-      if (!interior(row, g.P, g.H, g.W)) continue;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int col = c0 + 16 * ni + n;
-        if (col >= g.Cout) continue;
-        float v = acc[mi][ni][j] + (g.bias ? g.bias[col] : 0.f);
-        if (g.scale) {
-          v = v * g.scale[col] + g.shift[col];
-          v = v > 0.f ? v : g.slope * v;
-        }
-        C[row * g.ldc + col] = from_f32<T>(v);
-      }
-    }
+  f32x4 acc[2][4];
+  nt_reg_mainloop<T>(acc, g.ntap * kc, g.lda, ldw, a_of, [&](int kk) { return bp + 32 * kk; }, 0);
+  float st1[4] = {}, st2[4] = {};   // (this path leaves no statistics: dead)
+  conv_epilogue<T>(g, acc, r0 + 4 * q, c0 + n, st1, st2);
 }
 
 // LDS-staged variant (Cin a multiple of the 128-byte stage: 64 bf16 / 32 f32).  256 threads = 2 x 2 waves, block tile
-// 128 rows x BN output channels, one 128-byte K slice of ONE tap per stage, double-buffered LDS with register staging
-// (next stage's global loads are issued before the MFMAs and written to LDS after them), one barrier per stage.
-// LDS rows are 128 B = 8 chunks of 16 B stored at slot (chunk ^ (row & 7)): staging writes and fragment reads are
-// bank-conflict free.  The A tile of a stage is the pixel rows shifted by that tap's offset.
+// 128 rows x BN output channels, one 128-byte K slice of ONE tap per stage (nt_lds_mainloop).  The A tile of a stage is the
+// pixel rows shifted by that tap's offset.
 template <typename T, int BN>
 __global__ __launch_bounds__(256, 2) void conv_tiled_kernel(ConvArgs g) {
-  typedef typename Frag<T>::type frag;
   constexpr int EPC = 16 / (int)sizeof(T);
   constexpr int BK = 8 * EPC;
-  constexpr int KS = BK / 32;
   constexpr int NJ = BN / 32;                                      // 16-column MFMA tiles per wave
-  constexpr int NBI = BN / 32;                                     // B staging chunks per thread
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][(128 + BN) * 128];   // [buffer][A rows | B rows][128 B]
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * (128 + BN) * 128];   // [buffer][A rows | B rows][128 B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, q = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
-  // XCD-aware order (grid.x is a multiple of 8): the gridDim.y channel tiles of one pixel tile run back to back on the
-  // SAME XCD, so the pixel rows are fetched from HBM once and re-read from that XCD's L2
-  const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-  const unsigned xcd = lin & 7, jj = lin >> 3;
-  const long m0 = (long)((jj / gridDim.y) * 8 + xcd) * 128;
-  const int n0 = (int)(jj % gridDim.y) * BN;
+  long m0;
+  int n0;
+  xcd_tile<128, BN>(m0, n0);
   if (m0 >= g.P) return;
   const long ldw = (long)g.ntap * g.Cin;
   const int srow = tid >> 3, sc = tid & 7;
   const T* ga = reinterpret_cast<const T*>(g.A) + (m0 + srow) * g.lda + sc * EPC;
   const T* gb = reinterpret_cast<const T*>(g.Wp) + (long)(n0 + srow) * ldw + sc * EPC;
-  const int soff = srow * 128 + ((sc ^ (srow & 7)) << 4);
   const int kc = g.Cin / BK;
-  const int nstage = g.ntap * kc;
-  uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;   // named registers: an indexed array would be demoted to scratch / LDS
-  int tap = 0, cc = 0;
-#define CGLOAD(sidx)                                                                   \
-  {                                                                                    \
-    const T* pa = ga + (long)tap_offset(g, tap) * g.lda + cc * BK;                     \
-    ra0 = *reinterpret_cast<const uint4*>(pa);                                         \
-    ra1 = *reinterpret_cast<const uint4*>(pa + 32 * g.lda);                            \
-    ra2 = *reinterpret_cast<const uint4*>(pa + 64 * g.lda);                            \
-    ra3 = *reinterpret_cast<const uint4*>(pa + 96 * g.lda);                            \
-    const T* pb = gb + (long)(sidx) * BK;                                              \
-    rb0 = *reinterpret_cast<const uint4*>(pb);                                         \
-    rb1 = *reinterpret_cast<const uint4*>(pb + 32 * ldw);                              \
-    if constexpr (NBI == 4) {                                                          \
-      rb2 = *reinterpret_cast<const uint4*>(pb + 64 * ldw);                            \
-      rb3 = *reinterpret_cast<const uint4*>(pb + 96 * ldw);                            \
-    }                                                                                  \
-    if (++cc == kc) { cc = 0; ++tap; }                                                 \
-  }
-#define CLSTORE(buf)                                                                   \
-  {                                                                                    \
-    *reinterpret_cast<uint4*>(&lds[buf][soff]) = ra0;                                  \
-    *reinterpret_cast<uint4*>(&lds[buf][soff + 32 * 128]) = ra1;                       \
-    *reinterpret_cast<uint4*>(&lds[buf][soff + 64 * 128]) = ra2;                       \
-    *reinterpret_cast<uint4*>(&lds[buf][soff + 96 * 128]) = ra3;                       \
-    *reinterpret_cast<uint4*>(&lds[buf][128 * 128 + soff]) = rb0;                      \
-    *reinterpret_cast<uint4*>(&lds[buf][128 * 128 + soff + 32 * 128]) = rb1;           \
-    if constexpr (NBI == 4) {                                                          \
-      *reinterpret_cast<uint4*>(&lds[buf][128 * 128 + soff + 64 * 128]) = rb2;         \
-      *reinterpret_cast<uint4*>(&lds[buf][128 * 128 + soff + 96 * 128]) = rb3;         \
-    }                                                                                  \
-  }
-  auto lfrag = [&](const unsigned char* base, int row, int ks) -> frag {
-    if constexpr (sizeof(T) == 2) {
-      const int c = 4 * ks + q;
-      return *reinterpret_cast<const frag*>(base + row * 128 + ((c ^ (row & 7)) << 4));
-    } else {
-      const int c0 = 2 * q, c1 = 2 * q + 1;
-      const float4 lo = *reinterpret_cast<const float4*>(base + row * 128 + ((c0 ^ (row & 7)) << 4));
-      const float4 hi = *reinterpret_cast<const float4*>(base + row * 128 + ((c1 ^ (row & 7)) << 4));
-      frag f;
-      f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
-      return f;
-    }
+  int tap = 0, cc = 0;   // (tap, K slice) of the NEXT stage to load
+  auto a_of = [&](int) {
+    const T* pa = ga + (long)tap_offset(g, tap) * g.lda + cc * BK;
+    if (++cc == kc) { cc = 0; ++tap; }
+    return pa;
   };
   f32x4 acc[4][NJ];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  CGLOAD(0)
-  CLSTORE(0)
-  __syncthreads();
-  for (int s = 0; s < nstage; ++s) {
-    const int buf = s & 1;
-    if (s + 1 < nstage) CGLOAD(s + 1)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      frag af[4], bf[NJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = lfrag(lds[buf], wm * 64 + 16 * i + n, ks);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bf[j] = lfrag(lds[buf] + 128 * 128, wn * (BN / 2) + 16 * j + n, ks);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = mma16(af[i], bf[j], acc[i][j]);
-    }
-    if (s + 1 < nstage) CLSTORE(buf ^ 1)
-    __syncthreads();
-  }
-#undef CGLOAD
-#undef CLSTORE
-  T* C = reinterpret_cast<T*>(g.C);
-  float st1[NJ], st2[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) st1[j] = st2[j] = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const long row = m0 + wm * 64 + 16 * i + 4 * q + r;
-      if (!interior(row, g.P, g.H, g.W)) continue;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int col = n0 + wn * (BN / 2) + 16 * j + n;
-        if (col >= g.Cout) continue;
-        float v = acc[i][j][r] + (g.bias ? g.bias[col] : 0.f);
-        if (g.scale) {
-          v = v * g.scale[col] + g.shift[col];
-          v = v > 0.f ? v : g.slope * v;
-        }
-        const T o = from_f32<T>(v);
-        C[row * g.ldc + col] = o;
-        const float vo = to_f32<T>(o);                 // statistics of the stored (rounded) activations, as bn_stats_kernel read them
-        st1[j] += vo;
-        st2[j] += vo * vo;
-      }
-    }
-  if (g.stat_part) {
-    // column sums of this 128-row tile: 16 rows per lane -> the four row groups of a wave (lanes n, n+16, n+32, n+48) -> the
-    // two waves along M through LDS (the operand buffers are free: the main loop ended with a barrier) -> one store per column
-    float* sp = reinterpret_cast<float*>(&lds[0][0]);           // [wm][stat][BN]
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      float a = st1[j], b = st2[j];
-      a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
-      b += __shfl_xor(b, 16); b += __shfl_xor(b, 32);
-      if (q == 0) {
-        sp[(wm * 2 + 0) * BN + wn * (BN / 2) + 16 * j + n] = a;
-        sp[(wm * 2 + 1) * BN + wn * (BN / 2) + 16 * j + n] = b;
-      }
-    }
-    __syncthreads();
-    if (tid < BN) {
-      float* pt = g.stat_part + (size_t)(m0 / 128) * 2 * g.ldp + n0 + tid;
-      pt[0] = sp[(0 * 2 + 0) * BN + tid] + sp[(1 * 2 + 0) * BN + tid];
-      pt[g.ldp] = sp[(0 * 2 + 1) * BN + tid] + sp[(1 * 2 + 1) * BN + tid];
-    }
-  }
+  nt_lds_mainloop<T, BN>(acc, lds, g.ntap * kc, g.lda, ldw, a_of, [&](int s) { return gb + (long)s * BK; }, 0);
+  float st1[NJ] = {}, st2[NJ] = {};
+  conv_epilogue<T>(g, acc, m0 + wm * 64 + 4 * q, n0 + wn * (BN / 2) + n, st1, st2);
+  // (the operand buffers are free: the main loop ended with a barrier)
+  if (g.stat_part) conv_stat_part<BN, 1>(g, reinterpret_cast<float*>(lds), st1, st2, true, wm, wn, m0, n0);
 }
 
 // LDS-DMA ring variant of conv_tiled_kernel (bf16, round 4): 256 pixel rows x BN channels per workgroup; EIGHT COMPUTE WAVES
@@ -305,10 +113,9 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool dma_wave = wave >= 8;
   const int wm = (wave & 7) >> 1, wn = wave & 1;
-  const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;        // XCD-aware order, as in conv_tiled_kernel
-  const unsigned xcd = lin & 7, jj = lin >> 3;
-  const long m0 = (long)((jj / gridDim.y) * 8 + xcd) * BM;
-  const int n0 = (int)(jj % gridDim.y) * BN;
+  long m0;
+  int n0;
+  xcd_tile<BM, BN>(m0, n0);
   if (m0 >= g.P) return;
   const int kc = g.Cin / 64;
   const int nstage = g.ntap * kc;
@@ -334,12 +141,7 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
       src[h] = pz < APIECE ? pa : pb;
     }
     const unsigned lds_base = (unsigned)(unsigned long)(lds_void*)cd_lds;
-    auto dma = [&](const unsigned char* sp, unsigned ldst) {
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(sp), "s"(ldst) : "memory");
-    };
-    int ftap = 0, fcc = 0;                                         // (tap, K slice) of the next stage to request
+    int ftap = 0, fcc = 0;                                        // (tap, K slice) of the next stage to request
     auto fill = [&](int slot) {
       const unsigned l = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)slot * STAGE_BYTES);
       const long aoff = ((long)tap_offset(g, ftap) * g.lda + fcc * 64) * 2;
@@ -347,7 +149,7 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
 #pragma unroll
       for (int h = 0; h < NDMA; ++h) {
         const int pz = NDMA * dw + h;
-        dma(src[h] + (pz < APIECE ? aoff : boff), l + pz * 1024);  // (the stage image is [A pieces | B pieces]: piece pz at pz KB)
+        lds_dma16(src[h] + (pz < APIECE ? aoff : boff), l + pz * 1024);  // (the stage image is [A pieces | B pieces]: piece pz at pz KB)
       }
       if (++fcc == kc) { fcc = 0; ++ftap; }
     };
@@ -373,18 +175,14 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
     }
   } else {
     // ------------------------------------------------------------------------------------------ the eight compute waves
-    auto lfrag = [&](const unsigned char* base, int row, int ks) -> frag {
-      const int c = 4 * ks + q;
-      return *reinterpret_cast<const frag*>(base + row * 128 + ((c ^ (row & 7)) << 4));
-    };
     constexpr int LGKM0 = 0xC07F;                                  // s_waitcnt lgkmcnt(0); vmcnt / expcnt untouched (gfx9 encoding)
     auto read_set = [&](frag (&a)[4], frag (&b)[NJ], int slot, int ks) {
       const unsigned char* ta = cd_lds + (size_t)slot * STAGE_BYTES;
       const unsigned char* tb = ta + A_BYTES;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = lfrag(ta, wm * 64 + 16 * i + n, ks);
+      for (int i = 0; i < 4; ++i) a[i] = lds_frag<T>(ta, wm * 64 + 16 * i + n, ks, q);
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) b[j] = lfrag(tb, wn * (BN / 2) + 16 * j + n, ks);
+      for (int j = 0; j < NJ; ++j) b[j] = lds_frag<T>(tb, wn * (BN / 2) + 16 * j + n, ks, q);
     };
     auto mma_set = [&](const frag (&a)[4], const frag (&b)[NJ]) {
 #pragma unroll
@@ -445,60 +243,13 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
 #endif
 #undef CST
   }
-  T* C = reinterpret_cast<T*>(g.C);
-  float st1[NJ], st2[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) st1[j] = st2[j] = 0.f;
-  if (!dma_wave) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm * 64 + 16 * i + 4 * q + r;
-        if (!interior(row, g.P, g.H, g.W)) continue;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int col = n0 + wn * (BN / 2) + 16 * j + n;
-          if (col >= g.Cout) continue;
-          float v = acc[i][j][r] + (g.bias ? g.bias[col] : 0.f);
-          if (g.scale) {
-            v = v * g.scale[col] + g.shift[col];
-            v = v > 0.f ? v : g.slope * v;
-          }
-          const T o = from_f32<T>(v);
-          C[row * g.ldc + col] = o;
-          const float vo = to_f32<T>(o);
-          st1[j] += vo;
-          st2[j] += vo * vo;
-        }
-      }
-  }
+  float st1[NJ] = {}, st2[NJ] = {};
+  if (!dma_wave) conv_epilogue<T>(g, acc, m0 + wm * 64 + 4 * q, n0 + wn * (BN / 2) + n, st1, st2);
   if (g.stat_part) {
     // the workgroup covers TWO 128-row statistics tiles (waves wm = 0,1 and wm = 2,3): same sums in the same order as
     // conv_tiled_kernel's, tile by tile.  (All ten waves take the two barriers.)
     __syncthreads();                                             // the ring is free: every wave has left the main loop
-    float* sp = reinterpret_cast<float*>(cd_lds);                // [wm][stat][BN]
-    if (!dma_wave) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        float a = st1[j], b = st2[j];
-        a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
-        b += __shfl_xor(b, 16); b += __shfl_xor(b, 32);
-        if (q == 0) {
-          sp[(wm * 2 + 0) * BN + wn * (BN / 2) + 16 * j + n] = a;
-          sp[(wm * 2 + 1) * BN + wn * (BN / 2) + 16 * j + n] = b;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid < 2 * BN) {
-      const int t = tid / BN, c = tid % BN;
-      if (m0 + 128 * t < g.P) {
-        float* pt = g.stat_part + (size_t)(m0 / 128 + t) * 2 * g.ldp + n0 + c;
-        pt[0] = sp[((2 * t) * 2 + 0) * BN + c] + sp[((2 * t + 1) * 2 + 0) * BN + c];
-        pt[g.ldp] = sp[((2 * t) * 2 + 1) * BN + c] + sp[((2 * t + 1) * 2 + 1) * BN + c];
-      }
-    }
+    conv_stat_part<BN, 2>(g, reinterpret_cast<float*>(cd_lds), st1, st2, !dma_wave, wm, wn, m0, n0);
   }
 }
 
@@ -1325,22 +1076,22 @@ static inline int grid_for(long total, int cap = 4096) {
   return (int)(g > cap ? cap : (g < 1 ? 1 : g));
 }
 
-}  // namespace
+// conv_dma_kernel<BN, 3> with its ring of three stages in dynamic LDS
+template <int BN> int launch_conv_dma(dim3 grid, hipStream_t st, const ConvArgs& g) {
+  constexpr int smem = 3 * (256 + BN) * 128;
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dma_kernel<BN, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            smem) != hipSuccess)
+      return NPPC_ELAUNCH;
+    attr = true;
+  }
+  hipLaunchKernelGGL((conv_dma_kernel<BN, 3>), grid, dim3(640), smem, st, g);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
 
-// typed launch: KERNEL<bf16_t> or KERNEL<float> with the void* operands cast by the ARGS expression (uses `TT`)
-#define LAUNCH_T(prec, KERNEL, GRID, ...)                                                        \
-  do {                                                                                            \
-    if ((prec) == NPPC_PREC_BF16) {                                                               \
-      typedef bf16_t TT;                                                                          \
-      hipLaunchKernelGGL(KERNEL<TT>, GRID, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);       \
-    } else if ((prec) == NPPC_PREC_F32) {                                                         \
-      typedef float TT;                                                                           \
-      hipLaunchKernelGGL(KERNEL<TT>, GRID, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);       \
-    } else {                                                                                      \
-      return NPPC_EBADARG;                                                                        \
-    }                                                                                             \
-    NPPC_CHECK_LAUNCH();                                                                          \
-  } while (0)
+}  // namespace
 
 extern "C" {
 
@@ -1374,29 +1125,7 @@ static int conv_fwd_impl(int prec, const void* A, long lda, const void* Wp, void
       const char* mt = getenv("NPPC_CONV_DMA_MIN_TILES");          // (tests lower it to run small, ragged shapes through the ring kernel)
       if (tiles >= (mt ? atol(mt) : 256L)) {
         dim3 grid(round_up(ceil_div(g.P, 256), 8), Np / bn);
-        if (bn == 128) {
-          constexpr int smem = 3 * (256 + 128) * 128;
-          static bool attr = false;
-          if (!attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dma_kernel<128, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    smem) != hipSuccess)
-              return NPPC_ELAUNCH;
-            attr = true;
-          }
-          hipLaunchKernelGGL((conv_dma_kernel<128, 3>), grid, dim3(640), smem, st, g);
-        } else {
-          constexpr int smem = 3 * (256 + 64) * 128;
-          static bool attr = false;
-          if (!attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dma_kernel<64, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    smem) != hipSuccess)
-              return NPPC_ELAUNCH;
-            attr = true;
-          }
-          hipLaunchKernelGGL((conv_dma_kernel<64, 3>), grid, dim3(640), smem, st, g);
-        }
-        NPPC_CHECK_LAUNCH();
-        return NPPC_OK;
+        return bn == 128 ? launch_conv_dma<128>(grid, st, g) : launch_conv_dma<64>(grid, st, g);
       }
     }
     if (Np % 128 == 0) {
@@ -1411,8 +1140,12 @@ static int conv_fwd_impl(int prec, const void* A, long lda, const void* Wp, void
     NPPC_CHECK_LAUNCH();
     return NPPC_OK;
   }
+  // The register-path kernel.  Reached only in bf16 with Cin % 64 == 32: Cin % 32 == 0 is required above and the fp32 stage is
+  // 32 wide, so every fp32 shape takes the tiled kernel (there is no conv_kernel<float>).
+  if (prec != NPPC_PREC_BF16) return NPPC_EBADARG;
   dim3 grid(ceil_div(g.P, 128), Np / 64);
-  LAUNCH_T(prec, conv_kernel, grid, g);
+  hipLaunchKernelGGL(conv_kernel<bf16_t>, grid, dim3(256), 0, st, g);
+  NPPC_CHECK_LAUNCH();
   return NPPC_OK;
 }
 

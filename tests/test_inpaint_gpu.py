@@ -169,6 +169,40 @@ def test_conv_forward_input_gradient_weight_gradient(pname, prec, dtype, tol, B,
     assert rel(dW.cpu(), wr.grad) < (tol if pname == "fp32" else 1e-2)
 
 
+@pytest.mark.parametrize("folded", [False, True])
+@pytest.mark.parametrize("B,H,W,Cin,Cout,ks", [(2, 9, 13, 32, 64, 3), (1, 6, 37, 96, 100, 3), (3, 5, 7, 32, 5, 1)])
+def test_conv_register_path_kernel_matches_conv2d(B, H, W, Cin, Cout, ks, folded):
+    """csrc/unet.hip conv_kernel (fragments straight from global memory, two k-steps deep): the kernel that bf16 convolutions with
+    Cin % 64 == 32 take -- no layer of the U-Net has such a width, so the other convolution tests never reach it.  One and nine
+    taps, one and three k-steps per tap, a ragged last pixel tile, padded output columns, with and without the folded
+    BatchNorm + LeakyReLU epilogue; the halo stays zero."""
+    from nppc_audio import _hip as Hh
+    _, prec, dtype, tol = PRECS[1]
+    g = torch.Generator().manual_seed(B * 100 + Cin + Cout)
+    x = q(torch.randn(B, Cin, H, W, generator=g), dtype)
+    w = torch.randn(Cout, Cin, ks, ks, generator=g) / np.sqrt(Cin * ks * ks)
+    b = torch.randn(Cout, generator=g) * 0.1
+    sc, sh = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.1
+    Np = (Cout + 63) // 64 * 64
+    nt = ks * ks
+    wf = torch.empty(Np * nt * Cin, dtype=dtype, device="cuda")
+    wb = torch.empty(Cin * nt * Np, dtype=dtype, device="cuda")
+    s = Hh.stream()
+    Hh.call("nppc_conv_pack", prec, w.cuda(), wf, wb, Cout, Cin, ks, Np, Cin, Cin, Np, s)
+    X = Halo(B, H, W, Cin, dtype).put(x)
+    Y = Halo(B, H, W, Np, dtype)
+    Hh.call("nppc_conv_fwd", prec, X.t, Cin, wf, Y.t, Np, b.cuda(), sc.cuda() if folded else None, sh.cuda() if folded else None,
+            0.2, B, H, W, Cin, Cout, Np, ks, s)
+    torch.cuda.synchronize()
+    ref = F.conv2d(x, q(w, dtype), b, padding=ks // 2)
+    if folded:
+        ref = F.leaky_relu(ref * sc[None, :, None, None] + sh[None, :, None, None], 0.2)
+    err = rel(Y.get(Cout), ref)
+    print(f"register-path conv {B, H, W, Cin, Cout, ks} folded={folded}: rel err {err:.3e} (tol {tol})")
+    assert err < tol
+    assert Y.halo_is_zero()
+
+
 @pytest.mark.parametrize("pname,prec,dtype,tol", PRECS)
 @pytest.mark.parametrize("B,H,W,Cin", [(2, 9, 13, 1), (3, 6, 37, 2)])
 def test_thin_first_convolution_matches_conv2d(pname, prec, dtype, tol, B, H, W, Cin):
