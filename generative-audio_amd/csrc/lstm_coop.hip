@@ -59,18 +59,13 @@ struct CoopArgs {
 };
 
 constexpr unsigned SPIN_LIMIT = 1u << 22;
-#ifdef CF_NO_POLL
-constexpr bool CF_POLL = false;                      // diagnostic: never wait for a partner (timing only, results are garbage)
-#else
-constexpr bool CF_POLL = true;
-#endif
 
 // The bounded spin of the hand-off protocol, once per loop shape.  On time-out the caller's counting lane(s) add 1 to the
 // sticky time-out word `tmo` and the wave carries on.  Which lanes poll and which lane counts is the call site's choice.
 // Shape 1 -- load, compare, sleep, count: the calling lane waits until *flag >= ep; every calling lane counts its own time-out.
 __device__ __forceinline__ void spin_until(const gu32* flag, unsigned ep, gu32* tmo) {
   unsigned spins = 0;
-  while (CF_POLL && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ep) {
+  while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ep) {
     __builtin_amdgcn_s_sleep(1);
     if (++spins > SPIN_LIMIT) {
       __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -83,7 +78,7 @@ __device__ __forceinline__ void spin_until(const gu32* flag, unsigned ep, gu32* 
 // `counts`: this lane records the time-out.
 __device__ __forceinline__ void spin_reload(unsigned& fl, const gu32* flag, unsigned ep, gu32* tmo, bool counts) {
   unsigned spins = 0;
-  while (CF_POLL && fl < ep) {
+  while (fl < ep) {
     if (++spins > SPIN_LIMIT) {
       if (counts) __hip_atomic_fetch_add(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       break;
@@ -105,9 +100,6 @@ __device__ __forceinline__ u32x4 load_sc1_b128(__amdgpu_buffer_rsrc_t r, int off
 template <typename T>
 __device__ __forceinline__ int frag_boff(int gp, int ublk, int kk, int s, int nk) {
   const int w8 = ublk / 3, ub3 = ublk % 3;
-#ifdef CF_W_L1
-  return (((((gp * 8 + w8) * nk + kk) * 3 + ub3) * 2 + s) * 512 * (int)sizeof(T)) & 0x3fff;   // diagnostic: weights from L1
-#endif
   return ((((gp * 8 + w8) * nk + kk) * 3 + ub3) * 2 + s) * 512 * (int)sizeof(T);
 }
 
@@ -131,18 +123,9 @@ __device__ __forceinline__ void coop_prime(typename Frag<T>::type (&pre)[DEPTH -
 // cycles (SQ_LDS_BANK_CONFLICT = 0.48 of SQ_LDS_IDX_ACTIVE in all three recurrent kernels); with + 16 the conflicts are gone
 // (0.06) -- and the kernels take the SAME time (forwards +-0.5 %, the K-split backward 1.5 % SLOWER: its 8-byte gate stores
 // conflict more): the LDS array is not what these kernels wait for (profiles/r04_lstm_sq_counters.txt).  Default stays 8.
-#ifndef COOP_APAD
-#define COOP_APAD 8
-#endif
-#ifndef CF_H2_LATE
-#define CF_H2_LATE 1  // forward: the partner's h2 slice is polled / requested behind layer 1's first GEMM (0 = round 3: at the top of the step)
-#endif
-#ifndef CF_APF
-#define CF_APF 1      // 80-row forward: A-operand groups read this many groups ahead of their MFMAs (0 = round 3: read, wait, multiply)
-#endif
-#ifndef CF_AG
-#define CF_AG 1       // row tiles (A fragments) per group
-#endif
+constexpr int COOP_APAD = 8;
+constexpr int CF_APF = 1;      // 80-row forward: A-operand groups read this many groups ahead of their MFMAs
+constexpr int CF_AG = 1;       // row tiles (A fragments) per group
 template <typename T, int MT, int RS, int DEPTH, bool PRIMED = false>
 __device__ __forceinline__ void coop_gemm(f32x4 (&acc)[2][MT], const T* a_lane /* row n, col 8q of the segment */, int k0, int k1,
                                           int koff /* packed k-step of segment start */, int nk, __amdgpu_buffer_rsrc_t wr, int gp,
@@ -153,8 +136,8 @@ __device__ __forceinline__ void coop_gemm(f32x4 (&acc)[2][MT], const T* a_lane /
     for (int s = 0; s < 2; ++s) b[s] = BFrag<T>::load(wr, lane, frag_boff<T>(gp, ublk, koff + kk, s, nk));
   };
   constexpr int AG = CF_AG;
-  [[maybe_unused]] frag an[CF_APF ? CF_APF : 1][AG];   // (MT > 3, CF_APF) the A groups of the next MFMAs, read CF_APF groups ahead
-  if constexpr (MT > 3 && CF_APF != 0) {
+  [[maybe_unused]] frag an[CF_APF][AG];   // (MT > 3) the A groups of the next MFMAs, read CF_APF groups ahead
+  if constexpr (MT > 3) {
     constexpr int NG0 = (MT + AG - 1) / AG;
 #pragma unroll
     for (int p = 0; p < CF_APF; ++p)
@@ -179,7 +162,6 @@ __device__ __forceinline__ void coop_gemm(f32x4 (&acc)[2][MT], const T* a_lane /
       // (not 4*MT, twice that when the scheduler hoists the next k-step's reads) VGPRs hold A operands -- the 80-row
       // variant spilled its layer-2 cell state otherwise, and ANY scratch reload waits for every outstanding
       // memory operation of the wave (hand-off stores, HBM streams)
-#if CF_APF
       // round 4: LDS reads run CF_APF groups ahead of their MFMAs (behind the last group of a k-step: the first groups of
       // the next one): a wave's own matrix work covers part of the LDS latency of its next operands, the other waves of
       // the SIMD the rest (round 3 issued a group's reads and waited for them right there: three exposed LDS round trips
@@ -208,21 +190,6 @@ __device__ __forceinline__ void coop_gemm(f32x4 (&acc)[2][MT], const T* a_lane /
 #pragma unroll
         for (int i = 0; i < AG; ++i) an[CF_APF - 1][i] = nx[i];
       }
-#else
-#pragma unroll
-      for (int m0 = 0; m0 < MT; m0 += AG) {
-        frag af[AG];
-#pragma unroll
-        for (int i = 0; i < AG; ++i)
-          if (m0 + i < MT) af[i] = load_frag<T>(a_lane + 16 * (m0 + i) * RS + 32 * kk);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int i = 0; i < AG; ++i)
-            if (m0 + i < MT) acc[s][m0 + i] = mma16(af[i], b[s], acc[s][m0 + i]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#endif
     }
   };
   frag b[DEPTH][2];
@@ -264,35 +231,8 @@ template <typename T> __device__ __forceinline__ void store1_nt(T* p, float v) {
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // LDS row (elements): [X0 (KX) | X1 (KX) | H1 (H) | H2 (H)] + pad.  H = 384 = 12 k-steps.
-// diagnostic phase timers of the forward kernel (tools/diag/stamp_fwd.py builds with -DCF_STAMP)
-// diagnostic builds of the forward kernel (tools/diag/fwd_variants.py; timing only, results are garbage):
-//   CF_NO_CELL  the cell update without its transcendentals (a handful of VALU instructions per cell): what the pointwise
-//               phases cost a step, i.e. what ANY schedule that hides them behind the fragment stream could win at most
-//   CF_NO_BAR   no workgroup barrier inside the time step (the waves of a CU run free): what the step's barriers cost
-//   CF_PRIO=n   static wave priorities: 1 = older waves first (waves 0-3: 3, 4-7: 2, 8-11: 1), 2 = younger waves first
-#ifdef CF_NO_CELL
-#define CF_SIG(x) (0.5f * (x))
-#define CF_TANH(x) (x)
-#else
-#define CF_SIG(x) sigmoid_f(x)
-#define CF_TANH(x) tanh_f(x)
-#endif
-#ifdef CF_NO_BAR
-#define CF_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
-#define CF_BARRIER() __syncthreads()
-#endif
-#ifdef CF_STAMP
-#define FT(i) if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long nw = __builtin_readcyclecounter(); ft_acc[i] += nw - ft_last; ft_last = nw; }
-#else
-#define FT(i)
-#endif
-
 template <typename T, int G, int MT, int KX, bool TRAIN, bool HEAD = false>
 __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(CoopArgs a) {
-#ifdef CF_STAMP
-  unsigned long long ft_last = __builtin_readcyclecounter(), ft_acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
   constexpr int H = 384, HC = H / G, NW = HC / 16, NT = NW * 64, MC = 16 * MT;
   constexpr int VEC = 16 / (int)sizeof(T);
   constexpr int RS = 2 * KX + 2 * H + (sizeof(T) == 2 ? COOP_APAD : VEC);
@@ -318,10 +258,6 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
   int cluster, cu;
   coop_ids(G, cluster, cu);
   if (cluster >= a.clusters) return;
-#ifdef CF_PRIO
-  if (CF_PRIO == 1) { if (wave < 4) __builtin_amdgcn_s_setprio(3); else if (wave < 8) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
-  else { if (wave < 4) __builtin_amdgcn_s_setprio(1); else if (wave < 8) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
-#endif
   const int ublk = cu * NW + wave;                                // global 16-unit block of this wave
   const int unit_n = ublk * 16 + n;
   const long row0 = (long)cluster * MC;
@@ -408,7 +344,7 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
       store_sc1_b128(xr, base + ch * 16, v);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // every storing wave drains its write-through stores
-    CF_BARRIER();
+    __syncthreads();
     if (tid == 0) __hip_atomic_store(flags + layer * G + cu, (unsigned)ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   // wait for the partners' slices of (layer, epoch) and copy them into LDS
@@ -417,7 +353,7 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
       if (lane < G && lane != cu) spin_until(flags + layer * G + lane, (unsigned)ep, tmo);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");     // compiler ordering only: payload loads are sc1
     }
-    CF_BARRIER();
+    __syncthreads();
     const int par = ep & 1;
 #pragma unroll 1
     for (int p = 0; p < G; ++p) {
@@ -456,7 +392,7 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
     // are held across layer 1 (12 VGPRs per lane before: spilled in the 80-row variant, and a spill store made the
     // wave wait out the hand-off latency at the top of every step); nobody reads H2 during layer 1, and barrier (1)
     // drains the DMA (a pending LDS write on the vm counter) long after it landed.
-    // Round 4 (CF_H2_LATE): polled and requested BEHIND layer 1's first GEMM, in front of its pointwise phase, instead of
+    // Round 4: polled and requested BEHIND layer 1's first GEMM, in front of its pointwise phase, instead of
     // at the top of the step -- a wave's vector-memory operations retire in order, so at the top the first weight
     // fragments of the step queued behind the poll and the cross-CU read (in-kernel stamps: the step's first GEMM phase
     // took 15.8k cycles against 7-8k for the other 12-14 k-step phases); here the partner's flag is a third of a step old
@@ -476,13 +412,12 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
         }
       }
     };
-    if (!CF_H2_LATE) h2_fetch();
     const bool more = t + 1 < a.Tn;
     // x_{t+1} -> the X buffer this step does not read, by LDS-DMA as well (one 128-byte row per instruction,
     // non-temporal: read once).  Issued BEHIND layer 1's GEMMs, in front of its pointwise phase and the two barriers: a
     // wave's vector-memory operations retire in order, so at the top of the step this HBM read sat in front of the first
     // weight fragments of layer 1 and every wave waited out its latency there (0.3 ms per launch; here the pointwise
-    // phase covers most of it: restorer forward 9.10 -> 8.93 ms, tools/diag/lstm_variants.py)
+    // phase covers most of it: restorer forward 9.10 -> 8.93 ms)
     auto x_prefetch = [&]() {
       if (more) {
         typedef __attribute__((address_space(3))) void lds_void;
@@ -504,14 +439,13 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
       for (int mt = 0; mt < MT; ++mt) acc[0][mt] = acc[1][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
       coop_gemm<T, MT, RS, DEPTH>(acc, a_lane + (p ? OX1 : OX0), 0, NKX, 0, nk1, wr1, 0, ublk, lane);
       coop_gemm<T, MT, RS, DEPTH>(acc, a_lane + OH1, 0, NKH, NKX, nk1, wr1, 0, ublk, lane);
-      if (CF_H2_LATE) h2_fetch();
-      FT(0)
+      h2_fetch();
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float iv = CF_SIG(acc[0][mt][j] + bias(0, 0));
-          const float gv = CF_TANH(acc[1][mt][j] + bias(0, 2));
+          const float iv = sigmoid_f(acc[0][mt][j] + bias(0, 0));
+          const float gv = tanh_f(acc[1][mt][j] + bias(0, 2));
           ig[mt][j] = iv * gv;
           if (TRAIN) { iv1[mt][j] = iv; gv1[mt][j] = gv; }
         }
@@ -528,39 +462,31 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
       // before the barriers that publish it to the other waves; the next x follows and is drained by barrier (1)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       x_prefetch();
-      FT(1)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float fv = CF_SIG(acc[0][mt][j] + bias(0, 1));
-          const float ov = CF_SIG(acc[1][mt][j] + bias(0, 3));
+          const float fv = sigmoid_f(acc[0][mt][j] + bias(0, 1));
+          const float ov = sigmoid_f(acc[1][mt][j] + bias(0, 3));
           const float cn = fv * c1[mt][j] + ig[mt][j];
           c1[mt][j] = cn;
-          hn1[mt][j] = ov * CF_TANH(cn);
+          hn1[mt][j] = ov * tanh_f(cn);
           if (TRAIN && rbase + 16 * mt + j < N) {
             const size_t e = ebase + (size_t)(16 * mt + j) * H;
-#ifndef CF_NO_SAVE
             sc1[(4 * q + 16 * mt + j) * HC + wave * 16 + n] = from_f32<T>(cn);
             store4_nt<T>(g1o + e * 4, iv1[mt][j], gv1[mt][j], fv, ov);
-#endif
           }
         }
     }
     if (PR) coop_prime<T, DEPTH>(pre, NKH, NKH, nk2, wr2, 0, ublk, lane);       // layer 2, pair (i,g), h2 half
-    CF_BARRIER();                                              // (1) all waves done reading h1_{t-1} and x_t
-    FT(2)
+    __syncthreads();                                           // (1) all waves done reading h1_{t-1} and x_t
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) hw_lane[OH1 + (16 * mt + j) * RS] = from_f32<T>(hn1[mt][j]);
-    CF_BARRIER();                                              // (2a) own h1_t slice complete in LDS
-    FT(3)
+    __syncthreads();                                           // (2a) own h1_t slice complete in LDS
     publish(0, OH1, ep);
-    FT(4)
-#ifndef CF_NO_SAVE
     if (TRAIN) flush_state(h1o, c1o, sc1, OH1, t);                // after the hand-off drain, not in front of it
-#endif
     // ================= layer 2 =================
     // gate pair (i,g): the h2_{t-1} half first -- it does not need the partners' h1_t, so it hides the hand-off latency
     f32x4 ig2[MT];
@@ -570,19 +496,16 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) acc[0][mt] = acc[1][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
       coop_gemm<T, MT, RS, DEPTH, PR>(acc, a_lane + OH2, 0, NKH, NKH, nk2, wr2, 0, ublk, lane, pre);
-      FT(5)
       if (PR) coop_prime<T, DEPTH>(pre, NKH, 0, nk2, wr2, 0, ublk, lane);       // h1 half: in flight during the hand-off
       consume(0, OH1, ep);
-      CF_BARRIER();                                            // (2c) full h1_t in LDS
-      FT(6)
+      __syncthreads();                                         // (2c) full h1_t in LDS
       coop_gemm<T, MT, RS, DEPTH, PR>(acc, a_lane + OH1, 0, NKH, 0, nk2, wr2, 0, ublk, lane, pre);
-      FT(7)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float iv = CF_SIG(acc[0][mt][j] + bias(1, 0));
-          const float gv = CF_TANH(acc[1][mt][j] + bias(1, 2));
+          const float iv = sigmoid_f(acc[0][mt][j] + bias(1, 0));
+          const float gv = tanh_f(acc[1][mt][j] + bias(1, 2));
           ig2[mt][j] = iv * gv;
           if (TRAIN) { iv2[mt][j] = iv; gv2[mt][j] = gv; }
         }
@@ -594,38 +517,31 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) acc[0][mt] = acc[1][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
       coop_gemm<T, MT, RS, DEPTH>(acc, a_lane + OH1, 0, 2 * NKH, 0, nk2, wr2, 1, ublk, lane);
-      FT(9)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float fv = CF_SIG(acc[0][mt][j] + bias(1, 1));
-          const float ov = CF_SIG(acc[1][mt][j] + bias(1, 3));
+          const float fv = sigmoid_f(acc[0][mt][j] + bias(1, 1));
+          const float ov = sigmoid_f(acc[1][mt][j] + bias(1, 3));
           const float cn = fv * c2[mt][j] + ig2[mt][j];
           c2[mt][j] = cn;
-          hn2[mt][j] = ov * CF_TANH(cn);
+          hn2[mt][j] = ov * tanh_f(cn);
           if (rbase + 16 * mt + j < N) {
             const size_t e = ebase + (size_t)(16 * mt + j) * H;
             if (TRAIN) {
-#ifndef CF_NO_SAVE
               sc2[(4 * q + 16 * mt + j) * HC + wave * 16 + n] = from_f32<T>(cn);
               store4_nt<T>(g2o + e * 4, iv2[mt][j], gv2[mt][j], fv, ov);
-#endif
             }
           }
         }
     }
-    CF_BARRIER();                                              // (3) all waves done reading h2_{t-1} / h1_t
-    FT(10)
+    __syncthreads();                                           // (3) all waves done reading h2_{t-1} / h1_t
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) hw_lane[OH2 + (16 * mt + j) * RS] = from_f32<T>(hn2[mt][j]);
-    CF_BARRIER();                                              // own h2_t slice complete in LDS
-    FT(11)
+    __syncthreads();                                           // own h2_t slice complete in LDS
     if (more) publish(1, OH2, ep);
-    FT(12)
-#ifndef CF_NO_SAVE
     if constexpr (HEAD) {
       // Linear(H -> O) on the own h2_t slice, still in LDS as the MFMA A operand: wave w multiplies row tile w by the
       // own units' head weights (6 k-steps, B fragments from L2) and leaves O partial sums per row; the 1.6 GB of h2
@@ -648,12 +564,7 @@ __global__ __launch_bounds__((384 / G / 16) * 64) void lstm2_coop_fwd_kernel(Coo
       }
     }
     if constexpr (TRAIN || !HEAD) flush_state(h2o, c2o, sc2, OH2, t);   // training keeps h2 / c2; inference only without a fused head
-#endif
   }
-#ifdef CF_STAMP
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (int i = 0; i < 13; ++i) ((unsigned long long*)(a.flags + (size_t)a.clusters * 2 * G + 4))[i] = ft_acc[i];
-#endif
 }
 
 // =====================================================================================================
@@ -913,18 +824,11 @@ constexpr int C2_NKK = CB_KC / 32;                          // 24 k-steps over t
 constexpr int C2_SLOTS = 4;                                 // column tiles per wave (layer 2: 4, layer 1: 2 or 3)
 constexpr int C2_FPC = 2 * CB_G * CB_NW;                     // epoch words per cluster: [layer 2][cu 2][wave 12] (every wave hands off its own tiles)
 constexpr int C2_XW = 2 * CB_HC;                            // 384 partial columns exchanged per row (layer 1 uses 224)
-#ifndef C2_DEPTH
-#define C2_DEPTH 4                                          // fragment ring: C2_DEPTH - 1 k-steps requested ahead
-#endif
-#ifndef C2_KBAR
-#define C2_KBAR 8                                           // k-steps between the in-pass barriers that keep the waves in step (0: none)
-#endif
+constexpr int C2_DEPTH = 4;                                 // fragment ring: C2_DEPTH - 1 k-steps requested ahead
+constexpr int C2_KBAR = 8;                                  // k-steps between the in-pass barriers that keep the waves in step (0: none)
 
 // B fragment (cu, wave, kk, slot): [cu][wave][kk][slot][lane][8]
 __device__ __forceinline__ int c2_frag_boff(int cu, int wave, int kk, int slot) {
-#ifdef CF_W_L1
-  return (((((cu * CB_NW + wave) * C2_NKK + kk) * C2_SLOTS + slot) * 512) * 2) & 0x3fff;      // diagnostic: weights from L1
-#endif
   return ((((cu * CB_NW + wave) * C2_NKK + kk) * C2_SLOTS + slot) * 512) * 2;
 }
 
@@ -964,20 +868,6 @@ __device__ __forceinline__ void c2_wait(int m, bf16x8& x) {
   }
 #undef C2_W
 }
-
-// diagnostic phase timers (tools/diag/stamp_bwd2.py builds with -DC2_STAMP): thread 0 of workgroup 0 accumulates
-// s_memtime deltas per phase and leaves them behind the flag words
-#ifdef C2_STAMP
-#ifndef C2_STAMP_TID
-#define C2_STAMP_TID 0
-#endif
-#define C2_STAMP_INIT unsigned long long st_last = __builtin_readcyclecounter(), st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define C2T(i) if (blockIdx.x == 0 && tid == C2_STAMP_TID) { const unsigned long long nw = __builtin_readcyclecounter(); st_acc[i] += nw - st_last; st_last = nw; }
-#define C2_STAMP_FINI if (blockIdx.x == 0 && tid == C2_STAMP_TID) { for (int i = 0; i < 12; ++i) ((unsigned long long*)(a.flags + (size_t)a.clusters * C2_FPC + 4))[i] = st_acc[i]; }
-#else
-#define C2T(i)
-#endif
-
 
 template <int... I, typename F>
 __device__ __forceinline__ void c4_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
@@ -1086,9 +976,6 @@ struct KSplit {
   // moved in registers instead of being read from HBM a second time
   __device__ void fetch(Saved& sv, const T* gs, const T* cs, const T* dh_ext, int t, bool carry) const {
     if (!prow_ok || t < 0) return;
-#ifdef C2_NO_FETCH
-    return;                               // diagnostic: timing without the saved-state loads (results are garbage)
-#endif
     int tc = tc_;
     asm volatile("" : "+v"(tc));          // keep the per-chunk addresses out of the loop-invariant (spilled) set
     const size_t e = ((size_t)t * N + row0 + prow) * H + cu * HC;
@@ -1108,9 +995,6 @@ struct KSplit {
   // insertion drain the whole queue in front of the next fragment use.
   template <typename WithDh>
   __device__ void fetch_part(WithDh, Saved& sv, const T* gs, const T* cs, const T* dh_ext, int t, int j0, int j1) const {
-#ifdef C2_NO_FETCH
-    return;
-#endif
     int tc = tc_;
     asm volatile("" : "+v"(tc));
     const int tcl = t > 0 ? t : 0, tpl = t > 1 ? t - 1 : 0;
@@ -1157,9 +1041,7 @@ struct KSplit {
       }
       if (!prow_ok) { out = u32x4{0u, 0u, 0u, 0u}; dcv = float2{0.f, 0.f}; }
       *reinterpret_cast<float2*>(dcl + prow * HC + 2 * c) = dcv;
-#ifndef C2_NO_DG
       __builtin_amdgcn_raw_buffer_store_b128(out, dgr, rowoff + 16 * c, 0, 2);       // aux 2 = nt
-#endif
       *reinterpret_cast<u32x4*>(Abuf + prow * RSA + 8 * c) = out;
     }
   }
@@ -1231,17 +1113,11 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
   constexpr int MC = KS::MC, HC = KS::HC, KX = CB_KX, NT = CB_NT, RSA = KS::RSA;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
 
-#ifdef C2_STAMP
-  C2_STAMP_INIT
-#endif
   const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, q = lane >> 4, n_ = n, q_ = q;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int cluster, cu;
   coop_ids(CB_G, cluster, cu);
   if (cluster >= a.clusters) return;
-#ifdef C2_WPRIO
-  if (wave >= 9) asm volatile("s_setprio 3"); else if (wave >= 6) asm volatile("s_setprio 2"); else if (wave >= 3) asm volatile("s_setprio 1");
-#endif
   const int pcu = 1 - cu;
   const long N = a.N;
   KS ks;
@@ -1346,11 +1222,7 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
     constexpr int layer = decltype(layer_c)::value;
     constexpr bool l2 = layer == 1;
     typedef std::integral_constant<bool, l2 && !HEAD> with_dh;             // only layer 2 without the fused head reads d h2
-#ifdef C2_NO_FETCH
-    constexpr int P1 = 0;
-#else
     constexpr int P1 = 4 * (2 + (with_dh::value ? 1 : 0));
-#endif
     constexpr int RD = C2_DEPTH - 1;
     const unsigned char* wbase = reinterpret_cast<const unsigned char*>(wpacked) + (size_t)(cu * CB_NW + wave) * (C2_NKK * C2_SLOTS * 1024);
     const bool xw = !l2 && wave < 4;                   // this wave also has a d x tile (slot 2)
@@ -1465,9 +1337,6 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
     head_add();
     __syncthreads();
   }
-#ifdef C2_STAMP
-  st_last = __builtin_readcyclecounter();
-#endif
 
 #pragma unroll 1
   for (int t = a.Tn - 1; t >= 0; --t) {
@@ -1479,27 +1348,13 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
     // clusters an eighth of a step apart changed nothing.)
     // ---------------- LSTM layer 2 (exchange layer index 1)
     ks.cell_bwd(sv2, dhrec2, !HEAD, dc2, t, dg2T);
-    C2T(0)
-#ifdef C2_RAWBAR
-    lds_barrier();                                     // own dgates complete in LDS; everyone done reading dhrec2
-#else
     __syncthreads();                                   // own dgates complete in LDS; everyone done reading dhrec2
-#endif
-    C2T(1)
-    C2T(2)
     layer_gemm(std::integral_constant<int, 1>{}, a.wb2, ep, sv2, g2, c2, dh2_src, t - 1);   // d h1_t (both contributions) and d h2_{t-1} final
     if (t > 0) head_add();                             // HEAD: + dY_{t-1} . Wh (read by the next step's cell phase, barriers between)
     // ---------------- LSTM layer 1 (exchange layer index 0)
     ks.cell_bwd(sv1, dh1buf, false, dc1, t, dg1T);
-    C2T(9)
-#ifdef C2_RAWBAR
-    lds_barrier();
-#else
     __syncthreads();
-#endif
-    C2T(10)
     layer_gemm(std::integral_constant<int, 0>{}, a.wb1, ep, sv1, g1, c1, nullptr, t - 1);   // d h1_{t-1} (recurrent) and this CU's 32 columns of d x final
-    C2T(11)
     int ti = tid;
     asm volatile("" : "+v"(ti));                         // (a hoisted per-lane d x address was spilled: its reload sat behind the barrier)
     for (int i = ti; i < MC * 32; i += NT) {
@@ -1508,9 +1363,6 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd2_kernel(CoopBwd2Args a) 
     }
     // (dxbuf is rewritten by the next layer-1 GEMM only, several barriers later)
   }
-#ifdef C2_STAMP
-  C2_STAMP_FINI
-#endif
 }
 
 // =====================================================================================================
@@ -1539,9 +1391,7 @@ constexpr long C4_WFRAG = (long)C4_NKK * C4_G * 1024;       // packed weights of
 //   wait + the four MFMAs of k-step g
 //   tail(g)   g = 11, 23, 35: ship the finished partner tile (2 stores; g = 11 of layer 2 with the fused head: + 2 dY DMAs)
 // Every wait is vmcnt(M), M = operations issued after the one waited for (see c2_ring_load); this table holds the counts.
-#ifndef C4_DEPTH
-#define C4_DEPTH 8                                          // fragment ring of the four-CU kernel: C4_DEPTH - 1 k-steps (1 KB each) requested ahead
-#endif
+constexpr int C4_DEPTH = 8;                                 // fragment ring of the four-CU kernel: C4_DEPTH - 1 k-steps (1 KB each) requested ahead
 template <int DY, int D /* k-steps requested ahead */>
 struct C4Sched {
   int before[49];    // vector-memory operations issued before side(pos)
@@ -1682,9 +1532,6 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
       unsigned fla = 0, flb = 0;
       u32x4 pa[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}}, pb[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
       auto poll = [&](unsigned& fl, const gu32* pf) {
-#ifdef C4_DIAG_NOPOLL
-        return;                                         // diagnostic: never wait for a partner (garbage results, timing only)
-#endif
         spin_reload(fl, pf, (unsigned)ep, tmo, lane == 0);
       };
       bf16x8 b[C4_DEPTH];
@@ -1738,9 +1585,6 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
       KS::add_packed(acc, pb);
       // cu + 1 shipped these tiles in its pass 2 and raised the epoch two thirds into its own pass: normally there by now.  Its
       // two loads go out FIRST, then the saved state of this layer's next step (younger: the wait for the partials leaves it in flight)
-#ifdef C4_DIAG_NOFINAL
-      ks.fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);      // diagnostic: the last partner's partials are not fetched (garbage results)
-#else
       unsigned flc = __hip_atomic_load(pfc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       poll(flc, pfc);
       u32x4 pc[2];
@@ -1748,7 +1592,6 @@ __global__ __launch_bounds__(CB_NT) void lstm2_coop_bwd4_kernel(CoopBwd2Args a) 
       pc[1] = load_sc1_b128(xr, offc + 16);
       ks.fetch_part(with_dh{}, nsv, ngs, ncs, ndh, nt, 0, 4);
       KS::add_packed(acc, pc);
-#endif
       scatter(acc, layer);
     }
     __syncthreads();                                   // the layer's outputs complete in LDS

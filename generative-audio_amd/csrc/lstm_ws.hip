@@ -26,7 +26,6 @@
 // Results never depend on placement or dispatch order; what must hold is co-residency of a cluster's 12 workgroups, which
 // the launcher guarantees (one workgroup per CU: > 80 KB of LDS, grid <= CU count, occupancy checked).  Every spin is
 // bounded; a time-out adds 1 to the sticky counter behind the flag words (same contract as lstm_coop.hip).
-#include <stdlib.h>
 #include "common.h"
 #include "nppc_hip.h"
 
@@ -40,14 +39,7 @@ typedef unsigned char lds_u8;   // LDS bytes (the compiler infers the address sp
 constexpr int WS_H = 384, WS_G = 12, WS_UC = 32, WS_KX = 64, WS_MC = 32, WS_NT = 512;
 constexpr int WS_NK1 = (WS_KX + WS_H) / 16;              // 28 k-steps of 16: [x | h1]
 constexpr int WS_NK2 = 2 * WS_H / 16;                    // 48 k-steps: [h1 | h2]
-#ifndef WS_MFMA16
-#define WS_MFMA16 0      // 1: 16x16x32 MFMAs (2 x 2 blocks per wave and k-step) instead of one 32x32x16 per k-step of 16
-#endif
-#if WS_MFMA16
-constexpr int WS_ROWB = (WS_KX + 2 * WS_H) * 2 + 32;     // 1696 bytes per tile row (= 32 mod 64): conflict-free b128 reads of 16 rows x 4 k-groups
-#else
 constexpr int WS_ROWB = (WS_KX + 2 * WS_H) * 2 + 16;     // 1680 bytes per tile row: odd multiple of 16 -> conflict-free b128 reads
-#endif
 constexpr int WS_TILEB = WS_MC * WS_ROWB;                // 53760
 constexpr int WS_OFF_BIAS = 2 * WS_TILEB;                // [2 layers][32 units][4 gates (i,g,f,o)] fp32
 constexpr int WS_NKL = 4;                                // layer-2 A fragments (16 k each) that stay in LDS (register budget)
@@ -76,7 +68,6 @@ struct WsArgs {
   const void* whp;      // head weights [16][H] bf16 row-major (rows >= O zero); nullptr: no head
   float* hpart;         // [Tn][N][O] fp32 head sums (bias and re-layout: nppc_sb_head_finalize with G = 1)
   long N; int Tn; int O; int clusters; int nch_max; int nchunks;
-  int prio;             // 1: the layer-2 waves (the longer GEMM) run at raised priority
 };
 
 // workgroup -> (cluster, cu).  Blocks are dealt round-robin to the 8 XCDs (b % 8 labels the blocks that share one); with the
@@ -104,23 +95,7 @@ __device__ __forceinline__ bool ws_ids(int clusters, int& cluster, int& cu) {
 __device__ __forceinline__ unsigned pack2(float a, float b) { return (unsigned)f2bf(a) | ((unsigned)f2bf(b) << 16); }
 
 // LDS-only workgroup barrier: does not drain the wave's global stores (the publish stores of THIS item stay in flight)
-#ifdef WS_DIAG_NOBARRIER
-__device__ __forceinline__ void ws_barrier() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }   // diagnostic: waves run free
-#else
 __device__ __forceinline__ void ws_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#endif
-
-// diagnostic phase timers (tools/diag/stamp_ws.py builds with -DWS_STAMP): wave 0 (layer 1) and wave 4 (layer 2) of the
-// workgroup (cluster 0, cu 0) accumulate cycles per phase and leave them behind the time-out words of the flag block
-#ifdef WS_STAMP
-#define WST_INIT unsigned long long st_last = __builtin_readcyclecounter(), st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define WST(i) if (st_on) { __builtin_amdgcn_sched_barrier(0); const unsigned long long nw = __builtin_readcyclecounter(); st_acc[i] += nw - st_last; st_last = nw; __builtin_amdgcn_sched_barrier(0); }
-#define WST_FINI(base) if (st_on && lane == 0) { for (int i_ = 0; i_ < 8; ++i_) ((unsigned long long*)(a.flags + (size_t)a.clusters * a.nch_max * 16 + 4))[(base) + i_] = st_acc[i_]; }
-#else
-#define WST_INIT
-#define WST(i)
-#define WST_FINI(base)
-#endif
 
 struct WsItem {
   int s, c;             // fused step, local chunk
@@ -134,24 +109,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t ws_rsrc(const void* base, long
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, valid ? (unsigned)(N * row_bytes) : 0u, 0x00020000);
 }
 
-// cell update of one layer for this lane's 4 cells.  acc[4m + g]: cell m, gate g in (i, g, f, o).  32x32 MFMA: cell m = unit
-// 4 hh + m of sequence lane & 31; 16x16 MFMAs: cell m = 2 sb + rb = unit 2 q + rb of sequence 16 sb + (lane & 15).  Either
-// way cells 2k, 2k + 1 are neighbouring units of one sequence: hpk[k] / gpk[k] / cpk[k] pack those pairs.
+// cell update of one layer for this lane's 4 cells.  acc[4m + g]: cell m, gate g in (i, g, f, o).  Cell m = unit 4 hh + m of
+// sequence lane & 31: cells 2k, 2k + 1 are neighbouring units of one sequence, hpk[k] / gpk[k] / cpk[k] pack those pairs.
 template <bool TRAIN>
 __device__ __forceinline__ void ws_cell(const f32x16& acc, f32x4& c, unsigned (&hpk)[2], u32x4 (&gpk)[2], unsigned (&cpk)[2]) {
   float hv[4];
-#ifdef WS_DIAG_NOCELL
-  // diagnostic build (timing only, results are garbage): no transcendentals, a handful of VALU instructions
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    c[m] = acc[4 * m] + acc[4 * m + 1] * c[m];
-    hv[m] = acc[4 * m + 2] + acc[4 * m + 3];
-    if (TRAIN) { gpk[m >> 1][2 * (m & 1)] = pack2(acc[4 * m], acc[4 * m + 1]); gpk[m >> 1][2 * (m & 1) + 1] = pack2(acc[4 * m + 2], acc[4 * m + 3]); }
-  }
-  hpk[0] = pack2(hv[0], hv[1]); hpk[1] = pack2(hv[2], hv[3]);
-  if (TRAIN) { cpk[0] = pack2(c[0], c[1]); cpk[1] = pack2(c[2], c[3]); }
-  return;
-#endif
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     const float iv = sigmoid_f(acc[4 * m + 0]);
@@ -198,18 +160,6 @@ __device__ __forceinline__ void ws_stage_out(unsigned char* smem, int layer, int
     volatile unsigned* cnt = reinterpret_cast<volatile unsigned*>(smem + WS_OFF_CNT);
     for (unsigned spins = 0; *cnt < 4u * (unsigned)(i + 1) && spins < (1u << 20); ++spins) {}   // generation i - 1 has been read
   }
-#if WS_MFMA16
-  const int n = lane & 15, q = lane >> 4;
-#pragma unroll
-  for (int sb = 0; sb < 2; ++sb) {      // cells 2 sb, 2 sb + 1: units 2 q, 2 q + 1 of sequence 16 sb + n
-    unsigned char* wrow = ws_stg<TRAIN>(smem, layer, i & 1) + (16 * sb + n) * STROW;
-    if (TRAIN) {
-      *reinterpret_cast<u32x4*>(wrow + ug * 64 + q * 16) = gpk[sb];
-      *reinterpret_cast<unsigned*>(wrow + 256 + ug * 16 + q * 4) = cpk[sb];
-    }
-    *reinterpret_cast<unsigned*>(wrow + HOFF + ug * 16 + q * 4) = hpk[sb];
-  }
-#else
   const int seq = lane & 31, hh = lane >> 5;
   unsigned char* wrow = ws_stg<TRAIN>(smem, layer, i & 1) + seq * STROW;
   if (TRAIN) {
@@ -218,7 +168,6 @@ __device__ __forceinline__ void ws_stage_out(unsigned char* smem, int layer, int
     *reinterpret_cast<u32x2*>(wrow + 256 + ug * 16 + hh * 8) = u32x2{cpk[0], cpk[1]};
   }
   *reinterpret_cast<u32x2*>(wrow + HOFF + ug * 16 + hh * 8) = u32x2{hpk[0], hpk[1]};
-#endif
 }
 // flush of staging generation g (iteration g): layer-2 outputs of item g, layer-1 outputs of item g - 1 (layer 1 runs its
 // cell update one iteration late, see the kernel).  Done by the four layer-2 waves, wave ug rows [8 ug, 8 ug + 8) of both
@@ -261,32 +210,9 @@ __device__ __forceinline__ void ws_flush_store(const WsFlush& f, int layer, int 
 }
 
 __device__ __forceinline__ bf16x8 lds_frag(const lds_u8* p) { return *reinterpret_cast<const bf16x8*>(p); }
-#if WS_MFMA16
-// one k-step of 32 on the 2 x 2 blocks of 16x16: a[rb] = weights (gate rows 16 rb ..), b[sb] = activations (sequences 16 sb ..);
-// accumulator element block m = 2 sb + rb (see ws_cell)
-__device__ __forceinline__ void ws_mfma16x4(f32x16& acc, const bf16x8& a0, const bf16x8& a1, const bf16x8& b0, const bf16x8& b1) {
-  f32x4 c[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) c[m] = f32x4{acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]};
-  c[0] = mma16(a0, b0, c[0]);
-  c[1] = mma16(a1, b0, c[1]);
-  c[2] = mma16(a0, b1, c[2]);
-  c[3] = mma16(a1, b1, c[3]);
-#pragma unroll
-  for (int m = 0; m < 4; ++m) { acc[4 * m] = c[m][0]; acc[4 * m + 1] = c[m][1]; acc[4 * m + 2] = c[m][2]; acc[4 * m + 3] = c[m][3]; }
-}
-#endif
-#ifdef WS_DIAG_NOMFMA
-// diagnostic build: the matrix pipe is not used (one VALU instruction keeps the operands alive)
-__device__ __forceinline__ f32x16 ws_mfma(const bf16x8& a, const bf16x8& b, f32x16 c) {
-  c[0] += __builtin_bit_cast(f32x4, a)[0] * __builtin_bit_cast(f32x4, b)[0];
-  return c;
-}
-#else
 __device__ __forceinline__ f32x16 ws_mfma(const bf16x8& a, const bf16x8& b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
-#endif
 
 template <bool TRAIN>
 __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
@@ -319,13 +245,7 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
   gu32* tmo = (gu32*)(a.flags + (size_t)a.clusters * a.nch_max * 16);
   const lds_u8* ltile = reinterpret_cast<const lds_u8*>(smem);
   // B fragment (activations) of this lane: row seq, k = 8 hh + j of each 16-wide k-step
-#if WS_MFMA16
-  // 16x16x32: lane (n = lane & 15, q = lane >> 4) reads row 16 sb + n, k = 32 kk + 8 q + j
-  const int boff = (lane & 15) * WS_ROWB + (lane >> 4) * 16 + (layer ? WS_KX * 2 : 0);
-  const int bias_unit = ug * 8 + 2 * (lane >> 4);                       // cells 2 sb + rb: unit 2 q + rb
-#else
   const int boff = seq * WS_ROWB + hh * 16 + (layer ? WS_KX * 2 : 0);
-#endif
   // fp32 cell state of (chunk, layer, unit group): 16 bytes per lane, private to this wave (plain accesses, L2-resident);
   // addressed through a descriptor: scalar chunk offset + the lane offset, no 64-bit pointer per lane
   const __amdgpu_buffer_rsrc_t cstr = __builtin_amdgcn_make_buffer_rsrc(
@@ -333,25 +253,12 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
 
   // accumulators start from the biases of the lane's cells (LDS: [layer][32 units][i,g,f,o])
   auto bias_init = [&](f32x16& acc, int l) {
-#if WS_MFMA16
-    const lds_u8* bl = reinterpret_cast<const lds_u8*>(smem) + WS_OFF_BIAS + (l * WS_UC + bias_unit) * 16;
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-      const f32x4 b = *reinterpret_cast<const f32x4*>(bl + rb * 16);
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        const int m = 2 * sb + rb;
-        acc[4 * m] = b[0]; acc[4 * m + 1] = b[1]; acc[4 * m + 2] = b[2]; acc[4 * m + 3] = b[3];
-      }
-    }
-#else
     const lds_u8* bl = reinterpret_cast<const lds_u8*>(smem) + WS_OFF_BIAS + (l * WS_UC + ug * 8 + 4 * hh) * 16;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const f32x4 b = *reinterpret_cast<const f32x4*>(bl + m * 16);
       acc[4 * m] = b[0]; acc[4 * m + 1] = b[1]; acc[4 * m + 2] = b[2]; acc[4 * m + 3] = b[3];
     }
-#endif
   };
   auto mk_item = [&](int s_, int c_) {
     WsItem it;                                                     // readfirstlane: provably wave-uniform (SGPRs, no waterfall
@@ -369,9 +276,6 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), cstr, lane * 16, it.c * 2 * 4 * 256 * 4, 0);
   };
 
-#ifdef WS_STAMP
-  const bool st_on = cluster == 0 && cu == 0 && ug == 0;
-#endif
   // flush of generation g: layer 1 staged item i1 (h1 / gates / c of time s), layer 2 item i2 (state of time s - 1)
   auto flush_store = [&](const WsFlush& f, const WsItem& i1, const WsItem& i2, bool v1, bool v2) {
     const bool a1 = v1 && i1.s < Tn, a2 = v2 && i2.s >= 1 && i2.s <= Tn;
@@ -412,10 +316,6 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
 
     u32x4 st[13];
     auto stage_write = [&](int buf) {
-#ifdef WS_DIAG_NOTILEWRITE
-      asm volatile("" :: "v"(st[0]), "v"(st[12]));
-      return;
-#endif
       unsigned char* t = smem + buf * WS_TILEB;
 #pragma unroll
       for (int j = 0; j < 12; ++j) *reinterpret_cast<u32x4*>(t + dv[j % 3] + (j / 3) * 4 * WS_ROWB) = st[j];
@@ -439,36 +339,21 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
     f32x4 ccp = {0.f, 0.f, 0.f, 0.f};                              // its cell state
     __syncthreads();
-    WST_INIT
 #pragma unroll 1
     for (int i = 0; i < nitems; ++i) {
       const int buf = i & 1;
       const bool more = i + 1 < nitems;
-      WST(5)
       // ---- gather of the NEXT item (its flags were seen by wave 4 before the barrier just passed): 13 x 1 KB per wave, in
       // flight during the cell update and the GEMM below
       {
         const int th = (ug >> 1) ? itn.s - 2 : itn.s - 1;            // time of the h rows this wave gathers
         const __amdgpu_buffer_rsrc_t ghr = ws_rsrc((ug >> 1) ? a.h2 : a.h1, slot(th), N, WS_HB, more && th >= 0 && th < Tn);
         const __amdgpu_buffer_rsrc_t gxr = ws_rsrc(a.x, itn.s, N, WS_KX * 2, more && itn.s < Tn);
-#ifdef WS_DIAG_GATHERL2
-        const int gso = (16 * (ug & 1)) * WS_HB;      // diagnostic: always the same rows (L2 hits instead of freshly published lines)
-#else
         const int gso = (itn.row0 + 16 * (ug & 1)) * WS_HB;
-#endif
-#ifndef WS_DIAG_NOGATHER
 #pragma unroll
         for (int j = 0; j < 12; ++j) st[j] = __builtin_amdgcn_raw_buffer_load_b128(ghr, sv[j % 3] + gso + (j / 3) * 4 * WS_HB, 0, 16);
         st[12] = __builtin_amdgcn_raw_buffer_load_b128(gxr, lane * 16 + (itn.row0 + 8 * ug) * WS_KX * 2, 0, 0);
-#else
-#pragma unroll
-        for (int j = 0; j < 13; ++j) st[j] = u32x4{(unsigned)gso, 0u, 0u, 0u};
-#endif
       }
-#ifdef WS_STAMP
-      __builtin_amdgcn_sched_barrier(0);
-      WST(6)
-#endif
       // ---- cell update of item i - 1 (layer 1 of its time s), executed for every item: the steps behind the last time
       // step compute on zeros and are stored through an empty descriptor (no store sits in a conditional path)
       {
@@ -479,7 +364,6 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
         cst_store(itp, ccp);
         ws_stage_out<TRAIN>(smem, 0, ug, lane, i, hpk, gpk, cpk);
       }
-#ifndef WS_STAMP
       // spread the 13 gather loads over the cell update (issued in one burst, the 52 loads of the four gathering waves fill the
       // CU's vector-memory queue and every wave blocks at the issue for most of the 830 cycles the 52 KB take at 64 B/clk)
 #pragma unroll
@@ -487,9 +371,7 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
-      WST(0)
       // ---- head of time s - 2 from the full h2_{s-2} in the tile: waves 2, 3 of the chunk's designated CU.  Its
       // (conditional) stores must be older than the gather below, so that the waits for the gather can be counted ones
       if (a.whp && ug >= 2 && it.s >= 2 && (it.c + it.s) % WS_G == cu) {
@@ -510,30 +392,11 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
       // cell state of THIS item (its update runs in the next iteration)
       f32x4 cc = cst_load(it);
       __builtin_amdgcn_sched_barrier(0);
-      WST(1)
       {
         // ---- layer 1 of time s: gates = W1 . [x_s | h1_{s-1}]^T + b
         bias_init(acc, 0);
         const lds_u8* bp = ltile + buf * WS_TILEB + boff;
         bf16x8 b[WS_PF];
-#if WS_MFMA16
-        // B fragment e = 2 kk + sb: rows 16 sb .., k-step kk of 32; A fragments w[2 kk + rb]
-        auto rdb = [&](int e) { return lds_frag(bp + (e & 1) * 16 * WS_ROWB + (e >> 1) * 64); };
-#pragma unroll
-        for (int e = 0; e < WS_PF; ++e) b[e] = rdb(e);
-#pragma unroll
-        for (int kk = 0; kk < WS_NK1 / 2; ++kk) {
-          ws_mfma16x4(acc, w[2 * kk], w[2 * kk + 1], b[(2 * kk) % WS_PF], b[(2 * kk + 1) % WS_PF]);
-          if (2 * kk + WS_PF < WS_NK1) b[(2 * kk) % WS_PF] = rdb(2 * kk + WS_PF);
-          if (2 * kk + 1 + WS_PF < WS_NK1) b[(2 * kk + 1) % WS_PF] = rdb(2 * kk + 1 + WS_PF);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 + WS_PF, 0);
-#pragma unroll
-        for (int kk = 0; kk < WS_NK1 / 2; ++kk) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        }
-#else
 #pragma unroll
         for (int d = 0; d < WS_PF; ++d) b[d] = lds_frag(bp + d * 32);
 #pragma unroll
@@ -549,15 +412,11 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
           __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
-#endif
       }
       __builtin_amdgcn_sched_barrier(0);
-      WST(2)
       stage_write(buf ^ 1);
       ccp = cc;
-      WST(3)
       ws_barrier();
-      WST(4)
       if (tid == 0 && i >= 2)
         __hip_atomic_store(flags + itpp.c * 16 + cu, (unsigned)(itpp.s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       itpp = itp;
@@ -566,10 +425,8 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
       itn = next_item(itn);
     }
     // (the cell update of the last item is beyond the last time step: nothing to store)
-    WST_FINI(0)
   } else {
     // =============================== layer-2 waves (wave 4 also polls) ===============================
-    if (a.prio == 1) __builtin_amdgcn_s_setprio(1);                 // diagnostic switch (NPPC_WS_PRIO)
     constexpr int NKR = WS_NK2 - WS_NKL;                             // k-steps with register-resident weights: NKL .. 47
     bf16x8 w[NKR];
     {
@@ -586,12 +443,10 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
     __syncthreads();
     WsItem it = mk_item(0, 0), itn = next_item(it), it2 = next_item(itn), itp = it, itpp = it;
     __syncthreads();
-    WST_INIT
 #pragma unroll 1
     for (int i = 0; i < nitems; ++i) {
       const int buf = i & 1;
       const int t = it.s - 1;
-      WST(6)
       // wave 4: the flags of item i + 2 (its gather starts right behind this iteration's barrier): requested FIRST (older than
       // the flush stores below: the wait for them never covers a write-through store), looked at behind the GEMM.
       // Every CU of the cluster must have published item (c, s - 1).
@@ -603,16 +458,11 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
       // ---- outputs of the previous generation: staging -> registers -> global, by the layer-2 waves (the shorter chain of
       // an iteration).  Oldest stores of the iteration: complete long before the counted wait in front of the barrier
       {
-#ifndef WS_DIAG_NOFLUSH
         WsFlush fl;
         ws_flush_read<TRAIN>(fl, smem, ug, lane, i - 1);
         flush_store(fl, itpp, itp, i >= 2, i >= 1);
-#else
-        if (TRAIN && lane == 0) atomicAdd(reinterpret_cast<unsigned*>(smem + WS_OFF_CNT), 1u);
-#endif
       }
       __builtin_amdgcn_sched_barrier(0);
-      WST(0)
       // ---- layer 2 of time s - 1: gates = W2 . [h1_{s-1} | h2_{s-2}]^T + b (every item: see layer 1)
       f32x16 acc;
       bias_init(acc, 1);
@@ -622,43 +472,6 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
         const lds_u8* bp = ltile + buf * WS_TILEB + boff;
         constexpr int E = WS_NK2 + WS_NKL;
         bf16x8 r[WS_PF];
-#if WS_MFMA16
-        // operand stream: k-steps 0, 1 (of 32): W(kk,0) W(kk,1) B(kk,0) B(kk,1); then B(kk,0) B(kk,1); W2L holds fragments
-        // 2 kk + rb of the first two k-steps, registers w[2 kk + rb - WS_NKL] the rest
-        auto rd = [&](int e) {
-          if (e < 2 * WS_NKL) {
-            const int kk = e >> 2, j = e & 3;
-            return j < 2 ? lds_frag(wl + (2 * kk + j) * 1024) : lds_frag(bp + (j & 1) * 16 * WS_ROWB + kk * 64);
-          }
-          const int f = e - WS_NKL;                                  // B fragment index 2 kk + sb
-          return lds_frag(bp + (f & 1) * 16 * WS_ROWB + (f >> 1) * 64);
-        };
-#pragma unroll
-        for (int e = 0; e < WS_PF; ++e) r[e] = rd(e);
-#pragma unroll
-        for (int kk = 0; kk < WS_NK2 / 2; ++kk) {
-          if (2 * kk < WS_NKL) {
-            const int e = 4 * kk;
-            ws_mfma16x4(acc, r[e % WS_PF], r[(e + 1) % WS_PF], r[(e + 2) % WS_PF], r[(e + 3) % WS_PF]);
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-              if (e + d + WS_PF < E) r[(e + d) % WS_PF] = rd(e + d + WS_PF);
-          } else {
-            const int e = WS_NKL + 2 * kk;
-            ws_mfma16x4(acc, w[2 * kk - WS_NKL], w[2 * kk + 1 - WS_NKL], r[e % WS_PF], r[(e + 1) % WS_PF]);
-#pragma unroll
-            for (int d = 0; d < 2; ++d)
-              if (e + d + WS_PF < E) r[(e + d) % WS_PF] = rd(e + d + WS_PF);
-          }
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 + WS_PF, 0);
-#pragma unroll
-        for (int kk = 0; kk < WS_NK2 / 2; ++kk) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-          if (2 * kk < WS_NKL) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        }
-#else
         auto rd = [&](int e) {
           if (e < 2 * WS_NKL) return (e & 1) ? lds_frag(bp + (e >> 1) * 32) : lds_frag(wl + (e >> 1) * 1024);
           return lds_frag(bp + (e - WS_NKL) * 32);
@@ -685,9 +498,7 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
           if (ks < WS_NKL) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
           else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
-#endif
       }
-      WST(1)
       if (polls) {
         unsigned spins = 0;
         while (__builtin_amdgcn_ballot_w64(pv < (unsigned)it2.s) != 0) {
@@ -701,26 +512,19 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");     // compiler ordering only: the payload loads are sc1
       }
       __builtin_amdgcn_sched_barrier(0);
-      WST(2)
-      if (a.prio == 2) __builtin_amdgcn_s_setprio(3);
       {
         unsigned hpk[2], cpk[2];
         u32x4 gpk[2];
         if (t <= 0) cc = f32x4{0.f, 0.f, 0.f, 0.f};
         ws_cell<TRAIN>(acc, cc, hpk, gpk, cpk);
-        WST(7)
         cst_store(it, cc);
         ws_stage_out<TRAIN>(smem, 1, ug, lane, i, hpk, gpk, cpk);
       }
       __builtin_amdgcn_sched_barrier(0);
       // the flush stores of this iteration (generation i - 1: layer 2 of item i - 1, layer 1 of item i - 2) must be complete
       // before the barrier, the flag of item i - 2 rises behind it: everything but this iteration's cell-state store
-      if (a.prio == 2) __builtin_amdgcn_s_setprio(0);
-      WST(3)
       asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-      WST(4)
       ws_barrier();
-      WST(5)
       itpp = itp;
       itp = it;
       it = itn;
@@ -732,7 +536,6 @@ __global__ __launch_bounds__(WS_NT, 2) void lstm2_ws_fwd_kernel(WsArgs a) {
       ws_flush_read<TRAIN>(fl, smem, ug, lane, nitems - 1);
       flush_store(fl, itpp, itp, true, true);
     }
-    WST_FINI(8)
   }
 }
 
@@ -751,16 +554,9 @@ __global__ void lstm_ws_pack_kernel(const float* __restrict__ w_ih, const float*
     const int ug = f & 3;
     const int cu = (int)(f >> 2);
     const int tgmap[4] = {0, 2, 1, 3};
-#if WS_MFMA16
-    // fragment ks = 2 kk + rb: A operand of the 16x16x32 MFMA, row r16 = l & 15 = 4 q' + gate -> unit 2 q' + rb
-    const int kk = ks >> 1, rb = ks & 1, r16 = l & 15;
-    const int ul = 2 * (r16 >> 2) + rb, g = r16 & 3;
-    const int k = 32 * kk + 8 * (l >> 4) + j;
-#else
     const int r = l & 31, g = r & 3, ui = r >> 2;
     const int ul = 4 * (ui & 1) + (ui >> 1);
     const int k = 16 * ks + 8 * (l >> 5) + j;
-#endif
     const int row = tgmap[g] * WS_H + cu * WS_UC + ug * 8 + ul;
     float v;
     if (layer == 1) v = k < WS_KX ? (k < I ? w_ih[(size_t)row * I + k] : 0.f) : w_hh[(size_t)row * WS_H + (k - WS_KX)];
@@ -834,8 +630,7 @@ int nppc_lstm2_fwd_ws(int train, const void* x, const void* wp1, const void* wp2
   if (whp && (!hpart || O < 1 || O > 16)) return NPPC_EBADARG;
   const long nchunks = (N + WS_MC - 1) / WS_MC;
   if ((long)clusters * nch_max < nchunks || nchunks / clusters < 5 || N * (long)WS_H * 8 >= (1l << 31)) return NPPC_EBADARG;
-  static const int prio = [] { const char* e = getenv("NPPC_WS_PRIO"); return e ? atoi(e) : 0; }();
-  WsArgs a{x, wp1, wp2, bias1, bias2, h1, h2, g1, g2, c1, c2, cst, flags, whp, hpart, N, Tn, O, clusters, nch_max, (int)nchunks, prio};
+  WsArgs a{x, wp1, wp2, bias1, bias2, h1, h2, g1, g2, c1, c2, cst, flags, whp, hpart, N, Tn, O, clusters, nch_max, (int)nchunks};
   hipStream_t s = (hipStream_t)stream;
   const void* k = train ? reinterpret_cast<const void*>(lstm2_ws_fwd_kernel<true>)
                         : reinterpret_cast<const void*>(lstm2_ws_fwd_kernel<false>);

@@ -75,32 +75,15 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
   const int srow = tid >> 3, sc = tid & 7;
   const T* ga = reinterpret_cast<const T*>(g.A) + (size_t)z * g.strideA + (size_t)ksl * g.K + (long)(m0 + srow) * g.lda + sc * EPC;
   const T* gb = reinterpret_cast<const T*>(g.B) + (size_t)z * g.strideB + (size_t)ksl * g.K + (long)(n0 + srow) * g.ldb + sc * EPC;
-  // diagnostic builds (tools/diag/nt_variants.py; timing only): NT_DIAG_NOLOOP = one K stage instead of K / BK (what the launch,
-  // the first stage's latency and the epilogue cost without the main loop), NT_DIAG_NOEPI = no epilogue (one store per lane).
-  // Measured at the TCN shapes (profiles/r04_nt_variants.txt): 38 us = 12 us launch + first stage, 14 us for the other eight
+  // Measured at the TCN shapes with one K stage instead of K / BK and with no epilogue (profiles/r04_nt_variants.txt): 38 us = 12 us launch + first stage, 14 us for the other eight
   // stages (one stage of prefetch: a stage takes the memory latency, 4-6 us would be MFMA-bound), 12-15 us epilogue.  Two
   // register stages of prefetch were tried again in round 4 (named registers, unconditional clamped loads): hipcc still
   // drains the queue (vmcnt(0)) in front of the LDS stores and spills at 256 VGPRs -- a deeper pipeline here needs the
   // inline-asm LDS-DMA ring of gemm_tn_dma_kernel, not built.
-#ifdef NT_DIAG_NOLOOP
-  const int nstage = 1;
-#else
   const int nstage = g.K / BK;
-#endif
   f32x4 acc[4][NJ];
   nt_lds_mainloop<T, BN>(acc, &lds[0][0], nstage, g.lda, g.ldb, [&](int s) { return ga + s * BK; }, [&](int s) { return gb + s * BK; },
                          g.relu_in);
-#ifdef NT_DIAG_NOEPI
-  {
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) v += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    reinterpret_cast<T*>(g.C)[(size_t)blockIdx.z * g.strideC + (size_t)(m0 + (tid >> 1)) * g.ldc + n0 + (tid & 1)] = from_f32<T>(v);
-    return;
-  }
-#endif
   // ---- epilogue (identical to gemm_nt_kernel): element (row m0 + wm*64 + 16 i + 4 q + r, col n0 + wn*BN/2 + 16 j + n)
   const NtEpilogue<T, EPI> ep(g, z, m0);
   constexpr bool HAS_RES = EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_GN || EPI == EPI_MASK_POS;
@@ -407,16 +390,6 @@ __global__ __launch_bounds__(64) void pack_sconv_kernel(const float* __restrict_
 
 }  // namespace
 
-// NPPC_NT_STAGED=0: residual / mask epilogues in the accumulator layout (A/B switch for the coalesced epilogue)
-static int nt_staged() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("NPPC_NT_STAGED");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v;
-}
-
 // NPPC_NT_STAGED_PLAIN=0: the plain / PReLU / ReLU epilogues in the accumulator layout, as in rounds 1-3 (A/B switch)
 static int nt_staged_plain() {                       // (read per call: tests/test_tcn_gpu.py compares the two epilogues in one process)
   const char* e = getenv("NPPC_NT_STAGED_PLAIN");
@@ -464,7 +437,7 @@ static int launch_nt(int prec, int epi, const void* A, long lda, long sA, const 
   if (K % (32 * ksplit)) return NPPC_EUNSUPPORTED;
   GemmArgs g{A, lda, sA, B, ldb, sB, C, ldc, sC, bias, sBias, res, ldres, sRes, slope, sSlope, stats, sStats,
              R, N, K / ksplit, Tp, Tv, Nv, relu_in, ksplit, nullptr, 0, 1.0, 0.f,
-             ((res ? (ldres % 8 == 0 && nt_staged())
+             ((res ? ldres % 8 == 0
                    : ((epi == EPI_PLAIN || epi == EPI_PRELU_STATS || epi == EPI_RELU) && ksplit == 1 && nt_staged_plain())) &&
               ldc % 8 == 0) ? 1 : 0,
              colpart, (long)(R / 128) * N};
@@ -505,7 +478,7 @@ int nppc_gemm_nt_gn(int prec, const void* A, long lda, long sA, const void* Wg, 
   if (!A || !Wg || !C || !u || !v || !res || !stats || R <= 0 || N <= 0 || K <= 0 || batch <= 0 || cnt <= 0) return NPPC_EBADARG;
   if (R % 128 || N % 64 || K % 32 || Tp <= 0 || (Tp % 128) || lda % 8 || ldb % 8) return NPPC_EUNSUPPORTED;
   GemmArgs g{A, lda, sA, Wg, ldb, sB, C, ldc, sC, u, sUV, res, ldres, sRes, nullptr, 0, const_cast<double*>(stats), sStats,
-             R, N, K, Tp, Tv, Nv, 0, 1, v, sUV, cnt, eps, (ldc % 8 == 0 && ldres % 8 == 0 && nt_staged()) ? 1 : 0, nullptr, 0};
+             R, N, K, Tp, Tv, Nv, 0, 1, v, sUV, cnt, eps, (ldc % 8 == 0 && ldres % 8 == 0) ? 1 : 0, nullptr, 0};
   const int bk = prec == NPPC_PREC_BF16 ? 64 : 32;
   const int lds_path = (K % bk == 0) ? (N % 128 == 0 ? 128 : 64) : 0;
   return dispatch_nt(prec, EPI_RESIDUAL_GN, lds_path, batch, g, (hipStream_t)stream);
@@ -619,14 +592,15 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-// BM = 128 (4 waves, two workgroups per CU) or 256 (8 waves, one per CU: 0.75x the operand bytes per FLOP through the
-// CU's 64 B/clk global-load path, which is what bounds the 128 x 128 tile)
-template <int BN, int BM = 128>
-__global__ __launch_bounds__(2 * BM, BM == 128 ? 2 : 1) void gemm_tn_tiled_kernel(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict__ B,
+// 128-row tiles: 4 waves, two workgroups per CU.  (A 256-row, 8-wave variant -- 0.75x the operand bytes per FLOP through the
+// CU's 64 B/clk global-load path, which is what bounds the 128 x 128 tile -- lost every shape it could take to the LDS-DMA
+// ring kernel below.)
+template <int BN>
+__global__ __launch_bounds__(256, 2) void gemm_tn_tiled_kernel(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict__ B,
                                                                long ldb, float* __restrict__ C, long ldc, long slab_stride,
                                                                long Rz, int ntap, int Wp, int shift_a, int nzb, long bsA,
                                                                long bsB, long bsC) {
-  constexpr int BR = 64, NT = 2 * BM;
+  constexpr int BM = 128, BR = 64, NT = 2 * BM;
   constexpr int RSA = BM + 8, RSB = BN + 8;                 // LDS row strides (elements): 16-byte aligned rows
   constexpr int WN = BN / 2;                                // columns per wave (BM/64 x 2 waves)
   constexpr int NJ = WN / 16;
@@ -806,9 +780,7 @@ __device__ __forceinline__ void dma_tile(const bf16_t* __restrict__ A, long lda,
   // barrier the first waves go straight to their matrix instructions (round 4, from the convolution ring kernel: csrc/unet.hip).
   // LSTM weight-gradient shape alone 1.365 -> 1.315 ms, step -0.11 ms in an alternating A/B (profiles/r04_tn_producers_ab.txt);
   // 8 = every wave requests its share (rounds 2-3).
-#ifndef TN_DMA_PRODUCERS
-#define TN_DMA_PRODUCERS 4
-#endif
+  constexpr int TN_DMA_PRODUCERS = 4;
   constexpr int NPW = TN_DMA_PRODUCERS;
   constexpr int NA = A_BYTES / 1024 / NPW;                      // whole 1 KB DMA pieces per requesting wave and stage (A)
   constexpr int BW = B_BYTES / NPW;                             // B bytes per requesting wave and stage: NBF whole pieces + one half piece
@@ -1014,36 +986,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_dma2_kernel(const bf16_t* __re
 
 // C_slab[z] [M][N] = A[rows slice z][M]^T * B[rows slice z][N]  (bf16 operands, fp32 slabs).  M % 128 == 0,
 // N % 64 == 0, R % (64*ksplit) == 0, lda/ldb multiples of 8.
-// 256-row tiles are on unless NPPC_TN_BIG=0 (A/B switch for tools/bench_tn.py)
-static bool tn_big_tiles() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("NPPC_TN_BIG");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-// NPPC_TN_DMA=0 switches the LDS-DMA ring kernel off (A/B switch for tools/bench_tn.py)
-static bool tn_dma() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("NPPC_TN_DMA");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-// NPPC_TN_DMA192=0: 256 x 128 tiles only (A/B switch)
-static bool tn_dma192() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("NPPC_TN_DMA192");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
 static int launch_tn(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, long R, int ksplit,
                      int ntap, int Wp, int shift_a, void* stream, int batch = 1, long sA = 0, long sB = 0, long sC = 0,
                      float* rowsum = nullptr) {
@@ -1052,8 +994,8 @@ static int launch_tn(const void* A, long lda, const void* B, long ldb, float* C,
   hipStream_t s = (hipStream_t)stream;
   // LDS-DMA ring kernel (plain products and the nine-tap convolution weight gradient): 256 x 192 tiles (32-row stages x 5) when N is a multiple of 192, else
   // 256 x 128 tiles (64-row stages x 3), as long as there are enough workgroups to fill the chip
-  if (tn_dma() && M % DR_BM == 0 && (R / ksplit) % 64 == 0 && (ntap == 1 || batch == 1)) {
-    const int bn = (N % 192 == 0 && tn_dma192()) ? 192 : (N % 128 == 0 ? 128 : 0);
+  if (M % DR_BM == 0 && (R / ksplit) % 64 == 0 && (ntap == 1 || batch == 1)) {
+    const int bn = N % 192 == 0 ? 192 : (N % 128 == 0 ? 128 : 0);
     if (bn && (long)(M / DR_BM) * (N / bn) * ksplit * ntap * batch >= 256) {
       dim3 grid(M / DR_BM, N / bn, ksplit * ntap * batch);
       if (bn == 192) {
@@ -1084,12 +1026,7 @@ static int launch_tn(const void* A, long lda, const void* B, long ldb, float* C,
     }
   }
   if (rowsum) return NPPC_EUNSUPPORTED;            // only the LDS-DMA kernel produces row sums
-  // 256-row tiles (+4...11 % at these shapes) only when they still give every CU a few workgroups
-  if (N % 128 == 0 && M % 256 == 0 && tn_big_tiles() && (long)(M / 256) * (N / 128) * ksplit * ntap * batch >= 1024) {
-    dim3 grid(M / 256, N / 128, ksplit * ntap * batch);
-    hipLaunchKernelGGL((gemm_tn_tiled_kernel<128, 256>), grid, dim3(512), 0, s, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C,
-                       ldc, (long)M * ldc, R / ksplit, ntap, Wp, shift_a, ksplit * ntap, sA, sB, sC);
-  } else if (N % 128 == 0) {
+  if (N % 128 == 0) {
     dim3 grid(M / 128, N / 128, ksplit * ntap * batch);
     hipLaunchKernelGGL(gemm_tn_tiled_kernel<128>, grid, dim3(256), 0, s, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc,
                        (long)M * ldc, R / ksplit, ntap, Wp, shift_a, ksplit * ntap, sA, sB, sC);
@@ -1124,14 +1061,12 @@ extern "C" int nppc_gemm_tn_splitk2(const void* A, long lda, const void* B1, lon
                                     float* C, long ldc, int M, long R, int ksplit, float* rowsum, void* stream) {
   if (!A || !B1 || !B2 || !C || M <= 0 || N1 <= 0 || N2 <= 0 || R <= 0 || ksplit < 1) return NPPC_EBADARG;
   if (lda % 8 || ldb1 % 8 || ldb2 % 8 || ldc < N1 + N2) return NPPC_EBADARG;
-  if (!tn_dma() || N1 % 192 || (N2 != 64 && N2 % 192) || R % ksplit || (R / ksplit) % 64) return NPPC_EUNSUPPORTED;
+  if (N1 % 192 || (N2 != 64 && N2 % 192) || R % ksplit || (R / ksplit) % 64) return NPPC_EUNSUPPORTED;
   const int nt1 = N1 / 192, nt2 = N2 == 64 ? 1 : N2 / 192;
   hipStream_t s = (hipStream_t)stream;
   // 384-row tiles (4 stages of 32 K-rows) when M allows: 128 FLOP per operand byte in flight instead of 110, and for the
-  // LSTM shapes (M = 1536, 64 K slices) 4 x 4 x 64 = 1024 and 4 x 3 x 64 = 768 workgroups = whole rounds of the 256 CUs;
-  // NPPC_TN_BM384=0 keeps the 256-row tiles (A/B switch)
-  static const bool bm384 = [] { const char* e = getenv("NPPC_TN_BM384"); return !(e && e[0] == '0'); }();
-  if (bm384 && M % 384 == 0 && (long)(M / 384) * (nt1 + nt2) * ksplit >= 256) {
+  // LSTM shapes (M = 1536, 64 K slices) 4 x 4 x 64 = 1024 and 4 x 3 x 64 = 768 workgroups = whole rounds of the 256 CUs
+  if (M % 384 == 0 && (long)(M / 384) * (nt1 + nt2) * ksplit >= 256) {
     constexpr int smem = 4 * (32 * 384 * 2 + 32 * 192 * 2);
     static bool attr = false;
     if (!attr) {

@@ -7,15 +7,8 @@
 
 namespace {
 
-// frames per workgroup (each workgroup ends with per-channel atomics: fewer, larger workgroups); NPPC_TCN_RPB overrides
-static int tcn_rpb() {
-  static const int v = [] { const char* e = getenv("NPPC_TCN_RPB"); const int r = e ? atoi(e) : 64; return r >= 4 ? r : 64; }();
-  return v;
-}
-static int diag_noatom() {
-  static const int v = [] { const char* e = getenv("NPPC_DIAG_NOATOM"); return e ? atoi(e) : 0; }();
-  return v;
-}
+// frames per workgroup (each workgroup ends with per-channel atomics: fewer, larger workgroups); a host value, passed to the kernels
+constexpr int TCN_RPB = 64;
 
 constexpr int UNR = 4;     // rows in flight per thread and trip
 
@@ -35,7 +28,7 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
                                                             const double* __restrict__ st, const float* __restrict__ gamma,
                                                             double* __restrict__ S, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta, int Cc, int Tp, int Tv, float eps,
-                                                            long sAct, long sSt, long sP, int RPB, int noatom) {
+                                                            long sAct, long sSt, long sP, int RPB) {
   extern __shared__ float sm[];   // [2][Cc] channel partials
   const int z = blockIdx.z, b = blockIdx.y;
   dA += (size_t)z * sAct; y += (size_t)z * sAct;
@@ -93,7 +86,6 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
     atomicAdd(S + b * 2 + 1, d2);
   }
   __syncthreads();
-  if (noatom) return;
   for (int i = threadIdx.x; i < Cc; i += 256) {
     atomicAdd(dgamma + i, sm[i]);
     atomicAdd(dbeta + i, sm[Cc + i]);
@@ -107,7 +99,7 @@ __global__ __launch_bounds__(256) void gn_prelu_bwd_kernel(const T* __restrict__
                                                            const double* __restrict__ st, const float* __restrict__ gamma,
                                                            const double* __restrict__ S, const float* __restrict__ slope,
                                                            T* __restrict__ dpre, float* __restrict__ dslope, int Cc, int Tp,
-                                                           int Tv, float eps, long sAct, long sSt, long sP, int RPB, int noatom) {
+                                                           int Tv, float eps, long sAct, long sSt, long sP, int RPB) {
   const int z = blockIdx.z, b = blockIdx.y;
   dA += (size_t)z * sAct; y += (size_t)z * sAct; dpre += (size_t)z * sAct;
   st += (size_t)z * sSt; S += (size_t)z * sSt;
@@ -174,7 +166,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const T* __restrict__ d
                                                          const float* __restrict__ beta, const float* __restrict__ wd,
                                                          T* __restrict__ dz, float* __restrict__ dwd, float* __restrict__ dbd,
                                                          int Cc, int Tp, int Tv, int dil, float eps, long sAct, long sSt,
-                                                         long sP, int RPB, int noatom) {
+                                                         long sP, int RPB) {
   extern __shared__ float sm[];   // [4][Cc]: dwd k=0..2, dbd
   const int z = blockIdx.z, b = blockIdx.y;
   du += (size_t)z * sAct; y1 += (size_t)z * sAct; dz += (size_t)z * sAct;
@@ -252,7 +244,6 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const T* __restrict__ d
     }
   }
   __syncthreads();
-  if (noatom) return;
   for (int i = threadIdx.x; i < Cc; i += 256) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) atomicAdd(dwd + i * 3 + k, sm[k * Cc + i]);
@@ -639,13 +630,13 @@ int nppc_tcn_gn_bwd(int prec, const void* dA, const void* y, const double* st, c
     return NPPC_EBADARG;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(S, 0, sizeof(double) * 2 * B * batch, s) != hipSuccess) return NPPC_ELAUNCH;   // S laid out [batch][B][2], sSt = 2B
-  const int RPB = tcn_rpb(), noatom = diag_noatom();
+  const int RPB = TCN_RPB;
   dim3 g1(ceil_div(Tv, RPB), B, batch), g2(ceil_div(Tp, RPB), B, batch);
   const size_t smem = (size_t)2 * Cc * sizeof(float);
   LAUNCH_TS(prec, gn_bwd_reduce_kernel, g1, dim3(256), smem, (const TT*)dA, (const TT*)y, st, gamma, S, dgamma, dbeta, Cc, Tp, Tv,
-            eps, sAct, sSt, sP, RPB, noatom);
+            eps, sAct, sSt, sP, RPB);
   LAUNCH_T(prec, gn_prelu_bwd_kernel, g2, (const TT*)dA, (const TT*)y, st, gamma, S, slope, (TT*)dpre, dslope, Cc, Tp, Tv, eps, sAct,
-           sSt, sP, RPB, noatom);
+           sSt, sP, RPB);
   return NPPC_OK;
 }
 
@@ -653,11 +644,11 @@ int nppc_tcn_dwconv_bwd(int prec, const void* du, const void* y1, const double* 
                         const float* wd, void* dz, float* dwd, float* dbd, int B, int Cc, int Tp, int Tv, int dil, float eps,
                         long sAct, long sSt, long sP, int batch, void* stream) {
   if (!du || !y1 || !st1 || !gamma || !beta || !wd || !dz || !dwd || !dbd || Cc % 8 || Cc / 8 > 256) return NPPC_EBADARG;
-  const int RPB = tcn_rpb(), noatom = diag_noatom();
+  const int RPB = TCN_RPB;
   dim3 g(ceil_div(Tp, RPB), B, batch);
   const size_t smem = (size_t)4 * Cc * sizeof(float);
   LAUNCH_TS(prec, dwconv_bwd_kernel, g, dim3(256), smem, (const TT*)du, (const TT*)y1, st1, gamma, beta, wd, (TT*)dz, dwd, dbd, Cc,
-            Tp, Tv, dil, eps, sAct, sSt, sP, RPB, noatom);
+            Tp, Tv, dil, eps, sAct, sSt, sP, RPB);
   return NPPC_OK;
 }
 

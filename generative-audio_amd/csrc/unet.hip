@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void conv_tiled_kernel(ConvArgs g) {
 //     is read.  A hand-counted REGISTER ring is not safe (the register allocator may copy a destination that is still in flight,
 //     tools/check/asm_rings.py); an LDS-DMA has no register destination, its completion is counted by hand (`s_waitcnt vmcnt(N)`,
 //     N = DMA instructions the wave issued after the stage it needs; vector-memory operations retire in order).
-//   * The DMA waves do nothing else: in-kernel stamps (tools/diag/conv_stamp.py) showed a stage's 48 requests cost the issuing
+//   * The DMA waves do nothing else: in-kernel cycle stamps showed a stage's 48 requests cost the issuing
 //     waves 800-900 cycles (address arithmetic, M0 set-up, ~50 cycles of issue per 64-address DMA) -- as much as the stage's matrix
 //     work.  Issued by all compute waves they stopped every matrix pipe behind each stage barrier; issued by the second compute
 //     wave of every SIMD they serialised that SIMD's two waves (each alone on the pipe runs at ~25 cycles per MFMA: its fragment
@@ -168,9 +168,7 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       asm volatile("s_barrier" ::: "memory");                      // (B1..) stage st+1 visible; every compute wave has read all of stage st
-#ifndef CONV_DIAG_NOFILL   /* sizing build (timing only): no operand fetch behind the prologue stages */
       if (st + STAGES < nstage) fill(slot);
-#endif
       slot = slot == STAGES - 1 ? 0 : slot + 1;
     }
   } else {
@@ -195,12 +193,6 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
     read_set(a0, b0, 0, 0);
     __builtin_amdgcn_s_waitcnt(LGKM0);
     int slot = 0;
-#ifdef CONV_STAMP   /* diagnostic build (tools/diag/conv_stamp.py): cycles per phase of wave 0 of workgroup 0 */
-    unsigned long long sacc[5] = {0, 0, 0, 0, 0}, slast = __builtin_readcyclecounter();
-#define CST(i) { const unsigned long long nw = __builtin_readcyclecounter(); sacc[i] += nw - slast; slast = nw; }
-#else
-#define CST(i)
-#endif
     for (int st = 0; st < nstage; ++st) {
       const int nslot = slot == STAGES - 1 ? 0 : slot + 1;
       // ---- half 1: read set 1 <- (st, k-step 1) between the 16 MFMAs on set 0 = (st, k-step 0)
@@ -213,12 +205,9 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
         __builtin_amdgcn_sched_group_barrier(0x008, (4 * NJ) / (4 + NJ), 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-      CST(0)
       // ---- half 2: everything of stage st is in registers -> barrier -> read set 0 <- (st+1, k-step 0) between the MFMAs on set 1
       __builtin_amdgcn_s_waitcnt(LGKM0);
-      CST(1)
       asm volatile("s_barrier" ::: "memory");      // (B1..) stage st+1 visible; the slot of stage st may be refilled
-      CST(2)
       __builtin_amdgcn_sched_barrier(0);
       read_set(a0, b0, nslot, 0);                  // (behind the last stage: a harmless read of a stale slot -- unconditional, so that
       mma_set(a1, b1);                             //  the reads and the matrix instructions share a basic block and interleave)
@@ -231,17 +220,8 @@ __global__ __launch_bounds__(640, 1) void conv_dma_kernel(ConvArgs g) {
       // set 0 has had sixteen MFMAs to land: an explicit wait HERE costs nothing and leaves hipcc's wait-count pass with nothing
       // pending across the loop edge (without it the pass put lgkmcnt(0) between half 1's reads and its MFMAs)
       __builtin_amdgcn_s_waitcnt(LGKM0);
-      CST(4)
       slot = nslot;
     }
-#ifdef CONV_STAMP
-    if (blockIdx.x == 0 && blockIdx.y == 0 && g.stat_part && tid == 0) {
-      unsigned long long* dbgp = reinterpret_cast<unsigned long long*>(g.stat_part + (size_t)((g.P + 127) / 128) * 2 * g.ldp);   // behind the last tile's sums
-      for (int i = 0; i < 5; ++i) dbgp[i] = sacc[i];
-      dbgp[5] = (unsigned long long)nstage;
-    }
-#endif
-#undef CST
   }
   float st1[NJ] = {}, st2[NJ] = {};
   if (!dma_wave) conv_epilogue<T>(g, acc, m0 + wm * 64 + 4 * q, n0 + wn * (BN / 2) + n, st1, st2);

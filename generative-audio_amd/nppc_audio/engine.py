@@ -6,7 +6,6 @@ FullSubNet_Plus.forward (FullSubNet_plus/.../fullsubnet_plus.py:143-230) and
 MultiDirectionFullSubNet_Plus.forward (nppc_audio/networks.py:63-163) stage by stage.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -26,14 +25,8 @@ def rup(a, b):
     return (a + b - 1) // b * b
 
 
-TCN_WGRAD_ON_SIDE = os.environ.get("NPPC_TCN_WGRAD_SIDE", "1") != "0"    # A/B switch (tools/diag)
-TCN_WGRAD_SPLITS = int(os.environ.get("NPPC_TCN_S2", "8"))            # K-slices of the TCN weight-gradient GEMMs
-FC_WGRAD_AT_END = os.environ.get("NPPC_FC_AT_END", "1") != "0"       # fc_output_layer weight gradient at the end of the main chain (A/B switch)
-TCN_WGRAD_MAIN_BLOCKS = int(os.environ.get("NPPC_TCN_WGRAD_MAIN_BLOCKS", "1"))   # TCN blocks (0 .. n-1) whose weight gradients stay on the main queue
-MID_FINISH_DEFER = os.environ.get("NPPC_MID_FINISH_DEFER", "1") != "0"   # ONE finishing launch for the eight fused middle backwards (A/B switch)
-COLSUM_IN_GEMM = os.environ.get("NPPC_COLSUM_IN_GEMM", "1") != "0"   # sconv bias gradients from the producing GEMM's epilogue (A/B switch)
-TN_PAIRED = os.environ.get("NPPC_TN_PAIRED", "1") != "0"              # one pass over the gate gradients per LSTM layer (A/B switch)
-FUSED_HEAD = int(os.environ.get("NPPC_FUSED_HEAD", "3"))    # 0: head kernels; 1: fused in the inference forward; 2: + training forward; 3: + backward
+TCN_WGRAD_SPLITS = 8         # K-slices of the TCN weight-gradient GEMMs
+TCN_WGRAD_MAIN_BLOCKS = 1    # TCN blocks (0 .. n-1) whose weight gradients stay on the main queue
 
 
 class FlatParams:
@@ -382,7 +375,7 @@ class FSNEngine:
             H.call("nppc_subband_mean", prec, src, ldS, d["fb"], ldF, R * ldF, self.mult, d["sbscale"], d["sbwork"], B, F, Tp,
                    Tv, self.I, s)
         # mtile None: cooperative kernel when the shape allows; it also takes the output head to fuse (bf16 pair kernel)
-        head = (self.Whp, self.O) if (FUSED_HEAD > int(train) and prec == H.PREC_BF16 and self.Opad == 16) else None
+        head = (self.Whp, self.O) if (prec == H.PREC_BF16 and self.Opad == 16) else None
         # the frozen net's fused-head inference launch reads rows of 40 columns (the same buffer, viewed narrower): the
         # staging kernel writes 37 % less, the recurrent kernel fetches 80 instead of 128 bytes per sequence and step
         x_tm = d["x_tm"]
@@ -489,7 +482,7 @@ class FSNEngine:
             #   layer 1: dg1^T . [h1_{t-1} | x_t]   (x's spare column carries the bias gradient)
             #   layer 2: dg2^T . [h1_t | h2_{t-1}]  (+ row sums of dg2 = the bias gradient)
             # h_{t-1} is the guard view of the h rows (N zero rows in front), so the gate gradients are not shifted
-            if (guards is not None and TN_PAIRED and fold_bias and Hd % 192 == 0 and KX == 64 and Tv > 1
+            if (guards is not None and fold_bias and Hd % 192 == 0 and KX == 64 and Tv > 1
                     and (K4 // 256) * (Hd // 192 + 1) * S >= 256):
                 h1_guard, h2_guard = guards
                 rows = (Rr + 64 * S - 1) // (64 * S) * (64 * S)
@@ -580,7 +573,7 @@ class FSNEngine:
         lo = d["lstm"]
         # ---- 1. head: dh2 = dY Wh, dWh, dbh
         ws = lambda name, shape, dtype=dt, zero=False: workspace(("eng", id(self), name), shape, dtype, dev, zero)
-        if FUSED_HEAD >= 3 and prec == H.PREC_BF16 and O <= 16 and bwd_head_fusable(Nseq, self.lstm_bwd):
+        if prec == H.PREC_BF16 and O <= 16 and bwd_head_fusable(Nseq, self.lstm_bwd):
             # the K-split cooperative kernel forms d h2 = dY . Wh itself from the gathered dY rows: no dh2 tensor
             # dY rows [T'*N][16] (zero padded like the other GEMM operands: the head's weight gradient h2^T . dY runs with
             # the LSTM weight gradients on the side stream, behind the recurrence, instead of in front of it)
@@ -607,9 +600,9 @@ class FSNEngine:
         main = torch.cuda.current_stream()
         if self._side is None:
             # lowest priority: the dependent chain on the main stream is what the step waits for; the weight-gradient
-            # GEMMs are throughput work (NPPC_SIDE_PRIO=0: default priority, A/B switch)
+            # GEMMs are throughput work
             prio = 0
-            if os.environ.get("NPPC_SIDE_PRIO", "1") != "0" and hasattr(torch.cuda.Stream, "priority_range"):
+            if hasattr(torch.cuda.Stream, "priority_range"):
                 prio = max(torch.cuda.Stream.priority_range())
             self._side = torch.cuda.Stream(device=dev, priority=prio)
         self._side.wait_stream(main)
@@ -636,8 +629,6 @@ class FSNEngine:
 
         def on_side(fn):
             """run fn (which launches on the current stream) on the side stream once the main stream got here"""
-            if not TCN_WGRAD_ON_SIDE:
-                return fn()
             ev = torch.cuda.Event()
             ev.record(main)
             with torch.cuda.stream(self._side):
@@ -656,14 +647,10 @@ class FSNEngine:
         # bf16: the product waits until the END of the main chain -- the side queue (LSTM + TCN weight gradients) is the longer
         # one, the main queue would idle ~0.4 ms in front of the join -- with a slab of its own (slab2 belongs to the side queue)
         # (the generic path below re-uses tA / tB / slab2 on the main stream: there the product stays in line)
-        fc_ok = prec == H.PREC_BF16 and TCN_HIDDEN % 128 == 0 and ldC % 64 == 0 and R % (64 * S2) == 0
-        fc_at_end = fc_ok and FC_WGRAD_AT_END
-        if fc_ok and not fc_at_end:
-            on_side(lambda: fc_wgrad(slab2))
-        elif not fc_ok:
+        tn_ok = prec == H.PREC_BF16 and TCN_HIDDEN % 128 == 0 and ldC % 64 == 0 and R % (64 * S2) == 0
+        if not tn_ok:
             fc_wgrad(slab2)
         # bf16: the 1x1-conv weight gradients run on the TN GEMM straight from the row-major activations (no transposes)
-        tn_ok = prec == H.PREC_BF16 and TCN_HIDDEN % 128 == 0 and ldC % 64 == 0 and R % (64 * S2) == 0
         if tn_ok:
             # ... and on the side stream, behind the LSTM weight gradients: nothing downstream reads them before the
             # optimizer, and the end of the main chain (TSSE backward, small kernels) leaves most CUs idle.  Their operands
@@ -679,7 +666,7 @@ class FSNEngine:
         # the GEMMs that PRODUCE a block's upstream gradient also leave its column sums per 128-row tile (epilogue): the sconv
         # bias gradient is their sum over the tiles, added up by the block's fused middle backward -- no pass over dXo for it
         bk = 64 if prec == H.PREC_BF16 else 32
-        cs_ok = tn_ok and COLSUM_IN_GEMM and ldF % bk == 0 and TCN_HIDDEN % bk == 0
+        cs_ok = tn_ok and ldF % bk == 0 and TCN_HIDDEN % bk == 0
         cp_all = ws("colpart", (8, 3, R // 128, ldC), torch.float32) if cs_ok else None      # one block per TCN block
         cpL = [cp_all[i] for i in range(8)] if cs_ok else None
         if cs_ok:
@@ -710,7 +697,6 @@ class FSNEngine:
                    self.g(pre_ + "prelu2.weight"), self.g(pre_ + "conv1x1.bias"), self.g(pre_ + "sconv.bias") if cs_ok else None,
                    B, TCN_HIDDEN, sP, lay, 3, hi - lo, s)
         early = self.grad_range_hook is not None and self.early_buckets_ok
-        defer_finish = MID_FINISH_DEFER        # (A/B switch NPPC_MID_FINISH_DEFER=0: one finishing launch per block, as in round 3)
         dXo, dXi = dXa, dXb
         for i in range(7, -1, -1):
             pre = f"fb_model.sequence_model.{i}."
@@ -737,8 +723,8 @@ class FSNEngine:
                    self.g(pre + "depthwise_conv.weight"), self.g(pre + "depthwise_conv.bias"), self.g(pre + "prelu1.weight"),
                    self.g(pre + "prelu2.weight"), self.g(pre + "conv1x1.bias"),
                    cpL[i] if cs_ok else None, R // 128, ldC, C, self.g(pre + "sconv.bias") if cs_ok else None,
-                   B, TCN_HIDDEN, Tp, Tv, dil, 1e-8, sAct, B * 2, sP, 3, 0 if defer_finish else 1, s)
-            if i == 4 and early and defer_finish:
+                   B, TCN_HIDDEN, Tp, Tv, dil, 1e-8, sAct, B * 2, sP, 3, 0, s)
+            if i == 4 and early:
                 finish_mid(4, 8)              # blocks 7..4 are handed to the exchange below: their gradients must be final
             # sconv weight gradient: dW2[c][k] = sum_r dXo[r][c] * a2[r][k]
             if tn_ok:
@@ -797,8 +783,7 @@ class FSNEngine:
                         b, shp = self.fp.off[f"fb_model{br}.sequence_model.7.sconv.bias"]
                         self.grad_range_hook(G, a, b + int(np.prod(shp)))
                 on_side(blocks_done)
-        if defer_finish:
-            finish_mid(0, 4 if early else 8)
+        finish_mid(0, 4 if early else 8)
         if tn_ok:
             dXo = dXL[0]
         if self.nm == 1:
@@ -823,7 +808,7 @@ class FSNEngine:
                self.g(att + "feature_concate_fc.weight"), self.g(att + "feature_concate_fc.bias"),
                self.g(att + "fc1.weight"), self.g(att + "fc1.bias"), self.g(att + "fc2.weight"), self.g(att + "fc2.bias"),
                B, F, T, self.la, Tp, ldC, s)
-        if fc_at_end:
+        if tn_ok:
             fc_wgrad(ws("slab_fc", (3 * S2 * Fr * ldC,), torch.float32))
         if self.defer_join:
             self.join_pending = True          # joined (join_side) before anything reads the gradient

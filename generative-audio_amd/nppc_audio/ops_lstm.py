@@ -166,7 +166,7 @@ COOP_BWD_KSPLIT = True    # cooperative backward variant: True = K-split (bf16 p
 # K-split backward on four-CU clusters of 64 sequences instead of CU pairs of 32 (half the weight-fragment bytes per CU and step):
 # "1" whenever ceil(N / 64) * 4 CUs are free, "0" never
 BWD_G4 = os.environ.get("NPPC_LSTM_BWD_G4", "0")
-WGRAD_SPLITS = int(os.environ.get("NPPC_WGRAD_SPLITS", "64"))    # K-slices of the weight-gradient GEMMs (engine._lstm_wgrad)
+WGRAD_SPLITS = 64             # K-slices of the weight-gradient GEMMs (engine._lstm_wgrad)
 ROW_PAD = 64 * WGRAD_SPLITS   # row granularity of their operands: 64-row stages x K-slices; buffers carry this much slack
 
 
@@ -266,14 +266,11 @@ def lstm2_forward(x_tm, packed, train, mtile=None, head=None):
 
 
 # packed input rows for the frozen restorer's inference launch (CU-pair kernel with the fused head): 40 columns instead of 64
-# (34 features + the spare column + pad to 16 bytes), -37 % of the staged bytes and of the kernel's x reads.  "0" = 64 columns.
-X_PACKED = os.environ.get("NPPC_X_PACKED", "1") != "0"
-
-
+# (34 features + the spare column + pad to 16 bytes), -37 % of the staged bytes and of the kernel's x reads
 def forward_x_ld(N, packed, train, head):
     """row width (elements) the staging kernel should write for lstm2_forward(x, packed, train, None, head): packed.kx unless the
     launch will be the fused-head CU-pair inference kernel, which fetches rows of any 16-byte multiple width"""
-    if (not X_PACKED or train or head is None or not COOP or packed.prec != H.PREC_BF16 or packed.Hd != 384
+    if (train or head is None or not COOP or packed.prec != H.PREC_BF16 or packed.Hd != 384
             or head[1] > FUSED_HEAD_MAX_O or packed.I + 1 > 40):
         return packed.kx
     if WS and _ws_wanted(N, packed, train) and ws_plan(N, packed) is not None:

@@ -193,9 +193,6 @@ class HipAdam(optim.Optimizer):
         return loss
 
 
-PREPACK_AFTER_UPDATE = os.environ.get("NPPC_PREPACK", "1") != "0"     # A/B switch (tools/diag)
-
-
 class FlatAdamStepper:
     """Fast path used by NPPCAudioTrainer.train: one Adam kernel over the direction net's flat parameter /
     gradient buffers, sharing state tensors with a HipAdam instance so checkpoints stay interchangeable."""
@@ -429,7 +426,7 @@ class NPPCAudioTrainer(nn.Module):
             obj_d = objective.detach()
             self._poison = obj_d if (obj_d.dtype == torch.float32 and obj_d.is_contiguous() and obj_d.is_cuda) else None
             if not defer:
-                self._apply_pending(prepack=PREPACK_AFTER_UPDATE)
+                self._apply_pending(prepack=True)
         else:
             mean_reduce_parameter_grads(net.parameters())
             self.optimizer.step()

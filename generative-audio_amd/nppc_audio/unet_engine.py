@@ -7,7 +7,6 @@ BatchNorm folded into the convolution epilogue (eval mode); the direction U-Net 
 (batch statistics, running-buffer update) and keeps what its backward needs; so does the restorer while it is
 trained (InpaintingTrainer), with its nn.Dropout layers active in the differentiated pass.
 """
-import os
 
 import numpy as np
 import torch
@@ -27,8 +26,6 @@ OUT_LD = 64         # so is the K-channel output of the 1x1 convolution
 DROP_BLOCKS = ("down3", "down4", "up1", "up2")    # double_convs that end in nn.Dropout (unet.py:254-257)
 
 
-BN_STATS_IN_CONV = os.environ.get("NPPC_BN_STATS_IN_CONV", "1") != "0"   # train-mode BatchNorm statistics from the convolution's epilogue (A/B switch)
-THIN = os.environ.get("NPPC_UNET_THIN", "1") != "0"      # direct kernels for the first (1-2 channel) and last (1x1, K <= 8) convolutions
 PROFILE = None      # bench hook: list of (kind, algorithmic flops, start event, end event)
 
 
@@ -171,7 +168,7 @@ class UNetEngine:
         B = self.geo[0]
         h, w = self.lv[level]
         cinp, np_ = self._dims(name, cin, cout)
-        if (stats and BN_STATS_IN_CONV and not fold and ks == 3 and not (THIN and cin <= 2 and cout <= 64 and cout % 8 == 0)
+        if (stats and not fold and ks == 3 and not (cin <= 2 and cout <= 64 and cout % 8 == 0)
                 and cinp % (64 if self.prec == H.PREC_BF16 else 32) == 0):
             if cinp != ldx:
                 raise RuntimeError(f"{name}: input row width {ldx} != packed K {cinp}")
@@ -186,13 +183,13 @@ class UNetEngine:
         if ks == 3 and cinp != ldx:
             raise RuntimeError(f"{name}: input row width {ldx} != packed K {cinp}")
         ss = self.ss[name] if fold else None
-        if THIN and ks == 3 and cin <= 2 and cout <= 64 and cout % 8 == 0:
+        if ks == 3 and cin <= 2 and cout <= 64 and cout % 8 == 0:
             # first layer: memory-bound, 18 MACs per output -- direct kernel on the fp32 parameter tensor (csrc/unet.hip)
             with _timed("conv_fwd", 2.0 * B * h * w * cin * cout * ks * ks):
                 H.call("nppc_conv3x3_thin_fwd", self.prec, x, ldx, self.p(name + ".weight"), self.p(name + ".bias"), ss,
                        ss[cout:] if fold else None, LEAK, y, ldy, B, h, w, cin, cout, H.stream())
             return
-        if THIN and ks == 1 and cin == 64 and cout <= 8 and not fold:
+        if ks == 1 and cin == 64 and cout <= 8 and not fold:
             with _timed("conv_fwd", 2.0 * B * h * w * cin * cout * ks * ks):
                 H.call("nppc_conv1x1_thin_fwd", self.prec, x, ldx, self.p(name + ".weight"), self.p(name + ".bias"), y, ldy, B, h, w,
                        cin, cout, H.stream())
@@ -349,7 +346,7 @@ class UNetEngine:
         M, N = lddy, ldx
         S = self.ksplit[level]
         s = H.stream()
-        thin3, thin1 = THIN and ks == 3 and cin <= 2 and cout <= 64 and cout % 8 == 0, THIN and ks == 1 and cin == 64 and cout <= 8
+        thin3, thin1 = ks == 3 and cin <= 2 and cout <= 64 and cout % 8 == 0, ks == 1 and cin == 64 and cout <= 8
         if thin3 or thin1:
             if self._thin_part is None:
                 self._thin_part = torch.empty(H.conv_thin_part_elems(), dtype=torch.float32, device=self.dev)
@@ -367,7 +364,7 @@ class UNetEngine:
         B = self.geo[0]
         h, w = self.lv[level]
         cinp, np_ = self._dims(name, cin, cout)
-        if THIN and ks == 1 and cin == 64 and cout <= 8:
+        if ks == 1 and cin == 64 and cout <= 8:
             with _timed("conv_bwd_data", 2.0 * B * h * w * cin * cout * ks * ks):
                 H.call("nppc_conv1x1_thin_bwd_data", self.prec, dy, lddy, self.p(name + ".weight"), dx, lddx, B, h, w, cin, cout,
                        H.stream())

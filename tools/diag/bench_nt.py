@@ -1,6 +1,5 @@
 """Stand-alone timing of the NT GEMM at the TCN shapes (C2: 3 branches x 8192 rows): conv1x1 forward (PReLU + stats),
-sconv forward (residual), the two data-gradient products of the backward.  NPPC_NT_STAGED=0: residual / mask epilogues in the
-accumulator layout instead of the coalesced epilogue through LDS (A/B)."""
+sconv forward (residual), the two data-gradient products of the backward."""
 import os, sys
 root = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.join(root, "generative-audio_amd"))
