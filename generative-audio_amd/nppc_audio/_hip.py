@@ -5,6 +5,7 @@ without the built library, or calling an op without a HIP device, raises Runtime
 """
 import ctypes
 import os
+import threading
 
 import torch
 
@@ -295,20 +296,38 @@ SIGS = {
     "nppc_flac_enc_write": [P, L, P, I, P, L, I, I, I, P, P, P, P, P, L, P],
     "nppc_resample_sinc_shape": [I, I, I, I, I, PI, PL, PL, PL, PI],
     "nppc_resample_sinc": [P, L, P, I, P, I, I, I, I, I, P, L, P],
+    "nppc_png_bound": [L, L, P],
+    "nppc_png_encode_host": [P, L, L, P, P, L, P],
+    "nppc_png_encode": [P, L, P, I, P, P, L, P, P, P, P, P, L, P],
+    "nppc_spec_windows": [P, I, I, P, P],
+    "nppc_spec_render": [P, I, I, I, I, I, P, I, P, I, P, P, P, P, L, L, P],
+    "nppc_spec_render_png": [P, I, I, I, I, I, P, I, P, I, P, P, P, P, L, L, P, P, L, P, P, P, P, P, L, P],
 }
 _bound = set()
+_bind_lock = threading.Lock()
+_fns = {}
 # bench.py sets this to a list to collect (entry point, start_event, end_event) around EVERY launch of an untimed pass;
 # the events are recorded on the current stream, i.e. the stream the kernel is enqueued on
 PROFILE = None
 
 
+def _bind(name):
+    """the entry point with its argtypes set, made once: host pools make first calls from several threads, each of which
+    would otherwise get a function object of its own from ctypes, and only one of them would ever be given argtypes"""
+    with _bind_lock:
+        fn = _fns.get(name)
+        if fn is None:
+            fn = getattr(lib(), name)
+            fn.argtypes = SIGS[name]
+            fn.restype = c_i
+            _fns[name] = fn
+            _bound.add(name)
+        return fn
+
+
 def call(name, *args):
     """lib().<name>(*args); tensors -> device pointers; raises RuntimeError on a non-zero return."""
-    fn = getattr(lib(), name)
-    if name not in _bound:
-        fn.argtypes = SIGS[name]
-        fn.restype = c_i
-        _bound.add(name)
+    fn = _fns.get(name) or _bind(name)
     conv = [ptr(a) if (isinstance(a, torch.Tensor) or a is None) else a for a in args]
     if PROFILE is None:
         check(fn(*conv), name)

@@ -17,7 +17,11 @@ variation, tracked on the device (nppc_audio/pitch.py), and what each direction 
 `save_pc_audio_variations` writes what validate_batch(..., alphas=) synthesised in the reference's layout, as FLAC encoded
 on the device (nppc_audio/flac.py) or as wav.
 
-Outside this build: whisper / phoneme transcription, the plots themselves (pitch and spectrogram), wandb.
+`save_pc_spectrograms` writes the spectrogram panels of plot_pc_spectrograms (:273-478) under the reference's file names and
+one sheet per sample, as PNG files drawn and encoded on the device (nppc_audio/spectrogram_png.py): the whole batch in one
+device call.  Titles, axes and colour bars are not drawn; no pixel parity with matplotlib's figures is claimed.
+
+Outside this build: whisper / phoneme transcription, the pitch plots, wandb.
 Splicing a restoration or a variation into the full source recording is inpainting/restore.py (RecordingRestorer).
 """
 import json
@@ -37,7 +41,8 @@ from ..nppc.nppc_model import NPPCModel, NPPCModelConfig
 from ..utils import preprocess_data
 
 __all__ = ["NPPCModelValidatorConfig", "NPPCModelValidator", "pc_audio_variations", "compute_metrics",
-           "compute_metrics_batch", "save_metrics_to_json", "default_alphas", "save_pc_audio_variations"]
+           "compute_metrics_batch", "save_metrics_to_json", "default_alphas", "save_pc_audio_variations",
+           "save_pc_spectrograms", "pc_spectrogram_sheets"]
 
 compute_metrics = MB.compute_metrics
 compute_metrics_batch = MB.compute_metrics_batch
@@ -89,8 +94,8 @@ def save_pc_audio_variations(out, save_dir, alphas, first_index=0, fmt="flac", s
         pc_<k+1>/alpha_<a:.1f>_blind.<ext>     'audio_variations_blind'[b, k, a], when the dict holds them
     16-bit mono at sample_rate.  fmt "flac": all B (1 + K A [+ K A]) waveforms are quantised and encoded in ONE device call
     (flac.encode_waves) and cross to the host as FLAC bytes; fmt "wav": the same samples as wav.  The reference's *_full
-    files (the variation spliced into the source recording) are RecordingRestorer.save_variations; transcriptions,
-    phonemes and pitch plots are outside this build.  -> the paths written"""
+    files (the variation spliced into the source recording) are RecordingRestorer.save_variations, the spectrogram pictures
+    save_pc_spectrograms; transcriptions, phonemes and pitch plots are outside this build.  -> the paths written"""
     from ... import flac as FL
     var, clean = out["audio_variations"], out["clean_audio"]
     B, K, A, L = var.shape
@@ -110,6 +115,79 @@ def save_pc_audio_variations(out, save_dir, alphas, first_index=0, fmt="flac", s
         paths += [root / f"sample_{first_index + b}" / f"pc_{k + 1}" / f"alpha_{a:.1f}_blind.{fmt}"
                   for b in range(B) for k in range(K) for a in alphas]
     FL.write_waves(paths, torch.cat([w.float() for w in waves]), sample_rate, fmt, backend=backend)
+    return paths
+
+
+SPEC_RANGE, SPEC_ERROR_RANGE = (-3.0, 3.0), (0.0, 3.0)               # plot_pc_spectrograms :292-293
+
+
+def pc_spectrogram_sheets(B, K, alphas, individual=True, sx=2, sy=2, gutter=4):
+    """the panels of plot_pc_spectrograms over the planes (clean, masked, output, pc_1 .. pc_K) of every item:
+    -> (names, sheets), names[i] the file of sheets[i] below the sample's spectrograms directory, item by item.  Every
+    individual panel carries the gap markers, as save_individual_spectrogram draws them; on the sheet the first four panels
+    of row 0 do not, as in the reference's figure."""
+    from ...spectrogram_png import Cell, Sheet
+    CLEAN, MASKED, OUT, PC = 0, 1, 2, 3
+    rng = dict(vmin=SPEC_RANGE[0], vmax=SPEC_RANGE[1])
+    err = dict(p=CLEAN, q=OUT, alpha=-1.0, g="abs", vmin=SPEC_ERROR_RANGE[0], vmax=SPEC_ERROR_RANGE[1])
+    names, sheets = [], []
+    for b in range(B):
+        if individual:
+            panels = [("clean_spec.png", Cell(p=CLEAN, markers=True, **rng)), ("masked_spec.png", Cell(p=MASKED, markers=True, **rng)),
+                      ("output_spec.png", Cell(p=OUT, markers=True, **rng)), ("error_spec.png", Cell(markers=True, **err))]
+            for k in range(K):
+                panels.append((f"pc_direction_{k + 1}.png", Cell(q=PC + k, markers=True, **rng)))
+                panels += [(f"pc{k + 1}_alpha_{a:.1f}.png", Cell(p=OUT, q=PC + k, alpha=a, markers=True, **rng)) for a in alphas]
+            for name, cell in panels:
+                names.append((b, name))
+                sheets.append(Sheet(b, [[cell]], sx=sx, sy=sy))
+        cols = max(len(alphas) + 1, 6)
+        top = [Cell(p=CLEAN, **rng), Cell(p=MASKED, **rng), Cell(p=OUT, **rng), Cell(**err), Cell(p=CLEAN, markers=True, **rng),
+               Cell(p=OUT, markers=True, **rng)] + [None] * (cols - 6)
+        rows = [top]
+        for k in range(K):
+            row = [Cell(q=PC + k, markers=True, **rng)] + [Cell(p=OUT, q=PC + k, alpha=a, markers=True, **rng) for a in alphas]
+            rows.append(row + [None] * (cols - len(row)))
+        names.append((b, "sheet.png"))
+        sheets.append(Sheet(b, rows, sx=sx, sy=sy, gutter=gutter))
+    return names, sheets
+
+
+def save_pc_spectrograms(out, save_dir, alphas, first_index=0, max_dirs=None, individual=True, sx=2, sy=2, gutter=4,
+                         palette="viridis", max_frames=None):
+    """plot_pc_spectrograms (:273-478) for a whole batch, from the dict of validate_batch(..., spectrograms=True): under
+    <save_dir>/sample_<first_index + b>/spectrograms/ the reference's files
+        clean_spec.png, masked_spec.png, output_spec.png, error_spec.png            |clean - output| in [0, 3]
+        pc_direction_<k>.png, pc<k>_alpha_<a:.1f>.png                               output + a * direction k, in [-3, 3]
+    (individual=True) and one sheet.png: row 0 clean, masked, output, error, clean, output (the last two with the gap
+    markers), row k direction k and its variations.  Every panel shows the reference's context window (:296-302): the gap
+    widened by its own length on each side, found on the device from the mask, so widths differ within a batch; an item
+    without a gap shows the whole clip.  Every source pixel is sx x sy pixels; the dashed columns in the marker colour stand
+    at the gap's first frame and at the one past its last.  The whole batch, B (4 + K (1 + A) + 1) files, is drawn and
+    encoded in ONE device call (spectrogram_png.render_png).  max_frames: the widest window there can be (default T), which
+    sizes the workspace.  -> the paths written"""
+    from ... import png as PNG
+    from ...spectrogram_png import render_png, windows_from_mask
+    H.require_gpu()
+    pc, pred, clean, mask4 = out["pc_directions"], out["pred_spec_mag_norm"], out["clean_spec_mag_norm"], out["mask"]
+    if "masked_spec_mag_norm" not in out:
+        raise ValueError("save_pc_spectrograms takes the dict of validate_batch(..., spectrograms=True), which holds "
+                         "'masked_spec_mag_norm'")
+    masked = out["masked_spec_mag_norm"]
+    B, K, F, T = pc.shape
+    if max_dirs is not None:
+        K = min(K, int(max_dirs))
+    alphas = [float(a) for a in torch.as_tensor(alphas).reshape(-1).tolist()]
+    if not alphas:
+        raise ValueError("no alphas given")
+    f32 = lambda t: t.detach().float().reshape(B, -1, F, T)
+    planes = torch.cat([f32(clean), f32(masked), f32(pred), f32(pc)[:, :K]], dim=1).contiguous()
+    win = windows_from_mask(mask4.detach().float().reshape(B, -1, F, T)[:, 0, 0, :])
+    names, sheets = pc_spectrogram_sheets(B, K, alphas, individual, sx, sy, gutter)
+    files = render_png(planes, sheets, win, palette=palette, max_frames=max_frames)
+    root = Path(save_dir)
+    paths = [root / f"sample_{first_index + b}" / "spectrograms" / name for b, name in names]
+    PNG.write_files(paths, files)
     return paths
 
 
@@ -180,10 +258,12 @@ class NPPCModelValidator:
             gram = MB.metrics_gram_batch(pc_directions, mc['scaled_principal_components'], pred, mc['mean_prediction'],
                                          clean_norm, mask4)
         return {'pc_directions': pc_directions, 'pred_spec_mag_norm': pred, 'clean_spec_mag_norm': clean_norm,
-                'mask': mask4, 'mean': mean, 'std': std, 'mc_dropout': mc, 'gram': gram, 'clean_spec': clean_spec}
+                'mask': mask4, 'mean': mean, 'std': std, 'mc_dropout': mc, 'gram': gram, 'clean_spec': clean_spec,
+                'masked_spec_mag_norm': masked_norm}
 
     def validate_batch(self, masked_spec, mask, clean_spec, n_mc_samples=50, n_components=5, alphas=None, n_fft=255,
-                       hop_length=128, pitch=False, phase="clean", gl_iters=32, ragged_gaps=False, long_spans=False):
+                       hop_length=128, pitch=False, phase="clean", gl_iters=32, ragged_gaps=False, long_spans=False,
+                       spectrograms=False):
         """validate_sample + _validate_with_baseline (:930-1027) for a uniform batch: masked_spec, clean_spec [B,2,F,T],
         mask [B,T] (1 = known; the same number of gap frames in every item) -> dict with 'pc_directions' [B,K,F,T],
         'pred_spec_mag_norm', 'clean_spec_mag_norm', 'mask' [B,1,F,T], 'mean', 'std', 'mc_dropout' (calculate_unet_baseline's
@@ -203,7 +283,10 @@ class NPPCModelValidator:
         gap is 33 frames at 255 / 128), the default flags them with status 1 and NaN.
 
         ragged_gaps=True accepts items with different numbers of gap frames (every item needs at least one); the keys
-        and shapes are the same.  The default keeps raising ValueError for such a batch."""
+        and shapes are the same.  The default keeps raising ValueError for such a batch.
+
+        spectrograms=True adds 'masked_spec_mag_norm' [B,1,F,T], the normalised masked input, which save_pc_spectrograms
+        draws beside the clean and the restored spectrogram; the default returns the keys it always returned."""
         if phase not in ("clean", "griffin_lim"):
             raise ValueError(f"phase = {phase!r}: 'clean' or 'griffin_lim'")
         if pitch and alphas is None:
@@ -214,6 +297,8 @@ class NPPCModelValidator:
         out = self._run_batch(masked_spec, mask, clean_spec, n_mc_samples, n_components, ragged_gaps)
         out['metrics'] = MB.metrics_from_gram(out.pop('gram').cpu().numpy(), n_components)
         clean_spec = out.pop('clean_spec')
+        if not spectrograms:
+            out.pop('masked_spec_mag_norm')
         if alphas is not None:
             with torch.no_grad():
                 out['audio_variations'], out['clean_audio'] = pc_audio_variations(
@@ -229,16 +314,23 @@ class NPPCModelValidator:
                                                      hop_length=hop_length, long_spans=long_spans)
         return out
 
-    def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False, ragged_gaps=False):
+    def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False, ragged_gaps=False,
+                            spectrogram_alphas=None):
         """every item of every batch ((masked_spec, mask, clean_spec) or utils.collate_fn's five-tuple): the Gram
         matrices stay on the device until the loader is exhausted, then ONE copy to the host and the n x n algebra.
         -> {'per_item': [compute_metrics dicts], 'mean': {'nppc': {...}, 'mc_dropout': {...}, 'principal_angles': [...]},
             'n_items': int}; save=True also writes validation_metrics/sample_<i>.json under config.save_dir.
         ragged_gaps=True: batches whose items have different numbers of gap frames (one host read of the gap counts per
-        batch on top of the one copy per loader)."""
-        grams = []
+        batch on top of the one copy per loader).  With save=True and `spectrogram_alphas` (e.g. default_alphas()) every
+        batch's spectrogram panels and sheets are written too (save_pc_spectrograms, config.max_dirs_to_plot directions)."""
+        grams, seen = [], 0
         for batch in dataloader:
-            grams.append(self._run_batch(*batch[:3], n_mc_samples, n_components, ragged_gaps)['gram'])
+            out = self._run_batch(*batch[:3], n_mc_samples, n_components, ragged_gaps)
+            grams.append(out['gram'])
+            if save and spectrogram_alphas is not None and self.config.save_dir is not None:
+                save_pc_spectrograms(out, self.config.save_dir, spectrogram_alphas, first_index=seen,
+                                     max_dirs=self.config.max_dirs_to_plot)
+            seen += out['gram'].shape[0]
         if not grams:
             raise ValueError("the dataloader yielded no batches")
         per_item = MB.metrics_from_gram(torch.cat(grams).cpu().numpy(), n_components)

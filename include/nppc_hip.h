@@ -919,6 +919,53 @@ int nppc_resample_sinc_shape(int orig, int new_, int width, int maxcount, int ti
 int nppc_resample_sinc(const float* x, long ldx, const long* lengths, int B, const int* table, int orig, int new_, int width,
                        int maxcount, int tile, float* y, long ldy, void* stream);
 
+/* ---- spectrogram sheets as PNG (csrc/png_core.h + csrc/spec_png.hip; specification tests/png_ref.py)
+ * The file: signature, IHDR (8 bits, indexed), PLTE (256 entries), one IDAT, IEND.  Every scanline has filter type 2 (Up);
+ * zlib 78 01 and one fixed-Huffman deflate block whose only matches are distance-1 runs (the token rule: csrc/png_core.h), so
+ * the bytes are a function of the pixels alone, the same from the serial host encoder and from the device.
+ * W, H in 1..16384 and W H <= 2^26, else NPPC_EBADARG (as are null pointers and empty batches), before any launch. */
+#define NPPC_SPEC_CELL 8   /* ints per cell: plane of P (-1: none), plane of Q (-1: none), g (0 identity, 1 abs, 2 dB), flags (1
+                              autoscale, 2 gap markers), alpha, vmin, scale = fp32(254 / (vmax - vmin)) (three floats' bits), the
+                              cell's image.  P = Q = -1: a blank cell */
+#define NPPC_SPEC_IMG 8    /* ints per image: item b, rows R, columns C, first cell (row-major R x C), sx, sy, gutter, 0 */
+/* host only.  *bytes = 8 + 25 + 780 + 12 + (2 + ceil((3 + 9 H (W + 1) + 7) / 8) + 4) + 12: no file is longer */
+int nppc_png_bound(long W, long H, long* bytes);
+/* host only, serial.  idx [H][W], palette [256][3] -> out[0 .. *nbytes); cap below the bound: NPPC_EBADARG. */
+int nppc_png_encode_host(const unsigned char* idx, long W, long H, const unsigned char* palette, unsigned char* out, long cap,
+                         long* nbytes);
+/* A ragged batch of device index images -> files back to back in out (device, 4-byte aligned, out_cap a multiple
+ * of 4, cleared here).
+ *   pix [pix_elems] uint8; meta [nimg][4] long (device): the image's first pixel, W, H, unused;
+ *   ttab [ntiles][2] int (device): (image, tile number) of every 4096-byte tile of every filtered stream, image-major;
+ *   tfirst [nimg + 1] int (device): the first tile of every image; palette [256][3] (HOST);
+ *   work: plan [ntiles][4] int, toff [ntiles] long;
+ *   stats [nimg + 1][4] long: file begin, file end, Adler-32, token bits; stats[nimg][0] = the batch's bytes.
+ * A tile past its image's end, or an image whose meta cannot be (W = H = 0 included), is left out: its file has no bytes.
+ * A memset and four launches: plan, scan, write, finish. */
+int nppc_png_encode(const unsigned char* pix, long pix_elems, const long* meta, int nimg, const int* ttab, const int* tfirst,
+                    long ntiles, const unsigned char* palette, int* plan, long* toff, long* stats, unsigned char* out, long out_cap,
+                    void* stream);
+/* mask [B][T_frames] fp32, 0 inside the gap -> win [B][4] int: t0, t1, marker 0, marker 1.  The gap [s, e) (first to last
+ * zero frame) widened by its own length on each side and clamped to the clip; markers at s and e.  No gap: 0, T, -1, -1. */
+int nppc_spec_windows(const float* mask, int B, int T_frames, int* win, void* stream);
+/* planes [B][NP][CH][F][T_frames] fp32 (CH 1 real, 2 complex) -> the index images of nimg sheets.  A sheet is a grid of R x C
+ * cells of item b's frames [t0, t1); a cell shows g(P + alpha Q): idx = clamp(floor((v - vmin) scale), 0, 253), NaN 0; 254 the
+ * gap markers (the first pixel column of a marker frame, cell rows with (y / 4) % 2 == 0), 255 blank cells and gutters; bin 0
+ * is the bottom row; every source pixel is sx x sy pixels.  Real planes: multiply, add, subtract, multiply, floor, each rounded
+ * to fp32 on its own.  An autoscaled cell takes vmin and vmax from its finite values (equal: all zeros).
+ *   img [nimg][NPPC_SPEC_IMG], cell [ncells][NPPC_SPEC_CELL], win [B][4] (device);
+ *   rng [ncells][2] fp32 (work); meta [nimg][4] long: first pixel (given), W, H (written), pixels allowed (given; an image
+ *   that needs more gets W = H = 0); pix [pix_elems] uint8; max_pixels: the largest allowance.
+ * Three launches: layout, autoscale, render. */
+int nppc_spec_render(const float* planes, int B, int NP, int CH, int F, int T_frames, const int* img, int nimg, const int* cell,
+                     int ncells, const int* win, float* rng, long* meta, unsigned char* pix, long pix_elems, long max_pixels,
+                     void* stream);
+/* nppc_spec_render, then nppc_png_encode of what it drew (ttab and tfirst laid out for the pixels allowed) */
+int nppc_spec_render_png(const float* planes, int B, int NP, int CH, int F, int T_frames, const int* img, int nimg, const int* cell,
+                         int ncells, const int* win, float* rng, long* meta, unsigned char* pix, long pix_elems, long max_pixels,
+                         const int* ttab, const int* tfirst, long ntiles, const unsigned char* palette, int* plan, long* toff,
+                         long* stats, unsigned char* out, long out_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
