@@ -1022,7 +1022,8 @@ __global__ void unet_out_kernel(const T* __restrict__ raw, long ld, const float*
   }
 }
 
-// dRaw[p][k] = dOut[b][k][y][x] * (1 - mask[b][x]),  columns K..ld-1 zero
+// dRaw[p][k] = dOut[b][k][y][x] * (1 - mask[b][x]) for k < K on interior pixels.  Columns K..ld-1 and the halo are NOT
+// written: the caller's gradient buffer is zero there and stays so
 template <typename T>
 __global__ void unet_out_bwd_kernel(const float* __restrict__ dout, long ps, const float* __restrict__ mask, T* __restrict__ draw,
                                     long ld, int K, int B, int H, int W) {

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from oracle import inpaint_ref as R
 from oracle import weights as W
+from unet_halo import Halo
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -26,30 +27,6 @@ def rel(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
-
-
-class Halo:
-    """test-side staging of NCHW tensors into the haloed NHWC layout of csrc/unet.hip"""
-
-    def __init__(self, B, H, W, ld, dtype, guard_after=4096):
-        self.B, self.H, self.W, self.ld = B, H, W, ld
-        self.P = B * (H + 2) * (W + 2)
-        gb = W + 4
-        self.store = torch.zeros((gb + self.P + guard_after + W + 4) * ld, dtype=dtype, device="cuda")
-        self.t = self.store[gb * ld:]
-
-    def put(self, x, coff=0):           # x [B,C,H,W] cpu fp32
-        v = self.t[: self.P * self.ld].view(self.B, self.H + 2, self.W + 2, self.ld)
-        v[:, 1:-1, 1:-1, coff:coff + x.shape[1]] = x.permute(0, 2, 3, 1).to(v.dtype).cuda()
-        return self
-
-    def get(self, C, coff=0):           # -> [B,C,H,W] cpu fp32 (interior)
-        v = self.t[: self.P * self.ld].view(self.B, self.H + 2, self.W + 2, self.ld)
-        return v[:, 1:-1, 1:-1, coff:coff + C].float().permute(0, 3, 1, 2).cpu().contiguous()
-
-    def halo_is_zero(self):
-        v = self.t[: self.P * self.ld].view(self.B, self.H + 2, self.W + 2, self.ld).float()
-        return float(v[:, 0].abs().max() + v[:, -1].abs().max() + v[:, :, 0].abs().max() + v[:, :, -1].abs().max()) == 0.0
 
 
 def q(x, dtype):

@@ -13,34 +13,10 @@ import torch.nn.functional as F
 from golden_util import load, rel
 from oracle import weights as W
 from test_restoration_cpu import LR, fixture_batch, gap_values, is_pre_bn_bias, restorer_step
+from unet_halo import Halo
 
 pytestmark = pytest.mark.gpu
 PRECS = [("fp32", 1, torch.float32, 2e-5), ("bf16", 0, torch.bfloat16, 3e-2)]
-
-
-class Halo:
-    """test-side staging of NCHW tensors into the haloed NHWC layout of csrc/unet.hip"""
-
-    def __init__(self, B, H, W_, ld, dtype):
-        self.B, self.H, self.W, self.ld = B, H, W_, ld
-        self.P = B * (H + 2) * (W_ + 2)
-        gb = W_ + 4
-        self.store = torch.zeros((gb + self.P + 4096 + W_ + 4) * ld, dtype=dtype, device="cuda")
-        self.t = self.store[gb * ld:]
-
-    def view(self):
-        return self.t[: self.P * self.ld].view(self.B, self.H + 2, self.W + 2, self.ld)
-
-    def put(self, x, coff=0):
-        self.view()[:, 1:-1, 1:-1, coff:coff + x.shape[1]] = x.permute(0, 2, 3, 1).to(self.t.dtype).cuda()
-        return self
-
-    def get(self, C, coff=0):
-        return self.view()[:, 1:-1, 1:-1, coff:coff + C].float().permute(0, 3, 1, 2).cpu().contiguous()
-
-    def halo_is_zero(self):
-        v = self.view().float()
-        return float(v[:, 0].abs().max() + v[:, -1].abs().max() + v[:, :, 0].abs().max() + v[:, :, -1].abs().max()) == 0.0
 
 
 def q(x, dtype):
