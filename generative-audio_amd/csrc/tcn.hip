@@ -595,22 +595,14 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 // 128-row tiles: 4 waves, two workgroups per CU.  (A 256-row, 8-wave variant -- 0.75x the operand bytes per FLOP through the
 // CU's 64 B/clk global-load path, which is what bounds the 128 x 128 tile -- lost every shape it could take to the LDS-DMA
 // ring kernel below.)
-template <int BN>
-__global__ __launch_bounds__(256, 2) void gemm_tn_tiled_kernel(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict__ B,
-                                                               long ldb, float* __restrict__ C, long ldc, long slab_stride,
-                                                               long Rz, int ntap, int Wp, int shift_a, int nzb, long bsA,
-                                                               long bsB, long bsC) {
-  constexpr int BM = 128, BR = 64, NT = 2 * BM;
-  constexpr int RSA = BM + 8, RSB = BN + 8;                 // LDS row strides (elements): 16-byte aligned rows
-  constexpr int WN = BN / 2;                                // columns per wave (BM/64 x 2 waves)
-  constexpr int NJ = WN / 16;
-  __shared__ __attribute__((aligned(16))) bf16_t lds[2][BR * RSA + BR * RSB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, qq = lane >> 4;
-  const int wm = wave >> 1, wn = wave & 1;
-  // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2) in linear id order.
-  // All output tiles of one K slice read the same operand rows, so they are mapped to ONE XCD (slice = f(id % 8)):
-  // the slice is fetched from HBM once and the (M/128)*(N/BN)-fold re-reads hit that XCD's L2.
-  unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+constexpr int TT_BM = 128, TT_BR = 64;
+template <int BN> constexpr int tt_stage_elems() { return TT_BR * (TT_BM + 8) + TT_BR * (BN + 8); }   // one LDS stage (bf16)
+
+// XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2) in linear id order.
+// All output tiles of one blockIdx.z (a K slice, or one problem of a grouped launch) read the same operand rows, so they are
+// mapped to ONE XCD (z = f(id % 8)): the rows are fetched from HBM once and the (M/128)*(N/BN)-fold re-reads hit that XCD's
+// L2.  Remaps (bx, by, bz) when gridDim.z % 8 == 0.
+__device__ __forceinline__ void tn_xcd_remap(unsigned& bx, unsigned& by, unsigned& bz) {
   if (gridDim.z % 8 == 0) {
     const unsigned tiles = gridDim.x * gridDim.y;
     const unsigned lin = bx + gridDim.x * (by + gridDim.y * bz);
@@ -620,6 +612,140 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_tiled_kernel(const bf16_t* __r
     bx = t % gridDim.x;
     by = t / gridDim.x;
   }
+}
+
+// The register-staged main loop of one 128 x BN output tile: acc = sum over rows [0, 64 nstage) of Ab[r][0 .. 128)^T Bb[r][0 .. BN)
+// (Ab / Bb: the tile's first row and column; no row outside that range is read).  lds: 2 * tt_stage_elems<BN>() elements,
+// 16-byte aligned.  Ends with a barrier: the buffers are free for the caller's epilogue.  Wave (wm, wn) = (wave >> 1, wave & 1)
+// holds rows wm * 64 + 16 i + 4 (lane >> 4) + r, columns wn * BN/2 + 16 j + (lane & 15) in acc[i][j][r].
+// BLOCKED: the rows are summed in blocks of `chunk` stages (nstage % chunk == 0), each block from zero, and the block sums are
+// added in order from zero -- the very fp32 additions of a split-K launch with nstage / chunk slices followed by
+// reduce_slabs_kernel, and the shorter chains of blocked summation, inside ONE workgroup.
+template <int BN, bool BLOCKED = false>
+__device__ __forceinline__ void tn_tiled_mainloop(f32x4 (&acc)[4][BN / 32], bf16_t* lds, const bf16_t* __restrict__ Ab, long lda,
+                                                  const bf16_t* __restrict__ Bb, long ldb, long nstage, long chunk = 0) {
+  constexpr int BM = TT_BM, BR = TT_BR, NT = 2 * BM;
+  constexpr int RSA = BM + 8, RSB = BN + 8;                 // LDS row strides (elements): 16-byte aligned rows
+  constexpr int WN = BN / 2;                                // columns per wave (BM/64 x 2 waves)
+  constexpr int NJ = WN / 16;
+  constexpr int STAGE = tt_stage_elems<BN>();
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, qq = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+
+  // staging: A tile 64 rows x 16 chunks (16 B) = 1024 chunks -> 4 per thread; B tile 64 x BN/8 chunks
+  constexpr int ACH = BM / 8, BCH = BN / 8;
+  constexpr int NA = BR * ACH / NT, NB = BR * BCH / NT;
+  static_assert(NA == 4 && (NB == 4 || NB == 2 || NB == 1), "staging slots are named registers");
+  // chunk (row, c) of slot i: idx = tid + 256*i.  A: row = idx/16 -> rows (tid>>4) + 16*i, c = tid & 15.
+  const int arow = tid / ACH, ac = tid % ACH, brow = tid / BCH, bc = tid % BCH;
+  constexpr int ASTEP = NT / ACH, BSTEP = NT / BCH;                                      // rows between slots
+  const bf16_t* gA = Ab + (long)arow * lda + ac * 8;
+  const bf16_t* gB = Bb + (long)brow * ldb + bc * 8;
+  const int sA = arow * RSA + ac * 8, sB = BR * RSA + brow * RSB + bc * 8;
+  // the operands are global memory whatever the pointers' origin (kernel argument or problem table): global_load, not flat_load,
+  // so that the loads in flight do not count against the LDS reads' lgkmcnt
+  typedef const __attribute__((address_space(1))) u32x4* tn_gvec;   // (a native vector: HIP's uint4 is a class, copied through a generic reference)
+  u32x4 ra0, ra1, ra2, ra3, rb0, rb1 = {}, rb2 = {}, rb3 = {};
+#define TN_GLOAD(r0)                                                            \
+  ra0 = *(tn_gvec)(gA + ((r0) + 0 * ASTEP) * lda);         \
+  ra1 = *(tn_gvec)(gA + ((r0) + 1 * ASTEP) * lda);         \
+  ra2 = *(tn_gvec)(gA + ((r0) + 2 * ASTEP) * lda);         \
+  ra3 = *(tn_gvec)(gA + ((r0) + 3 * ASTEP) * lda);         \
+  rb0 = *(tn_gvec)(gB + ((r0) + 0 * BSTEP) * ldb);         \
+  if (NB >= 2) rb1 = *(tn_gvec)(gB + ((r0) + 1 * BSTEP) * ldb); \
+  if (NB == 4) {                                                                \
+    rb2 = *(tn_gvec)(gB + ((r0) + 2 * BSTEP) * ldb);       \
+    rb3 = *(tn_gvec)(gB + ((r0) + 3 * BSTEP) * ldb);       \
+  }
+#define TN_LSTORE(buf)                                                          \
+  *reinterpret_cast<u32x4*>(&lds[(buf) * STAGE + sA + 0 * ASTEP * RSA]) = ra0;             \
+  *reinterpret_cast<u32x4*>(&lds[(buf) * STAGE + sA + 1 * ASTEP * RSA]) = ra1;             \
+  *reinterpret_cast<u32x4*>(&lds[(buf) * STAGE + sA + 2 * ASTEP * RSA]) = ra2;             \
+  *reinterpret_cast<u32x4*>(&lds[(buf) * STAGE + sA + 3 * ASTEP * RSA]) = ra3;             \
+  *reinterpret_cast<u32x4*>(&lds[(buf) * STAGE + sB + 0 * BSTEP * RSB]) = rb0;             \
+  if (NB >= 2) *reinterpret_cast<u32x4*>(&lds[(buf) * STAGE + sB + 1 * BSTEP * RSB]) = rb1; \
+  if (NB == 4) {                                                                \
+    *reinterpret_cast<u32x4*>(&lds[(buf) * STAGE + sB + 2 * BSTEP * RSB]) = rb2;           \
+    *reinterpret_cast<u32x4*>(&lds[(buf) * STAGE + sB + 3 * BSTEP * RSB]) = rb3;           \
+  }
+  // transposed fragment: 8 consecutive r (starting r0 + 8*qq) of column (col0 + lane&15)
+  auto tfrag = [&](const bf16_t* tile, int rs, int r0, int col0) -> bf16x8 {
+    const int q4 = i16 >> 2, p4 = i16 & 3;                  // lane 4q+p of the group supplies row q, columns 4p..4p+3
+    const bf16_t* base = tile + (r0 + 8 * qq + q4) * rs + col0 + 4 * p4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 4 * rs));
+    typedef __attribute__((ext_vector_type(8))) short s16x8;
+    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, v);
+  };
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 tot[BLOCKED ? 4 : 1][NJ];                           // BLOCKED: the sum of the finished blocks
+#pragma unroll
+  for (int i = 0; i < (BLOCKED ? 4 : 1); ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  long left = chunk;
+
+  TN_GLOAD(0)
+  TN_LSTORE(0)
+  __syncthreads();
+  for (long s = 0; s < nstage; ++s) {
+    const int buf = (int)(s & 1);
+    if (s + 1 < nstage) { TN_GLOAD((s + 1) * BR) }
+    const bf16_t* ta = lds + buf * STAGE;
+    const bf16_t* tb = ta + BR * RSA;
+#pragma unroll
+    for (int ks = 0; ks < BR / 32; ++ks) {
+      bf16x8 af[4], bfr[NJ];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = tfrag(ta, RSA, 32 * ks, wm * 64 + 16 * i);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) bfr[j] = tfrag(tb, RSB, 32 * ks, wn * WN + 16 * j);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = mma16(af[i], bfr[j], acc[i][j]);
+    }
+    if constexpr (BLOCKED) {
+      if (--left == 0) {
+        left = chunk;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            tot[i][j] += acc[i][j];
+            acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+      }
+    }
+    if (s + 1 < nstage) { TN_LSTORE(buf ^ 1) }
+    __syncthreads();
+  }
+#undef TN_GLOAD
+#undef TN_LSTORE
+  if constexpr (BLOCKED) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = tot[i][j];
+  }
+}
+
+template <int BN>
+__global__ __launch_bounds__(256, 2) void gemm_tn_tiled_kernel(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict__ B,
+                                                               long ldb, float* __restrict__ C, long ldc, long slab_stride,
+                                                               long Rz, int ntap, int Wp, int shift_a, int nzb, long bsA,
+                                                               long bsB, long bsC) {
+  constexpr int BM = TT_BM, WN = BN / 2, NJ = WN / 16;
+  __shared__ __attribute__((aligned(16))) bf16_t lds[2 * tt_stage_elems<BN>()];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i16 = lane & 15, qq = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+  unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+  tn_xcd_remap(bx, by, bz);
   // batches (independent problems, e.g. the three full-band branches): bz = batch * nzb + (tap * ksplit + slice)
   const unsigned bb = bz / nzb;
   bz %= nzb;
@@ -635,83 +761,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_tiled_kernel(const bf16_t* __r
   const bf16_t* Ab = A + (rbase + (shift_a ? boff : 0)) * lda + m0;
   const bf16_t* Bb = B + (rbase + (shift_a ? 0 : boff)) * ldb + n0;
   float* Cz = C + (size_t)bz * slab_stride;
-
-  // staging: A tile 64 rows x 16 chunks (16 B) = 1024 chunks -> 4 per thread; B tile 64 x BN/8 chunks
-  constexpr int ACH = BM / 8, BCH = BN / 8;
-  constexpr int NA = BR * ACH / NT, NB = BR * BCH / NT;
-  static_assert(NA == 4 && (NB == 4 || NB == 2 || NB == 1), "staging slots are named registers");
-  // chunk (row, c) of slot i: idx = tid + 256*i.  A: row = idx/16 -> rows (tid>>4) + 16*i, c = tid & 15.
-  const int arow = tid / ACH, ac = tid % ACH, brow = tid / BCH, bc = tid % BCH;
-  constexpr int ASTEP = NT / ACH, BSTEP = NT / BCH;                                      // rows between slots
-  const bf16_t* gA = Ab + (long)arow * lda + ac * 8;
-  const bf16_t* gB = Bb + (long)brow * ldb + bc * 8;
-  const int sA = arow * RSA + ac * 8, sB = BR * RSA + brow * RSB + bc * 8;
-  uint4 ra0, ra1, ra2, ra3, rb0, rb1 = {}, rb2 = {}, rb3 = {};
-#define TN_GLOAD(r0)                                                            \
-  ra0 = *reinterpret_cast<const uint4*>(gA + ((r0) + 0 * ASTEP) * lda);         \
-  ra1 = *reinterpret_cast<const uint4*>(gA + ((r0) + 1 * ASTEP) * lda);         \
-  ra2 = *reinterpret_cast<const uint4*>(gA + ((r0) + 2 * ASTEP) * lda);         \
-  ra3 = *reinterpret_cast<const uint4*>(gA + ((r0) + 3 * ASTEP) * lda);         \
-  rb0 = *reinterpret_cast<const uint4*>(gB + ((r0) + 0 * BSTEP) * ldb);         \
-  if (NB >= 2) rb1 = *reinterpret_cast<const uint4*>(gB + ((r0) + 1 * BSTEP) * ldb); \
-  if (NB == 4) {                                                                \
-    rb2 = *reinterpret_cast<const uint4*>(gB + ((r0) + 2 * BSTEP) * ldb);       \
-    rb3 = *reinterpret_cast<const uint4*>(gB + ((r0) + 3 * BSTEP) * ldb);       \
-  }
-#define TN_LSTORE(buf)                                                          \
-  *reinterpret_cast<uint4*>(&lds[buf][sA + 0 * ASTEP * RSA]) = ra0;             \
-  *reinterpret_cast<uint4*>(&lds[buf][sA + 1 * ASTEP * RSA]) = ra1;             \
-  *reinterpret_cast<uint4*>(&lds[buf][sA + 2 * ASTEP * RSA]) = ra2;             \
-  *reinterpret_cast<uint4*>(&lds[buf][sA + 3 * ASTEP * RSA]) = ra3;             \
-  *reinterpret_cast<uint4*>(&lds[buf][sB + 0 * BSTEP * RSB]) = rb0;             \
-  if (NB >= 2) *reinterpret_cast<uint4*>(&lds[buf][sB + 1 * BSTEP * RSB]) = rb1; \
-  if (NB == 4) {                                                                \
-    *reinterpret_cast<uint4*>(&lds[buf][sB + 2 * BSTEP * RSB]) = rb2;           \
-    *reinterpret_cast<uint4*>(&lds[buf][sB + 3 * BSTEP * RSB]) = rb3;           \
-  }
-  // transposed fragment: 8 consecutive r (starting r0 + 8*qq) of column (col0 + lane&15)
-  auto tfrag = [&](const bf16_t* tile, int rs, int r0, int col0) -> bf16x8 {
-    const int q4 = i16 >> 2, p4 = i16 & 3;                  // lane 4q+p of the group supplies row q, columns 4p..4p+3
-    const bf16_t* base = tile + (r0 + 8 * qq + q4) * rs + col0 + 4 * p4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 4 * rs));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  };
-
   f32x4 acc[4][NJ];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const long nstage = Rz / BR;
-  TN_GLOAD(0)
-  TN_LSTORE(0)
-  __syncthreads();
-  for (long s = 0; s < nstage; ++s) {
-    const int buf = (int)(s & 1);
-    if (s + 1 < nstage) { TN_GLOAD((s + 1) * BR) }
-    const bf16_t* ta = lds[buf];
-    const bf16_t* tb = lds[buf] + BR * RSA;
-#pragma unroll
-    for (int ks = 0; ks < BR / 32; ++ks) {
-      bf16x8 af[4], bfr[NJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = tfrag(ta, RSA, 32 * ks, wm * 64 + 16 * i);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bfr[j] = tfrag(tb, RSB, 32 * ks, wn * WN + 16 * j);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = mma16(af[i], bfr[j], acc[i][j]);
-    }
-    if (s + 1 < nstage) { TN_LSTORE(buf ^ 1) }
-    __syncthreads();
-  }
-#undef TN_GLOAD
-#undef TN_LSTORE
+  tn_tiled_mainloop<BN>(acc, lds, Ab, lda, Bb, ldb, Rz / TT_BR);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -722,6 +773,61 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_tiled_kernel(const bf16_t* __r
         const long col = n0 + wn * WN + 16 * j + i16;
         Cz[row * ldc + col] = acc[i][j][r];
       }
+}
+
+// Grouped launch: blockIdx.z selects one of gridDim.z independent products of the same M, N, R out of a device-resident table
+// (nppc_tn_problem, include/nppc_hip.h).  No split-K: a workgroup owns one output tile of one problem for all R rows and writes
+// the FINISHED gradient to its place -- no fp32 slabs, no reduction launch.  It sums the rows in blocks of `chunk` stages (the
+// BLOCKED main loop): with R / (64 chunk) = the ksplit of the launches this one replaces, the result is theirs bit for bit.
+// Column tiles are 128 wide (half the operand bytes per FLOP of A through the CU's load path, and N = 576 x 24 problems =
+// 480 workgroups: ONE round of two per CU); a last 64-wide tile takes N % 128.  An element's sum does not depend on the
+// width of its tile.  The tile leaves through the LDS operand buffers (free behind the main loop) so that both store kinds
+// write whole rows of the destination:
+//   NPPC_TN_STORE_ASIS        dst[m][n] = sum_r A[r][m] B[r][n],  n < nvalid  (BN consecutive floats per row of the tile)
+//   NPPC_TN_STORE_TRANSPOSED  dst[n][m] = the same,              n < nvalid  (128 consecutive floats per row)
+// The operands' padding columns nvalid .. N-1 are computed and dropped: the destinations are dense slices of the flat
+// gradient buffer, whatever lies behind them belongs to another parameter.
+template <int BN>
+__device__ __forceinline__ void tn_grouped_tile(const nppc_tn_problem& p, bf16_t* lds, int m0, int n0, long nstage, long chunk) {
+  constexpr int BM = TT_BM, WN = BN / 2, NJ = WN / 16;
+  constexpr int EP = BN + 1;                                // row stride of the fp32 tile image (odd: both read orders spread over the banks)
+  static_assert(BM * EP * 4 <= 2 * tt_stage_elems<BN>() * 2, "the fp32 tile fits into the operand buffers");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, qq = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+  f32x4 acc[4][NJ];
+  tn_tiled_mainloop<BN, true>(acc, lds, (const bf16_t*)p.A + m0, p.lda, (const bf16_t*)p.B + n0, p.ldb, nstage, chunk);
+  float* tile = reinterpret_cast<float*>(lds);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tile[(wm * 64 + 16 * i + 4 * qq + r) * EP + wn * WN + 16 * j + i16] = acc[i][j][r];
+  __syncthreads();
+  const int nv = (int)p.nvalid - n0;                        // valid columns of this tile (<= 0: all padding)
+  __attribute__((address_space(1))) float* dst = (__attribute__((address_space(1))) float*)p.dst;
+  if (p.kind == NPPC_TN_STORE_TRANSPOSED) {
+    for (int e = tid; e < BM * BN; e += 256) {
+      const int n = e / BM, m = e % BM;
+      if (n < nv) dst[(long)(n0 + n) * p.dst_ld + m0 + m] = tile[m * EP + n];
+    }
+  } else {
+    for (int e = tid; e < BM * BN; e += 256) {
+      const int m = e / BN, n = e % BN;
+      if (n < nv) dst[(long)(m0 + m) * p.dst_ld + n0 + n] = tile[m * EP + n];
+    }
+  }
+}
+
+// grid (M / 128, nwide + (N % 128 != 0), problems): column tiles 0 .. nwide-1 are 128 wide, the last one 64 if N % 128 == 64
+__global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const nppc_tn_problem* __restrict__ table, long R,
+                                                                 long chunk, int nwide) {
+  __shared__ __attribute__((aligned(16))) bf16_t lds[2 * tt_stage_elems<128>()];
+  unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+  tn_xcd_remap(bx, by, bz);
+  const nppc_tn_problem p = table[bz];
+  if ((int)by < nwide) tn_grouped_tile<128>(p, lds, (int)bx * TT_BM, (int)by * 128, R / TT_BR, chunk);
+  else tn_grouped_tile<64>(p, lds, (int)bx * TT_BM, nwide * 128, R / TT_BR, chunk);
 }
 
 }  // namespace
@@ -923,26 +1029,13 @@ __device__ __forceinline__ void dma_tile(const bf16_t* __restrict__ A, long lda,
   }
 }
 
-// all output tiles of one K slice on ONE XCD (see gemm_tn_tiled_kernel): remaps (bx, by, bz) when gridDim.z % 8 == 0
-__device__ __forceinline__ void dr_xcd_remap(unsigned& bx, unsigned& by, unsigned& bz) {
-  if (gridDim.z % 8 == 0) {
-    const unsigned tiles = gridDim.x * gridDim.y;
-    const unsigned lin = bx + gridDim.x * (by + gridDim.y * bz);
-    const unsigned xcd = lin & 7, j = lin >> 3;
-    bz = xcd + 8 * (j / tiles);
-    const unsigned t = j % tiles;
-    bx = t % gridDim.x;
-    by = t / gridDim.x;
-  }
-}
-
 template <int BN, int BR, int STAGES>
 __global__ __launch_bounds__(512, 1) void gemm_tn_dma_kernel(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict__ B,
                                                              long ldb, float* __restrict__ C, long ldc, long slab_stride, long Rz,
                                                              int nzb, long bsA, long bsB, long bsC, float* __restrict__ rowsum,
                                                              int ntap, int Wp, int shift_a) {
   unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  dr_xcd_remap(bx, by, bz);
+  tn_xcd_remap(bx, by, bz);            // all output tiles of one K slice on ONE XCD
   const unsigned bb = bz / nzb;
   bz %= nzb;
   A += (size_t)bb * bsA;
@@ -969,7 +1062,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_dma2_kernel(const bf16_t* __re
                                                               float* __restrict__ C, long ldc, long slab_stride, long Rz,
                                                               float* __restrict__ rowsum) {
   unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  dr_xcd_remap(bx, by, bz);
+  tn_xcd_remap(bx, by, bz);            // all output tiles of one K slice on ONE XCD
   const long m0 = (long)bx * BM, rbase = (long)bz * Rz;
   float* Cz = C + (size_t)bz * slab_stride;
   float* rs = rowsum != nullptr && by == 0 ? rowsum + (size_t)bz * ((size_t)gridDim.x * BM) : nullptr;
@@ -1100,6 +1193,22 @@ extern "C" int nppc_gemm_tn_splitk_batched(const void* A, long lda, long sA, con
                                            long sC, int M, int N, long R, int ksplit, int batch, void* stream) {
   if (batch < 1) return NPPC_EBADARG;
   return launch_tn(A, lda, B, ldb, C, ldc, M, N, R, ksplit, 1, 0, 0, stream, batch, sA, sB, sC);
+}
+
+// `nprob` products of one shape (M, N, R) in ONE launch, each finished where its table entry says (gemm_tn_grouped_kernel):
+// no split-K, no slabs; the rows are summed in up to eight blocks whose sums are added in order.  `table`: nprob entries in DEVICE memory, read by the kernel only -- the caller vouches for them
+// (lda >= M, ldb >= N, both multiples of 8; operands of at least R rows; 0 <= nvalid <= N).  M % 128 == 0, N % 64 == 0, R % 64 == 0.
+extern "C" int nppc_gemm_tn_grouped(const nppc_tn_problem* table, int nprob, int M, int N, long R, void* stream) {
+  if (!table || nprob < 1 || M <= 0 || N <= 0 || R <= 0) return NPPC_EBADARG;
+  if (M % TT_BM || N % 64 || R % TT_BR || nprob > 65535) return NPPC_EUNSUPPORTED;
+  // eight row blocks (or the largest number up to eight that divides the stages), like the split-K launches this one replaces
+  const long nstage = R / TT_BR;
+  int nblk = 8;
+  while (nstage % nblk) --nblk;
+  hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(M / TT_BM, N / 128 + (N % 128 != 0), nprob), dim3(256), 0, (hipStream_t)stream,
+                     table, R, nstage / nblk, N / 128);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
 }
 
 // Nine row-shifted TN products in one launch (3x3 convolution weight gradient, csrc/unet.hip):

@@ -63,6 +63,26 @@ def ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+TN_STORE_ASIS, TN_STORE_TRANSPOSED = 0, 1
+
+
+def tn_problem_table(problems, M, N, R):
+    """device table of nppc_gemm_tn_grouped (nppc_tn_problem: 8 x 64 bits per entry) from (A, lda, B, ldb, dst, dst_ld, nvalid,
+    kind) tuples of bf16 operand tensors and fp32 destination views.  The kernel trusts the table, so everything it will
+    touch is checked here: operand rows [0, R) x columns [0, M) / [0, N) and the clipped destination lie inside the tensors.
+    The tensors must outlive every launch that uses the table."""
+    rows = []
+    for A, lda, B, ldb, dst, dst_ld, nvalid, kind in problems:
+        assert A.is_cuda and B.is_cuda and dst.is_cuda and A.dtype == B.dtype == torch.bfloat16 and dst.dtype == torch.float32
+        assert lda % 8 == 0 and ldb % 8 == 0 and lda >= M and ldb >= N and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0
+        assert (R - 1) * lda + M <= A.numel() and (R - 1) * ldb + N <= B.numel() and 0 <= nvalid <= N
+        assert kind in (TN_STORE_ASIS, TN_STORE_TRANSPOSED)
+        n_rows, n_cols = (M, nvalid) if kind == TN_STORE_ASIS else (nvalid, M)
+        assert dst_ld >= n_cols and (n_rows - 1) * dst_ld + n_cols <= dst.numel()
+        rows.append([A.data_ptr(), lda, B.data_ptr(), ldb, dst.data_ptr(), dst_ld, nvalid, kind])
+    return torch.tensor(rows, dtype=torch.int64).to(problems[0][0].device)
+
+
 def mid_bwd_part_elems(B, C, Tp, batch):
     n = c_l()
     call("nppc_tcn_mid_bwd_part_elems", B, C, Tp, batch, ctypes.byref(n))
@@ -149,6 +169,7 @@ SIGS = {
     "nppc_gemm_tn_splitk_rowsum": [P, L, P, L, P, L, I, I, L, I, P, P],
     "nppc_gemm_tn_splitk2": [P, L, P, L, I, P, L, I, P, L, I, L, I, P, P],
     "nppc_gemm_tn_splitk_batched": [P, L, L, P, L, L, P, L, L, I, I, L, I, I, P],
+    "nppc_gemm_tn_grouped": [P, I, I, I, L, P],
     "nppc_reduce_slabs_t": [P, I, L, L, P, L, I, I, L, L, I, P],
     "nppc_gemm_tn_splitk_taps": [P, L, P, L, P, L, I, I, L, I, I, I, P],
     "nppc_tcn_dwconv": [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, L, L, L, I, P],

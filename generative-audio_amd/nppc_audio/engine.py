@@ -25,8 +25,7 @@ def rup(a, b):
     return (a + b - 1) // b * b
 
 
-TCN_WGRAD_SPLITS = 8         # K-slices of the TCN weight-gradient GEMMs
-TCN_WGRAD_MAIN_BLOCKS = 1    # TCN blocks (0 .. n-1) whose weight gradients stay on the main queue
+TCN_WGRAD_SPLITS = 8         # K-slices of the split-K weight-gradient GEMMs of the full-band model (fc_output_layer; fp32: all)
 
 
 class FlatParams:
@@ -136,6 +135,7 @@ class FSNEngine:
         self.sP = flat.branch_stride()
         self.sAtt = flat.attention_stride()
         self.packed_version = None
+        self._tn_tables = {}                  # problem tables of the grouped TCN weight-gradient launches (_tcn_wgrad_tables)
         self._side = None                     # side stream for the LSTM weight-gradient GEMMs (backward)
         self._gen = 0                         # train-forward generation: backward must consume the LATEST train forward
         self.last_train = None
@@ -428,6 +428,26 @@ class FSNEngine:
     def g(self, name):
         return self.fp.gview(name)
 
+    def _tcn_wgrad_tables(self, G, d, dXL, a2L, h2L, R, blocks):
+        """the problem tables of nppc_gemm_tn_grouped for TCN blocks `blocks` x the three branches, (sconv.weight, conv1x1.weight):
+        built once per set of buffers (workspaces, saved activations and both flat gradient buffers keep their addresses)"""
+        key = (G.data_ptr(), d["X"].data_ptr(), a2L[0].data_ptr(), R, blocks)
+        tabs = self._tn_tables.get(key)
+        if tabs is None:
+            C, ldC = self.C, self.ldC
+            sc, c1 = [], []
+            for i in blocks:
+                for z, br in enumerate(BRANCHES):
+                    pre = f"fb_model{br}.sequence_model.{i}."
+                    # dW2^T[k][c] = sum_r a2[r][k] * dXo[r][c], stored transposed: sconv.weight is [C][512]
+                    sc.append((a2L[i][z], TCN_HIDDEN, dXL[i + 1][z], ldC, self.g(pre + "sconv.weight"), TCN_HIDDEN, C,
+                               H.TN_STORE_TRANSPOSED))
+                    # dW1[k][c] = sum_r dpre1[r][k] * Xin[r][c]: conv1x1.weight is [512][C]
+                    c1.append((h2L[i][z], TCN_HIDDEN, d["X"][i][z], ldC, self.g(pre + "conv1x1.weight"), C, C, H.TN_STORE_ASIS))
+            tabs = (H.tn_problem_table(sc, TCN_HIDDEN, ldC, R), H.tn_problem_table(c1, TCN_HIDDEN, ldC, R))
+            self._tn_tables[key] = tabs
+        return tabs
+
     def _wgrad(self, AT, lda, sA, BT, ldb, sB, rows, ncolsN, K, S, dst_name_or_tensor, dst_ld, out_rows, ncols, slab,
                batch=1, sDst=0, permH=0, col0=0, accumulate=0):
         """dst[r][c] = sum_k AT[r][k] * BT[c][k]  via split-K fp32 slabs + reduction (one launch pair)."""
@@ -623,7 +643,6 @@ class FSNEngine:
         Cr = rup(ldC, 128)
         tA = ws("tA", (3, max(Cr, TCN_HIDDEN, Fr), R), zero=True)       # transposed dY operand
         tB = ws("tB", (3, max(ldC, TCN_HIDDEN), R), zero=True)          # transposed activation operand
-        slab2 = ws("slab2", (3 * S2 * max(Cr * TCN_HIDDEN, TCN_HIDDEN * ldC, Fr * ldC),), torch.float32)
         X8 = d["X"][8]
         sTA, sTB = tA.shape[1] * R, tB.shape[1] * R
 
@@ -645,10 +664,11 @@ class FSNEngine:
             H.call("nppc_transpose", prec, X8, tB, R, ldC, ldC, R, R * ldC, sTB, 1, 3, q)
             self._wgrad(tA, R, sTA, tB, R, sTB, Fr, ldC, R, S2, "fb_model.fc_output_layer.weight", C, F, C, slab, batch=3, sDst=sP)
         # bf16: the product waits until the END of the main chain -- the side queue (LSTM + TCN weight gradients) is the longer
-        # one, the main queue would idle ~0.4 ms in front of the join -- with a slab of its own (slab2 belongs to the side queue)
+        # one, the main queue would idle in front of the join -- with a slab of its own
         # (the generic path below re-uses tA / tB / slab2 on the main stream: there the product stays in line)
         tn_ok = prec == H.PREC_BF16 and TCN_HIDDEN % 128 == 0 and ldC % 64 == 0 and R % (64 * S2) == 0
         if not tn_ok:
+            slab2 = ws("slab2", (3 * S2 * max(Cr * TCN_HIDDEN, TCN_HIDDEN * ldC, Fr * ldC),), torch.float32)
             fc_wgrad(slab2)
         # bf16: the 1x1-conv weight gradients run on the TN GEMM straight from the row-major activations (no transposes)
         if tn_ok:
@@ -659,6 +679,13 @@ class FSNEngine:
             a2L = [ws(f"a2_{i}", (3, B, Tp, TCN_HIDDEN), zero=True) for i in range(8)]
             h2L = [ws(f"h2b_{i}", (3, B, Tp, TCN_HIDDEN)) for i in range(8)]
             dXa, dXb = dXL[8], dXL[7]
+
+            def tcn_wgrad(blocks):
+                # both weight gradients of TCN blocks `blocks` x the three branches: one grouped launch per kind
+                sc_tab, c1_tab = self._tcn_wgrad_tables(G, d, dXL, a2L, h2L, R, blocks)
+                q = H.stream()
+                H.call("nppc_gemm_tn_grouped", sc_tab, sc_tab.shape[0], TCN_HIDDEN, ldC, R, q)
+                H.call("nppc_gemm_tn_grouped", c1_tab, c1_tab.shape[0], TCN_HIDDEN, ldC, R, q)
         else:
             dXa = ws("dXa", (3, B, Tp, ldC))
             dXb = ws("dXb", (3, B, Tp, ldC))
@@ -726,44 +753,21 @@ class FSNEngine:
                    B, TCN_HIDDEN, Tp, Tv, dil, 1e-8, sAct, B * 2, sP, 3, 0, s)
             if i == 4 and early:
                 finish_mid(4, 8)              # blocks 7..4 are handed to the exchange below: their gradients must be final
-            # sconv weight gradient: dW2[c][k] = sum_r dXo[r][c] * a2[r][k]
+            # sconv weight gradient dW2[c][k] = sum_r dXo[r][c] * a2[r][k] and conv1x1 weight gradient dW1[k][c] = sum_r
+            # dpre1[r][k] * Xin[r][c]
             if tn_ok:
-                # row-major operands as they are: slab[k][c] = sum_r a2[r][k] * dXo[r][c] = dW2^T, transposed in the reduction
-                # (blocks i < TCN_WGRAD_MAIN_BLOCKS -- the last ones of the chain -- keep their two products on the MAIN queue,
-                # with a slab of their own: since the eight finishing launches became one the side queue is the longer one,
-                # profiles/r04_bench_c2_bf16_windows.txt)
-                inline = i < TCN_WGRAD_MAIN_BLOCKS
-                wslab = ws("slab_main", (3 * S2 * TCN_HIDDEN * ldC,), torch.float32) if inline else slab2
-
-                def sconv_wgrad(a2=a2, dXo=dXo, dest=self.g(pre + "sconv.weight"), wslab=wslab):
-                    q = H.stream()
-                    H.call("nppc_gemm_tn_splitk_batched", a2, TCN_HIDDEN, sAct, dXo, ldC, R * ldC, wslab, ldC,
-                           S2 * TCN_HIDDEN * ldC, TCN_HIDDEN, ldC, R, S2, 3, q)
-                    H.call("nppc_reduce_slabs_t", wslab, S2, TCN_HIDDEN * ldC, ldC, dest, TCN_HIDDEN, C, TCN_HIDDEN,
-                           S2 * TCN_HIDDEN * ldC, sP, 3, q)
-                if inline:
-                    sconv_wgrad()
-                else:
-                    on_side(sconv_wgrad)
+                # row-major operands as they are, all blocks x branches of a kind in ONE grouped launch on the side queue, written
+                # finished into the flat gradient (no split-K slabs, no reductions): issued once the main chain has produced the
+                # operands of the last block of the group -- block 0, or block 4 and then block 0 when blocks 7..4 leave early
+                if i == 0 or (i == 4 and early):
+                    on_side(lambda blocks=tuple(range(3 if early and i == 0 else 7, i - 1, -1)): tcn_wgrad(blocks))
             else:
                 H.call("nppc_transpose", prec, dXo, tA, R, ldC, ldC, R, R * ldC, sTA, 0, 3, s)
                 H.call("nppc_transpose", prec, a2, tB, R, TCN_HIDDEN, TCN_HIDDEN, R, sAct, sTB, 0, 3, s)
                 self._wgrad(tA, R, sTA, tB, R, sTB, Cr, TCN_HIDDEN, R, S2, pre + "sconv.weight", TCN_HIDDEN, C, TCN_HIDDEN,
                             slab2, batch=3, sDst=sP)
             # conv1x1: weight, input gradients (the bias gradient came out of the fused kernel)
-            if tn_ok:
-                # slab[k][c] = sum_r dpre1[r][k] * Xin[r][c] = dW1
-                def c1_wgrad(h2b=h2b, Xin=Xin, dest=self.g(pre + "conv1x1.weight"), wslab=wslab):
-                    q = H.stream()
-                    H.call("nppc_gemm_tn_splitk_batched", h2b, TCN_HIDDEN, sAct, Xin, ldC, R * ldC, wslab, ldC,
-                           S2 * TCN_HIDDEN * ldC, TCN_HIDDEN, ldC, R, S2, 3, q)
-                    H.call("nppc_reduce_slabs", wslab, S2, TCN_HIDDEN * ldC, ldC, dest, C, TCN_HIDDEN, 0, C, 0, 0,
-                           S2 * TCN_HIDDEN * ldC, sP, 3, q)
-                if inline:
-                    c1_wgrad()
-                else:
-                    on_side(c1_wgrad)
-            else:
+            if not tn_ok:
                 H.call("nppc_transpose", prec, h2b, tA, R, TCN_HIDDEN, TCN_HIDDEN, R, sAct, sTA, 0, 3, s)
                 H.call("nppc_transpose", prec, Xin, tB, R, ldC, ldC, R, R * ldC, sTB, 0, 3, s)
                 self._wgrad(tA, R, sTA, tB, R, sTB, TCN_HIDDEN, ldC, R, S2, pre + "conv1x1.weight", C, TCN_HIDDEN, C, slab2,

@@ -105,6 +105,27 @@ int nppc_gemm_tn_splitk2(const void* A, long lda, const void* B1, long ldb1, int
                          long ldc, int M, long R, int ksplit, float* rowsum, void* stream);
 int nppc_gemm_tn_splitk_batched(const void* A, long lda, long sA, const void* B, long ldb, long sB, float* C, long ldc, long sC,
                                 int M, int N, long R, int ksplit, int batch, void* stream);
+/* `nprob` TN products of ONE shape in one launch, no split-K, each written FINISHED to its destination (no fp32 slabs, no
+ * reduction launch): the weight gradients of the TCN 1x1 convolutions of all blocks x branches.  `table` lives in DEVICE
+ * memory (nprob entries of 8 x 64 bits) and is read by the kernel only: the caller vouches for lda >= M, ldb >= N (multiples
+ * of 8), operands of at least R rows and 0 <= nvalid <= N.  Only columns n < nvalid of the product reach the destination:
+ *   NPPC_TN_STORE_ASIS        dst[m * dst_ld + n] = sum_r A[r][m] * B[r][n]
+ *   NPPC_TN_STORE_TRANSPOSED  dst[n * dst_ld + m] = the same
+ * One workgroup sums all R rows of its output tile (128 x 128; a last column tile of 64 takes N % 128): deterministic, one
+ * writer per element.  The rows are summed in k row blocks (k = 8, or the largest k < 8 that divides R / 64) from zero and
+ * the block sums added in order from zero: the same fp32 additions, hence
+ * the same bits, as nppc_gemm_tn_splitk_batched with ksplit = k followed by nppc_reduce_slabs / nppc_reduce_slabs_t
+ * (where that launch takes the register-staged kernel, as it does at the TCN shapes: its k-step order is the one used here).
+ * bf16; M % 128 == 0, N % 64 == 0, R % 64 == 0, nprob <= 65535; NPPC_EUNSUPPORTED otherwise */
+enum { NPPC_TN_STORE_ASIS = 0, NPPC_TN_STORE_TRANSPOSED = 1 };
+typedef struct nppc_tn_problem {
+  const void* A; long lda;      /* [R][lda] bf16 */
+  const void* B; long ldb;      /* [R][ldb] bf16 */
+  float* dst; long dst_ld;
+  long nvalid;
+  long kind;
+} nppc_tn_problem;
+int nppc_gemm_tn_grouped(const nppc_tn_problem* table, int nprob, int M, int N, long R, void* stream);
 int nppc_gemm_tn_splitk_taps(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, long R,
                              int ksplit, int Wp, int shift_a, void* stream);
 int nppc_pack_matrix(int prec, const float* src, void* dst, int N, int K, int Npad, int ldd, int transpose, void* stream);
