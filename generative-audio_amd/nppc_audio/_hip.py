@@ -323,6 +323,10 @@ SIGS = {
     "nppc_spec_windows": [P, I, I, P, P],
     "nppc_spec_render": [P, I, I, I, I, I, P, I, P, I, P, P, P, P, L, L, P],
     "nppc_spec_render_png": [P, I, I, I, I, I, P, I, P, I, P, P, P, P, L, L, P, P, L, P, P, P, P, P, L, P],
+    "nppc_curve_shape": [P, I, P, I, P, I, P, I, I, I, I, I, P, P, P],
+    "nppc_curve_render_host": [P, I, I, P, I, P, I, P, I, P, I, P, I, P, P, P, L],
+    "nppc_curve_render": [P, I, I, P, I, P, I, P, I, P, I, P, I, I, P, P, P, L, P],
+    "nppc_curve_render_png": [P, I, I, P, I, P, I, P, I, P, I, P, I, I, P, P, P, L, P, P, L, P, P, P, P, P, L, P],
 }
 _bound = set()
 _bind_lock = threading.Lock()

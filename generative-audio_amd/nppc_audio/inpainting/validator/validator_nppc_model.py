@@ -21,7 +21,13 @@ on the device (nppc_audio/flac.py) or as wav.
 one sheet per sample, as PNG files drawn and encoded on the device (nppc_audio/spectrogram_png.py): the whole batch in one
 device call.  Titles, axes and colour bars are not drawn; no pixel parity with matplotlib's figures is claimed.
 
-Outside this build: whisper / phoneme transcription, the pitch plots, wandb.
+`save_pc_pitch_plots` writes the pitch figures of plot_pitch_comparison (:19-154) from the contours of
+validate_batch(..., pitch=True): pc_<k>_pitch.png per direction and the stacked pitch_comparison.png, as PNG files drawn and
+encoded on the device (nppc_audio/curve_png.py), the whole batch in one device call.  Not reproduced: matplotlib's 0.7 line
+alpha (paint order stands in for it: later alphas lie over earlier ones), titles, axis names and anti-aliasing; no pixel
+parity with matplotlib's figures is claimed.
+
+Outside this build: whisper / phoneme transcription, wandb.
 Splicing a restoration or a variation into the full source recording is inpainting/restore.py (RecordingRestorer).
 """
 import json
@@ -42,7 +48,7 @@ from ..utils import preprocess_data
 
 __all__ = ["NPPCModelValidatorConfig", "NPPCModelValidator", "pc_audio_variations", "compute_metrics",
            "compute_metrics_batch", "save_metrics_to_json", "default_alphas", "save_pc_audio_variations",
-           "save_pc_spectrograms", "pc_spectrogram_sheets"]
+           "save_pc_spectrograms", "pc_spectrogram_sheets", "save_pc_pitch_plots", "pitch_windows"]
 
 compute_metrics = MB.compute_metrics
 compute_metrics_batch = MB.compute_metrics_batch
@@ -95,7 +101,8 @@ def save_pc_audio_variations(out, save_dir, alphas, first_index=0, fmt="flac", s
     16-bit mono at sample_rate.  fmt "flac": all B (1 + K A [+ K A]) waveforms are quantised and encoded in ONE device call
     (flac.encode_waves) and cross to the host as FLAC bytes; fmt "wav": the same samples as wav.  The reference's *_full
     files (the variation spliced into the source recording) are RecordingRestorer.save_variations, the spectrogram pictures
-    save_pc_spectrograms; transcriptions, phonemes and pitch plots are outside this build.  -> the paths written"""
+    save_pc_spectrograms, the pitch figures save_pc_pitch_plots; transcriptions and phonemes are outside this build.
+    -> the paths written"""
     from ... import flac as FL
     var, clean = out["audio_variations"], out["clean_audio"]
     B, K, A, L = var.shape
@@ -187,6 +194,62 @@ def save_pc_spectrograms(out, save_dir, alphas, first_index=0, max_dirs=None, in
     files = render_png(planes, sheets, win, palette=palette, max_frames=max_frames)
     root = Path(save_dir)
     paths = [root / f"sample_{first_index + b}" / "spectrograms" / name for b, name in names]
+    PNG.write_files(paths, files)
+    return paths
+
+
+PITCH_RANGE, PITCH_SR, PITCH_HOP = (80.0, 400.0), 16000, 512          # validate_batch's pYIN setting (plot_pitch_comparison :60-66)
+
+
+def pitch_windows(mask, stft_hop, n_pitch_frames, pitch_hop=PITCH_HOP):
+    """mask [B, T] (device, 0 inside the gap) -> int32 [B, 4] in pitch frames: the whole clip [0, n_pitch_frames) and the gap
+    markers.  Integer arithmetic on the device: STFT frame f is centred on sample f * stft_hop and pitch frame j on sample
+    j * pitch_hop, so frame f becomes the nearest pitch frame (f * stft_hop + pitch_hop // 2) // pitch_hop; the markers are
+    the gap's first STFT frame and the one past its last (spectrogram_png.windows_from_mask); an item without a gap has
+    none (-1)."""
+    from ...spectrogram_png import windows_from_mask
+    m = windows_from_mask(mask)[:, 2:4].long()
+    conv = torch.where(m >= 0, (m * int(stft_hop) + pitch_hop // 2) // pitch_hop, torch.full_like(m, -1))
+    whole = torch.tensor([0, int(n_pitch_frames)], dtype=torch.long, device=m.device).expand(m.shape[0], 2)
+    return torch.cat([whole, conv], dim=1).to(torch.int32).contiguous()
+
+
+def save_pc_pitch_plots(out, save_dir, alphas, first_index=0, max_dirs=None, individual=True, sx=8, plot_height=240,
+                        backend="auto", hop_length=None):
+    """plot_pitch_comparison (:19-154) for a whole batch, from the dict of validate_batch(..., pitch=True): under
+    <save_dir>/sample_<first_index + b>/
+        pitch_contours/pc_<k>_pitch.png     the clean contour (black, 2 pixels) under direction k's A variations in viridis
+                                            colours (curve_png.alpha_colours), a legend of every second alpha   (individual)
+        pitch_comparison.png                the clean panel and one such panel per direction, stacked
+    y runs over the call's 80..400 Hz with a grid line and a label every 100 Hz; x is the whole clip, every pitch frame sx
+    pixels wide, with a grid line and a label in seconds every 16 frames (0.512 s: the whole number of 32 ms frames nearest
+    to half a second).  The dashed columns stand at the gap's first frame and the one past its last, converted from
+    out['mask'] on the device (pitch_windows; hop_length: the STFT's hop, default L // (T - 1)).  The whole batch,
+    B (K + 1) files, is drawn and encoded in ONE curve_png.render_png call and written by one png.write_files.
+    -> the paths written"""
+    from ... import curve_png as CP
+    from ... import png as PNG
+    if "pitch" not in out:
+        raise ValueError("save_pc_pitch_plots takes the dict of validate_batch(..., pitch=True), which holds 'pitch'")
+    pitch = out["pitch"]
+    B, K, A, T = pitch["f0"].shape
+    alphas = [float(a) for a in torch.as_tensor(alphas).reshape(-1).tolist()]
+    if len(alphas) != A:
+        raise ValueError(f"{len(alphas)} alphas for {A} variations per direction")
+    if max_dirs is not None:
+        K = min(K, int(max_dirs))
+    mask = out["mask"].detach().float()
+    mask = mask.reshape(B, -1, mask.shape[-2], mask.shape[-1])[:, 0, 0, :]
+    L = out["clean_audio"].shape[-1]
+    hop = int(hop_length) if hop_length is not None else L // max(1, mask.shape[-1] - 1)
+    values = CP.stack_contours(pitch)
+    win = pitch_windows(mask.to(values.device), hop, T)
+    names, sheets = CP.pitch_sheets(B, K, alphas, T, PITCH_HOP / PITCH_SR, individual=individual, sx=sx, plot_height=plot_height,
+                                    fmin=PITCH_RANGE[0], fmax=PITCH_RANGE[1], per_item=1 + pitch["f0"].shape[1] * A)
+    files = CP.render_png(values, sheets, win, backend=backend)
+    root = Path(save_dir)
+    paths = [root / f"sample_{first_index + b}" / ("pitch_contours" if name != "pitch_comparison.png" else "") / name
+             for b, name in names]
     PNG.write_files(paths, files)
     return paths
 

@@ -171,6 +171,31 @@ class NPPCAudioValidator:
             enhanced_spec_db = 20 * torch.log10(torch.sqrt(e_re * e_re + e_im * e_im) + 1e-8)
         return pc_specs, enhanced_spec_db
 
+    def visualize_pc_pitch(self, noisy_audio: torch.Tensor, alphas=ALPHAS, save_dir=None, individual=True, sx=8, plot_height=240,
+                           backend="auto", fmin=80.0, fmax=400.0, sr=16000):
+        """noisy_audio [B,T] -> tracks the contours of the enhanced waveform and of every `enhanced + alpha * PC_k` on the
+        device, writes <save_dir>/pitch/pc_<k>_pitch.png (individual) and <save_dir>/pitch/pitch_comparison.png (under
+        <save_dir>/item_<b>/ when B > 1), the whole batch in one curve_png.render_png call, and returns (paths, the dict of
+        pc_pitch.pc_direction_pitch)."""
+        from . import curve_png as CP
+        from .pc_pitch import pc_direction_pitch
+        H.require_gpu()
+        if noisy_audio.dim() != 2:
+            raise ValueError(f"Expected noisy_audio shape [B,T], got {tuple(noisy_audio.shape)}")
+        if save_dir is None:
+            raise ValueError("visualize_pc_pitch writes files: pass save_dir")
+        alphas = [float(a) for a in alphas]
+        pitch = pc_direction_pitch(self.nppc_model, noisy_audio.to(self.device).float().contiguous(), alphas, fmin=fmin, fmax=fmax, sr=sr)
+        B, K, A, T = pitch["f0"].shape
+        hop = 2048 // 4                                             # pitch.pyin's default frame and hop
+        names, sheets = CP.pitch_sheets(B, K, alphas, T, hop / sr, individual=individual, sx=sx, plot_height=plot_height, fmin=fmin,
+                                        fmax=fmax, markers=False)
+        files = CP.render_png(CP.stack_contours(pitch), sheets, backend=backend)
+        root = Path(save_dir).absolute()
+        paths = [(root / f"item_{b}" if B > 1 else root) / "pitch" / name for b, name in names]
+        PNG.write_files(paths, files)
+        return paths, pitch
+
     def pc_spectrogram_indices(self, planes, has_clean=True, sx=1, sy=1, gutter=4):
         """the sheets of stacked complex planes [B, 3 + K, 2, F, T] (stack_planes) as index images: for tests and for
         callers who want pixels"""

@@ -987,6 +987,40 @@ int nppc_spec_render_png(const float* planes, int B, int NP, int CH, int F, int 
                          const int* ttab, const int* tfirst, long ntiles, const unsigned char* palette, int* plan, long* toff,
                          long* stats, unsigned char* out, long out_cap, void* stream);
 
+/* ---- curve sheets as index images and PNG files (csrc/curve_core.h) ------------------------------------
+ * plot_pitch_comparison of the reference's validator_nppc_model.py:19-154: curves over frames (values [N][T_frames] fp32, NaN: no
+ * point) in stacked panels with an axes box, grid lines, tick labels in a 5 x 7 font and a legend.  The drawing rule (fp32
+ * quantisation of rows, integer segments, widths, crop to the window, paint order, layout) is stated once in csrc/curve_core.h.
+ * Palette indices: the curves' own, 250 box and glyphs, 251 grid, 254 gap markers, 255 background.
+ *   sheet [nimg][8]: item, first panel, panels, sx, plot height, glyph scale, 0, 0
+ *   panel [npanels][8]: first curve, curves, flags (1 autoscale, 2 markers), ymin, scale = fp32(PH / (ymax - ymin)) (floats' bits),
+ *                       first stamp, stamps, xtick_every (0: none)
+ *   curve [ncurves][4]: row of values, colour, width 1..5, 0
+ *   stamp [nstamps][8]: kind (0 y tick, 1 x label, 2 legend entry), value (float's bits / frame / entry), swatch colour, characters
+ *                       (at most 16), glyph codes 4 bits each in two ints (0-9, 10 '.', 11 '-', 12 ' '), 0, 0
+ *   win [nitems][4]: t0, t1, marker 0, marker 1 in curve frames (-1: no marker), the layout of nppc_spec_windows.
+ * A panel's curves times (t1 - t0 + 2) may not exceed 16384 (the 16-bit rows a workgroup stages in LDS). */
+/* host only: the tables are host memory.  W, H of sheet i for a window of `frames` frames; margins (nullable) [4]: left margin,
+ * right margin, plot width, the most curves of a panel.  A sheet that cannot be drawn: NPPC_EBADARG. */
+int nppc_curve_shape(const int* sheet, int nimg, const int* panel, int npanels, const int* curve, int ncurves, const int* stamp,
+                     int nstamps, int N, int T_frames, int i, int frames, long* W, long* H, int* margins);
+/* host only, serial: everything is host memory.  rng [npanels][2] fp32 (written: ymin, scale); meta [nimg][4] long: first pixel
+ * (given), W, H (written), pixels allowed (given; a sheet that needs more, or cannot be drawn, gets W = H = 0). */
+int nppc_curve_render_host(const float* values, int N, int T_frames, const int* sheet, int nimg, const int* panel, int npanels,
+                           const int* curve, int ncurves, const int* stamp, int nstamps, const int* win, int nitems, float* rng,
+                           long* meta, unsigned char* pix, long pix_elems);
+/* the same on the device: everything is device memory; pix 4-byte aligned and every image's first pixel a multiple of 4;
+ * max_panels: the most panels of a sheet (at most 64).  Three launches: layout, autoscale, render. */
+int nppc_curve_render(const float* values, int N, int T_frames, const int* sheet, int nimg, const int* panel, int npanels,
+                      const int* curve, int ncurves, const int* stamp, int nstamps, const int* win, int nitems, int max_panels,
+                      float* rng, long* meta, unsigned char* pix, long pix_elems, void* stream);
+/* nppc_curve_render, then nppc_png_encode of what it drew (ttab and tfirst laid out for the pixels allowed) */
+int nppc_curve_render_png(const float* values, int N, int T_frames, const int* sheet, int nimg, const int* panel, int npanels,
+                          const int* curve, int ncurves, const int* stamp, int nstamps, const int* win, int nitems, int max_panels,
+                          float* rng, long* meta, unsigned char* pix, long pix_elems, const int* ttab, const int* tfirst, long ntiles,
+                          const unsigned char* palette, int* plan, long* toff, long* stats, unsigned char* out, long out_cap,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
