@@ -299,6 +299,12 @@ SIGS = {
     "nppc_rec_windows": [P, L, P, I, P, I, I, P, P, P, P],
     "nppc_rec_splice": [P, L, P, P, I, P, L, L, I, I, I, P, P, P],
     "nppc_zero_runs": [P, L, L, P, L, P, I, P, P],
+    "nppc_enh_shape": [I, I, I, I, PI, PL],
+    "nppc_enh_gram": [P, L, L, I, I, I, I, P, P],
+    "nppc_enh_chain": [P, I, I, I, I, P, P, P, P, P],
+    "nppc_enh_splice": [P, L, P, L, L, I, I, I, L, P, I, P, P, P, P, L, P],
+    "nppc_enh_chain_host": [P, L, L, I, I, I, I, P, P, P, P],
+    "nppc_enh_splice_host": [P, L, P, L, L, I, I, I, L, P, I, P, P, P, P, L],
     "nppc_flac_probe": [P, L, P, P],
     "nppc_flac_decode_host": [P, L, P, L, P, L, P],
     "nppc_flac_work_elems": [L, PL],

@@ -812,6 +812,42 @@ int nppc_rec_splice(const float* wave, long L, const long* gaps, const long* win
 int nppc_zero_runs(const float* wave, long L, long min_len, long* work, long work_elems, long* runs, int cap, long* count,
                    void* stream);
 
+/* ---- whole-recording enhancement (csrc/enhance_core.h + csrc/enhance_rec.hip; specification
+ * tests/enhance_ref.py) ---------------------------------------------------------------------------------------------------
+ * A recording of L samples enhanced in n chunks of C samples (C even) at a hop of H = C / 2: chunk c is an enhanced waveform
+ * e_c = enh + c e_cs and K direction waveforms p_{c,k} = pcs + c p_cs + k p_ks (strides in elements, samples contiguous),
+ * 0 < L - (n - 1) H <= C.  The rule (boundary Gram, chain, splice) is stated once in csrc/enhance_core.h.
+ * Null pointers, n < 1, an odd C, negative strides: NPPC_EBADARG; K > NPPC_ENH_MAX_K: NPPC_EUNSUPPORTED; before any launch. */
+#define NPPC_ENH_MAX_K 16          /* directions */
+#define NPPC_ENH_MAX_SPLIT 64      /* workgroups that share one boundary's H samples */
+#define NPPC_ENH_TILE 1024         /* output samples per workgroup of nppc_enh_splice */
+#define NPPC_ENH_MATCH_GREEDY 0
+#define NPPC_ENH_MATCH_SIGN 1
+/* *S = the split nppc_enh_gram should run with (split = 0: chosen to fill the machine; split > 0: that value, clamped to
+ * 1 .. min(NPPC_ENH_MAX_SPLIT, H)) and *work_bytes = 8 (n - 1) S K (K + 2), its workspace.  Either may be null.  No GPU. */
+int nppc_enh_shape(int n, int K, int C, int split, int* S, long* work_bytes);
+/* work [n - 1][S][K (K + 2)] (fp64): workgroup s of boundary c (1 <= c < n) sums samples [s seg, (s + 1) seg), seg =
+ * ceil(H / S), of G[j][k] = sum p_{c-1,j}[H + i] p_{c,k}[i], na[j], nb[k] (G row-major, then na, then nb).  n >= 2. */
+int nppc_enh_gram(const float* pcs, long p_cs, long p_ks, int n, int K, int C, int S, double* work, void* stream);
+/* one workgroup: the S partials of every boundary summed in index order into gram [n - 1][K (K + 2)] (fp64), then the chain
+ * -> perm [n][K], sign [n][K] (int), continuity [n - 1][K] (fp64).  n = 1 writes the identity (work, continuity and gram
+ * may be null). */
+int nppc_enh_chain(const double* work, int n, int K, int S, int match, int* perm, int* sign, double* continuity, double* gram,
+                   void* stream);
+/* out [1 + K A][ldo] (ldo >= L): row 0 the enhanced recording, row 1 + s A + a slot s at alphas[a]; w [H] the fp32 table
+ * 0.5 - 0.5 cos(2 pi i / C); perm / sign [n][K] device tables (an entry of perm outside 0 .. K - 1 is clamped).  A = 0 or
+ * K = 0: the enhanced row alone (pcs, alphas, perm, sign may be null); n = 1: w may be null.  16-byte loads when H, the
+ * strides and the bases allow them, 16-byte stores when ldo % 4 == 0 and out is 16-byte aligned; the bits are the same. */
+int nppc_enh_splice(const float* enh, long e_cs, const float* pcs, long p_cs, long p_ks, int n, int K, int C, long L,
+                    const float* alphas, int A, const float* w, const int* perm, const int* sign, float* out, long ldo,
+                    void* stream);
+/* host only, serial, the same core: the Gram in ascending sample order and the chain (gram nullable) */
+int nppc_enh_chain_host(const float* pcs, long p_cs, long p_ks, int n, int K, int C, int match, int* perm, int* sign,
+                        double* continuity, double* gram);
+/* host only, serial, the same core: nppc_enh_splice on host pointers */
+int nppc_enh_splice_host(const float* enh, long e_cs, const float* pcs, long p_cs, long p_ks, int n, int K, int C, long L,
+                         const float* alphas, int A, const float* w, const int* perm, const int* sign, float* out, long ldo);
+
 /* ---- FLAC decoding (csrc/flac_core.h + csrc/flac.hip; specification tests/flac_ref.py) --------------
  * Every entry point returns NPPC_OK / an NPPC_E* code for its ARGUMENTS; what is wrong with a FILE is a per-file status: */
 #define NPPC_FLAC_OK 0
