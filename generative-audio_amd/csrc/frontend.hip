@@ -6,45 +6,12 @@
 //   decompress  mask.py:57-60;  mask application utils.py:241-249 -> :75-79 (real/imag swapped: conj(mask)*noisy)
 //   drop_band   audio_zen/acoustics/feature.py:254-285
 #include "common.h"
+#include "fft_core.h"
 #include "nppc_hip.h"
 
 #include <type_traits>
 
 namespace {
-
-// ---------------------------------------------------------------- radix-2 FFT in LDS, shared by STFT and iSTFT
-// tw[i] = exp(sign 2 pi i / N) and the periodic hann window, generated in fp64 -> fp32 once per workgroup
-template <int LOGN>
-__device__ __forceinline__ void fft_tables(float2* tw, float* win, double sign) {
-  constexpr int N = 1 << LOGN;
-  for (int i = threadIdx.x; i < N / 2; i += 256) {
-    double s, c;
-    sincospi(sign * 2.0 * i / N, &s, &c);
-    tw[i] = make_float2((float)c, (float)s);
-  }
-  for (int i = threadIdx.x; i < N; i += 256) win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / N));
-}
-
-// DIT butterfly stages over nfr rows loaded in bit-reversed order; ends on a barrier
-template <int LOGN>
-__device__ __forceinline__ void fft_stages(float2 (*buf)[(1 << LOGN) + 1], const float2* tw, int nfr) {
-  constexpr int N = 1 << LOGN;
-#pragma unroll 1
-  for (int s = 0; s < LOGN; ++s) {
-    const int half = 1 << s;
-    for (int e = threadIdx.x; e < nfr * (N / 2); e += 256) {
-      const int j = e / (N / 2), k = e % (N / 2);
-      const int grp = k >> s, pos = k & (half - 1);
-      const int i0 = (grp << (s + 1)) + pos, i1 = i0 + half;
-      const float2 w = tw[pos << (LOGN - 1 - s)];
-      const float2 a = buf[j][i0], c = buf[j][i1];
-      const float xr = c.x * w.x - c.y * w.y, xi = c.x * w.y + c.y * w.x;
-      buf[j][i0] = make_float2(a.x + xr, a.y + xi);
-      buf[j][i1] = make_float2(a.x - xr, a.y - xi);
-    }
-    __syncthreads();
-  }
-}
 
 // ---------------------------------------------------------------- STFT
 // One workgroup = FR consecutive frames of one clip.  Radix-2 DIT FFT in LDS (complex N points, imaginary input 0).
@@ -118,19 +85,16 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wav
 // ---------------------------------------------------------------- iSTFT
 // torch.istft(center=True, periodic hann, onesided input, length=L): y[p] = sum_t w[p - t*hop] x_t[p - t*hop] / sum_t w^2[p - t*hop],
 // x_t = irfft(X_t), p = n + N/2.  One workgroup = ISTFT_FR*hop consecutive output samples of one clip; it inverts the
-// ISTFT_FR + N/hop - 1 frames that overlap them (radix-2 in LDS on the Hermitian-extended spectrum).
+// ISTFT_FR + N/hop - 1 frames that overlap them (radix-2 in LDS on the Hermitian-extended spectrum; fft_core.h).
 // re / im [B][F][T], out [B][ld].  RAGGED: samples n < L_b = lengths[b] as torch.istft(length=L_b) of the item's own
 // T_b = 1 + L_b / hop frames (window envelope of those frames only), samples L_b <= n < ld written as 0.
-constexpr int ISTFT_FR = 4;
-
 template <int LOGN, bool RAGGED>
 __global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ re, const float* __restrict__ im,
                                                     float* __restrict__ out, long ld, const int* __restrict__ lengths, int T,
                                                     int hop) {
   constexpr int N = 1 << LOGN;
   constexpr int F = N / 2 + 1;
-  constexpr int MAXFR = ISTFT_FR + 7;            // supports hop >= N/8
-  __shared__ float2 buf[MAXFR][N + 1];
+  __shared__ float2 buf[ISTFT_MAXFR][N + 1];
   __shared__ float2 tw[N / 2];
   __shared__ float win[N];
   const int tid = threadIdx.x, b = blockIdx.y;
@@ -171,17 +135,7 @@ __global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ re
       out[(size_t)b * ld + nidx] = 0.f;
       continue;
     }
-    float num = 0.f, den = 0.f;
-    for (int j = 0; j < nfr; ++j) {
-      const int t = tfirst + j;
-      const int off = p - t * hop;
-      if (t >= 0 && t < Tb && off >= 0 && off < N) {
-        const float w = win[off];
-        num += w * buf[j][off].x * (1.0f / N);
-        den += w * w;
-      }
-    }
-    out[(size_t)b * ld + nidx] = den > 1e-11f ? num / den : 0.f;
+    out[(size_t)b * ld + nidx] = istft_ola<LOGN>(buf, win, p, tfirst, nfr, Tb, hop);
   }
 }
 
@@ -306,11 +260,6 @@ __global__ __launch_bounds__(256) void crm_mse_bwd_kernel(const float* __restric
     dcrm[o] = coef * (crm[o] - gr);
     dcrm[o + FoT] = coef * (crm[o + FoT] - gi);
   }
-}
-
-__device__ __forceinline__ float decompress_cirm(float m) {
-  m = fminf(fmaxf(m, -9.9f), 9.9f);
-  return -10.f * logf((10.f - m) / (10.f + m));
 }
 
 // crm [B][2][F][T] compressed -> dec [B][F][T][2] (optional), enhanced mag/re/im [B][F][T]

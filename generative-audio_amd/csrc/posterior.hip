@@ -1,0 +1,298 @@
+// Posterior samples from the NPPC directions (nppc_audio/posterior.py; specification
+// tests/posterior_ref.py): mask build, true complex product and centred inverse STFT of S samples per item in one launch.
+//
+// The rule.  pred_crm [B][2][F][T] compressed, w_mat [B][K][2][F][T], noisy re / im [B][F][T], z [B][S][K][2] (a real
+// and an imaginary coefficient per direction).  Sample s, bin (f, t), fp32, k ascending, every multiply and add of the
+// mask rounded on its own (post_mask below is compiled with contraction off):
+//   compressed:    mr = pred_r; mi = pred_i; for k: mr = mr + (zr_k wr_k - zi_k wi_k); mi = mi + (zr_k wi_k + zi_k wr_k);
+//                  Mr = decompress_cirm(mr); Mi = decompress_cirm(mi)
+//   decompressed:  Mr = decompress_cirm(pred_r); Mi = decompress_cirm(pred_i);
+//                  for k: Mr = Mr + (zr_k D(wr_k) - zi_k D(wi_k)); Mi = Mi + (zr_k D(wi_k) + zi_k D(wr_k)),  D = decompress_cirm
+// then X = M * noisy by cirm_apply_true (the operations decompress_apply_kernel compiles to, conj_mask = 0) and the inverse
+// STFT of istft_kernel: the transform, the overlap-add and the ragged rule are the shared code of fft_core.h.
+//
+// One workgroup = one block of ISTFT_FR * hop output samples of one item (blockIdx.x, blockIdx.y) and one tile of
+// consecutive samples s (blockIdx.z), which it runs one after the other through the one LDS transform buffer.
+#include "common.h"
+#include "fft_core.h"
+#include "nppc_hip.h"
+
+#include <type_traits>
+
+namespace {
+
+constexpr int POST_TILE = NPPC_POST_TILE;
+constexpr int POST_MAX_K = NPPC_POST_MAX_K;
+
+struct PostArgs {
+  const float* pred;
+  const float* w;
+  const float* re;
+  const float* im;
+  const float* z;
+  const int* lengths;          // null: every item is ld samples long
+  float* samples;              // [B][S][ld] or null
+  double2* tpart;              // [tiles][B][ld] (sum y, sum y^2) or null
+  double2* mpart;              // [tiles][B][F][T] (sum |X|, sum |X|^2) or null
+  long ld;
+  int K, S, T, hop, spt, domain;
+};
+
+// mask * noisy, the true complex product, and the magnitude of the result, with the fused multiply-adds that
+// decompress_apply_kernel (frontend.hip, conj_mask = 0) compiles to spelled out: left to the compiler, the contraction of
+// these sums depends on the code around them, and the sampler at z = 0 has to give that kernel's bits (the tests hold the
+// two together).
+__device__ __forceinline__ void cirm_apply_true(float mr, float mi, float a, float c, float* xr, float* xi) {
+  *xr = __builtin_fmaf(mr, a, -(mi * c));
+  *xi = __builtin_fmaf(mr, c, mi * a);
+}
+__device__ __forceinline__ float spec_mag(float xr, float xi) { return sqrtf(__builtin_fmaf(xr, xr, xi * xi)); }
+
+// the sampled mask of one bin.  pr / pi: the restoration's compressed mask; wr / wi: direction k at wr[k * wstride];
+// z: this sample's K (real, imaginary) pairs.
+__device__ __forceinline__ void post_mask(float pr, float pi, const float* __restrict__ wr, const float* __restrict__ wi,
+                                          size_t wstride, const float* __restrict__ z, int K, int domain, float* Mr,
+                                          float* Mi) {
+#pragma clang fp contract(off)
+  float mr, mi;
+  if (domain == NPPC_POST_COMPRESSED) {
+    mr = pr;
+    mi = pi;
+    for (int k = 0; k < K; ++k) {
+      const float zr = z[2 * k], zi = z[2 * k + 1];
+      const float a = wr[k * wstride], c = wi[k * wstride];
+      const float t0 = zr * a, t1 = zi * c, t2 = zr * c, t3 = zi * a;
+      const float dr = t0 - t1, di = t2 + t3;
+      mr = mr + dr;
+      mi = mi + di;
+    }
+    mr = decompress_cirm(mr);
+    mi = decompress_cirm(mi);
+  } else {
+    mr = decompress_cirm(pr);
+    mi = decompress_cirm(pi);
+    for (int k = 0; k < K; ++k) {
+      const float zr = z[2 * k], zi = z[2 * k + 1];
+      const float a = decompress_cirm(wr[k * wstride]), c = decompress_cirm(wi[k * wstride]);
+      const float t0 = zr * a, t1 = zi * c, t2 = zr * c, t3 = zi * a;
+      const float dr = t0 - t1, di = t2 + t3;
+      mr = mr + dr;
+      mi = mi + di;
+    }
+  }
+  *Mr = mr;
+  *Mi = mi;
+}
+
+template <int LOGN, bool STATS>
+__global__ __launch_bounds__(256) void post_sample_kernel(PostArgs a) {
+  constexpr int N = 1 << LOGN;
+  constexpr int F = N / 2 + 1;
+  constexpr int OPT = (ISTFT_FR * N + 255) / 256;      // output samples a thread owns at most (hop <= N)
+  constexpr int MPT = (ISTFT_FR * F + 255) / 256;      // bins of the workgroup's own frames a thread owns at most
+  __shared__ float2 buf[ISTFT_MAXFR][N + 1];
+  __shared__ float2 tw[N / 2];
+  __shared__ float win[N];
+  const int tid = threadIdx.x, b = blockIdx.y, B = gridDim.y, tile = blockIdx.z;
+  const int T = a.T, hop = a.hop, K = a.K, S = a.S;
+  const long ld = a.ld;
+  const int L = a.lengths ? clampi(a.lengths[b], 0, (int)ld) : (int)ld;
+  const int Tb = min(1 + L / hop, T);
+  const int ov = N / hop;                              // frames overlapping one sample
+  const int nfr = ISTFT_FR + ov - 1;
+  const int p0 = blockIdx.x * ISTFT_FR * hop;          // first padded-coordinate sample of this block
+  const int tfirst = p0 / hop - (ov - 1);              // first frame that can touch [p0, p0 + FR*hop)
+  const int town = tfirst + ov - 1;                    // the ISTFT_FR frames this workgroup owns: town .. town + FR - 1
+  const int s0 = tile * a.spt, s1 = min(S, s0 + a.spt);
+  const size_t FT = (size_t)F * T;
+  const bool dead = p0 - N / 2 >= L && town >= Tb;     // nothing of the item reaches this block
+
+  double sy[OPT], syy[OPT], sm[MPT], smm[MPT];
+#pragma unroll
+  for (int i = 0; i < OPT; ++i) sy[i] = syy[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < MPT; ++i) sm[i] = smm[i] = 0.0;
+
+  if (!dead) {
+    fft_tables<LOGN>(tw, win, 1.0);                    // inverse transform: +i
+    const float* pred_r = a.pred + (size_t)b * 2 * FT;
+    const float* w_r = a.w + (size_t)b * K * 2 * FT;
+    const float* n_re = a.re + (size_t)b * FT;
+    const float* n_im = a.im + (size_t)b * FT;
+    // bin f of frame row j of sample s into the transform buffer, Hermitian-extended; returns |X|
+    auto build = [&](const float* zs, int j, int f) -> float {
+      const int t = tfirst + j;
+      float xr = 0.f, xi = 0.f;
+      if (t >= 0 && t < Tb) {
+        const size_t o = (size_t)f * T + t;
+        float Mr, Mi;
+        post_mask(pred_r[o], pred_r[FT + o], w_r + o, w_r + FT + o, 2 * FT, zs, K, a.domain, &Mr, &Mi);
+        cirm_apply_true(Mr, Mi, n_re[o], n_im[o], &xr, &xi);
+      }
+      const bool edge = f == 0 || f == N / 2;          // irfft ignores the imaginary part of DC / Nyquist
+      buf[j][__brev((unsigned)f) >> (32 - LOGN)] = make_float2(xr, edge ? 0.f : xi);
+      if (!edge) buf[j][__brev((unsigned)(N - f)) >> (32 - LOGN)] = make_float2(xr, -xi);
+      return spec_mag(xr, xi);
+    };
+    for (int s = s0; s < s1; ++s) {
+      const float* zs = a.z + ((size_t)b * S + s) * K * 2;
+      __syncthreads();                                 // tables written / the last sample's overlap-add has read buf
+      // the workgroup's own frames, frame fastest (T is the contiguous axis of the planes), then the ov - 1 before them
+#pragma unroll
+      for (int i = 0; i < MPT; ++i) {
+        const int e = tid + i * 256;
+        if (e < ISTFT_FR * F) {
+          const float m = build(zs, ov - 1 + e % ISTFT_FR, e / ISTFT_FR);
+          if (STATS) {
+            sm[i] += (double)m;
+            smm[i] += (double)m * (double)m;
+          }
+        }
+      }
+      for (int e = tid; e < (ov - 1) * F; e += 256) build(zs, e % (ov - 1), e / (ov - 1));
+      __syncthreads();
+      fft_stages<LOGN>(buf, tw, nfr);
+#pragma unroll
+      for (int i = 0; i < OPT; ++i) {
+        const int e = tid + i * 256;
+        const int p = p0 + e, nidx = p - N / 2;
+        if (e >= ISTFT_FR * hop || nidx < 0 || nidx >= ld) continue;
+        const float y = nidx < L ? istft_ola<LOGN>(buf, win, p, tfirst, nfr, Tb, hop) : 0.f;
+        if (a.samples) a.samples[((size_t)b * S + s) * ld + nidx] = y;
+        if (STATS) {
+          sy[i] += (double)y;
+          syy[i] += (double)y * (double)y;
+        }
+      }
+    }
+  } else if (a.samples) {
+    for (int s = s0; s < s1; ++s)
+      for (int e = tid; e < ISTFT_FR * hop; e += 256) {
+        const int nidx = p0 + e - N / 2;
+        if (nidx >= 0 && nidx < ld) a.samples[((size_t)b * S + s) * ld + nidx] = 0.f;
+      }
+  }
+  if (!STATS) return;
+  // this tile's partial sums (zeros where the item has ended: the sums above never left 0 there)
+  if (a.tpart) {
+#pragma unroll
+    for (int i = 0; i < OPT; ++i) {
+      const int e = tid + i * 256;
+      const int nidx = p0 + e - N / 2;
+      if (e < ISTFT_FR * hop && nidx >= 0 && nidx < ld)
+        a.tpart[((size_t)tile * B + b) * ld + nidx] = make_double2(sy[i], syy[i]);
+    }
+  }
+  if (a.mpart) {
+#pragma unroll
+    for (int i = 0; i < MPT; ++i) {
+      const int e = tid + i * 256;
+      const int t = town + e % ISTFT_FR, f = e / ISTFT_FR;
+      if (e < ISTFT_FR * F && t < T) a.mpart[((size_t)tile * B + b) * FT + (size_t)f * T + t] = make_double2(sm[i], smm[i]);
+    }
+  }
+}
+
+// the tiles' partial sums folded in tile order -> mean, unbiased standard deviation.  part [tiles][n], out [n].
+__global__ __launch_bounds__(256) void post_finish_kernel(const double2* __restrict__ part, size_t n, int tiles, int S,
+                                                          float* __restrict__ mean, float* __restrict__ sd) {
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int t = 0; t < tiles; ++t) {
+      const double2 v = part[(size_t)t * n + e];
+      s1 += v.x;
+      s2 += v.y;
+    }
+    const double var = (s2 - s1 * s1 / S) / (S - 1);
+    mean[e] = (float)(s1 / S);
+    sd[e] = (float)sqrt(var > 0.0 ? var : 0.0);
+  }
+}
+
+bool post_config_ok(int nfft, int hop) {
+  return (nfft == 64 || nfft == 128 || nfft == 256 || nfft == 512) && hop > 0 && nfft % hop == 0 && nfft / hop <= 8;
+}
+
+// blocks along x: every output sample and every frame has an owner
+int post_blocks(int T, int nfft, int hop, long ld) {
+  const int by_samples = ceil_div(ld + nfft / 2, (long)ISTFT_FR * hop), by_frames = ceil_div(T, ISTFT_FR);
+  return by_samples > by_frames ? by_samples : by_frames;
+}
+
+int post_shape(int B, int S, int K, int T, int nfft, int hop, long ld, int stats, int* tiles, int* spt, long* work_bytes) {
+  if (B <= 0 || B > 65535 || S < 1 || K < 0 || K > POST_MAX_K || T <= 0 || ld <= 0 || ld > 0x7fffffffL - nfft ||
+      !post_config_ok(nfft, hop) || (stats & ~3))
+    return NPPC_EBADARG;
+  if (stats && (S < 2 || S > NPPC_POST_MAX_STAT_S)) return NPPC_EBADARG;
+  long nt = ceil_div(S, POST_TILE);
+  if (stats) {                                         // partial sums cost memory per tile: only as many as fill the chip
+    long fill = ceil_div(NPPC_POST_FILL, (long)B * post_blocks(T, nfft, hop, ld));
+    fill = fill < 1 ? 1 : (fill > NPPC_POST_MAX_STAT_TILES ? NPPC_POST_MAX_STAT_TILES : fill);
+    nt = nt < fill ? nt : fill;
+  }
+  const int per = ceil_div(S, nt);
+  nt = ceil_div(S, per);
+  if (nt > 65535) return NPPC_EBADARG;
+  if (tiles) *tiles = (int)nt;
+  if (spt) *spt = per;
+  if (work_bytes) {
+    const long F = nfft / 2 + 1;
+    *work_bytes = 16 * nt * B * (((stats & 1) ? ld : 0) + ((stats & 2) ? F * T : 0));
+  }
+  return NPPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nppc_post_sample_shape(int B, int S, int K, int T, int nfft, int hop, long ld, int stats, int* tiles, int* tile_samples,
+                           long* work_bytes) {
+  return post_shape(B, S, K, T, nfft, hop, ld, stats, tiles, tile_samples, work_bytes);
+}
+
+int nppc_post_sample(const float* pred_crm, const float* w_mat, const float* re, const float* im, const float* z,
+                     const int* lengths, int domain, int B, int S, int K, int T, int nfft, int hop, long ld, float* samples,
+                     float* mean, float* std, float* mag_mean, float* mag_std, double* work, long work_bytes, void* stream) {
+  if (!pred_crm || !re || !im || (K > 0 && (!w_mat || !z)) || (!mean) != (!std) || (!mag_mean) != (!mag_std) ||
+      (domain != NPPC_POST_COMPRESSED && domain != NPPC_POST_DECOMPRESSED))
+    return NPPC_EBADARG;
+  const int stats = (mean ? 1 : 0) | (mag_mean ? 2 : 0);
+  if (!samples && !stats) return NPPC_EBADARG;
+  int tiles, spt;
+  long need;
+  const int rc = post_shape(B, S, K, T, nfft, hop, ld, stats, &tiles, &spt, &need);
+  if (rc != NPPC_OK) return rc;
+  if (stats && (!work || work_bytes < need || ((uintptr_t)work & 15))) return NPPC_EBADARG;
+  const long F = nfft / 2 + 1;
+  PostArgs a;
+  a.pred = pred_crm, a.w = w_mat, a.re = re, a.im = im, a.z = z, a.lengths = lengths, a.samples = samples;
+  a.tpart = mean ? (double2*)work : nullptr;
+  a.mpart = mag_mean ? (double2*)work + (mean ? (size_t)tiles * B * ld : 0) : nullptr;
+  a.ld = ld, a.K = K, a.S = S, a.T = T, a.hop = hop, a.spt = spt, a.domain = domain;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(post_blocks(T, nfft, hop, ld), B, tiles);
+  auto launch = [&](auto logn) {
+    if (stats)
+      hipLaunchKernelGGL((post_sample_kernel<decltype(logn)::value, true>), grid, dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((post_sample_kernel<decltype(logn)::value, false>), grid, dim3(256), 0, st, a);
+  };
+  switch (nfft) {
+    case 64: launch(std::integral_constant<int, 6>()); break;
+    case 128: launch(std::integral_constant<int, 7>()); break;
+    case 256: launch(std::integral_constant<int, 8>()); break;
+    default: launch(std::integral_constant<int, 9>()); break;
+  }
+  NPPC_CHECK_LAUNCH();
+  auto finish = [&](const double2* part, size_t n, float* m, float* s) {
+    size_t g = (n + 255) / 256;
+    hipLaunchKernelGGL(post_finish_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, st, part, n, tiles, S, m, s);
+  };
+  if (mean) finish(a.tpart, (size_t)B * ld, mean, std);
+  if (mag_mean) finish(a.mpart, (size_t)B * F * T, mag_mean, mag_std);
+  NPPC_CHECK_LAUNCH();
+  return NPPC_OK;
+}
+
+}  // extern "C"

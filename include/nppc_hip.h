@@ -848,6 +848,39 @@ int nppc_enh_chain_host(const float* pcs, long p_cs, long p_ks, int n, int K, in
 int nppc_enh_splice_host(const float* enh, long e_cs, const float* pcs, long p_cs, long p_ks, int n, int K, int C, long L,
                          const float* alphas, int A, const float* w, const int* perm, const int* sign, float* out, long ldo);
 
+/* ---- posterior samples from the NPPC directions (csrc/posterior.hip; specification
+ * tests/posterior_ref.py) ------------------------------------------------------------------------------------------------
+ * pred_crm [B][2][F][T] compressed cIRM, w_mat [B][K][2][F][T] directions, noisy re / im [B][F][T], z [B][S][K][2] a real and
+ * an imaginary coefficient per sample and direction.  Sample s is the centred inverse STFT (periodic hann, nppc_istft's
+ * rules) of mask_s * noisy, with, in fp32, k ascending, every multiply and add rounded on its own,
+ *   NPPC_POST_COMPRESSED:    mask_s = decompress(pred + sum_k z_sk w_k)           (complex z w, each part decompressed)
+ *   NPPC_POST_DECOMPRESSED:  mask_s = decompress(pred) + sum_k z_sk decompress(w_k)
+ * lengths (nullable) [B]: item b uses its first 1 + L_b / hop frames and is 0 in samples L_b .. ld - 1, as
+ * nppc_istft_ragged.  nfft in {64, 128, 256, 512}, nfft % hop == 0, nfft / hop <= 8, 0 <= K <= NPPC_POST_MAX_K,
+ * S >= 1; anything else NPPC_EBADARG before any launch.  No atomics: the same bits from run to run, an item of a batch equals
+ * the item alone and a sample does not depend on S. */
+#define NPPC_POST_MAX_K 16             /* directions */
+#define NPPC_POST_TILE 8               /* samples one workgroup runs when no statistics are asked for */
+#define NPPC_POST_MAX_STAT_S 4096      /* most samples when statistics are asked for */
+#define NPPC_POST_MAX_STAT_TILES 32    /* most sample tiles when statistics are asked for */
+#define NPPC_POST_FILL 1024            /* workgroups that count as a full machine */
+#define NPPC_POST_COMPRESSED 0
+#define NPPC_POST_DECOMPRESSED 1
+/* stats: bit 0 the time-domain mean / std, bit 1 the magnitude mean / std (then 2 <= S <= NPPC_POST_MAX_STAT_S).  With
+ * nblk = max(ceil((ld + nfft / 2) / (4 hop)), ceil(T / 4)) workgroups per item and sample tile:
+ *   n = ceil(S / NPPC_POST_TILE); stats: n = min(n, clamp(ceil(NPPC_POST_FILL / (B nblk)), 1, NPPC_POST_MAX_STAT_TILES));
+ *   *tile_samples = ceil(S / n), *tiles = ceil(S / *tile_samples) (gridDim.z),
+ *   *work_bytes = 16 *tiles B ((stats & 1 ? ld : 0) + (stats & 2 ? F T : 0)).  Each output may be null.  No GPU. */
+int nppc_post_sample_shape(int B, int S, int K, int T, int nfft, int hop, long ld, int stats, int* tiles, int* tile_samples,
+                           long* work_bytes);
+/* Outputs, each nullable (mean with std, mag_mean with mag_std; at least one output): samples [B][S][ld]; mean, std [B][ld]
+ * over s of the samples; mag_mean, mag_std [B][F][T] over s of |X_s| = sqrtf(xr^2 + xi^2) (0 in frames past an item's end).
+ * The statistics are fp64 sums of y and y^2 per sample tile (work, 16-byte aligned, work_bytes as above), folded in tile order
+ * by a finishing launch: mean = sum / S, std = sqrt(max(0, (sum y^2 - (sum y)^2 / S) / (S - 1))), rounded to fp32 once. */
+int nppc_post_sample(const float* pred_crm, const float* w_mat, const float* re, const float* im, const float* z,
+                     const int* lengths, int domain, int B, int S, int K, int T, int nfft, int hop, long ld, float* samples,
+                     float* mean, float* std, float* mag_mean, float* mag_std, double* work, long work_bytes, void* stream);
+
 /* ---- FLAC decoding (csrc/flac_core.h + csrc/flac.hip; specification tests/flac_ref.py) --------------
  * Every entry point returns NPPC_OK / an NPPC_E* code for its ARGUMENTS; what is wrong with a FILE is a per-file status: */
 #define NPPC_FLAC_OK 0
