@@ -145,6 +145,30 @@ template <typename T, int BN> struct NtStage {
 };
 
 // ------------------------------------------------------------------------------------------------ main loops
+// The MFMAs of one stage image `ta` ([A rows | B rows]) for wave (wm, wn): its 64 x BN/2 tile, k-steps in ascending order.
+template <typename T, int BN>
+__device__ __forceinline__ void nt_lds_stage_mma(f32x4 (&acc)[4][BN / 32], const unsigned char* ta, int wm, int wn, int n, int q,
+                                                 int relu_in) {
+  typedef typename Frag<T>::type frag;
+  constexpr int KS = (128 / (int)sizeof(T)) / 32;   // 32-wide MFMA k-steps per stage
+  constexpr int NJ = BN / 32;                       // 16-column MFMA tiles per wave
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    frag af[4], bf[NJ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      af[i] = lds_frag<T>(ta, wm * 64 + 16 * i + n, ks, q);
+      if (relu_in) af[i] = relu_frag<T>(af[i]);
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bf[j] = lds_frag<T>(ta + 128 * 128, wn * (BN / 2) + 16 * j + n, ks, q);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = mma16(af[i], bf[j], acc[i][j]);
+  }
+}
+
 // LDS-staged NT main loop: 256 threads = 2 x 2 waves, block tile 128 x BN (wave tile 64 x BN/2), 128-byte K slices per stage,
 // double-buffered LDS (lds: 2 * (128 + BN) * 128 bytes) with register staging (the next stage's global loads are issued before
 // the MFMAs and written to LDS after them), one barrier per stage.  Operand tiles are read from HBM/L2 once per workgroup.
@@ -154,9 +178,7 @@ template <typename T, int BN> struct NtStage {
 template <typename T, int BN, typename I, typename AOf, typename BOf>
 __device__ __forceinline__ void nt_lds_mainloop(f32x4 (&acc)[4][BN / 32], unsigned char* lds, I nstage, long lda, long ldb,
                                                 AOf a_of, BOf b_of, int relu_in) {
-  typedef typename Frag<T>::type frag;
-  constexpr int KS = (128 / (int)sizeof(T)) / 32;   // 32-wide MFMA k-steps per stage
-  constexpr int NJ = BN / 32;                       // 16-column MFMA tiles per wave
+  constexpr int NJ = BN / 32;
   constexpr int STAGE = (128 + BN) * 128;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, q = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
@@ -180,23 +202,48 @@ __device__ __forceinline__ void nt_lds_mainloop(f32x4 (&acc)[4][BN / 32], unsign
       const T* pa = a_of(s + 1);
       st.load(pa, lda, b_of(s + 1), ldb);
     }
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      frag af[4], bf[NJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        af[i] = lds_frag<T>(ta, wm * 64 + 16 * i + n, ks, q);
-        if (relu_in) af[i] = relu_frag<T>(af[i]);
-      }
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bf[j] = lds_frag<T>(ta + 128 * 128, wn * (BN / 2) + 16 * j + n, ks, q);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = mma16(af[i], bf[j], acc[i][j]);
-    }
+    nt_lds_stage_mma<T, BN>(acc, ta, wm, wn, n, q, relu_in);
     if (s + 1 < nstage) st.store(lds + (buf ^ 1) * STAGE + soff);
     __syncthreads();
+  }
+}
+
+// nt_lds_mainloop with ONE stage image in LDS ((128 + BN) * 128 bytes): the next stage's global loads are issued before the
+// MFMAs as there, the MFMAs read the image, then barrier, staging registers -> the same image, barrier.  The image, the
+// fragment reads, the MFMA order and the functor contract are those of nt_lds_mainloop, so every accumulator is bit-identical
+// to its; half the LDS buys a third or fourth workgroup per CU (more operand bytes in flight) for one more barrier per stage.
+// Ends with a barrier as well.
+template <typename T, int BN, typename I, typename AOf, typename BOf>
+__device__ __forceinline__ void nt_lds_mainloop_1buf(f32x4 (&acc)[4][BN / 32], unsigned char* lds, I nstage, long lda, long ldb,
+                                                     AOf a_of, BOf b_of, int relu_in) {
+  constexpr int NJ = BN / 32;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, q = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int srow = tid >> 3, sc = tid & 7;
+  const int soff = srow * 128 + ((sc ^ (srow & 7)) << 4);
+  NtStage<T, BN> st;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  {
+    const T* pa = a_of((I)0);
+    st.load(pa, lda, b_of((I)0), ldb);
+  }
+  st.store(lds + soff);
+  __syncthreads();
+  for (I s = 0; s < nstage; ++s) {
+    const bool more = s + 1 < nstage;
+    if (more) {
+      const T* pa = a_of(s + 1);
+      st.load(pa, lda, b_of(s + 1), ldb);
+    }
+    nt_lds_stage_mma<T, BN>(acc, lds, wm, wn, n, q, relu_in);
+    __syncthreads();
+    if (more) {
+      st.store(lds + soff);
+      __syncthreads();
+    }
   }
 }
 
@@ -276,8 +323,10 @@ template <typename T, int EPI> struct NtEpilogue {
   // the additive term of column `col` (0 in padding columns)
   __device__ __forceinline__ float col_bias(int col) const {
     const bool cvalid = col < g.Nv;
-    float bv = (bias && cvalid) ? bias[col] : 0.f;
-    if (EPI == EPI_RESIDUAL_GN && cvalid) bv -= gn_mr * gnv[col];
+    const int cl = cvalid ? col : 0;        // padding columns: read column 0, select 0 (no divergent branch around the loads)
+    float bv = bias ? bias[cl] : 0.f;
+    if (EPI == EPI_RESIDUAL_GN) bv -= gn_mr * gnv[cl];
+    if (!cvalid) bv = 0.f;
     return bv;
   }
   __device__ __forceinline__ float act(float a, float bv) const {
@@ -287,8 +336,10 @@ template <typename T, int EPI> struct NtEpilogue {
     return v;
   }
   // accumulator-layout store of element (row, col); returns the STORED (rounded) value
-  __device__ __forceinline__ float put(float a, float bv, int row, int col) const {
-    const bool valid = col < g.Nv && (row % g.Tp) < g.Tv;
+  __device__ __forceinline__ float put(float a, float bv, int row, int col) const { return put(a, bv, row, col, (row % g.Tp) < g.Tv); }
+  // ... for a caller that knows whether `row` is a valid frame (rvalid) without dividing
+  __device__ __forceinline__ float put(float a, float bv, int row, int col, bool rvalid) const {
+    const bool valid = col < g.Nv && rvalid;
     float v = act(a, bv);
     if (EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_GN) v += to_f32<T>(res[(size_t)row * g.ldres + col]);
     if (EPI == EPI_MASK_POS) {

@@ -58,14 +58,26 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs g) {
   }
 }
 
+// Workgroups per CU that gemm_nt_lds_kernel<T, EPI, BN> is compiled for.  bf16 keeps ONE stage image in LDS (nt_lds_mainloop_1buf:
+// 24 / 32 KB at BN = 64 / 128), so LDS allows 4 / 3; the register budget that goes with it (128 / 168 VGPRs) is asked for only
+// where the instantiation meets it without spilling (profiles/nt_occupancy_alone.txt).  fp32, the parity mode, keeps the
+// double-buffered loop at 2.
+template <typename T, int EPI, int BN> constexpr int nt_lds_wg_per_cu() {
+  if (sizeof(T) != 2) return 2;
+  if (BN == 64) return 4;                   // 92 - 118 VGPRs
+  // BN = 128: 140 - 165 VGPRs; the residual / mask epilogues (no launch of the training step) spill 1 - 7 registers at 168
+  return (EPI == EPI_RESIDUAL || EPI == EPI_MASK_POS || EPI == EPI_RESIDUAL_GN) ? 2 : 3;
+}
+
 // LDS-staged variant of gemm_nt_kernel (same arguments and epilogues) for K-slices that are multiples of the 128-byte
-// stage (64 bf16 / 32 f32): 256 threads = 2 x 2 waves, block tile 128 x BN (nt_lds_mainloop).
+// stage (64 bf16 / 32 f32): 256 threads = 2 x 2 waves, block tile 128 x BN (nt_lds_mainloop; bf16: nt_lds_mainloop_1buf).
 template <typename T, int EPI, int BN>
-__global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256, (nt_lds_wg_per_cu<T, EPI, BN>())) void gemm_nt_lds_kernel(GemmArgs g) {
   constexpr int EPC = 16 / (int)sizeof(T);
   constexpr int BK = 8 * EPC;
   constexpr int NJ = BN / 32;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][(128 + BN) * 128];
+  constexpr int NBUF = sizeof(T) == 2 ? 1 : 2;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[NBUF][(128 + BN) * 128];
   __shared__ double red[2][4];
   const int ks_ = g.ksplit > 1 ? g.ksplit : 1;
   const int z = blockIdx.z / ks_, ksl = blockIdx.z % ks_;
@@ -82,10 +94,15 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
   // inline-asm LDS-DMA ring of gemm_tn_dma_kernel, not built.
   const int nstage = g.K / BK;
   f32x4 acc[4][NJ];
-  nt_lds_mainloop<T, BN>(acc, &lds[0][0], nstage, g.lda, g.ldb, [&](int s) { return ga + s * BK; }, [&](int s) { return gb + s * BK; },
-                         g.relu_in);
+  if constexpr (NBUF == 1)
+    nt_lds_mainloop_1buf<T, BN>(acc, &lds[0][0], nstage, g.lda, g.ldb, [&](int s) { return ga + s * BK; },
+                                [&](int s) { return gb + s * BK; }, g.relu_in);
+  else
+    nt_lds_mainloop<T, BN>(acc, &lds[0][0], nstage, g.lda, g.ldb, [&](int s) { return ga + s * BK; }, [&](int s) { return gb + s * BK; },
+                           g.relu_in);
   // ---- epilogue (identical to gemm_nt_kernel): element (row m0 + wm*64 + 16 i + 4 q + r, col n0 + wn*BN/2 + 16 j + n)
   const NtEpilogue<T, EPI> ep(g, z, m0);
+  const int tp0 = m0 % g.Tp;                    // Tp % 128 == 0: row % Tp = tp0 + the row's index in the tile, no per-lane division
   constexpr bool HAS_RES = EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_GN || EPI == EPI_MASK_POS;
   // round 4: the plain / PReLU + statistics / ReLU epilogues take the same coalesced route (conv1x1 forward, dA2 of the backward,
   // the fc layer: 64 two-byte stores per lane were 12-15 of a launch's 38 us, profiles/r04_nt_variants.txt)
@@ -98,44 +115,60 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
       // residual came in as 32 dependent 2-byte gathers per lane AFTER the K loop (19 of the sconv product's 59 us) and the
       // output left the same way.  Here the tile goes through the LDS operand buffers (free after the loop) as fp32, row stride
       // BN + 4 words (the four row groups of a wave land on four different bank quarters), and comes back as 16-byte chunks of
-      // a row: ONE 16-byte residual load and ONE 16-byte store per 8 outputs.
+      // a row: ONE 16-byte residual load and ONE 16-byte store per 8 outputs.  The buffers hold ROWS rows of it at a time:
+      // 128 / ROWS passes (fp32: 1 at BN = 64, 2 at 128; bf16 with its single stage image: 2 at BN = 64, 4 at 128).
       constexpr int LD = BN + 4, VE = 8, CPR = BN / VE;
-      constexpr int HALVES = (128 * LD * 4 <= (int)sizeof(lds)) ? 1 : 2;   // BN = 128: two passes of 64 rows
-      constexpr int ROWS = 128 / HALVES;
+      constexpr int ROWS = 128 * LD * 4 <= (int)sizeof(lds) ? 128 : 64 * LD * 4 <= (int)sizeof(lds) ? 64 : 32;
+      constexpr int PASSES = 128 / ROWS;
+      // a thread takes chunks tid, tid + 256, ... of a pass: a whole number of them per pass, so the rows and the chunk column
+      // it sees, and with them the order in which csum adds, do not depend on the number of passes
+      static_assert(ROWS * LD * 4 <= (int)sizeof(lds) && (ROWS * CPR) % 256 == 0 && 256 % CPR == 0, "epilogue passes");
       float* ot = reinterpret_cast<float*>(&lds[0][0]);
       float csum[VE];
       float t1 = 0.f, t2 = 0.f;                 // EPI_PRELU_STATS: sums of the stored (rounded) activations
 #pragma unroll
       for (int e = 0; e < VE; ++e) csum[e] = 0.f;
-      for (int h = 0; h < HALVES; ++h) {
-        if (HALVES == 1 || wm == h) {
+      // the activation in place, all of the tile before the first pass: t1 / t2 keep the per-lane order (j, i, r) of the
+      // unstaged epilogue whatever the number of passes
 #pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            const int col = n0 + wn * (BN / 2) + 16 * j + n;
-            const bool cvalid = col < g.Nv;
-            const float bv = ep.col_bias(col);
+      for (int j = 0; j < NJ; ++j) {
+        const int col = n0 + wn * (BN / 2) + 16 * j + n;
+        const bool cvalid = col < g.Nv;
+        const float bv = ep.col_bias(col);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float pv = ep.act(acc[i][j][r], bv);
-                ot[((HALVES == 1 ? wm * 64 : 0) + 16 * i + 4 * q + r) * LD + wn * (BN / 2) + 16 * j + n] = pv;
-                if (EPI == EPI_PRELU_STATS) {
-                  // statistics of the stored (rounded, masked) activations, summed per lane in the accumulator layout and in
-                  // the order of the unstaged epilogue: the GroupNorm statistics stay bit-identical to rounds 1-3
-                  const int row = m0 + wm * 64 + 16 * i + 4 * q + r;
-                  const float vo = (cvalid && (row % g.Tp) < g.Tv) ? to_f32<T>(from_f32<T>(pv)) : 0.f;
-                  t1 += vo;
-                  t2 += vo * vo;
-                }
-              }
+          for (int r = 0; r < 4; ++r) {
+            const float pv = ep.act(acc[i][j][r], bv);
+            acc[i][j][r] = pv;
+            if (EPI == EPI_PRELU_STATS) {
+              // statistics of the stored (rounded, masked) activations, summed per lane in the accumulator layout and in
+              // the order of the unstaged epilogue: the GroupNorm statistics stay bit-identical to rounds 1-3
+              // (masked by bits, not by a branch around the rounding: 64 divergent branches cost this epilogue its registers)
+              const unsigned keep = (cvalid && tp0 + wm * 64 + 16 * i + 4 * q + r < g.Tv) ? ~0u : 0u;
+              const float vo = __uint_as_float(__float_as_uint(to_f32<T>(from_f32<T>(pv))) & keep);
+              t1 += vo;
+              t2 += vo * vo;
+            }
           }
+      }
+#pragma unroll
+      for (int h = 0; h < PASSES; ++h) {
+        // pass h = tile rows [h ROWS, (h + 1) ROWS): 16-row groups i of wave row wm with 4 wm + i in [h ROWS / 16, (h + 1) ROWS / 16)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if ((wm * 4 + i) / (ROWS / 16) != h) continue;
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              ot[(wm * 64 + 16 * i + 4 * q + r - h * ROWS) * LD + wn * (BN / 2) + 16 * j + n] = acc[i][j][r];
         }
         __syncthreads();
         for (int c = tid; c < ROWS * CPR; c += 256) {
           const int rl = c / CPR, cc = (c % CPR) * VE;
-          const int row = m0 + h * ROWS * (HALVES - 1) + rl, col = n0 + cc;
-          const bool rvalid = (row % g.Tp) < g.Tv;
+          const int row = m0 + h * ROWS + rl, col = n0 + cc;
+          const bool rvalid = tp0 + h * ROWS + rl < g.Tv;
           float v[VE], rv[VE];
           const float4 lo = *reinterpret_cast<const float4*>(ot + rl * LD + cc), hi = *reinterpret_cast<const float4*>(ot + rl * LD + cc + 4);
           v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
@@ -153,11 +186,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
           }
           store8<T>(reinterpret_cast<T*>(g.C) + (size_t)blockIdx.z * g.strideC + (size_t)row * g.ldc + col, v);
         }
-        if (HALVES == 2) __syncthreads();
+        if (h + 1 < PASSES) __syncthreads();
       }
       if (EPI == EPI_PRELU_STATS) {               // one sample per 128-row tile (Tp % 128 == 0): one atomic pair per workgroup
         const double d1 = wave_sum((double)t1), d2 = wave_sum((double)t2);
-        __syncthreads();                          // (the tile image in LDS is dead; `red` is separate, but keep the phases apart)
         if (lane == 0) { red[0][wave] = d1; red[1][wave] = d2; }
         __syncthreads();
         if (tid == 0) {
@@ -196,7 +228,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs g) {
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float vo = ep.put(acc[i][j][r], bv, m0 + wm * 64 + 16 * i + 4 * q + r, col);
+        const int rl = wm * 64 + 16 * i + 4 * q + r;
+        const float vo = ep.put(acc[i][j][r], bv, m0 + rl, col, tp0 + rl < g.Tv);
         if (EPI == EPI_RESIDUAL || EPI == EPI_MASK_POS) cs[j] += vo;
         if (EPI == EPI_PRELU_STATS) {
           s1 += vo;
@@ -404,6 +437,15 @@ template <typename T, int EPI> static void launch_nt_path(int lds_path, int nz, 
   else if (lds_path == 64) hipLaunchKernelGGL((gemm_nt_lds_kernel<T, EPI, 64>), grid, dim3(256), 0, s, g);
   else hipLaunchKernelGGL((gemm_nt_kernel<T, EPI>), grid, dim3(256), 0, s, g);
 }
+// Tile width of the product [R][N] = A[R][kslice] B[N][kslice]^T: 128 columns where they divide N, else 64 (N = 576, 320), or 0,
+// the register-staged kernel, where the K slice is no whole number of 128-byte stages.  (A 128 x 192 tile for N = 576 needs
+// 190 - 236 VGPRs, so two workgroups per CU and two rounds for the step's 576 workgroups: 52.8 us against 35 us on the
+// 64-wide tiles, profiles/nt_occupancy_alone.txt -- not built.)
+static int nt_tile_width(int prec, int N, int kslice) {
+  const int bk = prec == NPPC_PREC_BF16 ? 64 : 32;
+  if (kslice % bk) return 0;
+  return N % 128 == 0 ? 128 : 64;
+}
 template <typename T> static int dispatch_nt_epi(int epi, int lds_path, int nz, const GemmArgs& g, hipStream_t s) {
   switch (epi) {
 #define NT_CASE(E) case E: launch_nt_path<T, E>(lds_path, nz, g, s); break;
@@ -441,8 +483,7 @@ static int launch_nt(int prec, int epi, const void* A, long lda, long sA, const 
                    : ((epi == EPI_PLAIN || epi == EPI_PRELU_STATS || epi == EPI_RELU) && ksplit == 1 && nt_staged_plain())) &&
               ldc % 8 == 0) ? 1 : 0,
              colpart, (long)(R / 128) * N};
-  const int bk = prec == NPPC_PREC_BF16 ? 64 : 32;
-  const int lds_path = ((K / ksplit) % bk == 0) ? (N % 128 == 0 ? 128 : 64) : 0;
+  const int lds_path = nt_tile_width(prec, N, K / ksplit);
   // the tile column sums come out of the LDS kernels' epilogue for the two epilogues that produce an upstream gradient
   if (colpart && (lds_path == 0 || ksplit != 1 || (epi != EPI_RESIDUAL && epi != EPI_MASK_POS))) return NPPC_EUNSUPPORTED;
   return dispatch_nt(prec, epi, lds_path, batch * ksplit, g, (hipStream_t)stream);
@@ -456,6 +497,16 @@ int nppc_gemm_nt(int prec, int epi, const void* A, long lda, long sA, const void
                  int batch, int ksplit, void* stream) {
   return launch_nt(prec, epi, A, lda, sA, B, ldb, sB, C, ldc, sC, bias, sBias, res, ldres, sRes, slope, sSlope, stats, sStats, R, N,
                    K, Tp, Tv, Nv, relu_in, batch, ksplit, nullptr, stream);
+}
+
+// The tile width nppc_gemm_nt / nppc_gemm_nt_colsum / nppc_gemm_nt_gn run a product of these sizes on: 128 or 64 columns
+// of gemm_nt_lds_kernel, 0 = the register-staged gemm_nt_kernel.
+int nppc_gemm_nt_tile(int prec, int N, int K, int ksplit, int* bn) {
+  if (!bn || (prec != NPPC_PREC_BF16 && prec != NPPC_PREC_F32) || N <= 0 || K <= 0) return NPPC_EBADARG;
+  if (ksplit < 1) ksplit = 1;
+  if (N % 64 || K % (32 * ksplit)) return NPPC_EUNSUPPORTED;
+  *bn = nt_tile_width(prec, N, K / ksplit);
+  return NPPC_OK;
 }
 
 // nppc_gemm_nt (EPI_RESIDUAL or EPI_MASK_POS, LDS-staged shapes: K a multiple of 64 (bf16) / 32 (fp32), no K split) that also
@@ -479,8 +530,7 @@ int nppc_gemm_nt_gn(int prec, const void* A, long lda, long sA, const void* Wg, 
   if (R % 128 || N % 64 || K % 32 || Tp <= 0 || (Tp % 128) || lda % 8 || ldb % 8) return NPPC_EUNSUPPORTED;
   GemmArgs g{A, lda, sA, Wg, ldb, sB, C, ldc, sC, u, sUV, res, ldres, sRes, nullptr, 0, const_cast<double*>(stats), sStats,
              R, N, K, Tp, Tv, Nv, 0, 1, v, sUV, cnt, eps, (ldc % 8 == 0 && ldres % 8 == 0) ? 1 : 0, nullptr, 0};
-  const int bk = prec == NPPC_PREC_BF16 ? 64 : 32;
-  const int lds_path = (K % bk == 0) ? (N % 128 == 0 ? 128 : 64) : 0;
+  const int lds_path = nt_tile_width(prec, N, K);
   return dispatch_nt(prec, EPI_RESIDUAL_GN, lds_path, batch, g, (hipStream_t)stream);
 }
 

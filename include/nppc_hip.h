@@ -83,6 +83,9 @@ int nppc_gemm_nt(int prec, int epi, const void* A, long lda, long sA, const void
                  long sC, const float* bias, long sBias, const void* res, long ldres, long sRes, const float* slope,
                  long sSlope, double* stats, long sStats, int R, int N, int K, int Tp, int Tv, int Nv, int relu_in,
                  int batch, int ksplit, void* stream);
+/* *bn = the tile width nppc_gemm_nt / _colsum / _gn run a product of these sizes on: 128 or 64 columns (LDS-staged),
+ * 0 = the register-staged kernel (the K slice is no multiple of 64 bf16 / 32 fp32 elements) */
+int nppc_gemm_nt_tile(int prec, int N, int K, int ksplit, int* bn);
 /* long-K weight-gradient product: C_slab[z][M][N] (fp32) = A[M][K/ksplit slice z] * B[N][same slice]^T, LDS-staged
  * 128x128 tiles; M, N multiples of 128, K a multiple of (64 bf16 | 32 fp32) * ksplit */
 int nppc_gemm_nt_splitk(int prec, const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, long K,
