@@ -6,26 +6,43 @@ FullSubNet_Plus.forward (FullSubNet_plus/.../fullsubnet_plus.py:143-230) and
 MultiDirectionFullSubNet_Plus.forward (nppc_audio/networks.py:63-163) stage by stage.
 """
 import ctypes
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _hip as H
+from .gemm import gemm_nt, gemm_nt_gn, lstm_wgrad_mode, reduce_slabs, reduce_slabs_t
 from .ops_lstm import (PackedLSTM, PackedLSTMBwd, ROW_PAD, WGRAD_SPLITS, bwd_head_fusable, forward_x_ld, lstm2_backward, lstm2_forward,
-                       own_workspaces, padded_rows,
-                       rows_view, workspace)
+                       own_workspaces, padded_rows, rows_view, workspace)
 
 TCN_HIDDEN = 512
 TCN_DILATIONS = (1, 2, 5, 9, 1, 2, 5, 9)
 BRANCHES = ("", "_real", "_imag")   # channel_attention{,_real,_imag} / fb_model{,_real,_imag}
 EPI_PLAIN, EPI_PRELU_STATS, EPI_RESIDUAL, EPI_RELU, EPI_PLAIN_F32, EPI_MASK_POS = 0, 1, 2, 3, 4, 5
+LSTM_PARAMS = "sb_model.sequence_model."
+TSSE_PARAMS = tuple(f"channel_attention.{m}.{leaf}" for m in ("smallConv1d.0", "middleConv1d.0", "largeConv1d.0",
+                                                              "feature_concate_fc", "fc1", "fc2") for leaf in ("weight", "bias"))
+TCN_MID_GRADS = ("norm2.weight", "norm2.bias", "norm1.weight", "norm1.bias", "depthwise_conv.weight", "depthwise_conv.bias",
+                 "prelu1.weight", "prelu2.weight", "conv1x1.bias")       # gradients of the fused middle backward, in argument order
+TCN_WGRAD_SPLITS = 8         # K-slices of the split-K weight-gradient GEMMs of the full-band model (fc_output_layer; fp32: all)
 
 
 def rup(a, b):
     return (a + b - 1) // b * b
 
 
-TCN_WGRAD_SPLITS = 8         # K-slices of the split-K weight-gradient GEMMs of the full-band model (fc_output_layer; fp32: all)
+class BackwardPlan(NamedTuple):
+    """what one FSNEngine.backward does where: decided once per buffer set (FSNEngine._backward_plan), read by its stages"""
+    fused_head: bool  # the K-split cooperative LSTM kernel forms d h2 = dY . Wh itself from the gathered dY rows: no dh2 tensor
+    head_wgrad: bool  # the head's weight gradient h2^T . dY runs with the LSTM weight gradients on the side stream, not in front
+    S2: int           # K-slices of the split-K weight-gradient GEMMs of the full-band model: as many as divide the B * Tp rows
+    Fr: int           # F rounded up to the 128-row tiles of those GEMMs (rows of the fc_output_layer product)
+    Cr: int           # ldC likewise (rows of the sconv.weight product)
+    tn_ok: bool       # bf16: the 1x1-conv weight gradients run on the TN GEMM straight from the row-major activations (no transposes)
+    cs_ok: bool       # the GEMM that PRODUCES a block's upstream gradient also leaves its column sums: no pass over dXo for sconv.bias
+    early: bool       # grad_range_hook gets ranges of the flat gradient as they become final: the sub-band tail, TCN blocks 7..4
 
 
 class FlatParams:
@@ -135,7 +152,7 @@ class FSNEngine:
         self.sP = flat.branch_stride()
         self.sAtt = flat.attention_stride()
         self.packed_version = None
-        self._tn_tables = {}                  # problem tables of the grouped TCN weight-gradient launches (_tcn_wgrad_tables)
+        self._tn_tables = {}                  # problem tables of the grouped TCN weight-gradient launches (_tcn_wgrad_grouped)
         self._side = None                     # side stream for the LSTM weight-gradient GEMMs (backward)
         self._gen = 0                         # train-forward generation: backward must consume the LATEST train forward
         self.last_train = None
@@ -234,11 +251,9 @@ class FSNEngine:
                        self.F, ldC, ldF, 1, s)
             H.call("nppc_pack_matrix", self.prec, self.p("sb_model.fc_output_layer.weight"), self.WhT, self.Hd, self.O,
                    self.Hd, 32, 1, s)
-            q = "sb_model.sequence_model."
-            self.lstm_bwd.pack(*[self.p(q + n) for n in ("weight_ih_l0", "weight_hh_l0", "weight_ih_l1", "weight_hh_l1")])
-        q = "sb_model.sequence_model."
-        self.lstm.pack(*[self.p(q + n) for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
-                                                  "weight_ih_l1", "weight_hh_l1", "bias_ih_l1", "bias_hh_l1")])
+            self.lstm_bwd.pack(*[self.p(LSTM_PARAMS + n) for n in ("weight_ih_l0", "weight_hh_l0", "weight_ih_l1", "weight_hh_l1")])
+        self.lstm.pack(*[self.p(LSTM_PARAMS + n) for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
+                                                            "weight_ih_l1", "weight_hh_l1", "bias_ih_l1", "bias_hh_l1")])
         self.packed_version = ver
 
     # ------------------------------------------------------------------ buffers
@@ -302,21 +317,15 @@ class FSNEngine:
         self.pack_weights()
         d = self._buffers(B, T, train, ragged)
         s = H.stream()
-        Tv, Tp, prec = d["Tv"], d["Tp"], self.prec
-        C, ldC, ldF, sP = self.C, self.ldC, self.ldF, self.sP
+        Tp, prec, ldC, ldF = d["Tp"], self.prec, self.ldC, self.ldF
         R = B * Tp
         maps = [m.contiguous().float() for m in maps]
         d["maps"] = maps if train else None
         sv = d.get("tsse_saved")
         # 1-3: laplace norm + TSSE attention scale, transposed into the TCN input: all 3 * n_maps maps in three launches
-        att = "channel_attention."
         sv_ = [sv[k] if sv else None for k in ("ns", "pre", "sq", "h1", "sg")]
-        tsse_w = (self.p(att + "smallConv1d.0.weight"), self.p(att + "smallConv1d.0.bias"),
-                  self.p(att + "middleConv1d.0.weight"), self.p(att + "middleConv1d.0.bias"),
-                  self.p(att + "largeConv1d.0.weight"), self.p(att + "largeConv1d.0.bias"), self.ks[0], self.ks[1], self.ks[2],
-                  self.p(att + "feature_concate_fc.weight"), self.p(att + "feature_concate_fc.bias"),
-                  self.p(att + "fc1.weight"), self.p(att + "fc1.bias"), self.p(att + "fc2.weight"), self.p(att + "fc2.bias"),
-                  self.sAtt)
+        tw = [self.p(n) for n in TSSE_PARAMS]
+        tsse_w = (*tw[:6], self.ks[0], self.ks[1], self.ks[2], *tw[6:], self.sAtt)       # three convs, kernel sizes, three Linears
         if ragged:
             H.call("nppc_tsse_fwd_maps_ragged", prec, H.ptr_array(maps), 3 * self.nm, d["rs"], *tsse_w, d["scale"], d["X"][0],
                    R * ldC, frames, B, F, T, self.la, Tp, ldC, s)
@@ -328,9 +337,22 @@ class FSNEngine:
             H.call("nppc_rawmag_stage_ragged", prec, maps[0], d["rawmag"], frames, B, F, T, Tp, ldF, s)
         elif self.nm == 2:
             H.call("nppc_scale_transpose", prec, maps[0], None, d["rawmag"], B, F, T, Tp, ldF, 0, s)
-        # 4: eight TCN blocks, the three branches batched over blockIdx.z
+        self._fwd_fullband(d, train, frames)
+        out = self._fwd_subband(d, T, train, mtile, frames)
+        self.last = d
+        if train:
+            self._gen += 1
+            d["gen"] = self._gen
+            d["consumed"] = False            # the buffer dict is reused by every step of this shape
+            self.last_train = d
+        return out
+
+    def _fwd_fullband(self, d, train, frames):
+        """4: eight TCN blocks, the three branches batched over blockIdx.z; 5: trailing ReLU + Linear(C -> F) + ReLU"""
+        s, ragged = H.stream(), frames is not None
+        B, Tv, Tp, prec = d["B"], d["Tv"], d["Tp"], self.prec
+        F, C, ldC, ldF, sP, R, sAct = self.F, self.C, self.ldC, self.ldF, self.sP, B * Tp, B * Tp * TCN_HIDDEN
         d["stats"].zero_()
-        sAct = B * Tp * TCN_HIDDEN
         for i, dil in enumerate(TCN_DILATIONS):
             pre = f"fb_model.sequence_model.{i}."
             xi, xo = (i, i + 1) if train else ((0 if i == 0 else 1 + (i - 1) % 2), 1 + i % 2)
@@ -338,9 +360,9 @@ class FSNEngine:
             Xin, Xout = d["X"][xi], d["X"][xo]
             y1, y2 = d["y1"][bi], d["y2"][bi]
             st1, st2 = d["stats"][i, 0], d["stats"][i, 1]
-            H.call("nppc_gemm_nt", prec, EPI_PRELU_STATS, Xin, ldC, R * ldC, self.W1p[i], ldC, TCN_HIDDEN * ldC,
-                   y1, TCN_HIDDEN, sAct, self.p(pre + "conv1x1.bias"), sP, None, 0, 0, self.p(pre + "prelu1.weight"), sP,
-                   st1, B * 2, R, TCN_HIDDEN, self.KC, Tp, Tv, TCN_HIDDEN, 0, 3, 1, s)
+            gemm_nt(prec, EPI_PRELU_STATS, A=(Xin, ldC, R * ldC), B=(self.W1p[i], ldC, TCN_HIDDEN * ldC), C=(y1, TCN_HIDDEN, sAct),
+                    bias=(self.p(pre + "conv1x1.bias"), sP), slope=(self.p(pre + "prelu1.weight"), sP), stats=(st1, B * 2),
+                    R=R, N=TCN_HIDDEN, K=self.KC, Tp=Tp, Tv=Tv, Nv=TCN_HIDDEN, batch=3, stream=s)
             dw = (self.p(pre + "norm1.weight"), self.p(pre + "norm1.bias"), self.p(pre + "depthwise_conv.weight"),
                   self.p(pre + "depthwise_conv.bias"), self.p(pre + "prelu2.weight"))
             if ragged:
@@ -355,15 +377,18 @@ class FSNEngine:
             else:
                 H.call("nppc_tcn_dwconv", prec, y1, y2, st1, st2, *dw, B, TCN_HIDDEN, TCN_HIDDEN, Tp, Tv, dil, 1e-8, sAct,
                        B * 2, sP, 3, s)
-            H.call("nppc_gemm_nt_gn", prec, y2, TCN_HIDDEN, sAct, self.W2p[i], TCN_HIDDEN, ldC * TCN_HIDDEN, Xout, ldC, R * ldC,
-                   self.u2[i], self.v2[i], ldC, Xin, ldC, R * ldC, st2, B * 2, float(TCN_HIDDEN * Tv), 1e-8, R, ldC,
-                   TCN_HIDDEN, Tp, Tv, C, 3, s)
+            gemm_nt_gn(prec, A=(y2, TCN_HIDDEN, sAct), B=(self.W2p[i], TCN_HIDDEN, ldC * TCN_HIDDEN), C=(Xout, ldC, R * ldC),
+                       u=self.u2[i], v=self.v2[i], uv_stride=ldC, res=(Xin, ldC, R * ldC), stats=(st2, B * 2),
+                       count=float(TCN_HIDDEN * Tv), eps=1e-8, R=R, N=ldC, K=TCN_HIDDEN, Tp=Tp, Tv=Tv, Nv=C, batch=3, stream=s)
         Xlast = d["X"][8 if train else 2]
-        # 5: trailing ReLU + Linear(C -> F) + ReLU
-        H.call("nppc_gemm_nt", prec, EPI_RELU, Xlast, ldC, R * ldC, self.Wfcp, ldC, ldF * ldC, d["fb"], ldF, R * ldF,
-               self.p("fb_model.fc_output_layer.bias"), sP, None, 0, 0, None, 0, None, 0, R, ldF, self.KC, Tp, Tv, F, 1,
-               3, 1, s)
-        # 6: sub-band unfold + concat + norm + drop-band, staged time-major for the LSTM
+        gemm_nt(prec, EPI_RELU, A=(Xlast, ldC, R * ldC), B=(self.Wfcp, ldC, ldF * ldC), C=(d["fb"], ldF, R * ldF),
+                bias=(self.p("fb_model.fc_output_layer.bias"), sP), R=R, N=ldF, K=self.KC, Tp=Tp, Tv=Tv, Nv=F, relu_in=1, batch=3,
+                stream=s)
+
+    def _fwd_subband(self, d, T, train, mtile, frames):
+        """6: sub-band unfold + concat + norm + drop-band, staged time-major; 7: the LSTM; 8: the output head -> the net output"""
+        s, ragged = H.stream(), frames is not None
+        B, Tv, Tp, prec, F, ldC, ldF, R = d["B"], d["Tv"], d["Tp"], self.prec, self.F, self.ldC, self.ldF, d["B"] * d["Tp"]
         if self.nm == 1:
             src, ldS = d["X"][0, 0], ldC          # attention-scaled, normalised magnitude (fullsubnet_plus.py:203)
         else:
@@ -404,12 +429,6 @@ class FSNEngine:
                    self.la, self.Hd, self.O, d["Fo"], s)
         if ragged:                            # the output crop: frames t >= T_b of item b are 0
             H.call("nppc_crop_frames_ragged", out, self.O * d["Fo"], T, frames, B, s)
-        self.last = d
-        if train:
-            self._gen += 1
-            d["gen"] = self._gen
-            d["consumed"] = False            # the buffer dict is reused by every step of this shape
-            self.last_train = d
         return out
 
     # ------------------------------------------------------------------ backward (direction net, trainable restorer)
@@ -428,13 +447,15 @@ class FSNEngine:
     def g(self, name):
         return self.fp.gview(name)
 
-    def _tcn_wgrad_tables(self, G, d, dXL, a2L, h2L, R, blocks):
-        """the problem tables of nppc_gemm_tn_grouped for TCN blocks `blocks` x the three branches, (sconv.weight, conv1x1.weight):
-        built once per set of buffers (workspaces, saved activations and both flat gradient buffers keep their addresses)"""
+    def _tcn_wgrad_grouped(self, d, w, G, blocks):
+        """both weight gradients of TCN blocks `blocks` x the three branches, one grouped launch per kind (sconv.weight,
+        conv1x1.weight): row-major operands as they are, written finished into the flat gradient (no split-K slabs, no reductions).
+        The problem tables of nppc_gemm_tn_grouped are built once per set of buffers (workspaces, saved activations and both flat
+        gradient buffers keep their addresses)"""
+        C, ldC, R, dXL, a2L, h2L = self.C, self.ldC, d["B"] * d["Tp"], w.dXL, w.a2L, w.h2L
         key = (G.data_ptr(), d["X"].data_ptr(), a2L[0].data_ptr(), R, blocks)
         tabs = self._tn_tables.get(key)
         if tabs is None:
-            C, ldC = self.C, self.ldC
             sc, c1 = [], []
             for i in blocks:
                 for z, br in enumerate(BRANCHES):
@@ -446,122 +467,137 @@ class FSNEngine:
                     c1.append((h2L[i][z], TCN_HIDDEN, d["X"][i][z], ldC, self.g(pre + "conv1x1.weight"), C, C, H.TN_STORE_ASIS))
             tabs = (H.tn_problem_table(sc, TCN_HIDDEN, ldC, R), H.tn_problem_table(c1, TCN_HIDDEN, ldC, R))
             self._tn_tables[key] = tabs
-        return tabs
+        for tab in tabs:
+            H.call("nppc_gemm_tn_grouped", tab, tab.shape[0], TCN_HIDDEN, ldC, R, H.stream())
 
-    def _wgrad(self, AT, lda, sA, BT, ldb, sB, rows, ncolsN, K, S, dst_name_or_tensor, dst_ld, out_rows, ncols, slab,
-               batch=1, sDst=0, permH=0, col0=0, accumulate=0):
-        """dst[r][c] = sum_k AT[r][k] * BT[c][k]  via split-K fp32 slabs + reduction (one launch pair)."""
-        s = H.stream()
-        dst = self.g(dst_name_or_tensor) if isinstance(dst_name_or_tensor, str) else dst_name_or_tensor
-        bk = 64 if self.prec == H.PREC_BF16 else 32
-        if batch == 1 and rows % 128 == 0 and ncolsN % 128 == 0 and K % (bk * S) == 0:
-            H.call("nppc_gemm_nt_splitk", self.prec, AT, lda, BT, ldb, slab, ncolsN, rows, ncolsN, K, S, s)
-        else:
-            H.call("nppc_gemm_nt", self.prec, EPI_PLAIN_F32, AT, lda, sA, BT, ldb, sB, slab, ncolsN, rows * ncolsN, None,
-                   0, None, 0, 0, None, 0, None, 0, rows, ncolsN, K, rows, rows, ncolsN, 0, batch, S, s)
-        H.call("nppc_reduce_slabs", slab, S, rows * ncolsN, ncolsN, dst, dst_ld, out_rows, col0, ncols, permH, accumulate,
-               S * rows * ncolsN, sDst, batch, s)
+    def _ws(self, name, shape, dtype=None, zero=False):
+        return workspace(("eng", id(self), name), shape, dtype or self.dt, self.dev, zero)
+
+    def _wgrad(self, d, p, w, dst_name, *, A, rows, B, ncols, slab, relu_b=0):
+        """full-band weight gradient where the TN GEMM does not apply: dst[z][r][c] = sum_k A[z][k][r] * B[z][k][c] for the three
+        branches z, r < rows = (padded to the 128-row tile, valid), c < ncols.  A = (tensor [3][R][lda], columns, lda), B = (tensor
+        [3][R][ldb], ldb): two transposes into tA / tB, the NT product into split-K fp32 slabs, their reduction"""
+        s, prec, R, S = H.stream(), self.prec, d["B"] * d["Tp"], p.S2
+        (a, cols_a, lda), (b, ldb), (rows, out_rows) = A, B, rows
+        H.call("nppc_transpose", prec, a, w.tA, R, cols_a, lda, R, R * lda, w.sTA, 0, 3, s)
+        H.call("nppc_transpose", prec, b, w.tB, R, ldb, ldb, R, R * ldb, w.sTB, relu_b, 3, s)
+        gemm_nt(prec, EPI_PLAIN_F32, A=(w.tA, R, w.sTA), B=(w.tB, R, w.sTB), C=(slab, ldb, rows * ldb), R=rows, N=ldb, K=R,
+                Tp=rows, Tv=rows, Nv=ldb, batch=3, ksplit=S, stream=s)
+        reduce_slabs(slab, S, slab_stride=rows * ldb, ld=ldb, dst=self.g(dst_name), dst_ld=ncols, rows=out_rows, ncols=ncols,
+                     batch=3, s_slab=S * rows * ldb, s_dst=self.sP, stream=s)
+
+    def _scatter_slabs(self, slab, S, slab_stride, ld, dests, s):
+        """columns [col0, col0 + ncols) of the sum of the S slabs [4H][ld] -> the LSTM parameter gradient `name`, for every
+        (name, dst_ld, col0, ncols) of dests; a bias_ih_* gradient is also that of its bias_hh_* twin"""
+        for name, dst_ld, col0, ncols in dests:
+            reduce_slabs(slab, S, slab_stride=slab_stride, ld=ld, dst=self.g(name), dst_ld=dst_ld, rows=4 * self.Hd, col0=col0,
+                         ncols=ncols, permH=self.Hd, stream=s)
+            if ".bias_ih_" in name:
+                self.g(name.replace(".bias_ih_", ".bias_hh_")).copy_(self.g(name))
 
     def _lstm_wgrad(self, dg1, dg2, x_rows, h1_rows, h2_rows, Tv, Nseq, head=None, guards=None):
         """LSTM weight / bias gradients from the row-major gate gradients (runs on the side stream).
         head = (dyt_rows [Rpad][16] bf16, O): also the output head's weight / bias gradients, as one more TN product
         h2^T . dY (the 16-column dY rows are read as a 64-column operand: the extra columns are ignored)."""
         s = H.stream()
-        dt, dev, Hd, I, KX = self.dt, self.dev, self.Hd, self.I, self.KX
-        K4 = 4 * Hd
-        q = "sb_model.sequence_model."
-        Rr = Tv * Nseq
-        ws = lambda name, shape, dtype=dt, zero=False: workspace(("eng", id(self), name), shape, dtype, dev, zero)
-        jobs = [   # (dgates, row offset of dgates, input rows, input width, destination(s))
-            (dg1, 0, x_rows, KX, ("ih", q + "weight_ih_l0", q + "bias_ih_l0", q + "bias_hh_l0")),
-            (dg2, 0, x_rows, KX, ("bias", None, q + "bias_ih_l1", q + "bias_hh_l1")),
-            (dg2, 0, h1_rows, Hd, ("w", q + "weight_ih_l1")),
-        ]
+        Hd, I, KX, Rr, q = self.Hd, self.I, self.KX, Tv * Nseq, LSTM_PARAMS
+        jobs = [   # (dgates, row offset of dgates, input rows, input width, destinations (_scatter_slabs))
+            (dg1, 0, x_rows, KX, [(q + "weight_ih_l0", I, 0, I), (q + "bias_ih_l0", 1, I, 1)]),
+            (dg2, 0, x_rows, KX, [(q + "bias_ih_l1", 1, I, 1)]),
+            (dg2, 0, h1_rows, Hd, [(q + "weight_ih_l1", Hd, 0, Hd)])]
         if Tv > 1:
-            jobs += [(dg1, Nseq, h1_rows, Hd, ("w", q + "weight_hh_l0")), (dg2, Nseq, h2_rows, Hd, ("w", q + "weight_hh_l1"))]
+            jobs += [(dg1, Nseq, h1_rows, Hd, [(q + "weight_hh_l0", Hd, 0, Hd)]),
+                     (dg2, Nseq, h2_rows, Hd, [(q + "weight_hh_l1", Hd, 0, Hd)])]
+        mode, fold_bias = lstm_wgrad_mode(self.prec, Hd, KX, Tv, WGRAD_SPLITS, guards is not None)
+        if mode == "generic":
+            return self._lstm_wgrad_generic(jobs, dg1, dg2, Rr, s)
+        # 64 K-slices: (4H/128) * (H/128) * 64 = 2304 workgroups for 512 slots (16 slices = 576 left the second
+        # round of workgroups 1/8 full: 481 -> 674 TFLOP/s on the H x 4H products, tools/bench_tn.py)
+        S = WGRAD_SPLITS
+        assert 64 * S <= ROW_PAD                 # operand buffers are padded by ROW_PAD rows (ops_lstm.padded_rows)
+        slab = self._ws("slab", (S * 4 * Hd * max(Hd, KX),), torch.float32)
+        if mode == "fused2":
+            slab = self._lstm_wgrad_fused2(dg1, dg2, x_rows, h1_rows, guards, Rr, S, s)
+        else:
+            self._lstm_wgrad_tn(jobs, slab, fold_bias, Rr, S, s)
+        if head is not None:
+            dyt_rows, O = head
+            rows = (Rr + 64 * S - 1) // (64 * S) * (64 * S)
+            H.call("nppc_gemm_tn_splitk", h2_rows, Hd, dyt_rows, 16, slab, 64, Hd, 64, rows, S, s)
+            reduce_slabs_t(slab, S, slab_stride=Hd * 64, ld=64, dst=self.g("sb_model.fc_output_layer.weight"), dst_ld=Hd, rows=O,
+                           ncols=Hd, stream=s)
+            H.colsum(self.prec, dyt_rows, self.g("sb_model.fc_output_layer.bias"), Rr, O, 16, 0, 0, 1,
+                     lambda n: self._ws("cs_head", (n,), torch.float32), s)
 
-        def scatter(slab, S, rows, ncolsN, dest):
-            kind = dest[0]
-            if kind in ("ih", "w"):
-                ncol = I if kind == "ih" else Hd
-                H.call("nppc_reduce_slabs", slab, S, rows * ncolsN, ncolsN, self.g(dest[1]), ncol, K4, 0, ncol, Hd, 0, 0, 0, 1, s)
-            if kind in ("ih", "bias"):
-                H.call("nppc_reduce_slabs", slab, S, rows * ncolsN, ncolsN, self.g(dest[2]), 1, K4, I, 1, Hd, 0, 0, 0, 1, s)
-                self.g(dest[3]).copy_(self.g(dest[2]))
+    def _lstm_wgrad_fused2(self, dg1, dg2, x_rows, h1_rows, guards, Rr, S, s):
+        """ONE pass over each layer's gate gradients for both of its weight gradients (`nppc_gemm_tn_splitk2`):
+          layer 1: dg1^T . [h1_{t-1} | x_t]   (x's spare column carries the bias gradient)
+          layer 2: dg2^T . [h1_t | h2_{t-1}]  (+ row sums of dg2 = the bias gradient)
+        h_{t-1} is the guard view of the h rows (N zero rows in front), so the gate gradients are not shifted.  Returns its slab."""
+        Hd, I, KX, K4, q = self.Hd, self.I, self.KX, 4 * self.Hd, LSTM_PARAMS
+        (h1_guard, h2_guard), rows = guards, (Rr + 64 * S - 1) // (64 * S) * (64 * S)
+        slab = self._ws("slab2", (S * K4 * 2 * Hd,), torch.float32)
+        rsum = self._ws("rowsum", (S, K4), torch.float32)
+        H.call("nppc_gemm_tn_splitk2", dg1, K4, h1_guard, Hd, Hd, x_rows, KX, KX, slab, Hd + KX, K4, rows, S, None, s)
+        self._scatter_slabs(slab, S, K4 * (Hd + KX), Hd + KX, [(q + "weight_hh_l0", Hd, 0, Hd), (q + "weight_ih_l0", I, Hd, I),
+                                                              (q + "bias_ih_l0", 1, Hd + I, 1)], s)
+        H.call("nppc_gemm_tn_splitk2", dg2, K4, h1_rows, Hd, Hd, h2_guard, Hd, Hd, slab, 2 * Hd, K4, rows, S, rsum, s)
+        self._scatter_slabs(slab, S, K4 * 2 * Hd, 2 * Hd, [(q + "weight_ih_l1", Hd, 0, Hd), (q + "weight_hh_l1", Hd, Hd, Hd)], s)
+        self._scatter_slabs(rsum, S, K4, 1, [(q + "bias_ih_l1", 1, 0, 1)], s)
+        return slab
 
-        if self.prec == H.PREC_BF16 and K4 % 128 == 0 and Hd % 64 == 0 and KX % 64 == 0:
-            # 64 K-slices: (4H/128) * (H/128) * 64 = 2304 workgroups for 512 slots (16 slices = 576 left the second
-            # round of workgroups 1/8 full: 481 -> 674 TFLOP/s on the H x 4H products, tools/bench_tn.py)
-            S = WGRAD_SPLITS
-            assert 64 * S <= ROW_PAD                 # operand buffers are padded by ROW_PAD rows (ops_lstm.padded_rows)
-            slab = ws("slab", (S * K4 * max(Hd, KX),), torch.float32)
-            # the layer-2 bias gradient (column sums of dg2) comes out of the W_ih_l1 product as row sums of its A operand
-            # (LDS-DMA kernel, csrc/tcn.hip) instead of out of a 64-column product of its own that re-read all of dg2
-            fold_bias = K4 % 256 == 0 and Hd % 128 == 0 and (K4 // 256) * (Hd // 128) * S >= 256
-            # ONE pass over each layer's gate gradients for both of its weight gradients (`nppc_gemm_tn_splitk2`):
-            #   layer 1: dg1^T . [h1_{t-1} | x_t]   (x's spare column carries the bias gradient)
-            #   layer 2: dg2^T . [h1_t | h2_{t-1}]  (+ row sums of dg2 = the bias gradient)
-            # h_{t-1} is the guard view of the h rows (N zero rows in front), so the gate gradients are not shifted
-            if (guards is not None and fold_bias and Hd % 192 == 0 and KX == 64 and Tv > 1
-                    and (K4 // 256) * (Hd // 192 + 1) * S >= 256):
-                h1_guard, h2_guard = guards
-                rows = (Rr + 64 * S - 1) // (64 * S) * (64 * S)
-                slab = ws("slab2", (S * K4 * 2 * Hd,), torch.float32)
-                rsum = ws("rowsum", (S, K4), torch.float32)
-                H.call("nppc_gemm_tn_splitk2", dg1, K4, h1_guard, Hd, Hd, x_rows, KX, KX, slab, Hd + KX, K4, rows, S, None, s)
-                n1 = K4 * (Hd + KX)
-                H.call("nppc_reduce_slabs", slab, S, n1, Hd + KX, self.g(q + "weight_hh_l0"), Hd, K4, 0, Hd, Hd, 0, 0, 0, 1, s)
-                H.call("nppc_reduce_slabs", slab, S, n1, Hd + KX, self.g(q + "weight_ih_l0"), I, K4, Hd, I, Hd, 0, 0, 0, 1, s)
-                H.call("nppc_reduce_slabs", slab, S, n1, Hd + KX, self.g(q + "bias_ih_l0"), 1, K4, Hd + I, 1, Hd, 0, 0, 0, 1, s)
-                self.g(q + "bias_hh_l0").copy_(self.g(q + "bias_ih_l0"))
-                H.call("nppc_gemm_tn_splitk2", dg2, K4, h1_rows, Hd, Hd, h2_guard, Hd, Hd, slab, 2 * Hd, K4, rows, S, rsum, s)
-                n2 = K4 * 2 * Hd
-                H.call("nppc_reduce_slabs", slab, S, n2, 2 * Hd, self.g(q + "weight_ih_l1"), Hd, K4, 0, Hd, Hd, 0, 0, 0, 1, s)
-                H.call("nppc_reduce_slabs", slab, S, n2, 2 * Hd, self.g(q + "weight_hh_l1"), Hd, K4, Hd, Hd, Hd, 0, 0, 0, 1, s)
-                H.call("nppc_reduce_slabs", rsum, S, K4, 1, self.g(q + "bias_ih_l1"), 1, K4, 0, 1, Hd, 0, 0, 0, 1, s)
-                self.g(q + "bias_hh_l1").copy_(self.g(q + "bias_ih_l1"))
-                jobs = []
-            for dg, off, inp, width, dest in jobs:
-                rows = (Rr - off + 64 * S - 1) // (64 * S) * (64 * S)
-                if fold_bias and dest[0] == "bias":
-                    continue
-                if fold_bias and dest == ("w", q + "weight_ih_l1"):
-                    rsum = ws("rowsum", (S, K4), torch.float32)
-                    H.call("nppc_gemm_tn_splitk_rowsum", dg.view(-1)[off * K4:], K4, inp, width, slab, width, K4, width, rows, S,
-                           rsum, s)
-                    H.call("nppc_reduce_slabs", rsum, S, K4, 1, self.g(q + "bias_ih_l1"), 1, K4, 0, 1, Hd, 0, 0, 0, 1, s)
-                    self.g(q + "bias_hh_l1").copy_(self.g(q + "bias_ih_l1"))
-                else:
-                    H.call("nppc_gemm_tn_splitk", dg.view(-1)[off * K4:], K4, inp, width, slab, width, K4, width, rows, S, s)
-                scatter(slab, S, K4, width, dest)
-            if head is not None:
-                dyt_rows, O = head
-                rows = (Rr + 64 * S - 1) // (64 * S) * (64 * S)
-                H.call("nppc_gemm_tn_splitk", h2_rows, Hd, dyt_rows, 16, slab, 64, Hd, 64, rows, S, s)
-                H.call("nppc_reduce_slabs_t", slab, S, Hd * 64, 64, self.g("sb_model.fc_output_layer.weight"), Hd, O, Hd, 0, 0, 1, s)
-                H.colsum(self.prec, dyt_rows, self.g("sb_model.fc_output_layer.bias"), Rr, O, 16, 0, 0, 1,
-                         lambda n: ws("cs_head", (n,), torch.float32), s)
-            return
-        # generic path (fp32 parity mode, small hidden sizes): transposed copies + the NT split-K GEMM
+    def _lstm_wgrad_tn(self, jobs, slab, fold_bias, Rr, S, s):
+        """one split-K TN product per job, straight from the row-major operands.  fold_bias: the layer-2 bias gradient
+        (column sums of dg2) comes out of the W_ih_l1 product as row sums of its A operand (LDS-DMA kernel, csrc/tcn.hip)
+        instead of out of a 64-column product of its own that re-read all of dg2"""
+        K4, q = 4 * self.Hd, LSTM_PARAMS
+        for dg, off, inp, width, dests in jobs:
+            rows = (Rr - off + 64 * S - 1) // (64 * S) * (64 * S)
+            if fold_bias and dests[0][0] == q + "bias_ih_l1":
+                continue
+            if fold_bias and dests[0][0] == q + "weight_ih_l1":
+                rsum = self._ws("rowsum", (S, K4), torch.float32)
+                H.call("nppc_gemm_tn_splitk_rowsum", dg.view(-1)[off * K4:], K4, inp, width, slab, width, K4, width, rows, S,
+                       rsum, s)
+                self._scatter_slabs(rsum, S, K4, 1, [(q + "bias_ih_l1", 1, 0, 1)], s)
+            else:
+                H.call("nppc_gemm_tn_splitk", dg.view(-1)[off * K4:], K4, inp, width, slab, width, K4, width, rows, S, s)
+            self._scatter_slabs(slab, S, K4 * width, width, dests, s)
+
+    def _lstm_wgrad_generic(self, jobs, dg1, dg2, Rr, s):
+        """fp32 parity mode, small hidden sizes: transposed copies + the NT split-K GEMM"""
+        K4, KX = 4 * self.Hd, self.KX
         bk = 64 if self.prec == H.PREC_BF16 else 32
         # split-K: the products are (4H x H) outputs over T'*N rows -- 72 workgroups at C2 without it, each walking a million
         # rows (the fp32 step spent 372 of its 556 ms in these five launches, profiles/r03_bench_c2_fp32_kernel_stats.csv)
         Sg = max(1, min(64, Rr // (16 * bk)))
         Rp = rup(Rr, bk * Sg)
-        K4p, Hp, KXp = rup(K4, 128), rup(Hd, 128), rup(KX, 128)
-        dgT = [ws("dg1T", (K4p, Rp), zero=True), ws("dg2T", (K4p, Rp), zero=True)]
+        K4p, Hp, KXp = rup(K4, 128), rup(self.Hd, 128), rup(KX, 128)
+        dgT = [self._ws("dg1T", (K4p, Rp), zero=True), self._ws("dg2T", (K4p, Rp), zero=True)]
         for src, dst in ((dg1, dgT[0]), (dg2, dgT[1])):
             H.call("nppc_transpose", self.prec, src, dst, Rr, K4, K4, Rp, 0, 0, 0, 1, s)
-        slab = ws("slab", (Sg * K4p * max(Hp, KXp),), torch.float32)
-        for dg, off, inp, width, dest in jobs:
+        slab = self._ws("slab", (Sg * K4p * max(Hp, KXp),), torch.float32)
+        for dg, off, inp, width, dests in jobs:
             wp = rup(width, 128)
-            name = f"inT_{id(inp)}_{off}"
-            inT = ws(name, (wp, Rp), zero=True)
+            inT = self._ws(f"inT_{id(inp)}_{off}", (wp, Rp), zero=True)
             # shifted product: input row r pairs with dgates row r + off -> place it at column r + off (scalar stores)
             H.call("nppc_transpose", self.prec, inp, inT.view(-1)[off:], Rr - off, width, width, Rp, 0, 0, 0, 1, s)
-            A = dgT[0] if dg is dg1 else dgT[1]
-            H.call("nppc_gemm_nt_splitk", self.prec, A, Rp, inT, Rp, slab, wp, K4p, wp, Rp, Sg, s)
-            scatter(slab, Sg, K4p, wp, dest)
+            H.call("nppc_gemm_nt_splitk", self.prec, dgT[0] if dg is dg1 else dgT[1], Rp, inT, Rp, slab, wp, K4p, wp, Rp, Sg, s)
+            self._scatter_slabs(slab, Sg, K4p * wp, wp, dests, s)
+
+    def _backward_plan(self, d):
+        """the BackwardPlan of buffer set d, cached with it: shapes and precision decide, and `key` (the hook, ops_lstm's switches)"""
+        key = (self.grad_range_hook is not None and self.early_buckets_ok, bwd_head_fusable(d["Nseq"], self.lstm_bwd))
+        if d.get("bwd_plan", (None,))[0] != key:
+            prec, ldC, R = self.prec, self.ldC, d["B"] * d["Tp"]
+            bk = 64 if prec == H.PREC_BF16 else 32
+            fused = prec == H.PREC_BF16 and self.O <= 16 and key[1]
+            S2 = TCN_WGRAD_SPLITS if R % (64 * TCN_WGRAD_SPLITS) == 0 else (8 if R % (32 * 8) == 0 else 1)
+            tn_ok = prec == H.PREC_BF16 and TCN_HIDDEN % 128 == 0 and ldC % 64 == 0 and R % (64 * S2) == 0
+            d["bwd_plan"] = (key, BackwardPlan(
+                fused_head=fused, head_wgrad=fused and self.Hd % 128 == 0 and self.KX % 64 == 0, S2=S2, Fr=rup(self.F, 128),
+                Cr=rup(ldC, 128), tn_ok=tn_ok, cs_ok=tn_ok and self.ldF % bk == 0 and TCN_HIDDEN % bk == 0, early=key[0]))
+        return d["bwd_plan"][1]
 
     def backward(self, dout, gen=None):
         """dout [B', O, F', T] fp32 -> flat parameter gradient (same layout as the flat parameter buffer).
@@ -582,244 +618,212 @@ class FSNEngine:
             raise RuntimeError("direction-net backward called twice for one forward (retain_graph / double backward are "
                                "not supported: the flat gradient buffer is overwritten, not accumulated)")
         d["consumed"] = True
-        s = H.stream()
-        prec, dt, dev = self.prec, self.dt, self.dev
-        B, T, Tv, Tp = d["B"], d["T"], d["Tv"], d["Tp"]
-        F, C, ldC, ldF, sP, Hd, O = self.F, self.C, self.ldC, self.ldF, self.sP, self.Hd, self.O
-        R = B * Tp
-        Nseq, Fo = d["Nseq"], d["Fo"]
+        p = self._backward_plan(d)
         G = self._grad_buffer()
         G.zero_()
+        dx, dg1, dg2, head = self._bwd_head_lstm(d, p, dout)
+        self._bwd_lstm_wgrad(d, p, G, dg1, dg2, head)
+        dpre_fb, Dsb = self._bwd_staging(d, dx)
+        w = self._bwd_workspaces(d, p)
+        self._bwd_fc(d, p, w, dpre_fb)
+        dX0 = self._bwd_tcn(d, p, w, G)
+        self._bwd_tsse(d, dX0, dx, Dsb)
+        self._bwd_fc_wgrad_join(d, p, w, dpre_fb)
+        return G
+
+    def _on_side(self, fn):
+        """run fn (which launches on the current stream) on the side stream once the current stream got here"""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        with torch.cuda.stream(self._side):
+            self._side.wait_event(ev)
+            fn()
+
+    def _bwd_head_lstm(self, d, p, dout):
+        """1. head: dh2 = dY Wh, dWh, dbh; LSTM recurrence backward.  Returns dx, the gate gradients of both layers and the
+        `head` operand of _lstm_wgrad (None: the head's parameter gradients are done here)"""
+        s = H.stream()
+        lo, Nseq, Fo, Tv, Hd, O = d["lstm"], d["Nseq"], d["Fo"], d["Tv"], self.Hd, self.O
+        gW, gb = self.g("sb_model.fc_output_layer.weight"), self.g("sb_model.fc_output_layer.bias")
+        if not p.fused_head:
+            dh2 = self._ws("dh2", (Tv, Nseq, Hd))
+            H.call("nppc_sb_head_bwd", self.prec, dout, self.WhT, lo["h2"], dh2, gW, gb, Nseq, Tv, self.la, Hd, O, Fo, s)
+            return (*lstm2_backward(lo, dh2, self.lstm_bwd, self.KX), None)
+        dyt_rows = self._ws("dyt_rows", (padded_rows(Tv * Nseq) + 8, 16), zero=True)   # dY rows, zero padded like the GEMM operands
+        dyt = rows_view(dyt_rows, Tv, Nseq)
+        H.call("nppc_head_dy_gather", dout, dyt, Nseq, Tv, self.la, O, Fo, s)
+        if not p.head_wgrad:
+            H.call("nppc_sb_head_bwd_w", self.prec, dout, lo["h2"], gW, gb, Nseq, Tv, self.la, Hd, O, Fo, s)
+        return (*lstm2_backward(lo, None, self.lstm_bwd, self.KX, head=(dyt, self.WhT)), (dyt_rows, O) if p.head_wgrad else None)
+
+    def _bwd_lstm_wgrad(self, d, p, G, dg1, dg2, head):
+        """2. LSTM weight gradients: dW[k][c] = sum_rows dgates[row][k] * input[row][c], rows = (t, sequence).  Row-major operands
+        straight from the recurrent kernels; h_{t-1} is the same buffer one time block (Nseq rows) earlier; the staged input carries
+        a ones column (index I), so its product column is the bias gradient.  They only feed the flat gradient, so they run on a side
+        stream beside the full-band backward chain (dozens of small kernels that leave most CUs idle); joined at the end of backward."""
         lo = d["lstm"]
-        # ---- 1. head: dh2 = dY Wh, dWh, dbh
-        ws = lambda name, shape, dtype=dt, zero=False: workspace(("eng", id(self), name), shape, dtype, dev, zero)
-        if prec == H.PREC_BF16 and O <= 16 and bwd_head_fusable(Nseq, self.lstm_bwd):
-            # the K-split cooperative kernel forms d h2 = dY . Wh itself from the gathered dY rows: no dh2 tensor
-            # dY rows [T'*N][16] (zero padded like the other GEMM operands: the head's weight gradient h2^T . dY runs with
-            # the LSTM weight gradients on the side stream, behind the recurrence, instead of in front of it)
-            dyt_rows = ws("dyt_rows", (padded_rows(Tv * Nseq) + 8, 16), zero=True)
-            dyt = rows_view(dyt_rows, Tv, Nseq)
-            H.call("nppc_head_dy_gather", dout, dyt, Nseq, Tv, self.la, O, Fo, s)
-            head_wgrad = (dyt_rows, O) if (Hd % 128 == 0 and self.KX % 64 == 0) else None
-            if head_wgrad is None:
-                H.call("nppc_sb_head_bwd_w", prec, dout, lo["h2"], self.g("sb_model.fc_output_layer.weight"),
-                       self.g("sb_model.fc_output_layer.bias"), Nseq, Tv, self.la, Hd, O, Fo, s)
-            dx, dg1, dg2 = lstm2_backward(lo, None, self.lstm_bwd, self.KX, head=(dyt, self.WhT))
-        else:
-            head_wgrad = None
-            dh2 = ws("dh2", (Tv, Nseq, Hd))
-            H.call("nppc_sb_head_bwd", prec, dout, self.WhT, lo["h2"], dh2, self.g("sb_model.fc_output_layer.weight"),
-                   self.g("sb_model.fc_output_layer.bias"), Nseq, Tv, self.la, Hd, O, Fo, s)
-            # ---- 2. LSTM recurrence backward
-            dx, dg1, dg2 = lstm2_backward(lo, dh2, self.lstm_bwd, self.KX)
-        # ---- 3. LSTM weight gradients: dW[k][c] = sum_rows dgates[row][k] * input[row][c], rows = (t, sequence).
-        # Row-major operands straight from the recurrent kernels; h_{t-1} is the same buffer one time block (Nseq rows)
-        # earlier; the staged input carries a ones column (index I), so its product column is the bias gradient.
-        # They only feed the flat gradient, so they run on a side stream beside the full-band backward chain below
-        # (dozens of small kernels that leave most CUs idle); joined at the end of backward.
-        main = torch.cuda.current_stream()
         if self._side is None:
             # lowest priority: the dependent chain on the main stream is what the step waits for; the weight-gradient
             # GEMMs are throughput work
-            prio = 0
-            if hasattr(torch.cuda.Stream, "priority_range"):
-                prio = max(torch.cuda.Stream.priority_range())
-            self._side = torch.cuda.Stream(device=dev, priority=prio)
-        self._side.wait_stream(main)
+            prio = max(torch.cuda.Stream.priority_range()) if hasattr(torch.cuda.Stream, "priority_range") else 0
+            self._side = torch.cuda.Stream(device=self.dev, priority=prio)
+        self._side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._side):
-            self._lstm_wgrad(dg1, dg2, d["x_rows"], lo["h1_rows"], lo["h2_rows"], Tv, Nseq, head=head_wgrad,
+            self._lstm_wgrad(dg1, dg2, d["x_rows"], lo["h1_rows"], lo["h2_rows"], d["Tv"], d["Nseq"], head=head,
                              guards=(lo["h1_guard"], lo["h2_guard"]) if "h1_guard" in lo else None)
-            if self.grad_range_hook is not None and self.early_buckets_ok:
+            if p.early:
                 # the sub-band segment (LSTM + head: the tail of the flat buffer) is final once these GEMMs are done
-                self.grad_range_hook(G, self.fp.off["sb_model.sequence_model.weight_ih_l0"][0], G.numel())
-        # ---- 4. staging backward -> gradient of the pre-ReLU full-band outputs
-        dpre_fb = ws("dpre_fb", (3, B, Tp, ldF), zero=True)
-        Dsb = ws("Dsb", (B,), torch.float64)
-        H.call("nppc_subband_stage_bwd", prec, dx, d["x_tm"], d["fb"], d["sbscale"], Dsb, dpre_fb, B, F, Tp, Tv, ldF, R * ldF,
-               self.nb, self.G, self.KX, s)
-        # ---- 5. fc_output_layer backward
-        S2 = TCN_WGRAD_SPLITS if R % (64 * TCN_WGRAD_SPLITS) == 0 else (8 if R % (32 * 8) == 0 else 1)
-        Fr = rup(F, 128)
-        Cr = rup(ldC, 128)
-        tA = ws("tA", (3, max(Cr, TCN_HIDDEN, Fr), R), zero=True)       # transposed dY operand
-        tB = ws("tB", (3, max(ldC, TCN_HIDDEN), R), zero=True)          # transposed activation operand
-        X8 = d["X"][8]
-        sTA, sTB = tA.shape[1] * R, tB.shape[1] * R
+                self.grad_range_hook(G, self.fp.off[LSTM_PARAMS + "weight_ih_l0"][0], G.numel())
 
-        def on_side(fn):
-            """run fn (which launches on the current stream) on the side stream once the main stream got here"""
-            ev = torch.cuda.Event()
-            ev.record(main)
-            with torch.cuda.stream(self._side):
-                self._side.wait_event(ev)
-                fn()
+    def _bwd_staging(self, d, dx):
+        """3. sub-band staging backward -> gradient of the pre-ReLU full-band outputs (and the per-item sums Dsb)"""
+        B, Tp, ldF = d["B"], d["Tp"], self.ldF
+        dpre_fb = self._ws("dpre_fb", (3, B, Tp, ldF), zero=True)
+        Dsb = self._ws("Dsb", (B,), torch.float64)
+        H.call("nppc_subband_stage_bwd", self.prec, dx, d["x_tm"], d["fb"], d["sbscale"], Dsb, dpre_fb, B, self.F, Tp, d["Tv"], ldF,
+               B * Tp * ldF, self.nb, self.G, self.KX, H.stream())
+        return dpre_fb, Dsb
 
-        def fc_wgrad(slab):
-            # parameter gradients only (bias: column sums; weight: two transposes + the NT split-K product -- F and C are not
-            # multiples of the TN kernel's tiles)
-            q = H.stream()
-            H.colsum(prec, dpre_fb, self.g("fb_model.fc_output_layer.bias"), R, F, ldF, R * ldF, sP, 3,
-                     lambda n: ws("cs_fc", (n,), torch.float32), q)
-            H.call("nppc_transpose", prec, dpre_fb, tA, R, F, ldF, R, R * ldF, sTA, 0, 3, q)
-            H.call("nppc_transpose", prec, X8, tB, R, ldC, ldC, R, R * ldC, sTB, 1, 3, q)
-            self._wgrad(tA, R, sTA, tB, R, sTB, Fr, ldC, R, S2, "fb_model.fc_output_layer.weight", C, F, C, slab, batch=3, sDst=sP)
-        # bf16: the product waits until the END of the main chain -- the side queue (LSTM + TCN weight gradients) is the longer
-        # one, the main queue would idle in front of the join -- with a slab of its own
-        # (the generic path below re-uses tA / tB / slab2 on the main stream: there the product stays in line)
-        tn_ok = prec == H.PREC_BF16 and TCN_HIDDEN % 128 == 0 and ldC % 64 == 0 and R % (64 * S2) == 0
-        if not tn_ok:
-            slab2 = ws("slab2", (3 * S2 * max(Cr * TCN_HIDDEN, TCN_HIDDEN * ldC, Fr * ldC),), torch.float32)
-            fc_wgrad(slab2)
-        # bf16: the 1x1-conv weight gradients run on the TN GEMM straight from the row-major activations (no transposes)
-        if tn_ok:
-            # ... and on the side stream, behind the LSTM weight gradients: nothing downstream reads them before the
-            # optimizer, and the end of the main chain (TSSE backward, small kernels) leaves most CUs idle.  Their operands
-            # get one buffer per TCN block, so the main chain never waits for the side stream inside a step.
-            dXL = [ws(f"dX_{i}", (3, B, Tp, ldC)) for i in range(9)]
-            a2L = [ws(f"a2_{i}", (3, B, Tp, TCN_HIDDEN), zero=True) for i in range(8)]
-            h2L = [ws(f"h2b_{i}", (3, B, Tp, TCN_HIDDEN)) for i in range(8)]
-            dXa, dXb = dXL[8], dXL[7]
-
-            def tcn_wgrad(blocks):
-                # both weight gradients of TCN blocks `blocks` x the three branches: one grouped launch per kind
-                sc_tab, c1_tab = self._tcn_wgrad_tables(G, d, dXL, a2L, h2L, R, blocks)
-                q = H.stream()
-                H.call("nppc_gemm_tn_grouped", sc_tab, sc_tab.shape[0], TCN_HIDDEN, ldC, R, q)
-                H.call("nppc_gemm_tn_grouped", c1_tab, c1_tab.shape[0], TCN_HIDDEN, ldC, R, q)
-        else:
-            dXa = ws("dXa", (3, B, Tp, ldC))
-            dXb = ws("dXb", (3, B, Tp, ldC))
-
-        # the GEMMs that PRODUCE a block's upstream gradient also leave its column sums per 128-row tile (epilogue): the sconv
-        # bias gradient is their sum over the tiles, added up by the block's fused middle backward -- no pass over dXo for it
-        bk = 64 if prec == H.PREC_BF16 else 32
-        cs_ok = tn_ok and ldF % bk == 0 and TCN_HIDDEN % bk == 0
-        cp_all = ws("colpart", (8, 3, R // 128, ldC), torch.float32) if cs_ok else None      # one block per TCN block
-        cpL = [cp_all[i] for i in range(8)] if cs_ok else None
-        if cs_ok:
-            H.call("nppc_gemm_nt_colsum", prec, EPI_MASK_POS, dpre_fb, ldF, R * ldF, self.WfcT, ldF, ldC * ldF, dXa, ldC, R * ldC,
-                   None, 0, X8, ldC, R * ldC, R, ldC, ldF, Tp, Tv, C, 3, cpL[7], s)
-        else:
-            H.call("nppc_gemm_nt", prec, EPI_MASK_POS, dpre_fb, ldF, R * ldF, self.WfcT, ldF, ldC * ldF, dXa, ldC, R * ldC, None, 0,
-                   X8, ldC, R * ldC, None, 0, None, 0, R, ldC, ldF, Tp, Tv, C, 0, 3, 1, s)
-        # ---- 6. TCN blocks in reverse
-        sAct = B * Tp * TCN_HIDDEN
-        h1b = ws("h1b", (3, B, Tp, TCN_HIDDEN))
+    def _bwd_workspaces(self, d, p):
+        """the buffers that more than one stage of the full-band backward (4, 5, 7) touches, as the plan asks for them"""
+        B, Tp, ldC, R, ws = d["B"], d["Tp"], self.ldC, d["B"] * d["Tp"], self._ws
+        w = SimpleNamespace(slab2=None)
+        w.tA = ws("tA", (3, max(p.Cr, TCN_HIDDEN, p.Fr), R), zero=True)       # transposed dY operand
+        w.tB = ws("tB", (3, max(ldC, TCN_HIDDEN), R), zero=True)              # transposed activation operand
+        w.sTA, w.sTB = w.tA.shape[1] * R, w.tB.shape[1] * R
         h2b = ws("h2b", (3, B, Tp, TCN_HIDDEN))
-        Smid = ws("Smid", (3, B, TCN_HIDDEN // 64, 8), torch.float64)      # channel-group shares of the per-sample sums
+        # block i reads its upstream gradient dXL[i + 1] and writes dXL[i]; a2L[i] = GN2(y2), h2L[i] = gradient of its conv1x1 output
+        if p.tn_ok:      # read by the side stream later: one buffer per TCN block, so the main chain never waits for it inside a step
+            w.dXL = [ws(f"dX_{i}", (3, B, Tp, ldC)) for i in range(9)]
+            w.a2L = [ws(f"a2_{i}", (3, B, Tp, TCN_HIDDEN), zero=True) for i in range(8)]
+            w.h2L = [ws(f"h2b_{i}", (3, B, Tp, TCN_HIDDEN)) for i in range(8)]
+        else:
+            w.slab2 = ws("slab2", (3 * p.S2 * max(p.Cr * TCN_HIDDEN, TCN_HIDDEN * ldC, p.Fr * ldC),), torch.float32)
+            dXa, dXb = ws("dXa", (3, B, Tp, ldC)), ws("dXb", (3, B, Tp, ldC))
+            w.dXL = [dXb if i % 2 else dXa for i in range(9)]                 # everything is consumed in line: two buffers take turns
+            w.a2L, w.h2L = [d["a2"]] * 8, [h2b] * 8
+        # column sums per 128-row tile from the producing GEMMs' epilogues, per TCN block: the fused middle backward adds them up
+        w.cpL = list(ws("colpart", (8, 3, R // 128, ldC), torch.float32)) if p.cs_ok else [None] * 8
+        return w
+
+    def _fc_wgrad(self, d, p, w, dpre_fb, slab):
+        """fc_output_layer parameter gradients (bias: column sums; weight: two transposes + the NT split-K product -- F and C
+        are not multiples of the TN kernel's tiles)"""
+        F, ldF, R = self.F, self.ldF, d["B"] * d["Tp"]
+        H.colsum(self.prec, dpre_fb, self.g("fb_model.fc_output_layer.bias"), R, F, ldF, R * ldF, self.sP, 3,
+                 lambda n: self._ws("cs_fc", (n,), torch.float32), H.stream())
+        self._wgrad(d, p, w, "fb_model.fc_output_layer.weight", A=(dpre_fb, F, ldF), rows=(p.Fr, F), B=(d["X"][8], self.ldC),
+                    ncols=self.C, slab=slab, relu_b=1)
+
+    def _bwd_fc(self, d, p, w, dpre_fb):
+        """4. fc_output_layer backward -> dXL[8], the upstream gradient of TCN block 7"""
+        ldC, ldF, R = self.ldC, self.ldF, d["B"] * d["Tp"]
+        if not p.tn_ok:
+            self._fc_wgrad(d, p, w, dpre_fb, w.slab2)     # tA / tB / slab2 are re-used by the TCN blocks: the product stays in line
+        gemm_nt(self.prec, EPI_MASK_POS, A=(dpre_fb, ldF, R * ldF), B=(self.WfcT, ldF, ldC * ldF), C=(w.dXL[8], ldC, R * ldC),
+                res=(d["X"][8], ldC, R * ldC), R=R, N=ldC, K=ldF, Tp=d["Tp"], Tv=d["Tv"], Nv=self.C, batch=3, colpart=w.cpL[7],
+                stream=H.stream())
+
+    def _tcn_mid_finish(self, d, p, w, Pmid, lo, hi):
+        """finishing pass of the fused middle backwards of blocks lo .. hi-1: their partial rows summed into the parameter gradients"""
+        pre, ldC, R = f"fb_model.sequence_model.{lo}.", self.ldC, d["B"] * d["Tp"]
+        lay = self.fp.off["fb_model.sequence_model.1.conv1x1.weight"][0] - self.fp.off["fb_model.sequence_model.0.conv1x1.weight"][0]
+        H.call("nppc_tcn_mid_bwd_finish", Pmid[lo], Pmid.shape[1], w.cpL[lo], 3 * (R // 128) * ldC, R // 128, ldC, self.C,
+               *[self.g(pre + n) for n in TCN_MID_GRADS], self.g(pre + "sconv.bias") if p.cs_ok else None,
+               d["B"], TCN_HIDDEN, self.sP, lay, 3, hi - lo, H.stream())
+
+    def _tcn_wgrad_parity(self, d, p, w, i):
+        """the two weight gradients of TCN block i where the TN GEMM does not apply (fp32 parity mode, row counts no multiple of
+        64 * S2), in line on the main stream: sconv.weight [C][512] from (dXo, a2), conv1x1.weight [512][C] from (dpre1, Xin)"""
+        C, ldC, pre = self.C, self.ldC, f"fb_model.sequence_model.{i}."
+        self._wgrad(d, p, w, pre + "sconv.weight", A=(w.dXL[i + 1], ldC, ldC), rows=(p.Cr, C), B=(w.a2L[i], TCN_HIDDEN),
+                    ncols=TCN_HIDDEN, slab=w.slab2)
+        self._wgrad(d, p, w, pre + "conv1x1.weight", A=(w.h2L[i], TCN_HIDDEN, TCN_HIDDEN), rows=(TCN_HIDDEN, TCN_HIDDEN),
+                    B=(d["X"][i], ldC), ncols=C, slab=w.slab2)
+
+    def _announce_blocks_7_4(self, G):
+        for br in BRANCHES:
+            a = self.fp.off[f"fb_model{br}.sequence_model.4.conv1x1.weight"][0]
+            b, shp = self.fp.off[f"fb_model{br}.sequence_model.7.sconv.bias"]
+            self.grad_range_hook(G, a, b + int(np.prod(shp)))
+
+    def _bwd_tcn(self, d, p, w, G):
+        """5. TCN blocks in reverse -> dXL[0], the gradient of the TCN input X[0]"""
+        s, prec, B, Tp, Tv, C, ldC, sP = H.stream(), self.prec, d["B"], d["Tp"], d["Tv"], self.C, self.ldC, self.sP
+        R, sAct = B * Tp, B * Tp * TCN_HIDDEN
+        h1b =self._ws("h1b", (3, B, Tp, TCN_HIDDEN))
+        Smid = self._ws("Smid", (3, B, TCN_HIDDEN // 64, 8), torch.float64)      # channel-group shares of the per-sample sums
         # partial rows of the fused middle backward, one set per TCN block: their finishing pass (sum over the samples into the
         # parameter gradients) runs as ONE launch for all eight blocks behind the loop -- or as two (blocks 7..4, then 3..0) when the
         # data-parallel exchange sends blocks 7..4 early.  Eight 5-us launches each waited up to 0.5 ms for CUs beside the
         # weight-gradient GEMMs of the side queue (profiles/r03_bench_c2_bf16_windows.txt)
-        n_part = H.mid_bwd_part_elems(B, TCN_HIDDEN, Tp, 3)
-        Pmid = ws("Pmid", (8, n_part), torch.float32)
-        lay = self.fp.off["fb_model.sequence_model.1.conv1x1.weight"][0] - self.fp.off["fb_model.sequence_model.0.conv1x1.weight"][0]
-
-        def finish_mid(lo, hi):
-            """finishing pass of blocks lo .. hi-1"""
-            pre_ = f"fb_model.sequence_model.{lo}."
-            H.call("nppc_tcn_mid_bwd_finish", Pmid[lo], n_part, cpL[lo] if cs_ok else None, 3 * (R // 128) * ldC, R // 128, ldC, C,
-                   self.g(pre_ + "norm2.weight"), self.g(pre_ + "norm2.bias"), self.g(pre_ + "norm1.weight"), self.g(pre_ + "norm1.bias"),
-                   self.g(pre_ + "depthwise_conv.weight"), self.g(pre_ + "depthwise_conv.bias"), self.g(pre_ + "prelu1.weight"),
-                   self.g(pre_ + "prelu2.weight"), self.g(pre_ + "conv1x1.bias"), self.g(pre_ + "sconv.bias") if cs_ok else None,
-                   B, TCN_HIDDEN, sP, lay, 3, hi - lo, s)
-        early = self.grad_range_hook is not None and self.early_buckets_ok
-        dXo, dXi = dXa, dXb
+        Pmid = self._ws("Pmid", (8, H.mid_bwd_part_elems(B, TCN_HIDDEN, Tp, 3)), torch.float32)
         for i in range(7, -1, -1):
             pre = f"fb_model.sequence_model.{i}."
-            dil = TCN_DILATIONS[i]
-            st1, st2 = d["stats"][i, 0], d["stats"][i, 1]
-            y1, y2, Xin = d["y1"][i], d["y2"][i], d["X"][i]
-            if tn_ok:
-                dXo, dXi, a2, h2b = dXL[i + 1], dXL[i], a2L[i], h2L[i]
-            else:
-                a2 = d["a2"]
-            if not cs_ok:
+            dXo, dXi, a2, h2b = w.dXL[i + 1], w.dXL[i], w.a2L[i], w.h2L[i]
+            if not p.cs_ok:                   # no column sums from the producing GEMM: a pass over dXo for the sconv bias gradient
                 H.colsum(prec, dXo, self.g(pre + "sconv.bias"), R, C, ldC, R * ldC, sP, 3,
-                         lambda n: ws("cs_sconv", (n,), torch.float32), s)
+                         lambda n: self._ws("cs_sconv", (n,), torch.float32), s)
             # dA2 = dXo W2  (gradient of the normalised depthwise output)
-            H.call("nppc_gemm_nt", prec, EPI_PLAIN, dXo, ldC, R * ldC, self.W2T[i], ldC, TCN_HIDDEN * ldC, h1b, TCN_HIDDEN,
-                   sAct, None, 0, None, 0, 0, None, 0, None, 0, R, TCN_HIDDEN, ldC, Tp, Tv, TCN_HIDDEN, 0, 3, 1, s)
+            gemm_nt(prec, EPI_PLAIN, A=(dXo, ldC, R * ldC), B=(self.W2T[i], ldC, TCN_HIDDEN * ldC), C=(h1b, TCN_HIDDEN, sAct),
+                    R=R, N=TCN_HIDDEN, K=ldC, Tp=Tp, Tv=Tv, Nv=TCN_HIDDEN, batch=3, stream=s)
             # GroupNorm-2, PReLU-2, depthwise conv, GroupNorm-1, PReLU-1 backward in one reduce + one apply pass: h1b -> h2b
             # (= gradient of the conv1x1 output) with every parameter gradient of those stages and the conv1x1 bias gradient;
             # the reduce pass also leaves a2 = GN2(y2), the operand of the sconv weight gradient
-            H.call("nppc_tcn_mid_bwd", prec, h1b, y2, y1, st1, st2, Smid, Pmid[i], self.p(pre + "norm1.weight"), self.p(pre + "norm1.bias"),
-                   self.p(pre + "norm2.weight"), self.p(pre + "norm2.bias"), self.p(pre + "depthwise_conv.weight"),
-                   self.p(pre + "prelu1.weight"), self.p(pre + "prelu2.weight"), a2, h2b, self.g(pre + "norm2.weight"),
-                   self.g(pre + "norm2.bias"), self.g(pre + "norm1.weight"), self.g(pre + "norm1.bias"),
-                   self.g(pre + "depthwise_conv.weight"), self.g(pre + "depthwise_conv.bias"), self.g(pre + "prelu1.weight"),
-                   self.g(pre + "prelu2.weight"), self.g(pre + "conv1x1.bias"),
-                   cpL[i] if cs_ok else None, R // 128, ldC, C, self.g(pre + "sconv.bias") if cs_ok else None,
-                   B, TCN_HIDDEN, Tp, Tv, dil, 1e-8, sAct, B * 2, sP, 3, 0, s)
-            if i == 4 and early:
-                finish_mid(4, 8)              # blocks 7..4 are handed to the exchange below: their gradients must be final
+            H.call("nppc_tcn_mid_bwd", prec, h1b, d["y2"][i], d["y1"][i], d["stats"][i, 0], d["stats"][i, 1], Smid, Pmid[i],
+                   self.p(pre + "norm1.weight"), self.p(pre + "norm1.bias"), self.p(pre + "norm2.weight"), self.p(pre + "norm2.bias"),
+                   self.p(pre + "depthwise_conv.weight"), self.p(pre + "prelu1.weight"), self.p(pre + "prelu2.weight"), a2, h2b,
+                   *[self.g(pre + n) for n in TCN_MID_GRADS], w.cpL[i], R // 128, ldC, C, self.g(pre + "sconv.bias") if p.cs_ok else None,
+                   B, TCN_HIDDEN, Tp, Tv, TCN_DILATIONS[i], 1e-8, sAct, B * 2, sP, 3, 0, s)
+            if i == 4 and p.early:
+                self._tcn_mid_finish(d, p, w, Pmid, 4, 8)     # blocks 7..4 are handed to the exchange below: their gradients must be final
             # sconv weight gradient dW2[c][k] = sum_r dXo[r][c] * a2[r][k] and conv1x1 weight gradient dW1[k][c] = sum_r
-            # dpre1[r][k] * Xin[r][c]
-            if tn_ok:
-                # row-major operands as they are, all blocks x branches of a kind in ONE grouped launch on the side queue, written
-                # finished into the flat gradient (no split-K slabs, no reductions): issued once the main chain has produced the
+            # dpre1[r][k] * Xin[r][c] (the conv1x1 bias gradient came out of the fused kernel)
+            if not p.tn_ok:
+                self._tcn_wgrad_parity(d, p, w, i)
+            elif i == 0 or (i == 4 and p.early):
+                # all blocks x branches of a kind in ONE grouped launch on the side queue, issued once the main chain has produced the
                 # operands of the last block of the group -- block 0, or block 4 and then block 0 when blocks 7..4 leave early
-                if i == 0 or (i == 4 and early):
-                    on_side(lambda blocks=tuple(range(3 if early and i == 0 else 7, i - 1, -1)): tcn_wgrad(blocks))
-            else:
-                H.call("nppc_transpose", prec, dXo, tA, R, ldC, ldC, R, R * ldC, sTA, 0, 3, s)
-                H.call("nppc_transpose", prec, a2, tB, R, TCN_HIDDEN, TCN_HIDDEN, R, sAct, sTB, 0, 3, s)
-                self._wgrad(tA, R, sTA, tB, R, sTB, Cr, TCN_HIDDEN, R, S2, pre + "sconv.weight", TCN_HIDDEN, C, TCN_HIDDEN,
-                            slab2, batch=3, sDst=sP)
-            # conv1x1: weight, input gradients (the bias gradient came out of the fused kernel)
-            if not tn_ok:
-                H.call("nppc_transpose", prec, h2b, tA, R, TCN_HIDDEN, TCN_HIDDEN, R, sAct, sTA, 0, 3, s)
-                H.call("nppc_transpose", prec, Xin, tB, R, ldC, ldC, R, R * ldC, sTB, 0, 3, s)
-                self._wgrad(tA, R, sTA, tB, R, sTB, TCN_HIDDEN, ldC, R, S2, pre + "conv1x1.weight", C, TCN_HIDDEN, C, slab2,
-                            batch=3, sDst=sP)
-            if cs_ok and i > 0:
-                H.call("nppc_gemm_nt_colsum", prec, EPI_RESIDUAL, h2b, TCN_HIDDEN, sAct, self.W1T[i], TCN_HIDDEN, ldC * TCN_HIDDEN,
-                       dXi, ldC, R * ldC, None, 0, dXo, ldC, R * ldC, R, ldC, TCN_HIDDEN, Tp, Tv, C, 3, cpL[i - 1], s)
-            else:
-                H.call("nppc_gemm_nt", prec, EPI_RESIDUAL, h2b, TCN_HIDDEN, sAct, self.W1T[i], TCN_HIDDEN, ldC * TCN_HIDDEN, dXi, ldC,
-                       R * ldC, None, 0, dXo, ldC, R * ldC, None, 0, None, 0, R, ldC, TCN_HIDDEN, Tp, Tv, C, 0, 3, 1, s)
-            dXo, dXi = dXi, dXo
-            if i == 4 and self.grad_range_hook is not None and self.early_buckets_ok:
-                # TCN blocks 7..4 of every branch are final once both queues have passed this point
-                def blocks_done():
-                    for br in BRANCHES:
-                        a = self.fp.off[f"fb_model{br}.sequence_model.4.conv1x1.weight"][0]
-                        b, shp = self.fp.off[f"fb_model{br}.sequence_model.7.sconv.bias"]
-                        self.grad_range_hook(G, a, b + int(np.prod(shp)))
-                on_side(blocks_done)
-        finish_mid(0, 4 if early else 8)
-        if tn_ok:
-            dXo = dXL[0]
+                blocks = tuple(range(3 if p.early and i == 0 else 7, i - 1, -1))
+                self._on_side(lambda: self._tcn_wgrad_grouped(d, w, G, blocks))
+            # conv1x1 input gradient + the residual path; its column sums are block i-1's sconv bias gradient
+            gemm_nt(prec, EPI_RESIDUAL, A=(h2b, TCN_HIDDEN, sAct), B=(self.W1T[i], TCN_HIDDEN, ldC * TCN_HIDDEN), C=(dXi, ldC, R * ldC),
+                    res=(dXo, ldC, R * ldC), R=R, N=ldC, K=TCN_HIDDEN, Tp=Tp, Tv=Tv, Nv=C, batch=3,
+                    colpart=w.cpL[i - 1] if i > 0 else None, stream=s)
+            if i == 4 and p.early:            # TCN blocks 7..4 of every branch are final once both queues have passed this point
+                self._on_side(lambda: self._announce_blocks_7_4(G))
+        self._tcn_mid_finish(d, p, w, Pmid, 0, 4 if p.early else 8)
+        return w.dXL[0]
+
+    def _bwd_tsse(self, d, dX0, dx, Dsb):
+        """6. TSSE attention backward (parameter gradients only: the maps are data)"""
+        s, B, T, Tp, F, ldC = H.stream(), d["B"], d["T"], d["Tp"], self.F, self.ldC
         if self.nm == 1:
             # the restorer's sub-band rows unfold the attention-scaled magnitude X[0][0] (fullsubnet_plus.py:200-204), a
             # trainable tensor: the gradient of those columns joins the TCN-input gradient of branch 0 (the direction net
             # unfolds the raw magnitude, a constant: nothing to add there)
-            H.call("nppc_subband_unfold_bwd", prec, dx, d["sbscale"], Dsb, self.mult, dXo[0], ldC, B, F, Tp, Tv, self.nb, self.G,
-                   self.KX, s)
-        # ---- 7. TSSE attention backward (parameter gradients only: the maps are data)
+            H.call("nppc_subband_unfold_bwd", self.prec, dx, d["sbscale"], Dsb, self.mult, dX0[0], ldC, B, F, Tp, d["Tv"], self.nb,
+                   self.G, self.KX, s)
         sv = d["tsse_saved"]
         n_ws = ctypes.c_long()
         H.call("nppc_tsse_bwd_ws_elems", 3 * self.nm, B, F, self.ks[0], self.ks[1], self.ks[2], ctypes.byref(n_ws))
-        dsg = ws("dsg", (n_ws.value,), torch.float32)      # per map: dsg | da2 | da1 | per-sample contributions (csrc/spec.hip)
-        att = "channel_attention."
-        H.call("nppc_tsse_bwd_maps", prec, dXo, R * ldC, H.ptr_array(d["maps"]), 3 * self.nm, d["rs"],
-               self.p(att + "smallConv1d.0.weight"), self.p(att + "middleConv1d.0.weight"), self.p(att + "largeConv1d.0.weight"),
-               self.ks[0], self.ks[1], self.ks[2], self.p(att + "feature_concate_fc.weight"), self.p(att + "fc1.weight"),
-               self.p(att + "fc2.weight"), self.sAtt, sv["ns"], sv["pre"], sv["sq"], sv["h1"], sv["sg"], dsg,
-               self.g(att + "smallConv1d.0.weight"), self.g(att + "smallConv1d.0.bias"),
-               self.g(att + "middleConv1d.0.weight"), self.g(att + "middleConv1d.0.bias"),
-               self.g(att + "largeConv1d.0.weight"), self.g(att + "largeConv1d.0.bias"),
-               self.g(att + "feature_concate_fc.weight"), self.g(att + "feature_concate_fc.bias"),
-               self.g(att + "fc1.weight"), self.g(att + "fc1.bias"), self.g(att + "fc2.weight"), self.g(att + "fc2.bias"),
-               B, F, T, self.la, Tp, ldC, s)
-        if tn_ok:
-            fc_wgrad(ws("slab_fc", (3 * S2 * Fr * ldC,), torch.float32))
+        dsg = self._ws("dsg", (n_ws.value,), torch.float32)      # per map: dsg | da2 | da1 | per-sample contributions (csrc/spec.hip)
+        wts = [self.p(n) for n in TSSE_PARAMS if n.endswith(".weight")]      # the weights of the three convs, the three Linears
+        H.call("nppc_tsse_bwd_maps", self.prec, dX0, B * Tp * ldC, H.ptr_array(d["maps"]), 3 * self.nm, d["rs"], *wts[:3],
+               self.ks[0], self.ks[1], self.ks[2], *wts[3:], self.sAtt, sv["ns"], sv["pre"], sv["sq"], sv["h1"], sv["sg"], dsg,
+               *[self.g(n) for n in TSSE_PARAMS], B, F, T, self.la, Tp, ldC, s)
+
+    def _bwd_fc_wgrad_join(self, d, p, w, dpre_fb):
+        """7. the deferred fc_output_layer weight gradient, and the join of the weight-gradient stream"""
+        if p.tn_ok:
+            # bf16: the product waits until the END of the main chain -- the side queue (LSTM + TCN weight gradients) is the longer
+            # one, the main queue would idle in front of the join -- with a slab of its own
+            self._fc_wgrad(d, p, w, dpre_fb, self._ws("slab_fc", (3 * p.S2 * p.Fr * self.ldC,), torch.float32))
         if self.defer_join:
             self.join_pending = True          # joined (join_side) before anything reads the gradient
             FSNEngine._unjoined[id(self)] = self
         else:
             torch.cuda.current_stream().wait_stream(self._side)       # join the weight-gradient stream
-        return G
 
     def side_stream(self):
         return self._side
@@ -827,11 +831,7 @@ class FSNEngine:
     def prepack_on_side(self):
         """re-pack the (just updated) weights on the side stream behind everything the current stream has been given so far;
         the caller joins (join_side) before the packed copies are used and before the next cooperative LSTM launch"""
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        with torch.cuda.stream(self._side):
-            self._side.wait_event(ev)
-            self.pack_weights()
+        self._on_side(self.pack_weights)
         self.join_pending = True
         FSNEngine._unjoined[id(self)] = self
 
