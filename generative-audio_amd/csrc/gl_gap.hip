@@ -418,4 +418,14 @@ int nppc_gl_gap_pc(const float* pred, const float* pc, const float* mean, const 
                 L, n_iter, momentum, max_span, stream);
 }
 
+int nppc_gl_gap_post(const float* pred, const float* pc, const float* mean, const float* stdev, const float* z,
+                     const float* known_spec, const float* mask, const float* init_phase, float* out, double* dist,
+                     double* target_norm, int* status, void* work, long work_bytes, int B, int K, int S, int T, int nfft, int hop,
+                     int L, int n_iter, double momentum, int max_span, void* stream) {
+  GlMag ms;
+  if (gl_mag_post(pred, pc, mean, stdev, z, K, S, &ms) != NPPC_OK) return NPPC_EBADARG;
+  return gl_run(ms, known_spec, mask, init_phase, 0, out, dist, target_norm, status, work, work_bytes, B, S + 1, T, nfft, hop, L,
+                n_iter, momentum, max_span, stream);
+}
+
 }  // extern "C"

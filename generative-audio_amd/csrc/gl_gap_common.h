@@ -46,6 +46,8 @@ struct GlMag {
   const float* target;                       // [B][V][F][T], or null:
   const float *pred, *pc, *mean, *stdev, *alphas;
   int K, A;
+  const float* z;                            // [B][S][K] posterior coefficients, or null; then V = S + 1
+  int S;
 };
 
 inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
@@ -63,6 +65,17 @@ inline int gl_mag_pc(const float* pred, const float* pc, const float* mean, cons
   if (!pred || !pc || !mean || !stdev || !alphas || K <= 0 || A <= 0 || (long)K * A + 1 > 65535) return NPPC_EBADARG;
   *ms = {};
   ms->pred = pred, ms->pc = pc, ms->mean = mean, ms->stdev = stdev, ms->alphas = alphas, ms->K = K, ms->A = A;
+  return NPPC_OK;
+}
+
+// magnitudes of posterior samples (csrc/inpaint_posterior.hip states the rule): V = S + 1, v < S:
+// exp((pred + sum_k z[b][v][k] pc[b][k]) stdev + mean), v = S: the prediction (z = 0)
+inline int gl_mag_post(const float* pred, const float* pc, const float* mean, const float* stdev, const float* z, int K, int S,
+                       GlMag* ms) {
+  if (!pred || !pc || !mean || !stdev || !z || K <= 0 || K > NPPC_INP_POST_MAX_K || S <= 0 || (long)S + 1 > 65535)
+    return NPPC_EBADARG;
+  *ms = {};
+  ms->pred = pred, ms->pc = pc, ms->mean = mean, ms->stdev = stdev, ms->z = z, ms->K = K, ms->S = S;
   return NPPC_OK;
 }
 
@@ -101,6 +114,9 @@ struct GlMagRow {
   const float* ph;     // initial phase
   double alpha, mean, sd;
   bool form;           // magnitude = exp((tm + alpha dir) sd + mean)
+  const float* z;      // posterior sample: K coefficients, dir = direction 0 of K rows FT apart; null otherwise
+  int K;
+  size_t FT;
 };
 
 __device__ __forceinline__ GlMagRow gl_mag_row(const GlMag& ms, const float* phase, int phase_per_v, int b, int v, int V, size_t FT) {
@@ -109,9 +125,19 @@ __device__ __forceinline__ GlMagRow gl_mag_row(const GlMag& ms, const float* pha
   s.dir = nullptr;
   s.alpha = 0.0, s.mean = 0.0, s.sd = 1.0;
   s.form = !ms.target;
+  s.z = nullptr;
+  s.K = 0, s.FT = FT;
   if (ms.target)
     s.tm = ms.target + ((size_t)b * V + v) * FT;
-  else {
+  else if (ms.z) {
+    s.tm = ms.pred + (size_t)b * FT;
+    s.mean = (double)*ms.mean, s.sd = (double)*ms.stdev;
+    if (v < ms.S) {
+      s.dir = ms.pc + (size_t)b * ms.K * FT;
+      s.z = ms.z + ((size_t)b * ms.S + v) * ms.K;
+      s.K = ms.K;
+    }
+  } else {
     s.tm = ms.pred + (size_t)b * FT;
     s.mean = (double)*ms.mean, s.sd = (double)*ms.stdev;
     if (v < ms.K * ms.A) {
@@ -132,7 +158,10 @@ __device__ __forceinline__ double gl_init_bin(double tn, const GlMagRow& s, cons
   if (m[t] == 0.f) {
     const size_t o = (size_t)k * T + t;
     double mag = (double)s.tm[o];
-    if (s.form) mag = exp((mag + (s.dir ? s.alpha * (double)s.dir[o] : 0.0)) * s.sd + s.mean);
+    if (s.z) {                                                 // the posterior rule: k ascending, fused as the line below compiles
+      for (int j = 0; j < s.K; ++j) mag = __builtin_fma((double)s.z[j], (double)s.dir[j * s.FT + o], mag);
+      mag = exp(__builtin_fma(mag, s.sd, s.mean));
+    } else if (s.form) mag = exp((mag + (s.dir ? s.alpha * (double)s.dir[o] : 0.0)) * s.sd + s.mean);
     mg = (float)mag;
     double sn, cs;
     sincos((double)s.ph[o], &sn, &cs);

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "fft_core.h"
 #include "nppc_hip.h"
+#include "post_stats.h"
 
 #include <type_traits>
 
@@ -193,22 +194,6 @@ __global__ __launch_bounds__(256) void post_sample_kernel(PostArgs a) {
   }
 }
 
-// the tiles' partial sums folded in tile order -> mean, unbiased standard deviation.  part [tiles][n], out [n].
-__global__ __launch_bounds__(256) void post_finish_kernel(const double2* __restrict__ part, size_t n, int tiles, int S,
-                                                          float* __restrict__ mean, float* __restrict__ sd) {
-  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int t = 0; t < tiles; ++t) {
-      const double2 v = part[(size_t)t * n + e];
-      s1 += v.x;
-      s2 += v.y;
-    }
-    const double var = (s2 - s1 * s1 / S) / (S - 1);
-    mean[e] = (float)(s1 / S);
-    sd[e] = (float)sqrt(var > 0.0 ? var : 0.0);
-  }
-}
-
 bool post_config_ok(int nfft, int hop) {
   return (nfft == 64 || nfft == 128 || nfft == 256 || nfft == 512) && hop > 0 && nfft % hop == 0 && nfft / hop <= 8;
 }
@@ -285,12 +270,8 @@ int nppc_post_sample(const float* pred_crm, const float* w_mat, const float* re,
     default: launch(std::integral_constant<int, 9>()); break;
   }
   NPPC_CHECK_LAUNCH();
-  auto finish = [&](const double2* part, size_t n, float* m, float* s) {
-    size_t g = (n + 255) / 256;
-    hipLaunchKernelGGL(post_finish_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, st, part, n, tiles, S, m, s);
-  };
-  if (mean) finish(a.tpart, (size_t)B * ld, mean, std);
-  if (mag_mean) finish(a.mpart, (size_t)B * F * T, mag_mean, mag_std);
+  if (mean) post_finish(a.tpart, (size_t)B * ld, tiles, S, mean, std, st);
+  if (mag_mean) post_finish(a.mpart, (size_t)B * F * T, tiles, S, mag_mean, mag_std, st);
   NPPC_CHECK_LAUNCH();
   return NPPC_OK;
 }

@@ -308,6 +308,10 @@ SIGS = {
     "nppc_enh_splice_host": [P, L, P, L, L, I, I, I, L, P, I, P, P, P, P, L],
     "nppc_post_sample_shape": [I, I, I, I, I, I, L, I, PI, PI, PL],
     "nppc_post_sample": [P, P, P, P, P, P, I, I, I, I, I, I, I, L, P, P, P, P, P, P, L, P],
+    "nppc_inp_post_sample_shape": [I, I, I, I, I, I, I, I, I, PI, PI, PL, PI, PL],
+    "nppc_inp_post_sample": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, P, L, P],
+    "nppc_gl_gap_post": [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, I, I, D, I, P],
+    "nppc_gl_gap_post_long": [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, I, I, D, I, I, I, P],
     "nppc_flac_probe": [P, L, P, P],
     "nppc_flac_decode_host": [P, L, P, L, P, L, P],
     "nppc_flac_work_elems": [L, PL],

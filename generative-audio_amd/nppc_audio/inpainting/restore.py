@@ -229,7 +229,24 @@ class RecordingRestorer:
         c = self.config
         return plan_windows(length, gaps, c.window_samples, c.crossfade_samples, c.n_fft, c.hop_length, c.long_gaps)
 
-    def restore(self, wave, gaps, alphas=None, variations="windows", sample_rate=None):
+    def _check_samples(self, samples, coeffs, n_windows):
+        """the refusals of restore(samples=, coeffs=), from the plan and the configuration alone -> S, or None when no
+        samples are asked for"""
+        if samples is None and coeffs is None:
+            return None
+        K = int(self.config.model_configuration.audio_pc_wrapper_configuration.n_dirs)
+        if coeffs is not None:
+            from .posterior import as_coefficients
+            z = as_coefficients(coeffs)
+            if z.shape[0] != n_windows or z.shape[2] != K or z.shape[1] < 1 or (samples is not None and z.shape[1] != int(samples)):
+                raise ValueError(f"coeffs {tuple(z.shape)}: one draw per window and sample, [W, S, K] = [{n_windows}, "
+                                 f"{'S' if samples is None else int(samples)}, {K}]")
+            return int(z.shape[1])
+        if isinstance(samples, bool) or int(samples) != samples or int(samples) < 1:
+            raise ValueError(f"samples = {samples!r}: a positive number of posterior samples")
+        return int(samples)
+
+    def restore(self, wave, gaps, alphas=None, variations="windows", sample_rate=None, samples=None, seed=None, coeffs=None):
         """wave [L] float (host or device), gaps [(start, end)] half-open sample pairs -> dict:
           'restored' [L]; 'windows' (plan_windows' list); 'gain' (fp64 device scalar [1]); 'inconsistency' [W, V, gl_iters],
           'target_norm' [W, V], 'status' [W] as phase.griffin_lim_gap reports them, per window (V = 1, or K A + 1 with the
@@ -240,17 +257,28 @@ class RecordingRestorer:
         With no gaps the input comes back as it is (the same tensor) and nothing is launched.  One host read per call: the
         status check at the end.
         sample_rate: None or config.sample_rate runs exactly the above.  Another rate: `wave` and `gaps` are at that rate
-        and so are 'restored' and 'variations' (see _restore_native); 'variation_windows' stay at the model's rate."""
+        and so are 'restored' and 'variations' (see _restore_native); 'variation_windows' stay at the model's rate.
+        samples=S (or coeffs [W, S, K], real) adds S posterior samples of every gap (inpainting.posterior, DESIGN.md
+        section 8n): 'coeffs' [W, S, K], drawn by posterior.draw_coefficients(W, S, K, seed=seed) -- one independent draw
+        per window; plan_windows keeps the gaps apart (each is written back from its own window alone), so no alignment
+        of the directions across windows is needed -- run through posterior.sample_waveforms_blind on the windows:
+        'sample_windows' [W, S, window_samples], divided by the gain, and with variations='full' 'samples' [S, L], in
+        which sample s of the recording takes sample s of every window ('samples' at `sample_rate`, 'sample_windows' at
+        the model's rate, as the variations).  'restored' and every other key are what they are without `samples`;
+        `samples` together with `alphas` returns both.  'sample_status' [W] is the samples' own Griffin-Lim status."""
         if variations not in ("windows", "full"):
             raise ValueError(f"variations = {variations!r}: 'windows' or 'full'")
         if wave.dim() != 1:
             raise ValueError(f"wave {tuple(wave.shape)}: want one channel, [L]")
         c = self.config
         if sample_rate is not None and int(sample_rate) != int(c.sample_rate):
-            return self._restore_native(wave, gaps, alphas, variations, int(sample_rate))
+            return self._restore_native(wave, gaps, alphas, variations, int(sample_rate), samples, seed, coeffs)
         plan = self.plan(wave.numel(), gaps)
+        S = self._check_samples(samples, coeffs, len(plan))
         if not plan:
-            return {"restored": wave, "windows": [], "gain": None, "inconsistency": None, "target_norm": None, "status": None}
+            none = {} if S is None else {"coeffs": None, "sample_windows": None}
+            return {"restored": wave, "windows": [], "gain": None, "inconsistency": None, "target_norm": None, "status": None,
+                    **none}
         H.require_gpu()
         from .data import time_to_spec_mask
         from .utils import preprocess_data
@@ -291,12 +319,24 @@ class RecordingRestorer:
                 if alphas is not None:
                     out["variation_windows"] = var / gain.float()
             out.update(info)
+            if S is not None:
+                from . import posterior as IPOST
+                if alphas is None:
+                    pc = self.model(masked_norm, mask4)
+                    pred = self.model.get_pred_spec_mag_norm(masked_norm, mask4)
+                z = IPOST.as_coefficients(coeffs).to(x.device) if coeffs is not None else IPOST.draw_coefficients(
+                    W, S, pc.shape[1], seed=seed, device=x.device)
+                smp, _, sinfo = IPOST.sample_waveforms_blind(pred, pc, masked, mask_f, z, mean, std, **kw)
+                out["coeffs"], out["sample_status"] = z, sinfo["status"]
+                if variations == "full":
+                    out["samples"] = splice_windows(x, gaps_d, starts_d, smp, gain, c.crossfade_samples)
+                out["sample_windows"] = smp / gain.float()
         if bool(info["status"].any()):                                                  # the one host read
             raise RuntimeError(f"griffin_lim_gap refused windows {info['status'].nonzero().flatten().tolist()}: their gap "
                                "span exceeds the cap (plan_windows should have raised)")
         return out
 
-    def _restore_native(self, wave, gaps, alphas, variations, rate):
+    def _restore_native(self, wave, gaps, alphas, variations, rate, samples=None, seed=None, coeffs=None):
         """restore() for a recording at `rate` != config.sample_rate:
           the recording is resampled to config.sample_rate (nppc_audio.resample, the reference's windowed sinc); every gap
           [s, e) becomes resample.map_gap's [a, b), the outputs the gap's samples reach through the filter, so nothing
@@ -306,12 +346,16 @@ class RecordingRestorer:
           ceil(crossfade_samples rate / config.sample_rate) are merged) the upsampled signal, a raised-cosine blend over
           the native crossfade on both sides, and everywhere else the input's own samples, bit for bit and full band.
         The model is a config.sample_rate model: inside the gaps nothing above config.sample_rate / 2 is synthesised.
+        Posterior samples (samples / seed / coeffs, variations='full') ride through the same resample-up and splice as
+        the K A variations, as S more rows.
         Adds 'sample_rate', 'restored_model_rate' [ceil(L model / rate)], 'gaps_model_rate' (the mapped gaps, in the order
         given) and 'gaps_merged' (the native gaps as spliced).  Still one host read: the inner call's status check."""
         from .. import resample as RSM
         c = self.config
         if rate <= 0:
             raise ValueError(f"sample_rate = {rate}: not a rate")
+        if coeffs is None:
+            self._check_samples(samples, None, 0)                                       # a bad S, before anything is launched
         N = wave.numel()
         pairs = []
         for g in gaps:
@@ -324,6 +368,8 @@ class RecordingRestorer:
             pairs.append((s, e))
         extra = {"sample_rate": rate, "restored_model_rate": None, "gaps_model_rate": [], "gaps_merged": []}
         if not pairs:
+            if self._check_samples(samples, coeffs, 0) is not None:
+                extra.update(coeffs=None, sample_windows=None)
             return {"restored": wave, "windows": [], "gain": None, "inconsistency": None, "target_norm": None,
                     "status": None, **extra}
         down_t, up_t = RSM.sinc_table(rate, c.sample_rate), RSM.sinc_table(c.sample_rate, rate)
@@ -341,12 +387,14 @@ class RecordingRestorer:
         x = wave.to(self.device).float().contiguous()
         with torch.no_grad():
             low = RSM.resample(x, rate, c.sample_rate, backend="hip")
-            out = self.restore(low, mapped, alphas, variations)
+            out = self.restore(low, mapped, alphas, variations, samples=samples, seed=seed, coeffs=coeffs)
+            rows = []
             if "variations" in out:
                 K, A = out["variations"].shape[:2]
-                stack = torch.cat([out["variations"].reshape(K * A, -1), out["restored"][None]])
-            else:
-                stack = out["restored"][None]
+                rows.append(out["variations"].reshape(K * A, -1))
+            if "samples" in out:
+                rows.append(out["samples"])
+            stack = torch.cat(rows + [out["restored"][None]]) if rows else out["restored"][None]
             up = RSM.resample(stack, c.sample_rate, rate, backend="hip")                # [V, >= N], one batched launch
             gaps_d = torch.tensor(merged, dtype=torch.int64).to(x.device)
             zeros = torch.zeros(len(merged), dtype=torch.int64, device=x.device)
@@ -357,7 +405,9 @@ class RecordingRestorer:
         out["restored_model_rate"] = out["restored"]
         out["restored"] = full[V - 1]
         if "variations" in out:
-            out["variations"] = full[:V - 1].view(K, A, N)
+            out["variations"] = full[:K * A].view(K, A, N)
+        if "samples" in out:
+            out["samples"] = full[V - 1 - out["samples"].shape[0]:V - 1]
         out.update(sample_rate=rate, gaps_model_rate=mapped, gaps_merged=merged)
         return out
 
@@ -421,7 +471,8 @@ class RecordingRestorer:
     def save_variations(self, out, directory, fmt="flac", alphas=None):
         """restore's dict -> <directory>/restored.<ext> and, when it holds 'variations' [K, A, L] (restore(..., alphas,
         variations="full")), <directory>/pc_<k+1>/alpha_<a:.1f>.<ext>: 16-bit mono at the rate of the dict.  fmt "flac"
-        encodes every waveform in one device call (flac.encode_waves), "wav" writes the same samples.  alphas: the sweep,
+        encodes every waveform in one device call (flac.encode_waves), "wav" writes the same samples.  When it holds
+        'samples' [S, L] (restore(..., samples=S, variations="full")) also <directory>/posterior/sample_<s>.<ext>.  alphas: the sweep,
         when the dict does not carry it ('alphas', which restore adds).  -> the paths written"""
         import os
         from ..flac import write_waves
@@ -436,6 +487,10 @@ class RecordingRestorer:
                 raise ValueError(f"{len(alphas)} alphas for {A} variations per direction")
             paths += [os.path.join(str(directory), f"pc_{k + 1}", f"alpha_{a:.1f}.{fmt}") for k in range(K) for a in alphas]
             waves.append(var.reshape(K * A, L))
+        if out.get("samples") is not None:
+            smp = out["samples"]
+            paths += [os.path.join(str(directory), "posterior", f"sample_{i}.{fmt}") for i in range(smp.shape[0])]
+            waves.append(smp)
         write_waves(paths, torch.cat([w.to(self.device).float() for w in waves]) if fmt == "flac"
                     else torch.cat([w.float().cpu() for w in waves]), rate, fmt)
         return paths

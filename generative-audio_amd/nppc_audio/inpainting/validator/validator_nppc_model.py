@@ -48,7 +48,8 @@ from ..utils import preprocess_data
 
 __all__ = ["NPPCModelValidatorConfig", "NPPCModelValidator", "pc_audio_variations", "compute_metrics",
            "compute_metrics_batch", "save_metrics_to_json", "default_alphas", "save_pc_audio_variations",
-           "save_pc_spectrograms", "pc_spectrogram_sheets", "save_pc_pitch_plots", "pitch_windows"]
+           "save_pc_spectrograms", "pc_spectrogram_sheets", "save_pc_pitch_plots", "pitch_windows", "save_posterior_samples",
+           "posterior_std_planes"]
 
 compute_metrics = MB.compute_metrics
 compute_metrics_batch = MB.compute_metrics_batch
@@ -198,6 +199,51 @@ def save_pc_spectrograms(out, save_dir, alphas, first_index=0, max_dirs=None, in
     return paths
 
 
+def posterior_std_planes(out):
+    """the plane save_posterior_samples draws, [B,1,2,F,T] complex (imaginary part 0): 'mag_std' on the gap frames and NaN
+    on the known ones, where the directions are zero and the spread with them, so a cell's autoscale sees the gap alone"""
+    sd, mask4 = out["posterior"]["mag_std"], out["mask"]
+    B, F, T = sd.shape
+    gap = mask4.detach().float().reshape(B, -1, F, T)[:, 0] == 0
+    re = torch.where(gap, sd.detach().float(), torch.full_like(sd, float("nan")))
+    return torch.stack([re, torch.zeros_like(re)], 1)[:, None].contiguous()
+
+
+def save_posterior_samples(out, save_dir, first_index=0, fmt="flac", sample_rate=16000, backend="auto", sx=2, sy=2,
+                           palette="viridis", max_frames=None):
+    """from the dict of validate_batch(..., posterior_samples=S) writes, for sample b of the batch, under
+    <save_dir>/sample_<first_index + b>/posterior/
+        sample_<s>.<ext>          'posterior'['samples'][b, s] (and sample_<s>_blind.<ext> when the dict holds 'samples_blind'),
+                                  16-bit mono: fmt "flac" encodes all of them in one device call (flac.write_waves), "wav" writes
+                                  the same samples
+        std_spec.png              'posterior'['mag_std'][b] in dB (20 log10(std + 1e-8), autoscaled over the gap) over the
+                                  reference's context window with the gap markers (spectrogram_png: one Sheet per item, all
+                                  drawn and encoded in one device call); known frames, where the spread is zero, take index 0
+    -> the paths written"""
+    from ... import flac as FL
+    from ... import png as PNG
+    from ...spectrogram_png import Cell, Sheet, render_png, windows_from_mask
+    if "posterior" not in out:
+        raise ValueError("save_posterior_samples takes the dict of validate_batch(..., posterior_samples=S), which holds 'posterior'")
+    post = out["posterior"]
+    smp = post["samples"]
+    B, S, L = smp.shape
+    root = Path(save_dir)
+    folder = lambda b: root / f"sample_{first_index + b}" / "posterior"
+    paths, waves = [folder(b) / f"sample_{s}.{fmt}" for b in range(B) for s in range(S)], [smp.reshape(B * S, L)]
+    if "samples_blind" in post:
+        paths += [folder(b) / f"sample_{s}_blind.{fmt}" for b in range(B) for s in range(S)]
+        waves.append(post["samples_blind"].reshape(B * S, L))
+    FL.write_waves(paths, torch.cat([w.float() for w in waves]), sample_rate, fmt, backend=backend)
+    planes = posterior_std_planes(out)
+    F, T = planes.shape[-2:]
+    win = windows_from_mask(out["mask"].detach().float().reshape(B, -1, F, T)[:, 0, 0, :])
+    sheets = [Sheet(b, [[Cell(p=0, g="db", markers=True)]], sx=sx, sy=sy) for b in range(B)]
+    pngs = [folder(b) / "std_spec.png" for b in range(B)]
+    PNG.write_files(pngs, render_png(planes, sheets, win, palette=palette, max_frames=max_frames))
+    return paths + pngs
+
+
 PITCH_RANGE, PITCH_SR, PITCH_HOP = (80.0, 400.0), 16000, 512          # validate_batch's pYIN setting (plot_pitch_comparison :60-66)
 
 
@@ -326,7 +372,7 @@ class NPPCModelValidator:
 
     def validate_batch(self, masked_spec, mask, clean_spec, n_mc_samples=50, n_components=5, alphas=None, n_fft=255,
                        hop_length=128, pitch=False, phase="clean", gl_iters=32, ragged_gaps=False, long_spans=False,
-                       spectrograms=False):
+                       spectrograms=False, posterior_samples=None, posterior_seed=None):
         """validate_sample + _validate_with_baseline (:930-1027) for a uniform batch: masked_spec, clean_spec [B,2,F,T],
         mask [B,T] (1 = known; the same number of gap frames in every item) -> dict with 'pc_directions' [B,K,F,T],
         'pred_spec_mag_norm', 'clean_spec_mag_norm', 'mask' [B,1,F,T], 'mean', 'std', 'mc_dropout' (calculate_unet_baseline's
@@ -349,12 +395,23 @@ class NPPCModelValidator:
         and shapes are the same.  The default keeps raising ValueError for such a batch.
 
         spectrograms=True adds 'masked_spec_mag_norm' [B,1,F,T], the normalised masked input, which save_pc_spectrograms
-        draws beside the clean and the restored spectrogram; the default returns the keys it always returned."""
+        draws beside the clean and the restored spectrogram; the default returns the keys it always returned.
+
+        posterior_samples=S (2 <= S <= 4096) adds 'posterior' (inpainting.posterior): 'coeffs' [B,S,K]
+        drawn by draw_coefficients(seed=posterior_seed), 'samples' [B,S,L] on the clean phase, their per-sample 'std' [B,L]
+        and the spread 'mag_std' [B,F,T] of the linear magnitudes; with phase="griffin_lim" (which then does not need
+        `alphas`) also 'samples_blind' [B,S,L] from the damaged recording's STFT and their 'phase_info'.  Without it the call
+        returns exactly the keys it returned before."""
+        S_post = None
+        if posterior_samples is not None:
+            S_post = int(posterior_samples)
+            if isinstance(posterior_samples, bool) or S_post != posterior_samples or not 2 <= S_post <= 4096:
+                raise ValueError(f"posterior_samples = {posterior_samples!r}: 2 .. 4096 samples (their spread is part of the result)")
         if phase not in ("clean", "griffin_lim"):
             raise ValueError(f"phase = {phase!r}: 'clean' or 'griffin_lim'")
         if pitch and alphas is None:
             raise ValueError("pitch=True tracks the f0 of the PC audio variations: pass `alphas` (e.g. default_alphas())")
-        if phase == "griffin_lim" and alphas is None:
+        if phase == "griffin_lim" and alphas is None and S_post is None:
             raise ValueError("phase='griffin_lim' synthesises the PC audio variations: pass `alphas` (e.g. default_alphas())")
         masked_dev = masked_spec.to(self.device) if phase == "griffin_lim" else None
         out = self._run_batch(masked_spec, mask, clean_spec, n_mc_samples, n_components, ragged_gaps)
@@ -375,6 +432,19 @@ class NPPCModelValidator:
                         PH.pc_audio_variations_blind(out['pred_spec_mag_norm'], out['pc_directions'], masked_dev, out['mask'],
                                                      alphas, out['mean'], out['std'], n_iter=gl_iters, n_fft=n_fft,
                                                      hop_length=hop_length, long_spans=long_spans)
+        if S_post is not None:
+            from .. import posterior as IPOST
+            with torch.no_grad():
+                pc = out['pc_directions']
+                z = IPOST.draw_coefficients(pc.shape[0], S_post, pc.shape[1], seed=posterior_seed, device=pc.device)
+                r = IPOST.sample_waveforms(out['pred_spec_mag_norm'], pc, clean_spec, z, out['mean'], out['std'], n_fft=n_fft,
+                                           hop_length=hop_length, stats=True, spec_stats=True)
+                out['posterior'] = {'coeffs': z, 'samples': r['samples'], 'std': r['std'], 'mag_std': r['mag_std']}
+                if phase == "griffin_lim":
+                    blind, _, info = IPOST.sample_waveforms_blind(out['pred_spec_mag_norm'], pc, masked_dev, out['mask'], z,
+                                                                  out['mean'], out['std'], n_iter=gl_iters, n_fft=n_fft,
+                                                                  hop_length=hop_length, long_spans=long_spans)
+                    out['posterior'].update(samples_blind=blind, phase_info=info)
         return out
 
     def validate_dataloader(self, dataloader, n_mc_samples=50, n_components=5, save=False, ragged_gaps=False,

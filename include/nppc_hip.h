@@ -884,6 +884,49 @@ int nppc_post_sample(const float* pred_crm, const float* w_mat, const float* re,
                      const int* lengths, int domain, int B, int S, int K, int T, int nfft, int hop, long ld, float* samples,
                      float* mean, float* std, float* mag_mean, float* mag_std, double* work, long work_bytes, void* stream);
 
+/* ---- posterior samples of inpainted gaps (csrc/inpaint_posterior.hip; specification
+ * tests/inpaint_posterior_ref.py) ----------------------------------------------------------------------------------------
+ * pred [B][F][T] and pc [B][K][F][T] normalised log-magnitudes (the directions orthogonal, un-normalised, zero on known
+ * frames), mean / stdev device scalars, z [B][S][K] real coefficients.  Sample s of item b, bin o, in fp64, k ascending:
+ *   x = pred[b][o]; for k: x = fma(z[b][s][k], pc[b][k][o], x); mag = exp(fma(x, stdev, mean))
+ * (at z = alpha e_k the expression, and the bits, of nppc_pc_variation_waves / nppc_gl_gap_pc).
+ * nppc_inp_post_sample gives mag the phase of clean_spec [B][2][F][T] (angle(0) = 0) and inverts with nppc_istft_any's
+ * transform, S samples per item in one launch: a workgroup owns 256 output samples of one item and a tile of consecutive s.
+ * K <= NPPC_INP_POST_MAX_K, S >= 1, nfft <= 512 and nppc_istft_any's limits; anything else NPPC_EBADARG before any launch.
+ * No atomics: the same bits from run to run, an item alone equals the item in a batch, a sample does not depend on S. */
+#define NPPC_INP_POST_MAX_K 16
+#define NPPC_INP_POST_TILE 8               /* samples one workgroup runs when no statistics are asked for */
+#define NPPC_INP_POST_MAX_STAT_S 4096
+#define NPPC_INP_POST_MAX_STAT_TILES 32
+#define NPPC_INP_POST_FILL 1024            /* workgroups that count as a full machine */
+#define NPPC_INP_POST_LDS_STAGE 65536      /* most LDS bytes of a workgroup that stages its planes (2 workgroups per CU) */
+#define NPPC_INP_POST_NO_STAGE 1           /* flags: re-read the planes from global memory whatever the shape */
+/* stats: bit 0 the time-domain mean / std, bit 1 the magnitude mean / std (then 2 <= S <= NPPC_INP_POST_MAX_STAT_S).
+ *   n = ceil(S / NPPC_INP_POST_TILE); stats: n = min(n, clamp(ceil(NPPC_INP_POST_FILL / (B ceil(L / 256))), 1,
+ *   NPPC_INP_POST_MAX_STAT_TILES)); *tile_samples = ceil(S / n), *tiles = ceil(S / *tile_samples) (gridDim.z),
+ *   *work_bytes = 16 *tiles B ((stats & 1 ? L : 0) + (stats & 2 ? F T : 0)).
+ * With nfr = (254 + nfft) / hop + 1 frames per workgroup, *staged = 1 when 16 nfft + (24 + 4 (K + 1)) nfr F (twiddles, unit
+ * phasors, frame buffer, K + 1 planes) <= NPPC_INP_POST_LDS_STAGE and flags does not forbid it; *lds_bytes is what the chosen
+ * path takes.  Each output may be null.  No GPU. */
+int nppc_inp_post_sample_shape(int B, int S, int K, int T, int nfft, int hop, int L, int stats, int flags, int* tiles,
+                               int* tile_samples, long* work_bytes, int* staged, long* lds_bytes);
+/* Outputs, each nullable (mean with std, mag_mean with mag_std; at least one output): samples [B][S][L]; mean, std [B][L]
+ * over s of the samples; mag_mean, mag_std [B][F][T] over s of mag (fp64, every frame).  Statistics as nppc_post_sample's:
+ * fp64 sums of y and y^2 per sample tile in work (16-byte aligned), folded in tile order by a finishing launch. */
+int nppc_inp_post_sample(const float* pred, const float* pc, const float* clean_spec, const float* mean_p, const float* stdev,
+                         const float* z, int B, int S, int K, int T, int nfft, int hop, int L, int flags, float* samples,
+                         float* mean, float* std, float* mag_mean, float* mag_std, double* work, long work_bytes, void* stream);
+/* nppc_gl_gap_pc / nppc_gl_gap_pc_long with the magnitudes of S posterior samples: V = S + 1, v < S by the rule above from
+ * z [B][S][K], v = S the prediction (z = 0), formed bin by bin where the iteration starts (no [B][S][F][T] stack). */
+int nppc_gl_gap_post(const float* pred, const float* pc, const float* mean, const float* stdev, const float* z,
+                     const float* known_spec, const float* mask, const float* init_phase, float* out, double* dist,
+                     double* target_norm, int* status, void* work, long work_bytes, int B, int K, int S, int T, int nfft, int hop,
+                     int L, int n_iter, double momentum, int max_span, void* stream);
+int nppc_gl_gap_post_long(const float* pred, const float* pc, const float* mean, const float* stdev, const float* z,
+                          const float* known_spec, const float* mask, const float* init_phase, float* out, double* dist,
+                          double* target_norm, int* status, void* work, long work_bytes, int B, int K, int S, int T, int nfft,
+                          int hop, int L, int n_iter, double momentum, int max_span, int long_max_span, int mode, void* stream);
+
 /* ---- FLAC decoding (csrc/flac_core.h + csrc/flac.hip; specification tests/flac_ref.py) --------------
  * Every entry point returns NPPC_OK / an NPPC_E* code for its ARGUMENTS; what is wrong with a FILE is a per-file status: */
 #define NPPC_FLAC_OK 0
