@@ -17,6 +17,17 @@
 //      y_c = e_c + (alpha_a sign[c][s]) p_{c,perm[c][s]}.  Output sample m: cur = min(m / H, n - 1), i = m - cur H;
 //      cur >= 1 and i < H: out = y_prev[i + H] (1 - w[i]) + y_cur[i] w[i]; otherwise out = y_cur[i].
 //      w[i] = 0.5 - 0.5 cos(2 pi i / C), i < H, is a table made in fp64 on the host and rounded to fp32.
+// 4. Posterior samples (csrc/enhance_post.hip; specification tests/enhance_posterior_ref.py).  Chunk c keeps its planes:
+//      pred_crm[c] [2][F][T], w_mat[c] [K][2][F][T], the noisy re[c] / im[c] [F][T] and its length len[c] (C, the last chunk
+//      L - (n - 1) H).  The coefficients z [S][K][2] are drawn once for the recording and indexed by slot.  Sample s:
+//      mask of chunk c = post_mask (csrc/post_core.h) with the directions in slot order, k ascending over the slots,
+//      direction k = sign[c][k] w_mat[c][enh_dir(perm[c][k])] (the negation is exact), in either domain; then
+//      cirm_apply_true and the centred inverse STFT of fft_core.h with the ragged rule at len[c] -> y_{c,s}[i].
+//      Output sample m, (cur, i) by enh_locate: out = enh_blend(y_{cur-1,s}[i + H], y_{cur,s}[i], w[i]) where the chunk
+//      before is blended in, otherwise y_{cur,s}[i].  The sum runs over slots, so a signed permutation of a chunk's raw
+//      directions together with the tables the chain then gives performs the same operations on the same values.
+//      A workgroup owns a block of `block` consecutive output samples, block dividing H (enh_block_ok): by enh_locate every
+//      sample of a block then has the chunk and the blend of the block's first sample, at consecutive i.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -98,6 +109,10 @@ ENH_HD bool enh_locate(long m, int H, int n, int* cur, int* i) {
   *i = (int)(m - c * H);
   return c >= 1 && *i < H;
 }
+
+// blocks of `block` output samples from m = 0 never straddle a half-chunk: the samples m0 .. m0 + block - 1 of the block at
+// m0 (a multiple of block) share cur and the blend of enh_locate(m0), with i = i0, i0 + 1, ...
+ENH_HD bool enh_block_ok(int C, int block) { return block > 0 && C >= 2 && !(C & 1) && (C / 2) % block == 0; }
 
 ENH_HD float enh_vary(float e, float as, float p) { return enh_add(e, enh_mul(as, p)); }
 ENH_HD float enh_blend(float yp, float yc, float w) { return enh_add(enh_mul(yp, enh_add(1.f, -w)), enh_mul(yc, w)); }

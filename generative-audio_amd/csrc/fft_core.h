@@ -1,7 +1,7 @@
 // Radix-2 transform in LDS, the overlap-add of the centred inverse STFT and the cIRM decompression, shared by the front end
-// (frontend.hip: stft_kernel, istft_kernel, decompress_apply_kernel) and the posterior sampler (posterior.hip).  The
-// sampler at z = 0 has to equal decompress + iSTFT bit for bit; it does because both call these, so the order of the
-// operations below is a contract.  (stft_core.h holds the any-N helpers.)
+// (frontend.hip: stft_kernel, istft_kernel, decompress_apply_kernel) and the posterior samplers (posterior.hip,
+// enhance_post.hip).  The sampler at z = 0 has to equal decompress + iSTFT bit for bit; it does because both call these, so
+// the order of the operations below is a contract.  (stft_core.h holds the any-N helpers.)
 #pragma once
 #include "common.h"
 

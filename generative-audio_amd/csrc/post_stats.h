@@ -1,5 +1,6 @@
-// The finishing launch of the posterior samplers' statistics (posterior.hip, inpaint_posterior.hip): the sample tiles'
-// partial sums (sum y, sum y^2), fp64, folded in tile order -> mean and unbiased standard deviation, rounded to fp32 once.
+// The finishing launch of the posterior samplers' statistics (posterior.hip, inpaint_posterior.hip, enhance_post.hip): the
+// sample tiles' partial sums (sum y, sum y^2), fp64, folded in tile order -> mean and unbiased standard deviation, rounded to
+// fp32 once.
 #pragma once
 #include "common.h"
 

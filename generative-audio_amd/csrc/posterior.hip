@@ -16,13 +16,13 @@
 #include "common.h"
 #include "fft_core.h"
 #include "nppc_hip.h"
+#include "post_core.h"
 #include "post_stats.h"
 
 #include <type_traits>
 
 namespace {
 
-constexpr int POST_TILE = NPPC_POST_TILE;
 constexpr int POST_MAX_K = NPPC_POST_MAX_K;
 
 struct PostArgs {
@@ -38,52 +38,6 @@ struct PostArgs {
   long ld;
   int K, S, T, hop, spt, domain;
 };
-
-// mask * noisy, the true complex product, and the magnitude of the result, with the fused multiply-adds that
-// decompress_apply_kernel (frontend.hip, conj_mask = 0) compiles to spelled out: left to the compiler, the contraction of
-// these sums depends on the code around them, and the sampler at z = 0 has to give that kernel's bits (the tests hold the
-// two together).
-__device__ __forceinline__ void cirm_apply_true(float mr, float mi, float a, float c, float* xr, float* xi) {
-  *xr = __builtin_fmaf(mr, a, -(mi * c));
-  *xi = __builtin_fmaf(mr, c, mi * a);
-}
-__device__ __forceinline__ float spec_mag(float xr, float xi) { return sqrtf(__builtin_fmaf(xr, xr, xi * xi)); }
-
-// the sampled mask of one bin.  pr / pi: the restoration's compressed mask; wr / wi: direction k at wr[k * wstride];
-// z: this sample's K (real, imaginary) pairs.
-__device__ __forceinline__ void post_mask(float pr, float pi, const float* __restrict__ wr, const float* __restrict__ wi,
-                                          size_t wstride, const float* __restrict__ z, int K, int domain, float* Mr,
-                                          float* Mi) {
-#pragma clang fp contract(off)
-  float mr, mi;
-  if (domain == NPPC_POST_COMPRESSED) {
-    mr = pr;
-    mi = pi;
-    for (int k = 0; k < K; ++k) {
-      const float zr = z[2 * k], zi = z[2 * k + 1];
-      const float a = wr[k * wstride], c = wi[k * wstride];
-      const float t0 = zr * a, t1 = zi * c, t2 = zr * c, t3 = zi * a;
-      const float dr = t0 - t1, di = t2 + t3;
-      mr = mr + dr;
-      mi = mi + di;
-    }
-    mr = decompress_cirm(mr);
-    mi = decompress_cirm(mi);
-  } else {
-    mr = decompress_cirm(pr);
-    mi = decompress_cirm(pi);
-    for (int k = 0; k < K; ++k) {
-      const float zr = z[2 * k], zi = z[2 * k + 1];
-      const float a = decompress_cirm(wr[k * wstride]), c = decompress_cirm(wi[k * wstride]);
-      const float t0 = zr * a, t1 = zi * c, t2 = zr * c, t3 = zi * a;
-      const float dr = t0 - t1, di = t2 + t3;
-      mr = mr + dr;
-      mi = mi + di;
-    }
-  }
-  *Mr = mr;
-  *Mi = mi;
-}
 
 template <int LOGN, bool STATS>
 __global__ __launch_bounds__(256) void post_sample_kernel(PostArgs a) {
@@ -194,10 +148,6 @@ __global__ __launch_bounds__(256) void post_sample_kernel(PostArgs a) {
   }
 }
 
-bool post_config_ok(int nfft, int hop) {
-  return (nfft == 64 || nfft == 128 || nfft == 256 || nfft == 512) && hop > 0 && nfft % hop == 0 && nfft / hop <= 8;
-}
-
 // blocks along x: every output sample and every frame has an owner
 int post_blocks(int T, int nfft, int hop, long ld) {
   const int by_samples = ceil_div(ld + nfft / 2, (long)ISTFT_FR * hop), by_frames = ceil_div(T, ISTFT_FR);
@@ -209,14 +159,8 @@ int post_shape(int B, int S, int K, int T, int nfft, int hop, long ld, int stats
       !post_config_ok(nfft, hop) || (stats & ~3))
     return NPPC_EBADARG;
   if (stats && (S < 2 || S > NPPC_POST_MAX_STAT_S)) return NPPC_EBADARG;
-  long nt = ceil_div(S, POST_TILE);
-  if (stats) {                                         // partial sums cost memory per tile: only as many as fill the chip
-    long fill = ceil_div(NPPC_POST_FILL, (long)B * post_blocks(T, nfft, hop, ld));
-    fill = fill < 1 ? 1 : (fill > NPPC_POST_MAX_STAT_TILES ? NPPC_POST_MAX_STAT_TILES : fill);
-    nt = nt < fill ? nt : fill;
-  }
-  const int per = ceil_div(S, nt);
-  nt = ceil_div(S, per);
+  int per;
+  const long nt = post_tiles(S, (long)B * post_blocks(T, nfft, hop, ld), stats, &per);
   if (nt > 65535) return NPPC_EBADARG;
   if (tiles) *tiles = (int)nt;
   if (spt) *spt = per;

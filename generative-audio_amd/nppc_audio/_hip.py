@@ -308,6 +308,8 @@ SIGS = {
     "nppc_enh_splice_host": [P, L, P, L, L, I, I, I, L, P, I, P, P, P, P, L],
     "nppc_post_sample_shape": [I, I, I, I, I, I, L, I, PI, PI, PL],
     "nppc_post_sample": [P, P, P, P, P, P, I, I, I, I, I, I, I, L, P, P, P, P, P, P, L, P],
+    "nppc_enh_post_sample_shape": [I, I, I, I, L, I, I, I, I, PI, PI, PL],
+    "nppc_enh_post_sample": [P, P, P, P, P, P, P, P, I, I, I, I, I, L, I, I, I, P, L, P, P, P, L, P],
     "nppc_inp_post_sample_shape": [I, I, I, I, I, I, I, I, I, PI, PI, PL, PI, PL],
     "nppc_inp_post_sample": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, P, L, P],
     "nppc_gl_gap_post": [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, I, I, D, I, P],

@@ -19,6 +19,11 @@ the K x K cosines between the directions of the two chunks over their shared H s
 greedy walk matches and sign-aligns chunk c to chunk c - 1 (nppc_enh_chain), and the splice reads the resulting tables from
 device memory (nppc_enh_splice).  The host never sees them unless the caller reads the returned tensors.
 
+`enhance(..., samples=S)` also draws S posterior samples of the whole recording (the rule: item 4 of
+csrc/enhance_core.h; csrc/enhance_post.hip; specification tests/enhance_posterior_ref.py): ONE set of coefficients z [S, K]
+per recording, indexed by slot, which the alignment tables carry from chunk to chunk; `sample_chunks` builds every chunk's
+sampled mask in slot order, inverts and cross-fades in one launch, with no [n, S, C] intermediate.
+
 A spliced direction is NOT a principal direction of the whole recording's posterior: it is a chain of per-chunk directions,
 each the nearest one of the next chunk.  'continuity' says how near: where it is small the spliced variation means little.
 """
@@ -35,7 +40,8 @@ from . import ops
 from .nppc_model import NPPCModel, NPPCModelConfig
 
 __all__ = ["RecordingEnhancerConfig", "RecordingEnhancer", "plan_chunks", "splice_chunks", "hann_table", "enh_shape",
-           "boundary_gram", "chain", "splice", "chain_host", "splice_host", "MAX_K", "MAX_SPLIT", "MATCH"]
+           "boundary_gram", "chain", "splice", "chain_host", "splice_host", "enh_post_shape", "check_sample_chunk_args",
+           "sample_chunks", "MAX_K", "MAX_SPLIT", "MATCH"]
 
 MAX_K = 16                   # NPPC_ENH_MAX_K
 MAX_SPLIT = 64               # NPPC_ENH_MAX_SPLIT
@@ -248,6 +254,107 @@ def splice_host(enh, pcs, last_length, alphas, perm, sign):
     return out
 
 
+def enh_post_shape(n, S, K, chunk_samples, length, T, nfft, hop, stats=False):
+    """nppc_enh_post_sample_shape -> (sample tiles, samples per tile, workspace bytes); ValueError for what the kernel does
+    not take.  No GPU."""
+    tiles, per, nbytes = ctypes.c_int(), ctypes.c_int(), ctypes.c_long()
+    try:
+        H.call("nppc_enh_post_sample_shape", int(n), int(S), int(K), int(chunk_samples), int(length), int(T), int(nfft), int(hop),
+               1 if stats else 0, ctypes.byref(tiles), ctypes.byref(per), ctypes.byref(nbytes))
+    except RuntimeError as e:
+        raise ValueError(f"recording posterior: n {n}, S {S}, K {K}, chunk_samples {chunk_samples}, length {length}, T {T}, "
+                         f"n_fft {nfft}, hop {hop}: {e}") from e
+    return tiles.value, per.value, nbytes.value
+
+
+def check_sample_chunk_args(pred_shape, w_shape, re_shape, im_shape, lengths, z_shape, perm_shape, sign_shape, last_length,
+                            chunk_samples, nfft, hop, domain, samples, stats):
+    """every refusal of sample_chunks as a ValueError, from shapes alone (no GPU, no launch) -> (n, S, K, F, T, L)"""
+    from .posterior import DOMAINS, MAX_STAT_S, config_ok
+    C, nfft, hop = int(chunk_samples), int(nfft), int(hop)
+    if not config_ok(nfft, hop) or nfft // hop < 2:
+        raise ValueError(f"recording posterior: n_fft {nfft} / hop {hop} outside n_fft in (64, 128, 256, 512), n_fft % hop == 0, "
+                         "2 <= n_fft / hop <= 8")
+    if C <= 0 or C % 2 or (C // 2) % (4 * hop):
+        raise ValueError(f"chunk_samples = {C}: half a chunk has to be a multiple of 4 hop = {4 * hop} samples")
+    if domain not in DOMAINS:
+        raise ValueError(f"domain must be one of {sorted(DOMAINS)}, got {domain!r}")
+    if not (samples or stats):
+        raise ValueError("recording posterior: nothing asked for (samples and stats are both off)")
+    F = nfft // 2 + 1
+    if len(pred_shape) != 4 or pred_shape[0] < 1 or pred_shape[1] != 2 or pred_shape[2] != F:
+        raise ValueError(f"pred_crm is [n,2,{F},T], got {tuple(pred_shape)}")
+    n, _, _, T = pred_shape
+    if len(w_shape) != 5 or tuple(w_shape[:1]) + tuple(w_shape[2:]) != (n, 2, F, T):
+        raise ValueError(f"w_mat is [n,K,2,F,T] = [{n},K,2,{F},{T}], got {tuple(w_shape)}")
+    K = w_shape[1]
+    if K > MAX_K:
+        raise ValueError(f"{K} directions: at most {MAX_K}")
+    if tuple(re_shape) != (n, F, T) or tuple(im_shape) != (n, F, T):
+        raise ValueError(f"the noisy planes are [{n},{F},{T}], got {tuple(re_shape)} and {tuple(im_shape)}")
+    if len(z_shape) != 3 or z_shape[0] < 1 or z_shape[1] != K or z_shape[2] != 2:
+        raise ValueError(f"coefficients are [S,{K}], one set per recording, got {tuple(z_shape[:2])}")
+    S = z_shape[0]
+    if stats and not 2 <= S <= MAX_STAT_S:
+        raise ValueError(f"statistics need 2 <= S <= {MAX_STAT_S} samples, got {S}")
+    if tuple(perm_shape) != (n, K) or tuple(sign_shape) != (n, K):
+        raise ValueError(f"perm {tuple(perm_shape)}, sign {tuple(sign_shape)}: want [{n}, {K}]")
+    L = _check_last(n, C, last_length)
+    want = [C] * (n - 1) + [int(last_length)]
+    if lengths is not None:
+        host = [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+        if host != want:
+            raise ValueError(f"lengths {host}: the chunks of this plan have {want} samples")
+    if int(last_length) <= nfft // 2:
+        raise ValueError(f"last_length = {int(last_length)} is too short (needs more than {nfft // 2} samples)")
+    if ops.stft_frames(max(want), hop) > T:
+        raise ValueError(f"a chunk of {max(want)} samples needs {ops.stft_frames(max(want), hop)} frames, the planes have {T}")
+    return n, S, K, F, T, L
+
+
+def sample_chunks(pred_crm, w_mat, re, im, lengths, coeffs, perm, sign, last_length, chunk_samples, nfft, hop,
+                  domain="compressed", samples=True, stats=False):
+    """nppc_enh_post_sample: posterior samples of a whole recording from the planes of its chunks, in one launch.
+
+    pred_crm [n,2,F,T] compressed, w_mat [n,K,2,F,T], noisy re / im [n,F,T] (or [n,1,F,T]) of the n chunks of plan_chunks,
+    lengths their sample counts (None: chunk_samples each and last_length for the last; anything else is refused), coeffs
+    [S,K] real or complex, or [S,K,2]: ONE set per recording, indexed by slot; perm / sign [n,K] the device tables of `chain`.
+    Sample s of chunk c is posterior.sample_waveforms' sample with the directions sign[c][k] w_mat[c][perm[c][k]], k
+    ascending over the slots; the recording is their cross-fade by `splice`'s rule (hann_table).
+    -> dict: "samples" [S,L] (samples=True; a view of rows padded to a multiple of four samples), "mean", "std" [L] over the
+    samples (stats=True).  With samples=False nothing of size S L is allocated.  ValueError before any launch for what the
+    kernel does not take (check_sample_chunk_args)."""
+    from .posterior import DOMAINS, as_coefficients
+    if not isinstance(coeffs, torch.Tensor):
+        raise ValueError("coeffs is a tensor [S,K] (real or complex) or [S,K,2]")
+    z = as_coefficients(coeffs[None])[0]
+    if re.dim() == 4:
+        re, im = re.squeeze(1), im.squeeze(1)
+    n, S, K, F, T, L = check_sample_chunk_args(pred_crm.shape, w_mat.shape, re.shape, im.shape, lengths, z.shape, perm.shape,
+                                               sign.shape, last_length, chunk_samples, nfft, hop, domain, samples, stats)
+    C = int(chunk_samples)
+    _, _, nbytes = enh_post_shape(n, S, K, C, L, T, nfft, hop, stats)
+    H.require_gpu()
+    pred_crm, w_mat, re, im = (ops._f32c(t) for t in (pred_crm, w_mat, re, im))
+    dev = pred_crm.device
+    z = z.to(dev).contiguous()
+    perm, sign = perm.to(dev, torch.int32).contiguous(), sign.to(dev, torch.int32).contiguous()
+    w = hann_table(C, dev) if n > 1 else None
+    out = {}
+    ldo = (L + 3) // 4 * 4
+    rows = torch.empty(S, ldo, dtype=torch.float32, device=dev) if samples else None
+    if stats:
+        out["mean"], out["std"] = (torch.empty(L, dtype=torch.float32, device=dev) for _ in range(2))
+    work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        H.call("nppc_enh_post_sample", pred_crm, w_mat if K else None, re, im, z if K else None, perm if K else None,
+               sign if K else None, w, DOMAINS[domain], n, S, K, C, L, T, int(nfft), int(hop), rows, ldo, out.get("mean"),
+               out.get("std"), work, nbytes, H.stream())
+    if samples:
+        out["samples"] = rows[:, :L]
+    return out
+
+
 class RecordingEnhancer:
     """Loads the checkpoint NPPCAudioValidator loads ({'model_state_dict': ...} of an NPPCModel: frozen restorer and
     direction net) and enhances whole recordings with it."""
@@ -278,11 +385,14 @@ class RecordingEnhancer:
         kersize = list(self.model.pretrained_restoration_model.kersize) + list(self.model.audio_pc_wrapper.net.kersize)
         return plan_chunks(length, self.config.chunk_samples, st.nfft, st.hop_length, kersize)
 
-    def chunk_waveforms(self, x, plan, with_directions=True):
+    def chunk_waveforms(self, x, plan, with_directions=True, keep_planes=False):
         """x [L] (device) and its plan -> buf [n, K + 1, C] (or [n, 1, C]): per chunk the enhanced waveform e_c, then the
         waveform p_{c,k} of ops.crm_directions_to_spectrograms' direction k.  Chunks run through NPPCModel's ragged path
         (lengths=) in batches of chunk_batch, so a chunk's output does not depend on its batch; each batch ends in ONE
-        ragged ops.istft launch of its (K + 1) b spectra.  Samples past the last chunk's length are not written."""
+        ragged ops.istft launch of its (K + 1) b spectra.  Samples past the last chunk's length are not written.
+        keep_planes (with directions): -> (buf, planes), planes = {"pred_crm" [n, 2, F, T], "w_mat" [n, K, 2, F, T], "re",
+        "im" [n, F, T]}, what sample_chunks reads: (2 K + 4) F T 4 bytes per chunk on top of buf, about 1.1 GB for a 10 min
+        recording at K = 5 and the default chunks (292 chunks of 257 x 257 bins)."""
         c, st = self.config, self._stft()
         n, C = len(plan), c.chunk_samples
         Hh = C // 2
@@ -293,7 +403,7 @@ class RecordingEnhancer:
         else:
             chunks[:n - 1] = x.unfold(0, C, Hh)[:n - 1]
             chunks[n - 1, :plan[-1][1]] = x[plan[-1][0]:]
-        buf = None
+        buf = planes = None
         with torch.no_grad():
             for b0 in range(0, n, max(1, c.chunk_batch)):
                 xb = chunks[b0:b0 + max(1, c.chunk_batch)]
@@ -314,9 +424,16 @@ class RecordingEnhancer:
                 if buf is None:
                     buf = torch.empty(n, V, C, dtype=torch.float32, device=x.device)
                 buf[b0:b0 + b, :, :W] = waves.view(b, V, W)
-        return buf
+                if keep_planes and with_directions:
+                    kept = {"pred_crm": f["pred_crm"], "w_mat": w_mat, "re": f["re"], "im": f["im"]}
+                    if planes is None:
+                        planes = {k: torch.empty(n, *t.shape[1:], dtype=torch.float32, device=x.device) for k, t in kept.items()}
+                    for k, t in kept.items():
+                        planes[k][b0:b0 + b] = t
+        return (buf, planes) if keep_planes and with_directions else buf
 
-    def enhance(self, wave, alphas=None, sample_rate=None):
+    def enhance(self, wave, alphas=None, sample_rate=None, samples=0, seed=None, coeffs=None, domain="compressed", temperature=1.0,
+                keep_samples=True, stats=False):
         """wave [L] float (host or device) -> dict: 'enhanced' [L]; 'chunks' (plan_chunks' list); with `alphas` [A] also
         'variations' [K, A, L] (enhanced + alpha PC_k, the K directions aligned from chunk to chunk), 'perm' [n, K] int32,
         'sign' [n, K] int32 and 'continuity' [n - 1, K] fp64, device tensors (module docstring).
@@ -325,25 +442,84 @@ class RecordingEnhancer:
         sample_rate: None or config.sample_rate runs exactly the above.  Another rate: the recording is resampled to
         config.sample_rate (nppc_audio.resample), enhanced there, and every output row is resampled back and cut to L; the
         WHOLE output is then band-limited to config.sample_rate / 2 (unlike restoration, which keeps the input outside its
-        gaps, every sample of an enhanced recording comes from the nets).  'chunks' is the plan at the model's rate."""
+        gaps, every sample of an enhanced recording comes from the nets).  'chunks' is the plan at the model's rate.
+
+        samples=S > 0 (or coeffs [S, K] real or complex, or [S, K, 2]) also draws S posterior samples of the recording
+        (sample_chunks; module docstring): the dict gains 'samples' [S, L] (keep_samples), 'coeffs' [S, K, 2]
+        (posterior.draw_coefficients(1, S, K, seed=seed, temperature=temperature)[0] unless given), with stats 'sample_mean'
+        and 'sample_std' [L], and 'perm', 'sign', 'continuity', which are formed as above whether or not `alphas` is given.
+        keep_samples=False with stats=True allocates nothing of size S L.  Every chunk's planes are then kept until the
+        launch: (2 K + 4) F T 4 bytes per chunk, about 1.1 GB for a 10 min recording at K = 5 (chunk_waveforms); there is no
+        budget logic.  At another sample_rate the sample rows go up through the resampler in one batch with the other rows;
+        the statistics are not formed there (a standard deviation does not pass through a resampler): ValueError.
+        A chain of per-chunk Gaussians is not the recording's posterior; 'continuity' says where it means least."""
         if wave.dim() != 1:
             raise ValueError(f"wave {tuple(wave.shape)}: want one channel, [L]")
         c = self.config
         if c.match not in MATCH:
             raise ValueError(f"match = {c.match!r}: 'greedy' or 'sign'")
+        sampling = int(samples) > 0 or coeffs is not None
+        if not sampling and int(samples) < 0:
+            raise ValueError(f"samples = {samples}: a count")
+        if sampling:
+            from .posterior import DOMAINS, MAX_STAT_S
+            if domain not in DOMAINS:
+                raise ValueError(f"domain must be one of {sorted(DOMAINS)}, got {domain!r}")
+            if not (keep_samples or stats):
+                raise ValueError("recording posterior: nothing asked for (keep_samples and stats are both off)")
+            if coeffs is not None and (not isinstance(coeffs, torch.Tensor) or coeffs.dim() < 2):
+                raise ValueError("coeffs is a tensor [S,K] (real or complex) or [S,K,2]")
+            S = int(samples) if coeffs is None else int(coeffs.shape[0])
+            if stats and not 2 <= S <= MAX_STAT_S:
+                raise ValueError(f"statistics need 2 <= S <= {MAX_STAT_S} samples, got {S}")
         if sample_rate is not None and int(sample_rate) != int(c.sample_rate):
-            return self._enhance_at_rate(wave, alphas, int(sample_rate))
+            if sampling and stats:
+                raise ValueError("the sample statistics are formed at the model's rate only: a standard deviation does not "
+                                 "pass through the resampler")
+            more = dict(samples=samples, seed=seed, coeffs=coeffs, domain=domain, temperature=temperature) if sampling else {}
+            return self._enhance_at_rate(wave, alphas, int(sample_rate), **more)
         plan = self.plan(wave.numel())
         H.require_gpu()
         x = wave.to(self.device).float().contiguous()
-        buf = self.chunk_waveforms(x, plan, with_directions=alphas is not None)
-        out = splice_chunks(buf[:, 0], buf[:, 1:], plan[-1][1], alphas, c.match)
+        if not sampling:
+            buf = self.chunk_waveforms(x, plan, with_directions=alphas is not None)
+            out = splice_chunks(buf[:, 0], buf[:, 1:], plan[-1][1], alphas, c.match)
+        else:
+            out = self._enhance_and_sample(x, plan, alphas, S, seed, coeffs, domain, temperature, keep_samples, stats)
         out["chunks"] = plan
         if alphas is not None:
             out["alphas"] = alphas if isinstance(alphas, torch.Tensor) else [float(a) for a in alphas]
         return out
 
-    def _enhance_at_rate(self, wave, alphas, rate):
+    def _enhance_and_sample(self, x, plan, alphas, S, seed, coeffs, domain, temperature, keep_samples, stats):
+        from .posterior import as_coefficients, draw_coefficients
+        c, st = self.config, self._stft()
+        n, last = len(plan), plan[-1][1]
+        buf, planes = self.chunk_waveforms(x, plan, keep_planes=True)
+        K = buf.shape[1] - 1
+        if K < 1:
+            raise ValueError("the model has no directions to sample along")
+        if coeffs is not None:
+            z = as_coefficients(coeffs[None])[0].to(self.device)
+        else:
+            z = draw_coefficients(1, S, K, seed=seed, temperature=temperature, device=self.device)[0]
+        if alphas is not None:
+            out = splice_chunks(buf[:, 0], buf[:, 1:], last, alphas, c.match)
+        else:                                                                   # the tables as splice_chunks forms them
+            out = {"enhanced": splice(buf[:, 0], None, last, None, None, None)[0]}
+            work = boundary_gram(buf[:, 1:])[0] if n > 1 else None
+            out["perm"], out["sign"], out["continuity"] = chain(work, n, K, c.match, device=buf.device)
+        r = sample_chunks(planes["pred_crm"], planes["w_mat"], planes["re"], planes["im"], [ln for _, ln in plan], z, out["perm"],
+                          out["sign"], last, c.chunk_samples, st.nfft, st.hop_length, domain=domain, samples=keep_samples,
+                          stats=stats)
+        out["coeffs"] = z
+        if keep_samples:
+            out["samples"] = r["samples"]
+        if stats:
+            out["sample_mean"], out["sample_std"] = r["mean"], r["std"]
+        return out
+
+    def _enhance_at_rate(self, wave, alphas, rate, **sampling):
         from . import resample as RSM
         c = self.config
         if rate <= 0:
@@ -356,25 +532,33 @@ class RecordingEnhancer:
         N = wave.numel()
         x = wave.to(self.device).float().contiguous()
         low = RSM.resample(x, rate, c.sample_rate, backend="hip")
-        out = self.enhance(low, alphas)
-        rows = out["enhanced"][None]
+        out = self.enhance(low, alphas, **sampling)
+        rows, V = [out["enhanced"][None]], 0
         if "variations" in out:
             K, A = out["variations"].shape[:2]
-            rows = torch.cat([rows, out["variations"].reshape(K * A, -1)])
+            V = K * A
+            rows.append(out["variations"].reshape(V, -1))
+        if "samples" in out:
+            rows.append(out["samples"])
+        rows = torch.cat(rows) if len(rows) > 1 else rows[0]
         up = RSM.resample(rows.contiguous(), c.sample_rate, rate, backend="hip")[:, :N]
         out["enhanced_model_rate"] = out["enhanced"]
         out["enhanced"] = up[0]
         if "variations" in out:
-            out["variations"] = up[1:].unflatten(0, (K, A))
+            out["variations"] = up[1:1 + V].unflatten(0, (K, A))
+        if "samples" in out:
+            out["samples"] = up[1 + V:]
         out["sample_rate"] = rate
         return out
 
-    def enhance_file(self, path, out_path, alphas=None, keep_rate=True, out_format="auto", verify_flac_md5=True):
+    def enhance_file(self, path, out_path, alphas=None, keep_rate=True, out_format="auto", verify_flac_md5=True, samples=0,
+                     seed=None):
         """wav or flac -> wav or flac, as RecordingRestorer.restore_file reads and writes them: decoded to mono
         (data._decode_wav, data._decode_flac for a name ending in .flac), enhanced, written as 16-bit PCM; out_format "wav",
         "flac" or "auto" (flac when out_path ends in .flac).  keep_rate=True: the file is decoded at ITS rate and
         enhance(..., sample_rate=rate) returns that rate and sample count, band-limited to config.sample_rate / 2;
-        keep_rate=False: decoded to config.sample_rate and written at it.  -> enhance's dict"""
+        keep_rate=False: decoded to config.sample_rate and written at it.  samples, seed: enhance's (the samples are in the
+        dict; save_posterior_samples writes them).  -> enhance's dict"""
         from .data import _decode_flac, _decode_wav
         from .flac import write_waves
         if out_format not in ("wav", "flac", "auto"):
@@ -394,7 +578,7 @@ class RecordingEnhancer:
         if wave is None:
             raise ValueError(f"{path} holds no samples")
         wave = torch.as_tensor(wave)
-        out = self.enhance(wave, alphas, sample_rate=rate)
+        out = self.enhance(wave, alphas, sample_rate=rate, samples=samples, seed=seed)
         out.setdefault("sample_rate", rate)
         write_waves([out_path], out["enhanced"][None].contiguous(), rate, out_format)
         return out
@@ -420,4 +604,18 @@ class RecordingEnhancer:
             os.makedirs(os.path.dirname(p), exist_ok=True)
         stack = torch.cat([w.to(self.device).float() for w in waves]) if fmt == "flac" else torch.cat([w.float().cpu() for w in waves])
         write_waves(paths, stack, rate, fmt)
+        return paths
+
+    def save_posterior_samples(self, result, folder, fmt="flac"):
+        """enhance's dict with 'samples' [S, L] -> <folder>/posterior/sample_<s>.<ext> (the layout of
+        NPPCAudioValidator.save_posterior_samples), 16-bit mono at the rate of the dict, as they are (not normalised), in one
+        flac.write_waves call.  -> the paths written"""
+        from .flac import write_waves
+        if "samples" not in result:
+            raise ValueError("the dict holds no 'samples': call enhance(..., samples=S) with keep_samples=True")
+        rate = int(result.get("sample_rate", self.config.sample_rate))
+        rows = result["samples"]
+        paths = [os.path.join(str(folder), "posterior", f"sample_{s}.{fmt}") for s in range(rows.shape[0])]
+        os.makedirs(os.path.dirname(paths[0]), exist_ok=True)
+        write_waves(paths, (rows.to(self.device) if fmt == "flac" else rows.cpu()).float().contiguous(), rate, fmt)
         return paths

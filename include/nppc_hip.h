@@ -884,6 +884,31 @@ int nppc_post_sample(const float* pred_crm, const float* w_mat, const float* re,
                      const int* lengths, int domain, int B, int S, int K, int T, int nfft, int hop, long ld, float* samples,
                      float* mean, float* std, float* mag_mean, float* mag_std, double* work, long work_bytes, void* stream);
 
+/* ---- posterior samples of a whole recording (csrc/enhance_post.hip; the rule: item 4 of
+ * csrc/enhance_core.h; specification tests/enhance_posterior_ref.py) -----------------------------------------------------
+ * The planes of the n chunks of a recording of L samples (chunks of C at a hop of H = C / 2, the last one L - (n - 1) H
+ * long): pred_crm [n][2][F][T], w_mat [n][K][2][F][T], noisy re / im [n][F][T]; z [S][K][2], one set of coefficients per
+ * sample for the whole recording, indexed by slot; perm, sign [n][K] the device tables of nppc_enh_chain; w [H] the
+ * cross-fade table of nppc_enh_splice.  Sample s of chunk c is nppc_post_sample's sample with direction k =
+ * (sign[c][k] < 0 ? -1 : 1) w_mat[c][perm[c][k]] (an entry of perm outside 0 .. K - 1 is clamped) at the chunk's length; the
+ * recording is their cross-fade by nppc_enh_splice's rule.  One launch: a workgroup owns 4 hop output samples of the
+ * recording and a tile of consecutive s.  Beyond nppc_post_sample's limits: nfft / hop >= 2, H % (4 hop) == 0, stats 0 or 1
+ * (then 2 <= S <= NPPC_POST_MAX_STAT_S) and nppc_enh_splice's plan (0 < L - (n - 1) H <= C, K <= NPPC_ENH_MAX_K); anything
+ * else NPPC_EBADARG from the shape function, before any launch.  No atomics: the same bits from run to run, and a sample
+ * does not depend on S.
+ *   nblk = ceil(L / (4 hop)); n_t = ceil(S / NPPC_POST_TILE); stats: n_t = min(n_t, clamp(ceil(NPPC_POST_FILL / nblk), 1,
+ *   NPPC_POST_MAX_STAT_TILES)); *tile_samples = ceil(S / n_t), *tiles = ceil(S / *tile_samples) (gridDim.y),
+ *   *work_bytes = stats ? 16 *tiles L : 0.  Each output may be null.  No GPU. */
+int nppc_enh_post_sample_shape(int n, int S, int K, int C, long L, int T, int nfft, int hop, int stats, int* tiles,
+                               int* tile_samples, long* work_bytes);
+/* Outputs, each nullable (mean with std; at least one): samples [S][ldo] (ldo >= L; the first L samples of every row are
+ * written, nothing else); mean, std [L] over s, by nppc_post_sample's fp64 sums per sample tile in work (16-byte aligned)
+ * and its finishing launch.  perm, sign, w_mat and z may be null when K == 0, w when n == 1. */
+int nppc_enh_post_sample(const float* pred_crm, const float* w_mat, const float* re, const float* im, const float* z,
+                         const int* perm, const int* sign, const float* w, int domain, int n, int S, int K, int C, long L,
+                         int T, int nfft, int hop, float* samples, long ldo, float* mean, float* std, double* work,
+                         long work_bytes, void* stream);
+
 /* ---- posterior samples of inpainted gaps (csrc/inpaint_posterior.hip; specification
  * tests/inpaint_posterior_ref.py) ----------------------------------------------------------------------------------------
  * pred [B][F][T] and pc [B][K][F][T] normalised log-magnitudes (the directions orthogonal, un-normalised, zero on known

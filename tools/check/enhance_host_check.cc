@@ -10,7 +10,10 @@
 // all zeros in an overlap.  The serial core (enh_chain_serial, enh_splice_serial: the functions the kernels walk) is
 // compared with an implementation of the rule in this file that works chunk by chunk: it sorts the cosines of a boundary to
 // match them, and it lays every chunk down whole and then cross-fades the overlaps in place.  Exit status 0 and a line of
-// counts.
+// counts.  The posterior sampler's workgroups (csrc/enhance_post.hip) own blocks of output samples that divide H
+// (enh_block_ok): walk_blocks visits every block of every such plan the way a workgroup does, from enh_locate of its first
+// sample alone, reads the (at most two) chunks it names from heap blocks of exactly their lengths, writes a recording of
+// exactly L samples and holds every sample against enh_locate of that sample.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -143,6 +146,39 @@ long run(const Plan& pl) {
   return (long)V * L;
 }
 
+// blocks of `block` samples over the plan (n, C, last): -> samples visited
+long walk_blocks(int n, int C, int last, int block) {
+  const int H = C / 2;
+  const long L = (long)(n - 1) * H + last;
+  if (!enh_block_ok(C, block) || !enh_plan_ok(n, 0, C, L)) fail("walk_blocks: not a plan", n, C, block);
+  std::vector<float*> chunk(n);
+  for (int c = 0; c < n; ++c) {
+    const int len = c == n - 1 ? last : C;
+    chunk[c] = (float*)malloc(sizeof(float) * len);
+    for (int i = 0; i < len; ++i) chunk[c][i] = (float)(c * C + i);
+  }
+  float* out = (float*)malloc(sizeof(float) * L);
+  float* w = (float*)malloc(sizeof(float) * (H > 0 ? H : 1));
+  for (int i = 0; i < H; ++i) w[i] = 0.25f;
+  long seen = 0;
+  for (long m0 = 0; m0 < L; m0 += block) {
+    int cur, i0;
+    const bool blend = enh_locate(m0, H, n, &cur, &i0);
+    if (i0 % block) fail("a block off the chunk's block grid", m0, i0, block);
+    for (int e = 0; e < block && m0 + e < L; ++e, ++seen) {
+      int c1, i1;
+      const bool b1 = enh_locate(m0 + e, H, n, &c1, &i1);
+      if (c1 != cur || i1 != i0 + e || b1 != blend) fail("a block straddles a region", m0, e, c1);
+      const float yc = chunk[cur][i0 + e];
+      out[m0 + e] = blend ? enh_blend(chunk[cur - 1][i0 + e + H], yc, w[i0 + e]) : yc;
+    }
+  }
+  for (int c = 0; c < n; ++c) free(chunk[c]);
+  free(out), free(w);
+  if (seen != L) fail("walk_blocks: samples missed", seen, L);
+  return seen;
+}
+
 }  // namespace
 
 int main() {
@@ -166,6 +202,22 @@ int main() {
   if (!enh_plan_ok(1, 0, 2, 1) || enh_plan_ok(0, 1, 16, 8) || enh_plan_ok(3, 1, 15, 20) || enh_plan_ok(3, 17, 16, 20) ||
       enh_plan_ok(3, 1, 16, 16) || enh_plan_ok(3, 1, 16, 33) || !enh_plan_ok(3, 1, 16, 32))
     fail("enh_plan_ok");
-  printf("enhance_host_check: %ld plans, %ld output samples, all equal\n", plans, samples);
+  long walked = 0, walks = 0;
+  for (int C : {2, 16, 64, 1024})
+    for (int n : ns)
+      for (int block : {1, 2, 4, 8, 128, 512}) {
+        const int H = C / 2;
+        if (H % block) {
+          if (enh_block_ok(C, block)) fail("enh_block_ok takes a block that does not divide H", C, block);
+          continue;
+        }
+        std::vector<int> lasts = {C};
+        if (n == 1) lasts.push_back(1), lasts.push_back(H);
+        else if (H + 1 < C) lasts.push_back(H + 1), lasts.push_back(C - 1);
+        for (int last : lasts) walked += walk_blocks(n, C, last, block), ++walks;
+      }
+  if (enh_block_ok(16, 0) || enh_block_ok(15, 1) || enh_block_ok(16, 3) || !enh_block_ok(1024, 128)) fail("enh_block_ok");
+  printf("enhance_host_check: %ld plans, %ld output samples, all equal; %ld block walks, %ld samples\n", plans, samples, walks,
+         walked);
   return 0;
 }
