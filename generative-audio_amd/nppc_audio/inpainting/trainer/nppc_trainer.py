@@ -17,13 +17,11 @@ from typing import List, Optional, Union
 import pydantic
 import torch
 import torch.nn as nn
-import torch.optim as optim
 
-from ... import _hip as H
 from ...data import DataLoaderConfig
 from ...nppc_model import StftConfig
 from ...pc_ops import NPPCLoss, planes, second_moment_weight
-from ...trainer import FlatAdamStepper, HipAdam, LoopLoader, OptimizerConfig
+from ...trainer import ClippedFlatStep, HipAdam, LoopLoader, OptimizerConfig, make_optimizer
 from ..nppc.nppc_model import NPPCModel, NPPCModelConfig
 from ..utils import preprocess_data
 from ..vad import EnergyVadConfig
@@ -121,13 +119,8 @@ class NPPCAudioInpaintingTrainer(nn.Module):
         print(f"Total sample pairs in dataset: {len(dataset)}")
         self.nppc_model = NPPCModel(self.config.nppc_model_configuration)
         self.step = 0
-        okind = config.optimizer_configuration.type
-        if okind == "Adam":
-            self.optimizer = HipAdam(self.nppc_model.parameters(), **config.optimizer_configuration.args)
-        else:
-            self.optimizer = getattr(optim, okind)(self.nppc_model.parameters(), **config.optimizer_configuration.args)
-        self._flat_adam = None
-        self._sumsq = None
+        self.optimizer = make_optimizer(self.nppc_model.parameters(), config.optimizer_configuration)
+        self._clip_step = ClippedFlatStep()
         self.val_loss_history = []
         self.val_reconst_err_history = []
 
@@ -184,15 +177,7 @@ class NPPCAudioInpaintingTrainer(nn.Module):
         finally:
             net.flat_grad_only = False
         if fast:
-            eng = net.engine()
-            gflat = eng.fp.grad
-            if self._sumsq is None:
-                self._sumsq = torch.zeros(1, dtype=torch.float64, device=gflat.device)
-            self._sumsq.zero_()
-            H.call("nppc_sumsq", gflat, gflat.numel(), self._sumsq, H.stream())
-            if self._flat_adam is None or self._flat_adam.eng is not eng:
-                self._flat_adam = FlatAdamStepper(self.optimizer, eng)
-            self._flat_adam.step(gflat, 1.0, clip=(self._sumsq, float(self.config.max_grad_norm)))
+            self._clip_step(self.optimizer, net.engine(), self.config.max_grad_norm)
         else:
             torch.nn.utils.clip_grad_norm_(self.nppc_model.parameters(), max_norm=self.config.max_grad_norm)
             self.optimizer.step()

@@ -21,11 +21,10 @@ from typing import List, Optional
 import pydantic
 import torch
 import torch.nn as nn
-import torch.optim as optim
 
 from ... import _hip as H
 from ...data import DataLoaderConfig
-from ...trainer import FlatAdamStepper, HipAdam, LoopLoader, OptimizerConfig
+from ...trainer import ClippedFlatStep, HipAdam, LoopLoader, OptimizerConfig, make_optimizer
 from ..networks.unet import RestorationWrapper, UNet, UNetConfig
 from ..utils import preprocess_data
 from .nppc_trainer import AudioInpaintingConfig, build_device_loader
@@ -100,11 +99,7 @@ class InpaintingTrainer(nn.Module):
             self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.model.to(self.device)
 
-        okind = config.optimizer_configuration.type
-        if okind == "Adam":
-            self.optimizer = HipAdam(self.model.parameters(), **config.optimizer_configuration.args)
-        else:
-            self.optimizer = getattr(optim, okind)(self.model.parameters(), **config.optimizer_configuration.args)
+        self.optimizer = make_optimizer(self.model.parameters(), config.optimizer_configuration)
 
         print(f"Total sample pairs in dataset: {len(dataset)}")
         if self.dataloader is None:
@@ -113,8 +108,7 @@ class InpaintingTrainer(nn.Module):
                                                           num_workers=dl.num_workers, pin_memory=dl.pin_memory)
         self.step = 0
         self.loss_history: List[float] = []
-        self._flat_adam = None
-        self._sumsq = None
+        self._clip_step = ClippedFlatStep()
 
     # ---------------------------------------------------------------------------------- reference API
     def base_step(self, batch):
@@ -159,16 +153,7 @@ class InpaintingTrainer(nn.Module):
         finally:
             net.flat_grad_only = False
         if fast:
-            eng = net.engine()
-            gflat = eng.fp.grad
-            if self._sumsq is None:
-                self._sumsq = torch.zeros(1, dtype=torch.float64, device=gflat.device)
-            self._sumsq.zero_()
-            H.call("nppc_sumsq", gflat, gflat.numel(), self._sumsq, H.stream())
-            if self._flat_adam is None or self._flat_adam.eng is not eng:
-                self._flat_adam = FlatAdamStepper(self.optimizer, eng)
-            self._flat_adam.step(gflat, 1.0, clip=(self._sumsq, float(self.config.max_grad_norm)))
-            log['grad_norm'] = self._sumsq.sqrt()
+            log['grad_norm'] = self._clip_step(self.optimizer, net.engine(), self.config.max_grad_norm)
         else:
             log['grad_norm'] = torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=self.config.max_grad_norm)
             self.optimizer.step()

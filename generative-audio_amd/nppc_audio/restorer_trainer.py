@@ -24,7 +24,6 @@ from typing import List, Optional, Tuple
 import pydantic
 import torch
 import torch.nn as nn
-import torch.optim as optim
 
 from . import _hip as H
 from . import metrics
@@ -34,7 +33,7 @@ from .data import AudioDataset, DataConfig, DataLoaderConfig, DeviceMixLoader, R
 from .dns_data import DeviceReverbMixLoader, DNSDatasetConfig, DynamicMixDataset
 from .fullsubnet import FullSubNet_Plus, FullSubNetPlusConfig
 from .nppc_model import StftConfig
-from .trainer import FlatAdamStepper, HipAdam, LoopLoader, OptimizerConfig
+from .trainer import ClippedFlatStep, HipAdam, LoopLoader, OptimizerConfig, make_optimizer
 
 __all__ = ["FullSubNetPlusTrainerConfig", "FullSubNetPlusTrainer", "CrmMSE", "crm_mse"]
 
@@ -115,11 +114,7 @@ class FullSubNetPlusTrainer(nn.Module):
         self.model.to(self.device)
         self.model.train()
 
-        okind = config.optimizer_configuration.type
-        if okind == "Adam":
-            self.optimizer = HipAdam(self.model.parameters(), **config.optimizer_configuration.args)
-        else:
-            self.optimizer = getattr(optim, okind)(self.model.parameters(), **config.optimizer_configuration.args)
+        self.optimizer = make_optimizer(self.model.parameters(), config.optimizer_configuration)
 
         if dataset is None:
             if config.train_dataset_configuration is not None:
@@ -133,8 +128,7 @@ class FullSubNetPlusTrainer(nn.Module):
         self.step = 0
         self.epoch = 0
         self.loss_history: List[float] = []
-        self._flat_adam = None
-        self._sumsq = None
+        self._clip_step = ClippedFlatStep()
         self.best_score = float("-inf")
         self.val_history: List[dict] = []
 
@@ -264,16 +258,7 @@ class FullSubNetPlusTrainer(nn.Module):
         finally:
             net.flat_grad_only = False
         if fast:
-            eng = net.engine()
-            gflat = eng.fp.grad
-            if self._sumsq is None:
-                self._sumsq = torch.zeros(1, dtype=torch.float64, device=gflat.device)
-            self._sumsq.zero_()
-            H.call("nppc_sumsq", gflat, gflat.numel(), self._sumsq, H.stream())
-            if self._flat_adam is None or self._flat_adam.eng is not eng:
-                self._flat_adam = FlatAdamStepper(self.optimizer, eng)
-            self._flat_adam.step(gflat, 1.0, clip=(self._sumsq, float(self.config.clip_grad_norm_value)))
-            log["grad_norm"] = self._sumsq.sqrt()
+            log["grad_norm"] = self._clip_step(self.optimizer, net.engine(), self.config.clip_grad_norm_value)
         else:
             log["grad_norm"] = torch.nn.utils.clip_grad_norm_(net.parameters(), self.config.clip_grad_norm_value)
             self.optimizer.step()

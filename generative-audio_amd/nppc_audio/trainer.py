@@ -249,6 +249,32 @@ class FlatAdamStepper:
         self._step_t.fill_(float(self.t))
 
 
+class ClippedFlatStep:
+    """clip_grad_norm_(max_norm) + Adam over an engine's flat gradient, all on the device (the HipAdam path of the trainers that
+    clip): owns the fp64 sum-of-squares cell and the FlatAdamStepper, which is rebuilt when the engine object changes."""
+
+    def __init__(self):
+        self.sumsq = self.stepper = None
+
+    def __call__(self, optimizer, eng, max_norm):
+        """-> the total gradient norm before clipping (a device tensor: no host round trip)"""
+        gflat = eng.fp.grad
+        if self.sumsq is None:
+            self.sumsq = torch.zeros(1, dtype=torch.float64, device=gflat.device)
+        self.sumsq.zero_()
+        H.call("nppc_sumsq", gflat, gflat.numel(), self.sumsq, H.stream())
+        if self.stepper is None or self.stepper.eng is not eng:
+            self.stepper = FlatAdamStepper(optimizer, eng)
+        self.stepper.step(gflat, 1.0, clip=(self.sumsq, float(max_norm)))
+        return self.sumsq.sqrt()
+
+
+def make_optimizer(params, optimizer_configuration):
+    """`type: Adam` is HipAdam; any other type is the torch.optim class of that name"""
+    kind = HipAdam if optimizer_configuration.type == "Adam" else getattr(optim, optimizer_configuration.type)
+    return kind(params, **optimizer_configuration.args)
+
+
 class NPPCAudioTrainer(nn.Module):
     def __init__(self, config: NPPCAudioTrainerConfig, dataset=None):
         super().__init__()
@@ -283,11 +309,7 @@ class NPPCAudioTrainer(nn.Module):
         self.step = 0
         # the frozen restorer never needs gradient buffers; the reference leaves requires_grad on and relies on
         # no_grad (nppc_model.py:94) -- same effect, and its parameters are still handed to the optimizer below
-        okind = config.optimizer_configuration.type
-        if okind == "Adam":
-            self.optimizer = HipAdam(self.nppc_model.parameters(), **config.optimizer_configuration.args)
-        else:
-            self.optimizer = getattr(optim, okind)(self.nppc_model.parameters(), **config.optimizer_configuration.args)
+        self.optimizer = make_optimizer(self.nppc_model.parameters(), config.optimizer_configuration)
         self._flat_adam = None
         # Data parallel: ONE all-reduce of the flat gradient on the main stream behind backward is the default; the bucketed
         # exchange that starts inside backward (dp.py) and the parked update (pipeline_update) are opt-in

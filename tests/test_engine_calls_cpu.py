@@ -1,9 +1,10 @@
-"""CPU: the keyword launch wrappers of nppc_audio/gemm.py emit the positional lists of the C ABI (`_hip.SIGS`), and
-`lstm_wgrad_mode` picks the LSTM weight-gradient strategy by the conditions FSNEngine._lstm_wgrad has always used."""
+"""CPU: the keyword launch wrappers of nppc_audio/gemm.py and nppc_audio/unet_engine.py emit the positional lists of the C ABI
+(`_hip.SIGS`), and `lstm_wgrad_mode` picks the LSTM weight-gradient strategy by the conditions FSNEngine._lstm_wgrad has always used."""
 import pytest
 
 from nppc_audio import _hip as H
 from nppc_audio import gemm
+from nppc_audio import unet_engine as UE
 from nppc_audio.engine import (EPI_MASK_POS, EPI_PLAIN_F32, EPI_PRELU_STATS, EPI_RESIDUAL, TCN_HIDDEN)
 from nppc_audio.ops_lstm import WGRAD_SPLITS
 
@@ -124,6 +125,38 @@ def test_wgrad_split_k_site(calls):
     assert calls == [("nppc_gemm_nt", [
         prec, EPI_PLAIN_F32, AT, lda, sA, BT, ldb, sB, slab, ncolsN, rows * ncolsN, None,
         0, None, 0, 0, None, 0, None, 0, rows, ncolsN, K, rows, rows, ncolsN, 0, 3, Sk, S])]
+
+
+def test_unet_conv_fwd_sites(calls):
+    """UNetEngine: the forward (plain and with the folded BatchNorm) and the input gradient, which swaps the roles of the pack's
+    two widths"""
+    X, Wf, Wb, Y, DX, SC, SH = (_T(n) for n in "x wf wb y dx scale shift".split())
+    geo = dict(B=2, hw=(17, 33), ks=3, stream=S)
+    UE.conv_fwd(prec, A=UE._View(X, 128), Wp=Wf, C=UE._View(Y, 256), bias=BIAS, Cin=128, Cout=200, Np=256, **geo)
+    UE.conv_fwd(prec, A=UE._View(X, 128), Wp=Wf, C=UE._View(Y, 256), bias=BIAS, fold=(SC, SH), Cin=128, Cout=200, Np=256, **geo)
+    UE.conv_fwd(prec, A=UE._View(Y, 256), Wp=Wb, C=UE._View(DX, 128), Cin=256, Cout=128, Np=128, **geo)
+    for name, args in calls:
+        _check_kinds(name, args)
+    assert calls == [
+        ("nppc_conv_fwd", [prec, X, 128, Wf, Y, 256, BIAS, None, None, UE.LEAK, 2, 17, 33, 128, 200, 256, 3, S]),
+        ("nppc_conv_fwd", [prec, X, 128, Wf, Y, 256, BIAS, SC, SH, UE.LEAK, 2, 17, 33, 128, 200, 256, 3, S]),
+        ("nppc_conv_fwd", [prec, Y, 256, Wb, DX, 128, None, None, None, UE.LEAK, 2, 17, 33, 256, 128, 128, 3, S])]
+
+
+def test_unet_bn_bwd_sites(calls):
+    """UNetEngine._double_conv_bwd: one gradient, two gradients (decoder + skip), and the block that ends in nn.Dropout"""
+    DA, DB, Y, X, SS, ST, DX, DG, DBETA = (_T(n) for n in "dyA dyB y x ss st dx dgamma dbeta".split())
+    kw = dict(dyA=UE._View(DA, 512), Y=UE._View(Y, 1024), X=UE._View(X, 512), ss=SS, S=ST, dX=UE._View(DX, 512), dgamma=DG,
+              dbeta=DBETA, C=512, B=2, hw=(4, 8), stream=S)
+    UE.bn_bwd(prec, **kw)
+    UE.bn_bwd(prec, dyB=UE._View(DB, 1024), **kw)
+    UE.bn_bwd(prec, dyB=UE._View(DB, 1024), drop=(0.2, 5, 29), **kw)
+    for name, args in calls:
+        _check_kinds(name, args)
+    tail = [Y, 1024, X, 512, SS, ST, DX, 512, DG, DBETA, 512, 2, 4, 8, UE.LEAK]
+    assert calls == [("nppc_bn_bwd", [prec, DA, 512, None, 0] + tail + [S]),
+                     ("nppc_bn_bwd", [prec, DA, 512, DB, 1024] + tail + [S]),
+                     ("nppc_bn_bwd_dropout", [prec, DA, 512, DB, 1024] + tail + [0.2, 5, 29, S])]
 
 
 @pytest.mark.parametrize("case, args, expect", [
