@@ -14,8 +14,8 @@ import torch
 
 from . import _hip as H
 from .gemm import gemm_nt, gemm_nt_gn, lstm_wgrad_mode, reduce_slabs, reduce_slabs_t
-from .ops_lstm import (PackedLSTM, PackedLSTMBwd, ROW_PAD, WGRAD_SPLITS, bwd_head_fusable, forward_x_ld, lstm2_backward, lstm2_forward,
-                       own_workspaces, padded_rows, rows_view, workspace)
+from .ops_lstm import (PackedLSTM, PackedLSTMBwd, ROW_PAD, WGRAD_SPLITS, lstm2_backward, lstm2_forward, own_workspaces, padded_rows,
+                       plan_backward, plan_forward, rows_view, workspace)
 
 TCN_HIDDEN = 512
 TCN_DILATIONS = (1, 2, 5, 9, 1, 2, 5, 9)
@@ -403,8 +403,8 @@ class FSNEngine:
         head = (self.Whp, self.O) if (prec == H.PREC_BF16 and self.Opad == 16) else None
         # the frozen net's fused-head inference launch reads rows of 40 columns (the same buffer, viewed narrower): the
         # staging kernel writes 37 % less, the recurrent kernel fetches 80 instead of 128 bytes per sequence and step
-        x_tm = d["x_tm"]
-        xld = forward_x_ld(d["Nseq"], self.lstm, train, head) if mtile is None else self.KX
+        plan = plan_forward(d["Nseq"], self.lstm, train, mtile, head and head[1])
+        x_tm, xld = d["x_tm"], plan.x_ld
         if xld != self.KX:
             x_tm = d["x_rows"].view(-1)[:Tv * d["Nseq"] * xld].view(Tv, d["Nseq"], xld)
         H.call("nppc_subband_stage", prec, src, ldS, d["fb"], ldF, R * ldF, d["sbscale"], x_tm, B, F, Tp, Tv,
@@ -417,7 +417,7 @@ class FSNEngine:
             hook, self.pre_lstm_hook = self.pre_lstm_hook, None
             hook()
         FSNEngine.join_all()                  # (a no-op after the trainer's hook; any other caller gets the join for free)
-        lo = lstm2_forward(x_tm, self.lstm, train, mtile, head=head)
+        lo = lstm2_forward(x_tm, self.lstm, train, head=head, plan=plan)
         d["lstm"] = lo
         # 8: Linear(H -> O) + re-layout + look-ahead crop
         out = torch.empty(B, self.O, d["Fo"], T, dtype=torch.float32, device=self.dev)
@@ -586,8 +586,8 @@ class FSNEngine:
             self._scatter_slabs(slab, Sg, K4p * wp, wp, dests, s)
 
     def _backward_plan(self, d):
-        """the BackwardPlan of buffer set d, cached with it: shapes and precision decide, and `key` (the hook, ops_lstm's switches)"""
-        key = (self.grad_range_hook is not None and self.early_buckets_ok, bwd_head_fusable(d["Nseq"], self.lstm_bwd))
+        """the BackwardPlan of buffer set d, cached with it: shapes and precision decide, and `key` (the hook; ops_lstm's backward plan takes the head)"""
+        key = (self.grad_range_hook is not None and self.early_buckets_ok, plan_backward(d["Nseq"], self.lstm_bwd).head_entry is not None)
         if d.get("bwd_plan", (None,))[0] != key:
             prec, ldC, R = self.prec, self.ldC, d["B"] * d["Tp"]
             bk = 64 if prec == H.PREC_BF16 else 32

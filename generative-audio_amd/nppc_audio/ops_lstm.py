@@ -1,6 +1,12 @@
-"""Host side of the fused 2-layer LSTM kernels (csrc/lstm.hip)."""
+"""Host side of the fused 2-layer LSTM kernels (csrc/lstm.hip, csrc/lstm_coop.hip, csrc/lstm_ws.hip).
+
+Every launch is decided once: `plan_forward` / `plan_backward` turn the shape, the packed weights and the module switches
+into a plan (which kernel, cluster geometry, staging width, workspace sizes, profile label), and `lstm2_forward` /
+`lstm2_backward` only obtain the workspaces the plan names and make the one launch it names.  The rest of the
+module is the packed weights and the registry of step-persistent workspaces with their sticky time-out counters."""
 import ctypes
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -65,15 +71,8 @@ def pick_mtile(n_seq, prec, train, n_cu=256):
 
 _WS = {}
 COOP = True          # use the cooperative (weights split over CU pairs) kernels when the shape allows it
-# weight-stationary 12-CU clusters (csrc/lstm_ws.hip) for the forward when the plan allows: "0" never (default), "1" inference
-# launches, "2" also the training forward.  Measured at C2 (profiles/r03_lstm_ws_variants.txt, r03_bench_ws_modes.txt): ALONE
-# the restorer launch takes 8.9 ms against 9.8 ms for the CU-pair kernel and the no-grad direction launch 4.4 against 5.6,
-# but INSIDE the train step the same launches are slower (9.3 vs 9.1 ms) and so are the launches behind them: these kernels
-# are bound by what the chip may draw, and the cluster kernel's hidden-state gather (4.3 TB/s from L2) costs 20 % of its clock
-# Round 4 default "auto": the cluster kernel takes the INFERENCE launches of small problems -- those for which the streaming
-# plan falls back to four-CU clusters because CU pairs would leave most of the chip idle (BASELINE config 5: 2056 sequences
-# x 1878 steps: 23.4 ms against 48.3 ms for the four-CU streaming plan, step 145.3 -> 120.1 ms; the training forward at
-# N = 1024 stays on the streaming kernel: 35.4 vs 32.9 ms; profiles/r04_bench_c5_ws_modes.txt)
+# weight-stationary 12-CU clusters (csrc/lstm_ws.hip) for the forward: "0" never, "1" inference launches, "2" also the training
+# forward, "auto" (default) inference launches the streaming plan would give to clusters of four CUs or more
 WS_MODE = os.environ.get("NPPC_LSTM_WS", "auto")
 WS = WS_MODE != "0"
 N_CU = None
@@ -191,102 +190,6 @@ def _coop_plan(N, packed, train):
     return G.value, cmt.value, ncl.value
 
 
-def lstm2_forward(x_tm, packed, train, mtile=None, head=None):
-    """x_tm [Tn][N][kx] (time-major, zero padded to kx) -> dict(h2[, h1, g1, g2, c1, c2]) time-major.
-    In train mode h1/h2 are prefixes of zero-padded row buffers (`h1_rows`, `h2_rows`: [Rpad][H]) that the
-    weight-gradient GEMMs read directly.
-    head = (whp [16][H] packed head weights, O): when the cooperative pair kernel runs, the output head is fused into it
-    and the result carries head_partial [2][Tn][N][O] fp32 (the caller finishes with nppc_sb_head_finalize) -- in
-    inference INSTEAD of h2, in training beside the saved state; any other plan ignores `head`."""
-    Tn, N, kx = x_tm.shape
-    # kx < packed.kx: rows staged at a packed width (forward_x_ld) -- only the fused-head CU-pair inference launch takes them
-    assert (kx == packed.kx or (kx == forward_x_ld(N, packed, train, head) and mtile is None)) and x_tm.dtype == H.dtype_of(packed.prec)
-    Hd = packed.Hd
-    dt, dev = x_tm.dtype, x_tm.device
-    tag = ("lstm", id(packed), train)
-    out = {}
-    if train:
-        # N zero guard rows in front (h_{-1} = 0): `h1_guard` row r is h1 row r - N, the B operand of the weight-gradient
-        # product that pairs the gate gradients of step t with h_{t-1} without shifting the gate gradients
-        Rp = padded_rows(Tn * N, N)
-        # (N, Tn) in the key: the guard rows in front and the padding rows behind Tn * N must be zero and are zeroed once per
-        # buffer; two (N, Tn) pairs with equal N + Rp must not share one (the larger N's guard rows would hold stale h)
-        out["h1_guard"] = workspace(tag + ("h1", N, Tn), (N + Rp, Hd), dt, dev, zero=True)
-        out["h2_guard"] = workspace(tag + ("h2", N, Tn), (N + Rp, Hd), dt, dev, zero=True)
-        out["h1_rows"] = out["h1_guard"][N:]
-        out["h2_rows"] = out["h2_guard"][N:]
-        out["h1"] = rows_view(out["h1_rows"], Tn, N)
-        out["h2"] = rows_view(out["h2_rows"], Tn, N)
-        out["c1"] = workspace(tag + ("c1",), (Tn, N, Hd), dt, dev)
-        out["c2"] = workspace(tag + ("c2",), (Tn, N, Hd), dt, dev)
-        out["g1"] = workspace(tag + ("g1",), (Tn, N, Hd, 4), dt, dev)
-        out["g2"] = workspace(tag + ("g2",), (Tn, N, Hd, 4), dt, dev)
-    if mtile == "ws" or (WS and COOP and mtile is None and (not train or WS_MODE == "2") and _ws_wanted(N, packed, train)):
-        ws_out = _lstm2_forward_ws(x_tm, packed, train, head, out, tag)
-        if ws_out is not None:
-            return ws_out
-        assert mtile != "ws", "the weight-stationary plan does not apply to this shape"
-        mtile = None
-    if (COOP and mtile is None) or isinstance(mtile, tuple):
-        if isinstance(mtile, tuple):               # (G, mtile) forced by a test / benchmark
-            G, cmt = mtile
-            ncl = (N + 16 * cmt - 1) // (16 * cmt)
-            assert ncl * G <= _n_cu(), "cooperative launch needs one CU per workgroup"
-        else:
-            G, cmt, ncl = _coop_plan(N, packed, train)
-        if ncl > 0:
-            xch = workspace(tag + ("coop_xch",), (ncl * 2 * 2 * 16 * cmt * Hd,), dt, dev)
-            flags = workspace(tag + ("coop_flags",), (ncl * 2 * G + 4,), torch.int32, dev, zero=True)
-            if head is not None and G == 2 and head[1] <= FUSED_HEAD_MAX_O and (not train or cmt == 2):
-                whp, O = head
-                out["head_partial"] = workspace(tag + ("hpart", O), (2, Tn, N, O), torch.float32, dev)
-                _timed((f"lstm2_fwd_coop_g{G}", int(train), N, Tn, cmt), lambda: H.call(
-                    "nppc_lstm2_fwd_coop_head", packed.prec, int(train), cmt, x_tm, packed.wp1, packed.wp2, packed.bias1,
-                    packed.bias2, out.get("h2"), out.get("h1"), out.get("g1"), out.get("g2"), out.get("c1"), out.get("c2"),
-                    xch, xch.numel() * xch.element_size(), flags, N, Tn, packed.I, Hd, whp, out["head_partial"], O, kx,
-                    H.stream()))
-                return out
-            assert kx == packed.kx
-            if not train:
-                out["h2"] = workspace(tag + ("h2",), (Tn, N, Hd), dt, dev)
-            _timed((f"lstm2_fwd_coop_g{G}", int(train), N, Tn, cmt), lambda: H.call(
-                "nppc_lstm2_fwd_coop", packed.prec, int(train), G, cmt, x_tm, packed.wp1, packed.wp2, packed.bias1,
-                packed.bias2, out["h2"], out.get("h1"), out.get("g1"), out.get("g2"), out.get("c1"), out.get("c2"), xch,
-                xch.numel() * xch.element_size(), flags, N, Tn, packed.I, Hd, H.stream()))
-            return out
-    if mtile is None:
-        mtile = pick_mtile(N, packed.prec, train)
-    if not train:
-        out["h2"] = workspace(tag + ("h2",), (Tn, N, Hd), dt, dev)
-    _timed(("lstm2_fwd", int(train), N, Tn, mtile), lambda: H.call(
-        "nppc_lstm2_fwd", packed.prec, int(train), mtile, x_tm, packed.wp1, packed.wp2, packed.bias1, packed.bias2,
-        out["h2"], out.get("h1"), out.get("g1"), out.get("g2"), out.get("c1"), out.get("c2"), N, Tn, packed.I, Hd,
-        H.stream()))
-    return out
-
-
-# packed input rows for the frozen restorer's inference launch (CU-pair kernel with the fused head): 40 columns instead of 64
-# (34 features + the spare column + pad to 16 bytes), -37 % of the staged bytes and of the kernel's x reads
-def forward_x_ld(N, packed, train, head):
-    """row width (elements) the staging kernel should write for lstm2_forward(x, packed, train, None, head): packed.kx unless the
-    launch will be the fused-head CU-pair inference kernel, which fetches rows of any 16-byte multiple width"""
-    if (train or head is None or not COOP or packed.prec != H.PREC_BF16 or packed.Hd != 384
-            or head[1] > FUSED_HEAD_MAX_O or packed.I + 1 > 40):
-        return packed.kx
-    if WS and _ws_wanted(N, packed, train) and ws_plan(N, packed) is not None:
-        return packed.kx
-    G, _, ncl = _coop_plan(N, packed, False)
-    return 40 if (ncl > 0 and G == 2) else packed.kx
-
-
-def _ws_wanted(N, packed, train):
-    """NPPC_LSTM_WS=1|2: whenever the plan applies; "auto": only where the streaming plan would not be CU pairs"""
-    if WS_MODE != "auto":
-        return True
-    G, _, ncl = _coop_plan(N, packed, train)
-    return ncl > 0 and G >= 4
-
-
 def ws_plan(N, packed):
     """(clusters, nch_max) of the weight-stationary forward for N sequences, or None"""
     if not getattr(packed, "ws", False):
@@ -296,30 +199,107 @@ def ws_plan(N, packed):
     return (cl.value, nch.value) if cl.value > 0 else None
 
 
-def _lstm2_forward_ws(x_tm, packed, train, head, out, tag):
-    """weight-stationary cluster forward (csrc/lstm_ws.hip).  Inference needs the fused head (h2 only lives in a two-slot
-    exchange ring); training keeps the whole saved state and takes the head along when asked.  Returns None when the
-    plan does not apply."""
-    Tn, N, _ = x_tm.shape
-    plan = ws_plan(N, packed)
-    if plan is None or (not train and head is None) or (head is not None and head[1] > FUSED_HEAD_MAX_O):
-        return None
-    ncl, nch = plan
-    dt, dev, Hd = x_tm.dtype, x_tm.device, packed.Hd
-    cst = workspace(tag + ("ws_cst",), (ncl * 12 * nch * 2048,), torch.float32, dev)
-    flags = workspace(tag + ("ws", "coop_flags"), (ncl * nch * 16 + 4,), torch.int32, dev, zero=True)
+class ForwardPlan(NamedTuple):
+    """the one launch of lstm2_forward for (N, packed, train, mtile, head): decided by plan_forward, read by the launcher"""
+    kernel: str        # "single" (nppc_lstm2_fwd), "coop" (nppc_lstm2_fwd_coop), "coop_head" (nppc_lstm2_fwd_coop_head), "ws" (nppc_lstm2_fwd_ws)
+    G: int             # CUs per cluster: 1, streaming clusters of 2 / 4 / 8, weight-stationary clusters of 12
+    mtile: int         # 16-row tiles per workgroup ("single") or per cluster ("coop*"); 0 for "ws"
+    clusters: int      # cooperative clusters (0 for "single")
+    nch: int           # "ws": chunks of sequences per cluster (nch_max of nppc_lstm2_ws_plan); else 0
+    fused_head: bool   # the kernel takes the output head and leaves head_partial
+    x_ld: int          # row width (elements) of x_tm: packed.kx, or 40 for the fused-head CU-pair inference launch
+    label: str         # name of the launch in ops_lstm.PROFILE
+
+
+# packed input rows for the frozen restorer's inference launch (CU-pair kernel with the fused head, which fetches rows of any
+# 16-byte multiple width): 40 columns instead of 64 (34 features + the spare column + pad to 16 bytes), -37 % of the staged
+# bytes and of the kernel's x reads
+X_LD_PACKED = 40
+
+
+def plan_forward(N, packed, train, mtile=None, head_O=None):
+    """mtile: None = the default plan, under the switches COOP / WS / WS_MODE; an int = the single-workgroup kernel with that
+    tile; (G, mtile) = that streaming cooperative plan; "ws" = the weight-stationary kernel.  The last three are forced by tests
+    and benchmarks and refuse (AssertionError) what they cannot run.  head_O: outputs of the head the caller offers to fuse."""
+    default, kx = mtile is None, packed.kx
+    fusable = head_O is not None and head_O <= FUSED_HEAD_MAX_O         # one MFMA column tile
+    coop = _coop_plan(N, packed, train) if (COOP and default) else (0, 0, 0)
+    # "1" | "2": the weight-stationary kernel whenever its plan applies; "auto": only where the streaming plan would not be CU pairs
+    if mtile == "ws" or (default and COOP and WS and (not train or WS_MODE == "2")
+                         and (WS_MODE != "auto" or (coop[2] > 0 and coop[0] >= 4))):
+        ws = ws_plan(N, packed)
+        # inference needs the fused head: h2 only lives in a two-slot exchange ring
+        if ws is not None and (train or head_O is not None) and (head_O is None or fusable):
+            return ForwardPlan("ws", 12, 0, ws[0], ws[1], head_O is not None, kx, "lstm2_fwd_ws")
+        assert mtile != "ws", "the weight-stationary plan does not apply to this shape"
+    if isinstance(mtile, tuple):
+        coop = (*mtile, (N + 16 * mtile[1] - 1) // (16 * mtile[1]))
+        assert coop[2] * coop[0] <= _n_cu(), "cooperative launch needs one CU per workgroup"
+    G, cmt, ncl = coop
+    if ncl > 0 and fusable and G == 2 and (not train or cmt == 2):
+        x_ld = X_LD_PACKED if (default and not train and packed.I + 1 <= X_LD_PACKED) else kx
+        return ForwardPlan("coop_head", G, cmt, ncl, 0, True, x_ld, f"lstm2_fwd_coop_g{G}")
+    if ncl > 0:
+        return ForwardPlan("coop", G, cmt, ncl, 0, False, kx, f"lstm2_fwd_coop_g{G}")
+    return ForwardPlan("single", 1, pick_mtile(N, packed.prec, train) if default else mtile, 0, 0, False, kx, "lstm2_fwd")
+
+
+def lstm2_forward(x_tm, packed, train, mtile=None, head=None, plan=None):
+    """x_tm [Tn][N][plan.x_ld] (time-major, zero padded) -> dict(h2[, h1, g1, g2, c1, c2]) time-major.
+    In train mode h1/h2 are prefixes of zero-padded row buffers (`h1_rows`, `h2_rows`: [Rpad][H]) that the
+    weight-gradient GEMMs read directly.
+    head = (whp [16][H] packed head weights, O): when the plan fuses the output head (CU-pair and weight-stationary kernels),
+    the result carries head_partial [2 or 1][Tn][N][O] fp32 (the caller finishes with nppc_sb_head_finalize) -- in
+    inference INSTEAD of h2, in training beside the saved state; any other plan ignores `head`.
+    plan: plan_forward(N, packed, train, mtile, O) when the caller has made it already (it staged x_tm at plan.x_ld)."""
+    Tn, N, kx = x_tm.shape
+    p = plan or plan_forward(N, packed, train, mtile, None if head is None else head[1])
+    # rows at the plan's width; full-width rows suit every kernel (the one that takes packed rows is told the pitch)
+    assert kx in (p.x_ld, packed.kx) and x_tm.dtype == H.dtype_of(packed.prec)
+    Hd, dt, dev = packed.Hd, x_tm.dtype, x_tm.device
+    tag, out = ("lstm", id(packed), train), {}
     if train:
-        h1, h2 = out["h1"], out["h2"]
+        # N zero guard rows in front (h_{-1} = 0): `h1_guard` row r is h1 row r - N, the B operand of the weight-gradient
+        # product that pairs the gate gradients of step t with h_{t-1} without shifting the gate gradients
+        Rp = padded_rows(Tn * N, N)
+        # (N, Tn) in the key: the guard rows in front and the padding rows behind Tn * N must be zero and are zeroed once per
+        # buffer; two (N, Tn) pairs with equal N + Rp must not share one (the larger N's guard rows would hold stale h)
+        for k in ("h1", "h2"):
+            out[k + "_guard"] = workspace(tag + (k, N, Tn), (N + Rp, Hd), dt, dev, zero=True)
+            out[k + "_rows"] = out[k + "_guard"][N:]
+            out[k] = rows_view(out[k + "_rows"], Tn, N)
+        for k, gates in (("c1", ()), ("c2", ()), ("g1", (4,)), ("g2", (4,))):
+            out[k] = workspace(tag + (k,), (Tn, N, Hd) + gates, dt, dev)
+    whp, O = head if p.fused_head else (None, 0)
+    ncl, G, cmt, nch = p.clusters, p.G, p.mtile, p.nch
+    saved = [out.get(k) for k in ("g1", "g2", "c1", "c2")]
+    if p.kernel == "ws":
+        # weight-stationary cluster forward (csrc/lstm_ws.hip).  Inference: h1 / h2 only live in two-slot exchange rings;
+        # training keeps the whole saved state and takes the head along when asked
+        cst = workspace(tag + ("ws_cst",), (ncl * G * nch * 2048,), torch.float32, dev)
+        flags = workspace(tag + ("ws", "coop_flags"), (ncl * nch * 16 + 4,), torch.int32, dev, zero=True)
+        h1, h2 = (out["h1"], out["h2"]) if train else [workspace(tag + (k,), (2, N, Hd), dt, dev) for k in ("ws_h1ring", "ws_h2ring")]
+        if p.fused_head:
+            out["head_partial"] = workspace(tag + ("ws_hpart", O), (1, Tn, N, O), torch.float32, dev)
+        launch = ("nppc_lstm2_fwd_ws", int(train), x_tm, packed.wsp1, packed.wsp2, packed.bias1, packed.bias2, h1, h2, *saved, cst,
+                  flags, whp, out.get("head_partial"), O, N, Tn, ncl, nch)
     else:
-        h1 = workspace(tag + ("ws_h1ring",), (2, N, Hd), dt, dev)
-        h2 = workspace(tag + ("ws_h2ring",), (2, N, Hd), dt, dev)
-    whp, O, hpart = None, 0, None
-    if head is not None:
-        whp, O = head
-        hpart = out["head_partial"] = workspace(tag + ("ws_hpart", O), (1, Tn, N, O), torch.float32, dev)
-    _timed(("lstm2_fwd_ws", int(train), N, Tn, nch), lambda: H.call(
-        "nppc_lstm2_fwd_ws", int(train), x_tm, packed.wsp1, packed.wsp2, packed.bias1, packed.bias2, h1, h2, out.get("g1"),
-        out.get("g2"), out.get("c1"), out.get("c2"), cst, flags, whp, hpart, O, N, Tn, ncl, nch, H.stream()))
+        if p.kernel != "single":
+            xch = workspace(tag + ("coop_xch",), (ncl * 2 * 2 * 16 * cmt * Hd,), dt, dev)
+            flags = workspace(tag + ("coop_flags",), (ncl * 2 * G + 4,), torch.int32, dev, zero=True)
+            xch_args = (xch, xch.numel() * xch.element_size(), flags, N, Tn, packed.I, Hd)
+        if p.kernel == "coop_head":
+            out["head_partial"] = workspace(tag + ("hpart", O), (2, Tn, N, O), torch.float32, dev)
+        elif not train:
+            out["h2"] = workspace(tag + ("h2",), (Tn, N, Hd), dt, dev)
+        state = (x_tm, packed.wp1, packed.wp2, packed.bias1, packed.bias2, out.get("h2"), out.get("h1"), *saved)
+        if p.kernel == "coop_head":
+            launch = ("nppc_lstm2_fwd_coop_head", packed.prec, int(train), cmt, *state, *xch_args, whp, out["head_partial"], O, kx)
+        elif p.kernel == "coop":
+            launch = ("nppc_lstm2_fwd_coop", packed.prec, int(train), G, cmt, *state, *xch_args)
+        else:
+            launch = ("nppc_lstm2_fwd", packed.prec, int(train), cmt, *state, N, Tn, packed.I, Hd)
+    _timed((p.label, int(train), N, Tn, nch or cmt), lambda: H.call(*launch, H.stream()))
     return out
 
 
@@ -361,9 +341,50 @@ class PackedLSTMBwd:
         return self
 
 
+class BackwardPlan(NamedTuple):
+    """one launch shape of lstm2_backward: a row of BWD_PLANS, with the sizes for N sequences filled in by plan_backward"""
+    entry: str               # entry point for dh2 given
+    head_entry: str          # entry point for the fused head backward (dyt, whT instead of dh2); None: this kernel has none
+    label: str               # name of the launch in ops_lstm.PROFILE
+    G: int                   # CUs per cluster (1: the single-workgroup kernel, no exchange and no flags)
+    weights: tuple           # attributes of PackedLSTMBwd: the packing this kernel reads
+    xch_key: tuple           # workspace key of the exchange buffer ...
+    xch_elems: int           # ... its elements: per cluster in the table, in all in a plan
+    xch_dtype: torch.dtype   # ... None: the dtype of the saved state
+    flag_key: tuple          # workspace key of the flag block (allocated ZEROED: a stale epoch word is a hand-off that spins) ...
+    flag_words: int          # ... its words: per cluster in the table; in all, with the 4 sticky time-out words behind them, in a plan
+
+
+BWD_PLANS = {
+    # K-split on four-CU clusters of 64 sequences; one entry point for both gradient forms; sizes from nppc_lstm2_coop_bwd4_sizes
+    "ksplit_g4": BackwardPlan("nppc_lstm2_bwd_coop4", "nppc_lstm2_bwd_coop4", "lstm2_bwd_coop_ksplit_g4", 4, ("k4wb1", "k4wb2"),
+                              ("coop_xch4",), None, torch.uint8, ("g4", "coop_flags"), None),
+    # K-split on CU pairs of 32 sequences.  C2_XCH bytes of bf16 partial sums [layer][parity][cu][32][384]; C2_FPC = 48: epochs
+    # [layer][cu][wave]
+    "ksplit": BackwardPlan("nppc_lstm2_bwd_coop2", "nppc_lstm2_bwd_coop2_head", "lstm2_bwd_coop_ksplit", 2, ("kwb1", "kwb2"),
+                           ("coop_xch",), 2 * 2 * 2 * 32 * 384, None, ("coop_flags",), 48),
+    # output-split on CU pairs of 32 sequences.  Gate gradients [layer][parity][cu] x CB_MC * CB_KC = [32][768]; epochs [layer][cu]
+    "osplit": BackwardPlan("nppc_lstm2_bwd_coop", None, "lstm2_bwd_coop_g2", 2, ("cwb1", "cwb2"),
+                           ("coop_xch",), 2 * 2 * 2 * 32 * 768, None, ("coop_flags",), 4),
+    "single": BackwardPlan("nppc_lstm2_bwd", None, "lstm2_bwd", 1, ("wb1", "wb2"), None, 0, None, None, 0),
+}
+
+
+def plan_backward(N, packed_bwd, coop=None):
+    """the BackwardPlan of lstm2_backward(saved of N sequences, ..., packed_bwd, coop=coop) under COOP / COOP_BWD_KSPLIT / BWD_G4"""
+    if not ((COOP if coop is None else coop) and packed_bwd.coop and ((N + 31) // 32) * 2 <= _n_cu()):
+        return BWD_PLANS["single"]
+    if COOP_BWD_KSPLIT and BWD_G4 != "0" and ((N + 63) // 64) * 4 <= _n_cu():
+        npk, nx, nf = ctypes.c_long(), ctypes.c_long(), ctypes.c_long()
+        H.call("nppc_lstm2_coop_bwd4_sizes", N, ctypes.byref(npk), ctypes.byref(nx), ctypes.byref(nf))
+        return BWD_PLANS["ksplit_g4"]._replace(xch_elems=nx.value, flag_words=nf.value)
+    p, ncl = BWD_PLANS["ksplit" if COOP_BWD_KSPLIT else "osplit"], (N + 31) // 32
+    return p._replace(xch_elems=ncl * p.xch_elems, flag_words=ncl * p.flag_words + 4)
+
+
 def bwd_head_fusable(N, packed_bwd, coop=None):
-    """True when lstm2_backward will run the K-split cooperative kernel, which can take the head backward (dyt, whT)"""
-    return bool((COOP if coop is None else coop) and packed_bwd.coop and ((N + 31) // 32) * 2 <= _n_cu() and COOP_BWD_KSPLIT)
+    """True when lstm2_backward will run a K-split cooperative kernel, which can take the head backward (dyt, whT)"""
+    return plan_backward(N, packed_bwd, coop).head_entry is not None
 
 
 def lstm2_backward(saved, dh2, packed_bwd, kx, coop=None, head=None):
@@ -378,33 +399,18 @@ def lstm2_backward(saved, dh2, packed_bwd, kx, coop=None, head=None):
     Rp = padded_rows(Tn * N, N)
     dg1 = workspace(tag + ("dg1",), (Rp, 4 * Hd), dt, dev, zero=True)
     dg2 = workspace(tag + ("dg2",), (Rp, 4 * Hd), dt, dev, zero=True)
-    use_coop = (COOP if coop is None else coop) and packed_bwd.coop and ((N + 31) // 32) * 2 <= _n_cu()
-    st = (saved["g1"], saved["g2"], saved["c1"], saved["c2"])
-
-    def launch(label, G, fn, grads, wb, xch_key, xch_elems, flag_key, flag_words, xch_dt=dt):
-        """what the cooperative launches share: exchange workspace, flag block (epoch words + 4 for the sticky time-outs), timed call"""
-        xch = workspace(tag + xch_key, (xch_elems,), xch_dt, dev)
-        flags = workspace(tag + flag_key, (flag_words,), torch.int32, dev, zero=True)
-        _timed((label, 1, N, Tn, G), lambda: H.call(fn, *st, *grads, *wb, dx, dg1, dg2, xch, xch.numel() * xch.element_size(),
-                                                   flags, N, Tn, _n_cu(), H.stream()))
+    p = plan_backward(N, packed_bwd, coop)
+    assert head is None or p.head_entry is not None, "the fused head backward needs the K-split cooperative kernel"
+    st, wb = [saved[k] for k in ("g1", "g2", "c1", "c2")], [getattr(packed_bwd, w) for w in p.weights]
+    if p.G == 1:
+        _timed((p.label, 1, N, Tn, 1), lambda: H.call(
+            p.entry, packed_bwd.prec, *st, dh2, *wb, dx, dg1, dg2, N, Tn, packed_bwd.I, Hd, H.stream()))
         return dx, dg1, dg2
-
-    ncl = (N + 31) // 32
-    if use_coop and COOP_BWD_KSPLIT and BWD_G4 != "0" and ((N + 63) // 64) * 4 <= _n_cu():
-        npk, nx, nf = ctypes.c_long(), ctypes.c_long(), ctypes.c_long()
-        H.call("nppc_lstm2_coop_bwd4_sizes", N, ctypes.byref(npk), ctypes.byref(nx), ctypes.byref(nf))
-        grads = (dh2, None, None) if head is None else (None,) + tuple(head)
-        return launch("lstm2_bwd_coop_ksplit_g4", 4, "nppc_lstm2_bwd_coop4", grads, (packed_bwd.k4wb1, packed_bwd.k4wb2),
-                      ("coop_xch4",), nx.value, ("g4", "coop_flags"), nf.value, xch_dt=torch.uint8)
-    if use_coop and COOP_BWD_KSPLIT:      # partial sums [cluster][layer][parity][cu][32][384]; epochs [cluster][layer][cu][wave]
-        fn, grads = ("nppc_lstm2_bwd_coop2", (dh2,)) if head is None else ("nppc_lstm2_bwd_coop2_head", tuple(head))
-        return launch("lstm2_bwd_coop_ksplit", 2, fn, grads, (packed_bwd.kwb1, packed_bwd.kwb2),
-                      ("coop_xch",), ncl * 2 * 2 * 2 * 32 * 384, ("coop_flags",), ncl * 48 + 4)
-    assert head is None, "the fused head backward needs the K-split cooperative kernel"
-    if use_coop:                          # gate gradients [cluster][layer][parity][cu][32][768]; epochs [cluster][layer][cu]
-        return launch("lstm2_bwd_coop_g2", 2, "nppc_lstm2_bwd_coop", (dh2,), (packed_bwd.cwb1, packed_bwd.cwb2),
-                      ("coop_xch",), ncl * 2 * 2 * 2 * 32 * 768, ("coop_flags",), ncl * 4 + 4)
-    _timed(("lstm2_bwd", 1, N, Tn, 1), lambda: H.call(
-        "nppc_lstm2_bwd", packed_bwd.prec, saved["g1"], saved["g2"], saved["c1"], saved["c2"], dh2, packed_bwd.wb1,
-        packed_bwd.wb2, dx, dg1, dg2, N, Tn, packed_bwd.I, Hd, H.stream()))
+    fn, grads = (p.entry, (dh2,)) if head is None else (p.head_entry, tuple(head))
+    if p.entry == p.head_entry:           # one entry point takes (dh2, dyt, whT), the form not given as null pointers
+        grads = (dh2, None, None) if head is None else (None, *head)
+    xch = workspace(tag + p.xch_key, (p.xch_elems,), p.xch_dtype or dt, dev)
+    flags = workspace(tag + p.flag_key, (p.flag_words,), torch.int32, dev, zero=True)
+    _timed((p.label, 1, N, Tn, p.G), lambda: H.call(fn, *st, *grads, *wb, dx, dg1, dg2, xch, xch.numel() * xch.element_size(),
+                                                   flags, N, Tn, _n_cu(), H.stream()))
     return dx, dg1, dg2
