@@ -4,13 +4,32 @@
 // (tools/check/flac_enc_host_check.cc) take every decision with the same text.
 //
 // The stream: fLaC, one STREAMINFO (last), frames of a fixed block size (the last one shorter).  Lossless, fixed predictors
-// only, no escape partitions, no wasted bits.  The decision rule, a function of the samples alone:
+// (and, on request, LPC: below), no escape partitions, no wasted bits.  The decision rule, a function of the samples alone:
 //   subframe of width b: constant when all samples are equal; else for o = 0..min(4, bs) and p = 0..min(8, ctz(bs)) with
 //   (bs >> p) >= o, every partition takes the Rice parameter k (0..14 method 0, 0..30 method 1; lowest on ties) of the
 //   smallest exact bit count sum(u >> k) + cnt (1 + k), u = zigzag(residual); cost = 8 + o b + 6 + sum(pbits + bits);
 //   cheapest (o, p), ties to the lower o then the lower p; verbatim when that cost >= 8 + bs b.
 //   stereo: L, R, M = (L + R) >> 1, S = L - R costed as above; cheapest of 0 (L,R), 1 (L,S), 2 (S,R), 3 (M,S), lowest on ties.
 // sum(u >> k) is additive over sub-partitions: the sums of the finest partition order are merged upward.
+//
+// predictor "lpc" (specification tests/flac_lpc_ref.py) adds candidates of order m = 1..min(M, bs),
+// 1 <= M <= 12, to the fixed ones of a non-constant subframe of block bs:
+//   1. window, integers only: N = bs + 1, d_i = 2 i - (bs - 1), w_i = floor(2^15 (N^2 - d_i^2) / N^2) (Welch, Q15),
+//      x_i = (s_i w_i) >> 15, an arithmetic shift in int64
+//   2. r_l = sum_i x_i x_{i+l} in int64, l = 0..M (an empty sum, l >= bs, is 0); r_0 == 0: no LPC candidates
+//   3. Levinson-Durbin in fp64 on (double) r_l, every product, sum and quotient rounded on its own (contraction off):
+//        err = r_0;  order m:  acc = r_m;  for j = 0..m-2: acc = acc - a_j r_{m-1-j};  k = acc / err
+//        k not finite or |k| >= 1: this order and every higher one are no candidates
+//        t_j = a_j - k a_{m-2-j} (j = 0..m-2), t_{m-1} = k;  err = err (1 - k k)
+//        err not finite or <= 0: this order and every higher one are no candidates;  a = t, the coefficients of order m
+//   4. precision P = 12 (bps <= 16) or 15; shift = the largest s in 0..15 with floor(max|a_j| 2^s + 0.5) <= 2^(P-1) - 1, none:
+//      the order is no candidate; q_j = floor(a_j 2^shift + 0.5) clamped to [-2^(P-1), 2^(P-1) - 1], no error feedback
+//   5. e_i = s_i - ((sum_j q_j s_{i-1-j}) >> shift), the sum in int64, as the decoder forms it; any e_i outside
+//      [-2^28, 2^28): the order is no candidate
+//   6. partition orders and parameters as for the fixed orders; cost = 8 + m b + 4 + 5 + m P + 6 + sum(pbits + bits)
+//   7. the cheapest of all fixed (o, p) and LPC (m, p); ties to fixed before LPC, then the lower order, then the lower p;
+//      constant and the verbatim comparison as above; stereo costs L, R, M, S with the larger candidate set.
+// The fixed candidates stay in the set: an LPC frame is never longer than the fixed frame of the same samples.
 //
 // Safety rules: the bit writer ORs into a zero-filled buffer and touches only bytes that receive a one bit, all of which
 // lie inside the frame's exact length; every loop is bounded by the block size, 256 partitions or 31 parameters.
@@ -24,11 +43,22 @@
 #define FLAC_ENC_MAX_BS 4608
 #define FLAC_ENC_PARTS 256       // 2^8: the finest partition order tried
 #define FLAC_ENC_STREAM_HEAD 42  // fLaC + block header + STREAMINFO
+#define FLAC_ENC_MAX_LPC 12      // the subset's limit up to 48 kHz
+#define FLAC_ENC_LAGS (FLAC_ENC_MAX_LPC + 1)
+#define FLAC_ENC_CANDS (5 + FLAC_ENC_MAX_LPC)      // fixed 0..4, then LPC 1..12
 
 struct FlacEncSub {
-  int type;                      // 0 constant, 1 verbatim, 2 fixed
+  int type;                      // 0 constant, 1 verbatim, 2 fixed, 3 LPC
   int order, porder;
   long bits;                     // the subframe's exact length
+  int shift, precision;          // LPC only
+  int qlp[FLAC_ENC_MAX_LPC];
+};
+
+// the LPC candidates of one subframe: shift[m - 1] < 0: order m is no candidate
+struct FlacEncLpcTab {
+  int shift[FLAC_ENC_MAX_LPC];
+  int qlp[FLAC_ENC_MAX_LPC][FLAC_ENC_MAX_LPC];
 };
 
 FLAC_HD bool flac_enc_bps_ok(int bps) { return bps == 8 || bps == 12 || bps == 16 || bps == 20 || bps == 24; }
@@ -50,6 +80,13 @@ FLAC_HD int32_t flac_enc_residual(const int32_t* s, int o) {
     default: return s[0] - 4 * s[-1] + 6 * s[-2] - 4 * s[-3] + s[-4];
   }
 }
+// the LPC residual as the decoder forms it (flac_core.h: flac_predict), in int64
+FLAC_HD int64_t flac_enc_lpc_residual(const int32_t* s, int m, const int* q, int shift) {
+  int64_t sum = 0;
+  for (int j = 0; j < m; ++j) sum += (int64_t)q[j] * (int64_t)s[-1 - j];
+  return (int64_t)s[0] - (sum >> shift);
+}
+FLAC_HD bool flac_enc_residual_ok(int64_t e) { return e >= -((int64_t)1 << 28) && e < ((int64_t)1 << 28); }
 FLAC_HD uint32_t flac_enc_zigzag(int32_t r) { return ((uint32_t)r << 1) ^ (uint32_t)(r >> 31); }
 
 // the parameter of one partition from its sums[k * stride] = sum(u >> k): the exact bit count, lowest k on ties
@@ -80,6 +117,35 @@ FLAC_HD void flac_enc_pick(const uint64_t* rice, int bs, int b, FlacEncSub* out)
   else out->type = 2, out->bits = (long)best;
 }
 
+// the same over the larger set: rice[c * 9 + p], c = o for the fixed orders and 4 + m for the LPC orders of tab.  Strict
+// comparisons in this order of visits are the tie rule: fixed before LPC, the lower order, the lower p.
+FLAC_HD void flac_enc_pick_lpc(const uint64_t* rice, int bs, int b, int P, int max_order, const FlacEncLpcTab* tab,
+                               FlacEncSub* out) {
+  const int maxo = bs < 4 ? bs : 4, pmax = flac_enc_pmax(bs), top = max_order < bs ? max_order : bs;
+  uint64_t best = 0;
+  int have = 0, lpc = 0;
+  for (int c = 0; c <= 4 + top; ++c) {
+    const int o = c <= 4 ? c : c - 4;
+    if (c <= 4 ? c > maxo : tab->shift[o - 1] < 0) continue;
+    const uint64_t head = c <= 4 ? 8 + (uint64_t)o * b + 6 : 8 + (uint64_t)o * b + 4 + 5 + (uint64_t)o * P + 6;
+    for (int p = 0; p <= pmax; ++p) {
+      if ((bs >> p) < o) continue;
+      const uint64_t cost = head + rice[c * 9 + p];
+      if (!have || cost < best) best = cost, out->order = o, out->porder = p, lpc = c > 4, have = 1;
+    }
+  }
+  const uint64_t verbatim = 8 + (uint64_t)bs * b;
+  if (best >= verbatim) {
+    out->type = 1, out->order = 0, out->porder = 0, out->bits = (long)verbatim;
+    return;
+  }
+  out->type = lpc ? 3 : 2, out->bits = (long)best;
+  if (lpc) {
+    out->shift = tab->shift[out->order - 1], out->precision = P;
+    for (int j = 0; j < out->order; ++j) out->qlp[j] = tab->qlp[out->order - 1][j];
+  }
+}
+
 FLAC_HD void flac_enc_constant(int b, FlacEncSub* out) { out->type = 0, out->order = 0, out->porder = 0, out->bits = 8 + b; }
 
 // bits of the four candidates L, R, M, S -> the assignment; *bits = the two subframes' length
@@ -98,6 +164,76 @@ FLAC_HD int flac_enc_cand(int assign, int c) {
 }
 FLAC_HD int32_t flac_enc_cand_sample(int cand, int32_t l, int32_t r) {
   return cand == 0 ? l : cand == 1 ? r : cand == 2 ? (l + r) >> 1 : l - r;
+}
+
+// ------------------------------------------------------------------------------------------------------ LPC analysis
+FLAC_HD int flac_enc_lpc_precision(int bps) { return bps <= 16 ? 12 : 15; }
+// the Welch window in Q15: 0 < N^2 - d^2 <= N^2, so the quotient is a floor and at most 2^15
+FLAC_HD int32_t flac_enc_window(int i, int bs) {
+  const int64_t N = (int64_t)bs + 1, d = 2 * (int64_t)i - ((int64_t)bs - 1);
+  return (int32_t)((((int64_t)1 << 15) * (N * N - d * d)) / (N * N));
+}
+FLAC_HD int32_t flac_enc_windowed(int32_t s, int i, int bs) { return (int32_t)(((int64_t)s * flac_enc_window(i, bs)) >> 15); }
+
+// r[0 .. FLAC_ENC_MAX_LPC] of the windowed block x; |x| <= 2^24 and bs <= 4608 keep every sum under 2^61
+FLAC_HD void flac_enc_autocorr(const int32_t* x, int bs, int64_t* r) {
+  for (int l = 0; l < FLAC_ENC_LAGS; ++l) {
+    int64_t acc = 0;
+    for (int i = 0; i + l < bs; ++i) acc += (int64_t)x[i] * (int64_t)x[i + l];
+    r[l] = acc;
+  }
+}
+
+FLAC_HD bool flac_enc_finite(double v) { return v - v == 0.0; }     // false for NaN and the infinities
+FLAC_HD double flac_enc_round_half_up(double v) { return __builtin_floor(v + 0.5); }
+
+// Levinson-Durbin and the quantiser (steps 3 and 4 of the rule): r -> tab, for orders 1..min(max_order, bs).  ws: two rows of
+// FLAC_ENC_MAX_LPC doubles.  A few hundred operations, serial.
+FLAC_HD void flac_enc_lpc_table(const int64_t* r, int bs, int max_order, int P, FlacEncLpcTab* tab, double* ws) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  for (int m = 0; m < FLAC_ENC_MAX_LPC; ++m) tab->shift[m] = -1;
+  if (r[0] == 0) return;
+  const int top = max_order < bs ? max_order : bs;
+  const double lim = (double)((1 << (P - 1)) - 1), low = -(double)(1 << (P - 1));
+  double* a = ws;
+  double* t = ws + FLAC_ENC_MAX_LPC;
+  double err = (double)r[0];
+  for (int m = 1; m <= top; ++m) {
+    double acc = (double)r[m];
+    for (int j = 0; j < m - 1; ++j) {
+      const double prod = a[j] * (double)r[m - 1 - j];
+      acc = acc - prod;
+    }
+    const double k = acc / err;
+    if (!flac_enc_finite(k) || !((k < 0 ? -k : k) < 1.0)) return;
+    for (int j = 0; j < m - 1; ++j) {
+      const double prod = k * a[m - 2 - j];
+      t[j] = a[j] - prod;
+    }
+    t[m - 1] = k;
+    const double kk = k * k;
+    const double one = 1.0 - kk;
+    err = err * one;
+    if (!flac_enc_finite(err) || !(err > 0.0)) return;
+    double cmax = 0.0;
+    for (int j = 0; j < m; ++j) {
+      a[j] = t[j];
+      const double c = a[j] < 0 ? -a[j] : a[j];
+      if (c > cmax) cmax = c;
+    }
+    int shift = -1;
+    for (int s = 15; s >= 0 && shift < 0; --s)
+      if (flac_enc_round_half_up(cmax * (double)(1 << s)) <= lim) shift = s;
+    if (shift < 0) continue;                                        // too large for the precision: this order only
+    tab->shift[m - 1] = shift;
+    for (int j = 0; j < m; ++j) {
+      double q = flac_enc_round_half_up(a[j] * (double)(1 << shift));
+      q = q < low ? low : q > lim ? lim : q;
+      tab->qlp[m - 1][j] = (int)q;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- headers
@@ -209,21 +345,35 @@ struct FlacBitWriter {           // big-endian, ORs into a zero-filled buffer
 struct FlacEncScratch {
   int32_t* cand;                 // [4][FLAC_ENC_MAX_BS]: L, R, M, S of the frame
   uint64_t* sums;                // [31][FLAC_ENC_PARTS]
+  int32_t* win;                  // [FLAC_ENC_MAX_BS]: the windowed block; the LPC predictor only
 };
 
-// sums[k][part] over the residuals of order o at partition order p (cleared here)
-FLAC_HD void flac_enc_part_sums(const int32_t* s, int bs, int o, int p, int kmax, uint64_t* sums) {
+// sums[k][part] over the residuals of order o at partition order p (cleared here); q: the LPC coefficients, or null for the
+// fixed predictor.  False when an LPC residual leaves [-2^28, 2^28).
+FLAC_HD bool flac_enc_part_sums(const int32_t* s, int bs, int o, int p, int kmax, uint64_t* sums, const int* q = nullptr,
+                                int shift = 0) {
   const int np = 1 << p, ps = bs >> p;
   for (int k = 0; k <= kmax; ++k)
-    for (int q = 0; q < np; ++q) sums[k * FLAC_ENC_PARTS + q] = 0;
+    for (int part = 0; part < np; ++part) sums[k * FLAC_ENC_PARTS + part] = 0;
   for (int i = o; i < bs; ++i) {
-    const uint32_t u = flac_enc_zigzag(flac_enc_residual(s + i, o));
-    const int q = i / ps;
-    for (int k = 0; k <= kmax; ++k) sums[k * FLAC_ENC_PARTS + q] += u >> k;
+    int32_t e;
+    if (q) {
+      const int64_t e64 = flac_enc_lpc_residual(s + i, o, q, shift);
+      if (!flac_enc_residual_ok(e64)) return false;
+      e = (int32_t)e64;
+    } else {
+      e = flac_enc_residual(s + i, o);
+    }
+    const uint32_t u = flac_enc_zigzag(e);
+    const int part = i / ps;
+    for (int k = 0; k <= kmax; ++k) sums[k * FLAC_ENC_PARTS + part] += u >> k;
   }
+  return true;
 }
 
-FLAC_HD void flac_enc_plan_sub(const int32_t* s, int bs, int b, int method, uint64_t* sums, FlacEncSub* out) {
+// max_order 0: the fixed predictors alone; 1..12: the LPC candidates too (win: scratch of bs samples)
+FLAC_HD void flac_enc_plan_sub(const int32_t* s, int bs, int b, int method, uint64_t* sums, FlacEncSub* out, int max_order = 0,
+                               int P = 0, int32_t* win = nullptr) {
   bool same = true;
   for (int i = 1; i < bs && same; ++i) same = s[i] == s[0];
   if (same) {
@@ -231,10 +381,23 @@ FLAC_HD void flac_enc_plan_sub(const int32_t* s, int bs, int b, int method, uint
     return;
   }
   const int kmax = flac_enc_kmax(method), pbits = flac_enc_pbits(method);
-  const int maxo = bs < 4 ? bs : 4, pmax = flac_enc_pmax(bs);
-  uint64_t rice[5 * 9] = {};
-  for (int o = 0; o <= maxo; ++o) {
-    flac_enc_part_sums(s, bs, o, pmax, kmax, sums);
+  const int maxo = bs < 4 ? bs : 4, pmax = flac_enc_pmax(bs), top = max_order < bs ? max_order : bs;
+  uint64_t rice[FLAC_ENC_CANDS * 9] = {};
+  FlacEncLpcTab tab;
+  if (max_order) {
+    int64_t r[FLAC_ENC_LAGS];
+    double ws[2 * FLAC_ENC_MAX_LPC];
+    for (int i = 0; i < bs; ++i) win[i] = flac_enc_windowed(s[i], i, bs);
+    flac_enc_autocorr(win, bs, r);
+    flac_enc_lpc_table(r, bs, max_order, P, &tab, ws);
+  }
+  for (int c = 0; c <= (max_order ? 4 + top : maxo); ++c) {
+    const int o = c <= 4 ? c : c - 4;
+    if (c <= 4 ? c > maxo : tab.shift[o - 1] < 0) continue;
+    if (!flac_enc_part_sums(s, bs, o, pmax, kmax, sums, c <= 4 ? nullptr : tab.qlp[o - 1], c <= 4 ? 0 : tab.shift[o - 1])) {
+      tab.shift[o - 1] = -1;
+      continue;
+    }
     for (int p = pmax; p >= 0; --p) {
       const int np = 1 << p, ps = bs >> p;
       if (ps >= o) {
@@ -243,7 +406,7 @@ FLAC_HD void flac_enc_plan_sub(const int32_t* s, int bs, int b, int method, uint
           int k;
           tot += pbits + flac_enc_best_k(sums + q, FLAC_ENC_PARTS, q == 0 ? ps - o : ps, kmax, &k);
         }
-        rice[o * 9 + p] = tot;
+        rice[c * 9 + p] = tot;
       }
       if (p > 0)
         for (int q = 0; q < np / 2; ++q)                          // ascending q: q <= 2 q, nothing read after it is written
@@ -251,12 +414,17 @@ FLAC_HD void flac_enc_plan_sub(const int32_t* s, int bs, int b, int method, uint
             sums[k * FLAC_ENC_PARTS + q] = sums[k * FLAC_ENC_PARTS + 2 * q] + sums[k * FLAC_ENC_PARTS + 2 * q + 1];
     }
   }
-  flac_enc_pick(rice, bs, b, out);
+  if (max_order) flac_enc_pick_lpc(rice, bs, b, P, max_order, &tab, out);
+  else flac_enc_pick(rice, bs, b, out);
 }
+
+// the LPC subframe's head: type 31 + m, the warm-up samples, P - 1 in 4 bits, the shift in 5 (signed, never negative here),
+// m coefficients of P bits
+FLAC_HD long flac_enc_lpc_head_bits(int m, int b, int P) { return 8 + (long)m * b + 4 + 5 + (long)m * P; }
 
 FLAC_HD void flac_enc_write_sub(FlacBitWriter& w, const int32_t* s, int bs, int b, int method, const FlacEncSub& sub,
                                 uint64_t* sums) {
-  w.put(sub.type == 0 ? 0u : sub.type == 1 ? 2u : (unsigned)(8 + sub.order) << 1, 8);
+  w.put(sub.type == 0 ? 0u : sub.type == 1 ? 2u : (unsigned)((sub.type == 3 ? 31 : 8) + sub.order) << 1, 8);
   if (sub.type == 0) {
     w.put_signed(s[0], b);
     return;
@@ -266,19 +434,26 @@ FLAC_HD void flac_enc_write_sub(FlacBitWriter& w, const int32_t* s, int bs, int 
     return;
   }
   const int o = sub.order, p = sub.porder, kmax = flac_enc_kmax(method), pbits = flac_enc_pbits(method);
+  const int* q = sub.type == 3 ? sub.qlp : nullptr;
   for (int i = 0; i < o; ++i) w.put_signed(s[i], b);
+  if (q) {
+    w.put((unsigned)(sub.precision - 1), 4);
+    w.put((unsigned)sub.shift, 5);
+    for (int j = 0; j < o; ++j) w.put_signed(q[j], sub.precision);
+  }
   w.put((unsigned)method, 2);
   w.put((unsigned)p, 4);
-  flac_enc_part_sums(s, bs, o, p, kmax, sums);
+  flac_enc_part_sums(s, bs, o, p, kmax, sums, q, sub.shift);
   const int np = 1 << p, ps = bs >> p;
   int i = o;
-  for (int q = 0; q < np; ++q) {
-    const int cnt = q == 0 ? ps - o : ps;
+  for (int part = 0; part < np; ++part) {
+    const int cnt = part == 0 ? ps - o : ps;
     int k;
-    flac_enc_best_k(sums + q, FLAC_ENC_PARTS, cnt, kmax, &k);
+    flac_enc_best_k(sums + part, FLAC_ENC_PARTS, cnt, kmax, &k);
     w.put((unsigned)k, pbits);
     for (int e = i + cnt; i < e; ++i) {
-      const uint32_t u = flac_enc_zigzag(flac_enc_residual(s + i, o));
+      const int32_t res = q ? (int32_t)flac_enc_lpc_residual(s + i, o, q, sub.shift) : flac_enc_residual(s + i, o);
+      const uint32_t u = flac_enc_zigzag(res);
       w.bit += u >> k;                                            // the unary zeros are the cleared buffer
       w.put((1u << k) | (u & ((1u << k) - 1u)), k + 1);
     }
@@ -288,8 +463,8 @@ FLAC_HD void flac_enc_write_sub(FlacBitWriter& w, const int32_t* s, int bs, int 
 // One frame of pcm [C][n] (channel c at pcm + c n) at sample pos, into the zero-filled out; returns its length in bytes
 // (at most flac_enc_frame_bound).  Channels 3..8 are coded independently.
 FLAC_HD long flac_enc_frame(const int32_t* pcm, long n, int C, int bps, int rate, long number, long pos, int bs,
-                            const FlacEncScratch& sc, uint8_t* out) {
-  const int method = bps <= 16 ? 0 : 1;
+                            const FlacEncScratch& sc, uint8_t* out, int max_order = 0) {
+  const int method = bps <= 16 ? 0 : 1, P = flac_enc_lpc_precision(bps);
   FlacEncSub sub[8];
   int assign = 0;
   const int32_t* ch[8];
@@ -300,7 +475,7 @@ FLAC_HD long flac_enc_frame(const int32_t* pcm, long n, int C, int bps, int rate
     FlacEncSub cs[4];
     long cb[4], bits;
     for (int c = 0; c < 4; ++c) {
-      flac_enc_plan_sub(sc.cand + c * FLAC_ENC_MAX_BS, bs, bps + (c == 3), method, sc.sums, &cs[c]);
+      flac_enc_plan_sub(sc.cand + c * FLAC_ENC_MAX_BS, bs, bps + (c == 3), method, sc.sums, &cs[c], max_order, P, sc.win);
       cb[c] = cs[c].bits;
     }
     assign = flac_enc_pick_assign(cb, &bits);
@@ -311,7 +486,7 @@ FLAC_HD long flac_enc_frame(const int32_t* pcm, long n, int C, int bps, int rate
   } else {
     for (int c = 0; c < C; ++c) {
       ch[c] = pcm + (long)c * n + pos, width[c] = bps;
-      flac_enc_plan_sub(ch[c], bs, bps, method, sc.sums, &sub[c]);
+      flac_enc_plan_sub(ch[c], bs, bps, method, sc.sums, &sub[c], max_order, P, sc.win);
     }
   }
   FlacBitWriter w{out, 0};
@@ -325,14 +500,15 @@ FLAC_HD long flac_enc_frame(const int32_t* pcm, long n, int C, int bps, int rate
 
 // The serial encoder: pcm [C][n] -> out [cap] (cleared here), cap >= flac_enc_bound(n, C, bps, block_size).  Returns the
 // stream's length.  Arguments are the caller's to check (1 <= C <= 8, a supported bps, 16 <= block_size <= 4608, n >= 1,
-// 1 <= rate < 2^20, every sample inside bps bits).
+// 1 <= rate < 2^20, every sample inside bps bits).  max_order 0: predictor "fixed"; 1..12: predictor "lpc", which needs
+// sc.win.
 FLAC_HD long flac_encode_serial(const int32_t* pcm, long n, int C, int bps, int rate, int block_size, const FlacEncScratch& sc,
-                                uint8_t* out, long cap) {
+                                uint8_t* out, long cap, int max_order = 0) {
   for (long i = 0; i < cap; ++i) out[i] = 0;
   long off = FLAC_ENC_STREAM_HEAD, min_frame = 0, max_frame = 0, number = 0;
   for (long pos = 0; pos < n; pos += block_size, ++number) {
     const int bs = n - pos < block_size ? (int)(n - pos) : block_size;
-    const long len = flac_enc_frame(pcm, n, C, bps, rate, number, pos, bs, sc, out + off);
+    const long len = flac_enc_frame(pcm, n, C, bps, rate, number, pos, bs, sc, out + off, max_order);
     if (number == 0 || len < min_frame) min_frame = len;
     if (len > max_frame) max_frame = len;
     off += len;

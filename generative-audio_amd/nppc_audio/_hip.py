@@ -330,6 +330,10 @@ SIGS = {
     "nppc_flac_enc_plan": [P, L, P, I, P, L, I, I, P, P],
     "nppc_flac_enc_scan": [P, P, L, I, P, P, P],
     "nppc_flac_enc_write": [P, L, P, I, P, L, I, I, I, P, P, P, P, P, L, P],
+    "nppc_flac_encode_host_lpc": [P, L, I, I, I, I, I, P, L, PL],
+    "nppc_flac_enc_plan_lpc": [P, L, P, I, P, L, I, I, I, P, P],
+    "nppc_flac_enc_scan_stride": [P, I, P, L, I, P, P, P],
+    "nppc_flac_enc_write_lpc": [P, L, P, I, P, L, I, I, I, P, P, P, P, P, L, P],
     "nppc_resample_sinc_shape": [I, I, I, I, I, PI, PL, PL, PL, PI],
     "nppc_resample_sinc": [P, L, P, I, P, I, I, I, I, I, P, L, P],
     "nppc_png_bound": [L, L, P],

@@ -552,13 +552,14 @@ class RecordingEnhancer:
         return out
 
     def enhance_file(self, path, out_path, alphas=None, keep_rate=True, out_format="auto", verify_flac_md5=True, samples=0,
-                     seed=None):
+                     seed=None, flac_predictor="fixed"):
         """wav or flac -> wav or flac, as RecordingRestorer.restore_file reads and writes them: decoded to mono
         (data._decode_wav, data._decode_flac for a name ending in .flac), enhanced, written as 16-bit PCM; out_format "wav",
         "flac" or "auto" (flac when out_path ends in .flac).  keep_rate=True: the file is decoded at ITS rate and
         enhance(..., sample_rate=rate) returns that rate and sample count, band-limited to config.sample_rate / 2;
         keep_rate=False: decoded to config.sample_rate and written at it.  samples, seed: enhance's (the samples are in the
-        dict; save_posterior_samples writes them).  -> enhance's dict"""
+        dict; save_posterior_samples writes them).  flac_predictor: the FLAC encoder's predictor, "fixed" or "lpc"
+        (flac.encode_pcm).  -> enhance's dict"""
         from .data import _decode_flac, _decode_wav
         from .flac import write_waves
         if out_format not in ("wav", "flac", "auto"):
@@ -580,14 +581,15 @@ class RecordingEnhancer:
         wave = torch.as_tensor(wave)
         out = self.enhance(wave, alphas, sample_rate=rate, samples=samples, seed=seed)
         out.setdefault("sample_rate", rate)
-        write_waves([out_path], out["enhanced"][None].contiguous(), rate, out_format)
+        write_waves([out_path], out["enhanced"][None].contiguous(), rate, out_format, predictor=flac_predictor)
         return out
 
-    def save_variations(self, result, folder, fmt="flac", alphas=None):
+    def save_variations(self, result, folder, fmt="flac", alphas=None, flac_predictor="fixed"):
         """enhance's dict -> <folder>/enhanced.<ext> and, when it holds 'variations' [K, A, L],
         <folder>/pc_<k+1>/alpha_<a:.1f>.<ext> (the layout of inpainting.restore's save_variations): 16-bit mono at the rate
         of the dict, through flac.write_waves (fmt "flac": every waveform encoded in one device call; "wav": the same
-        samples).  alphas: the sweep, when the dict does not carry it.  -> the paths written"""
+        samples).  alphas: the sweep, when the dict does not carry it.  flac_predictor: the FLAC encoder's predictor, "fixed"
+        or "lpc" (flac.encode_pcm).  -> the paths written"""
         from .flac import write_waves
         rate = int(result.get("sample_rate", self.config.sample_rate))
         paths, waves = [os.path.join(str(folder), f"enhanced.{fmt}")], [result["enhanced"].reshape(1, -1)]
@@ -603,13 +605,13 @@ class RecordingEnhancer:
         for p in paths:
             os.makedirs(os.path.dirname(p), exist_ok=True)
         stack = torch.cat([w.to(self.device).float() for w in waves]) if fmt == "flac" else torch.cat([w.float().cpu() for w in waves])
-        write_waves(paths, stack, rate, fmt)
+        write_waves(paths, stack, rate, fmt, predictor=flac_predictor)
         return paths
 
-    def save_posterior_samples(self, result, folder, fmt="flac"):
+    def save_posterior_samples(self, result, folder, fmt="flac", flac_predictor="fixed"):
         """enhance's dict with 'samples' [S, L] -> <folder>/posterior/sample_<s>.<ext> (the layout of
         NPPCAudioValidator.save_posterior_samples), 16-bit mono at the rate of the dict, as they are (not normalised), in one
-        flac.write_waves call.  -> the paths written"""
+        flac.write_waves call (flac_predictor: its predictor, "fixed" or "lpc").  -> the paths written"""
         from .flac import write_waves
         if "samples" not in result:
             raise ValueError("the dict holds no 'samples': call enhance(..., samples=S) with keep_samples=True")
@@ -617,5 +619,6 @@ class RecordingEnhancer:
         rows = result["samples"]
         paths = [os.path.join(str(folder), "posterior", f"sample_{s}.{fmt}") for s in range(rows.shape[0])]
         os.makedirs(os.path.dirname(paths[0]), exist_ok=True)
-        write_waves(paths, (rows.to(self.device) if fmt == "flac" else rows.cpu()).float().contiguous(), rate, fmt)
+        write_waves(paths, (rows.to(self.device) if fmt == "flac" else rows.cpu()).float().contiguous(), rate, fmt,
+                    predictor=flac_predictor)
         return paths

@@ -18,8 +18,11 @@ Encoding (csrc/flac_enc_core.h + csrc/flac_enc.hip; specif
 `encode_pcm` turns int32 PCM into FLAC streams, `encode_waves` quantises fp32 waveforms first, `write_files` stores them.
 Lossless, fixed predictors with exact Rice-parameter search, one stated decision rule: the bytes are a function of the
 samples alone, the same from the serial host encoder and from the device (plan, scan, MD5, write: four launches, one small
-host read and one copy of exactly the encoded bytes per batch).  Not built: LPC subframes, escape partitions, wasted bits,
-variable block sizes, seek tables and comments, more than two channels on the device.
+host read and one copy of exactly the encoded bytes per batch).  predictor="lpc" (specification
+tests/flac_lpc_ref.py) adds LPC subframes of order 1..max_lpc_order to the candidates of every subframe, costed exactly like
+the fixed ones, so a stream is never longer than the fixed stream of the same samples; the default stays "fixed".  Not
+built: escape partitions, wasted bits, variable block sizes, seek tables and comments, more than two channels on the
+device, error feedback in the quantiser, a search over the coefficient precision.
 """
 import ctypes
 import os
@@ -303,6 +306,9 @@ def decode_files(paths, out="mono", backend="auto", device="cuda", max_batch_byt
 # ---- encoding --------------------------------------------------------------------------------------------------------
 ENC_BITS = (8, 12, 16, 20, 24)
 ENC_MIN_BLOCK, ENC_MAX_BLOCK = 16, 4608
+ENC_PREDICTORS = ("fixed", "lpc")
+ENC_MAX_LPC_ORDER = 12
+PLAN_INTS, PLAN_LPC_INTS = 8, 34                                      # NPPC_FLAC_ENC_PLAN, NPPC_FLAC_ENC_PLAN_LPC
 
 
 def _enc_args(bits_per_sample, sample_rate, block_size):
@@ -314,30 +320,44 @@ def _enc_args(bits_per_sample, sample_rate, block_size):
         raise ValueError(f"sample_rate must be in 1..{(1 << 20) - 1}, got {sample_rate!r}")
 
 
+def _enc_predictor(predictor, max_lpc_order):
+    """-> the LPC order limit the C entry points take: 0 for the fixed predictors"""
+    if predictor not in ENC_PREDICTORS:
+        raise ValueError(f"predictor must be one of {ENC_PREDICTORS}, got {predictor!r}")
+    if isinstance(max_lpc_order, bool) or not isinstance(max_lpc_order, int) or not 1 <= max_lpc_order <= ENC_MAX_LPC_ORDER:
+        raise ValueError(f"max_lpc_order must be an int in 1..{ENC_MAX_LPC_ORDER}, got {max_lpc_order!r}")
+    return max_lpc_order if predictor == "lpc" else 0
+
+
 def _enc_bound(n, channels, bps, block_size):
     nbytes, frames = ctypes.c_long(), ctypes.c_long()
     H.call("nppc_flac_enc_bound", n, channels, bps, block_size, ctypes.byref(nbytes), ctypes.byref(frames))
     return nbytes.value, frames.value
 
 
-def _encode_host(a, bps, rate, block_size):
-    """nppc_flac_encode_host of a C-contiguous int32 array [C, n]"""
+def _encode_host(a, bps, rate, block_size, lpc=0):
+    """nppc_flac_encode_host (lpc = 0) or nppc_flac_encode_host_lpc of a C-contiguous int32 array [C, n]"""
     cap, _ = _enc_bound(a.shape[1], a.shape[0], bps, block_size)
     out = np.empty(cap, np.uint8)
     nbytes = ctypes.c_long()
-    H.call("nppc_flac_encode_host", a.ctypes.data, a.shape[1], a.shape[0], bps, rate, block_size, out.ctypes.data, cap,
-           ctypes.byref(nbytes))
+    if lpc:
+        H.call("nppc_flac_encode_host_lpc", a.ctypes.data, a.shape[1], a.shape[0], bps, rate, block_size, lpc, out.ctypes.data,
+               cap, ctypes.byref(nbytes))
+    else:
+        H.call("nppc_flac_encode_host", a.ctypes.data, a.shape[1], a.shape[0], bps, rate, block_size, out.ctypes.data, cap,
+               ctypes.byref(nbytes))
     return out[:nbytes.value].tobytes()
 
 
-def _encode_host_pool(arrays, bps, rate, block_size):
+def _encode_host_pool(arrays, bps, rate, block_size, lpc=0):
     with ThreadPoolExecutor(max_workers=max(1, min(HOST_THREADS, os.cpu_count() or 1, len(arrays) or 1))) as ex:
-        return list(ex.map(lambda a: _encode_host(a, bps, rate, block_size), arrays))   # ctypes releases the GIL
+        return list(ex.map(lambda a: _encode_host(a, bps, rate, block_size, lpc), arrays))   # ctypes releases the GIL
 
 
-def _encode_device(flat, channels, lengths, bps, rate, block_size):
+def _encode_device(flat, channels, lengths, bps, rate, block_size, lpc=0):
     """flat: int32 device tensor, the files' planar [C, n] blocks back to back -> list of bytes.  Four launches, one small
-    host read (per-file begin / end / min / max frame size, the batch's byte count, the digests), one copy of the bytes."""
+    host read (per-file begin / end / min / max frame size, the batch's byte count, the digests), one copy of the bytes.
+    lpc: 0 for the fixed predictors, else the LPC order limit (the wider plan record and its three entry points)."""
     dev = flat.device
     nf = len(lengths)
     channels, lengths = np.asarray(channels, np.int64), np.asarray(lengths, np.int64)
@@ -358,16 +378,20 @@ def _encode_device(flat, channels, lengths, bps, rate, block_size):
     small = torch.empty(4 * (nf + 1) + 2 * nf, dtype=torch.int64, device=dev)
     stats, digest = small[:4 * (nf + 1)], small[4 * (nf + 1):].view(torch.uint8)
     verdict = torch.empty(nf, dtype=torch.int32, device=dev)
-    plan = torch.empty(nfr * 8, dtype=torch.int32, device=dev)
+    plan = torch.empty(nfr * (PLAN_LPC_INTS if lpc else PLAN_INTS), dtype=torch.int32, device=dev)
     goff = torch.empty(nfr, dtype=torch.int64, device=dev)
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         s = H.stream()
-        H.call("nppc_flac_enc_plan", flat, flat.numel(), d_meta, nf, d_ftab, nfr, bps, block_size, plan, s)
-        H.call("nppc_flac_enc_scan", plan, d_ftab, nfr, nf, goff, stats, s)
+        if lpc:
+            H.call("nppc_flac_enc_plan_lpc", flat, flat.numel(), d_meta, nf, d_ftab, nfr, bps, block_size, lpc, plan, s)
+            H.call("nppc_flac_enc_scan_stride", plan, PLAN_LPC_INTS, d_ftab, nfr, nf, goff, stats, s)
+        else:
+            H.call("nppc_flac_enc_plan", flat, flat.numel(), d_meta, nf, d_ftab, nfr, bps, block_size, plan, s)
+            H.call("nppc_flac_enc_scan", plan, d_ftab, nfr, nf, goff, stats, s)
         H.call("nppc_flac_md5", flat, flat.numel(), d_meta, nf, d_order, None, None, digest, verdict, s)
-        H.call("nppc_flac_enc_write", flat, flat.numel(), d_meta, nf, d_ftab, nfr, bps, rate, block_size, plan, goff, stats,
-               digest, out, cap, s)
+        H.call("nppc_flac_enc_write_lpc" if lpc else "nppc_flac_enc_write", flat, flat.numel(), d_meta, nf, d_ftab, nfr, bps, rate,
+               block_size, plan, goff, stats, digest, out, cap, s)
         host = small.cpu().numpy()[:4 * (nf + 1)].reshape(nf + 1, 4)  # the small read
         total = int(host[nf, 0])
         data = out[:total].cpu().numpy()                              # exactly the encoded bytes
@@ -380,13 +404,18 @@ def _enc_backend(backend):
     return _use_device("device" if backend == "hip" else backend)
 
 
-def encode_pcm(pcm, bits_per_sample, sample_rate=16000, block_size=4096, backend="auto", device="cuda"):
+def encode_pcm(pcm, bits_per_sample, sample_rate=16000, block_size=4096, backend="auto", device="cuda", predictor="fixed",
+               max_lpc_order=8):
     """int32 PCM -> FLAC streams: a list of [C, n] tensors (host or device) -> a list of bytes.  One call has one sample
     size, rate and block size; every file has its own length and channel count.  backend "host" runs the serial encoder on
     a pool of 16 threads (1..8 channels), "hip" the device kernels (1 or 2 channels) and "auto" the device when there is
     one; both give the same bytes.  ValueError, before anything is launched, for an empty file, an unsupported
-    bits_per_sample or block_size, more than 2 channels on the device, or a sample outside bits_per_sample bits."""
+    bits_per_sample or block_size, more than 2 channels on the device, or a sample outside bits_per_sample bits.
+    predictor "fixed" (the default) tries the fixed predictors of order 0..4; "lpc" also LPC subframes of order
+    1..max_lpc_order (at most 12), each costed exactly, so its streams are never longer.  Any other predictor or order
+    limit is a ValueError before anything is launched."""
     _enc_args(bits_per_sample, sample_rate, block_size)
+    lpc = _enc_predictor(predictor, max_lpc_order)
     tensors = [pcm] if isinstance(pcm, torch.Tensor) else list(pcm)
     for t in tensors:
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or not 1 <= t.shape[0] <= 8:
@@ -403,14 +432,14 @@ def encode_pcm(pcm, bits_per_sample, sample_rate=16000, block_size=4096, backend
         arrays = [np.ascontiguousarray(t.cpu().numpy()) for t in tensors]
         if any(a.min() < lo or a.max() > hi for a in arrays):
             raise ValueError(f"encode_pcm: a sample lies outside {bits_per_sample} bits")
-        return _encode_host_pool(arrays, bits_per_sample, int(sample_rate), block_size)
+        return _encode_host_pool(arrays, bits_per_sample, int(sample_rate), block_size, lpc)
     tensors = [t if t.is_cuda else t.to(device) for t in tensors]
     flat = tensors[0].contiguous().view(-1) if len(tensors) == 1 else torch.cat([t.reshape(-1) for t in tensors])
     mn, mx = torch.aminmax(flat)
     if int(mn) < lo or int(mx) > hi:
         raise ValueError(f"encode_pcm: a sample lies outside {bits_per_sample} bits")
     return _encode_device(flat, [t.shape[0] for t in tensors], [t.shape[1] for t in tensors], bits_per_sample, int(sample_rate),
-                          block_size)
+                          block_size, lpc)
 
 
 def quantize_waves_host(waves, bits_per_sample=16):
@@ -420,10 +449,13 @@ def quantize_waves_host(waves, bits_per_sample=16):
     return np.clip(np.nan_to_num(y, nan=0.0, posinf=np.inf, neginf=-np.inf), -full, full - 1).astype(np.int32)
 
 
-def encode_waves(waves, lengths=None, sample_rate=16000, bits_per_sample=16, block_size=4096, backend="auto", device="cuda"):
+def encode_waves(waves, lengths=None, sample_rate=16000, bits_per_sample=16, block_size=4096, backend="auto", device="cuda",
+                 predictor="fixed", max_lpc_order=8):
     """fp32 waveforms [V, L] (or [L]) in [-1, 1) -> V mono FLAC streams of lengths[v] samples each (default L): quantised as
-    clip(rint(x 2^(bits-1))) (on the device by nppc_pcm_quantize, straight into the encoder's layout), then encoded."""
+    clip(rint(x 2^(bits-1))) (on the device by nppc_pcm_quantize, straight into the encoder's layout), then encoded.
+    predictor, max_lpc_order: as for encode_pcm."""
     _enc_args(bits_per_sample, sample_rate, block_size)
+    lpc = _enc_predictor(predictor, max_lpc_order)
     if not isinstance(waves, torch.Tensor) or waves.dtype != torch.float32 or waves.dim() not in (1, 2):
         raise ValueError("encode_waves takes a float32 tensor [V, L] or [L]")
     waves = waves.reshape(-1, waves.shape[-1])
@@ -436,7 +468,7 @@ def encode_waves(waves, lengths=None, sample_rate=16000, bits_per_sample=16, blo
     if not _enc_backend(backend):
         q = quantize_waves_host(waves.cpu().numpy(), bits_per_sample)
         return _encode_host_pool([np.ascontiguousarray(q[v:v + 1, :lens[v]]) for v in range(V)], bits_per_sample,
-                                 int(sample_rate), block_size)
+                                 int(sample_rate), block_size, lpc)
     waves = (waves if waves.is_cuda else waves.to(device)).contiguous()
     off = np.concatenate([[0], np.cumsum(lens)])
     flat = torch.empty(int(off[-1]), dtype=torch.int32, device=waves.device)
@@ -446,7 +478,7 @@ def encode_waves(waves, lengths=None, sample_rate=16000, bits_per_sample=16, blo
         with torch.cuda.device(waves.device):
             H.call("nppc_pcm_quantize", waves[v0:v1], L, d_len[v0:v1], v1 - v0, bits_per_sample, flat, d_off[v0:v1],
                    flat.numel(), H.stream())
-    return _encode_device(flat, np.ones(V, np.int64), lens, bits_per_sample, int(sample_rate), block_size)
+    return _encode_device(flat, np.ones(V, np.int64), lens, bits_per_sample, int(sample_rate), block_size, lpc)
 
 
 def write_files(paths, streams):
@@ -462,14 +494,17 @@ def write_files(paths, streams):
             f.write(b)
 
 
-def write_waves(paths, waves, sample_rate=16000, fmt="flac", lengths=None, backend="auto"):
+def write_waves(paths, waves, sample_rate=16000, fmt="flac", lengths=None, backend="auto", predictor="fixed", max_lpc_order=8):
     """fp32 waveforms [V, L] -> V 16-bit mono files: fmt "flac" (encode_waves: the whole batch in one device call) or "wav"
-    (the same samples, through scipy)"""
+    (the same samples, through scipy).  predictor, max_lpc_order: the FLAC encoder's, as for encode_pcm; "wav" ignores them
+    once they are checked."""
     if fmt not in ("flac", "wav"):
         raise ValueError(f"fmt must be 'flac' or 'wav', got {fmt!r}")
+    _enc_predictor(predictor, max_lpc_order)
     waves = waves.detach().reshape(-1, waves.shape[-1])
     if fmt == "flac":
-        write_files(paths, encode_waves(waves.float(), lengths, sample_rate, 16, backend=backend))
+        write_files(paths, encode_waves(waves.float(), lengths, sample_rate, 16, backend=backend, predictor=predictor,
+                                        max_lpc_order=max_lpc_order))
         return
     from scipy.io import wavfile
     paths = [str(p) for p in paths]

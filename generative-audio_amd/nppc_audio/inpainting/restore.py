@@ -426,7 +426,8 @@ class RecordingRestorer:
                 return [(int(s), int(e)) for s, e in host[1:1 + 2 * n].view(-1, 2).tolist()]
             cap = n
 
-    def restore_file(self, path_in, path_out, gaps=None, verify_flac_md5=True, keep_rate=False, out_format="wav"):
+    def restore_file(self, path_in, path_out, gaps=None, verify_flac_md5=True, keep_rate=False, out_format="wav",
+                     flac_predictor="fixed"):
         """wav or flac -> wav or flac: decodes with data._decode_wav, or data._decode_flac for a name ending in .flac (mono,
         config.sample_rate), detects the gaps when none are given, restores, writes 16-bit PCM: out_format "wav" (the
         default), "flac" (flac.encode_waves: the same samples, at the rate the wav would have had) or "auto" (flac when
@@ -435,7 +436,8 @@ class RecordingRestorer:
         keep_rate=True: the file is decoded at ITS rate (the wav header's, flac.probe's), the gaps are detected on those
         samples -- a filter would smear the exact zeros of a dropout -- and given at that rate, restore(...,
         sample_rate=rate) keeps every sample outside the crossfaded gaps, and the wav written has the file's rate and
-        sample count.  Inside the gaps there is nothing above config.sample_rate / 2."""
+        sample count.  Inside the gaps there is nothing above config.sample_rate / 2.
+        flac_predictor: the FLAC encoder's predictor, "fixed" or "lpc" (flac.encode_pcm)."""
         import numpy as np
         from scipy.io import wavfile
         from ..data import _decode_flac, _decode_wav
@@ -462,18 +464,19 @@ class RecordingRestorer:
         out = self.restore(wave, gaps, sample_rate=rate) if keep_rate else self.restore(wave, gaps)
         if out_format == "flac":
             from ..flac import write_waves
-            write_waves([path_out], out["restored"][None], rate, "flac")
+            write_waves([path_out], out["restored"][None], rate, "flac", predictor=flac_predictor)
             return out
         pcm = np.clip(np.rint(out["restored"].detach().cpu().double().numpy() * 32768.0), -32768, 32767).astype(np.int16)
         wavfile.write(str(path_out), rate, pcm)
         return out
 
-    def save_variations(self, out, directory, fmt="flac", alphas=None):
+    def save_variations(self, out, directory, fmt="flac", alphas=None, flac_predictor="fixed"):
         """restore's dict -> <directory>/restored.<ext> and, when it holds 'variations' [K, A, L] (restore(..., alphas,
         variations="full")), <directory>/pc_<k+1>/alpha_<a:.1f>.<ext>: 16-bit mono at the rate of the dict.  fmt "flac"
         encodes every waveform in one device call (flac.encode_waves), "wav" writes the same samples.  When it holds
         'samples' [S, L] (restore(..., samples=S, variations="full")) also <directory>/posterior/sample_<s>.<ext>.  alphas: the sweep,
-        when the dict does not carry it ('alphas', which restore adds).  -> the paths written"""
+        when the dict does not carry it ('alphas', which restore adds).  flac_predictor: the FLAC encoder's predictor, "fixed" or
+        "lpc" (flac.encode_pcm).  -> the paths written"""
         import os
         from ..flac import write_waves
         rate = int(out.get("sample_rate", self.config.sample_rate))
@@ -492,7 +495,7 @@ class RecordingRestorer:
             paths += [os.path.join(str(directory), "posterior", f"sample_{i}.{fmt}") for i in range(smp.shape[0])]
             waves.append(smp)
         write_waves(paths, torch.cat([w.to(self.device).float() for w in waves]) if fmt == "flac"
-                    else torch.cat([w.float().cpu() for w in waves]), rate, fmt)
+                    else torch.cat([w.float().cpu() for w in waves]), rate, fmt, predictor=flac_predictor)
         return paths
 
 

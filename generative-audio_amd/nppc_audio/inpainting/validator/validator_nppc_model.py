@@ -93,7 +93,8 @@ def pc_audio_variations(clean_spec_mag_norm_log, pred_spec_mag, pc_directions_ma
     return out, clean_wave
 
 
-def save_pc_audio_variations(out, save_dir, alphas, first_index=0, fmt="flac", sample_rate=16000, backend="auto"):
+def save_pc_audio_variations(out, save_dir, alphas, first_index=0, fmt="flac", sample_rate=16000, backend="auto",
+                             flac_predictor="fixed"):
     """save_pc_audio_variations (:579-634), the audio files, for a whole batch: from validate_batch's dict (called with
     `alphas`) writes, for sample b of the batch, under <save_dir>/sample_<first_index + b>/
         clean.<ext>                            'clean_audio'[b]
@@ -103,7 +104,7 @@ def save_pc_audio_variations(out, save_dir, alphas, first_index=0, fmt="flac", s
     (flac.encode_waves) and cross to the host as FLAC bytes; fmt "wav": the same samples as wav.  The reference's *_full
     files (the variation spliced into the source recording) are RecordingRestorer.save_variations, the spectrogram pictures
     save_pc_spectrograms, the pitch figures save_pc_pitch_plots; transcriptions and phonemes are outside this build.
-    -> the paths written"""
+    flac_predictor: the FLAC encoder's predictor, "fixed" or "lpc" (flac.encode_pcm).  -> the paths written"""
     from ... import flac as FL
     var, clean = out["audio_variations"], out["clean_audio"]
     B, K, A, L = var.shape
@@ -122,7 +123,7 @@ def save_pc_audio_variations(out, save_dir, alphas, first_index=0, fmt="flac", s
         waves.append(blind.reshape(B * K * A, L))
         paths += [root / f"sample_{first_index + b}" / f"pc_{k + 1}" / f"alpha_{a:.1f}_blind.{fmt}"
                   for b in range(B) for k in range(K) for a in alphas]
-    FL.write_waves(paths, torch.cat([w.float() for w in waves]), sample_rate, fmt, backend=backend)
+    FL.write_waves(paths, torch.cat([w.float() for w in waves]), sample_rate, fmt, backend=backend, predictor=flac_predictor)
     return paths
 
 
@@ -210,7 +211,7 @@ def posterior_std_planes(out):
 
 
 def save_posterior_samples(out, save_dir, first_index=0, fmt="flac", sample_rate=16000, backend="auto", sx=2, sy=2,
-                           palette="viridis", max_frames=None):
+                           palette="viridis", max_frames=None, flac_predictor="fixed"):
     """from the dict of validate_batch(..., posterior_samples=S) writes, for sample b of the batch, under
     <save_dir>/sample_<first_index + b>/posterior/
         sample_<s>.<ext>          'posterior'['samples'][b, s] (and sample_<s>_blind.<ext> when the dict holds 'samples_blind'),
@@ -219,7 +220,7 @@ def save_posterior_samples(out, save_dir, first_index=0, fmt="flac", sample_rate
         std_spec.png              'posterior'['mag_std'][b] in dB (20 log10(std + 1e-8), autoscaled over the gap) over the
                                   reference's context window with the gap markers (spectrogram_png: one Sheet per item, all
                                   drawn and encoded in one device call); known frames, where the spread is zero, take index 0
-    -> the paths written"""
+    flac_predictor: the FLAC encoder's predictor, "fixed" or "lpc" (flac.encode_pcm).  -> the paths written"""
     from ... import flac as FL
     from ... import png as PNG
     from ...spectrogram_png import Cell, Sheet, render_png, windows_from_mask
@@ -234,7 +235,7 @@ def save_posterior_samples(out, save_dir, first_index=0, fmt="flac", sample_rate
     if "samples_blind" in post:
         paths += [folder(b) / f"sample_{s}_blind.{fmt}" for b in range(B) for s in range(S)]
         waves.append(post["samples_blind"].reshape(B * S, L))
-    FL.write_waves(paths, torch.cat([w.float() for w in waves]), sample_rate, fmt, backend=backend)
+    FL.write_waves(paths, torch.cat([w.float() for w in waves]), sample_rate, fmt, backend=backend, predictor=flac_predictor)
     planes = posterior_std_planes(out)
     F, T = planes.shape[-2:]
     win = windows_from_mask(out["mask"].detach().float().reshape(B, -1, F, T)[:, 0, 0, :])

@@ -197,11 +197,12 @@ class NPPCAudioValidator:
         return paths, pitch
 
     def save_posterior_samples(self, noisy_audio: torch.Tensor, save_dir, n_samples=8, seed=0, fmt="flac", sx=1, sy=1,
-                               palette="viridis"):
+                               palette="viridis", flac_predictor="fixed"):
         """noisy_audio [B,T] -> n_samples waveforms drawn from the posterior the net states (posterior.py: z ~ N(0, 1) along
         every direction, compressed domain), written peak-normalised as <save_dir>/posterior/sample_<s>.<fmt>, and the
         standard deviation of the samples' spectrogram magnitudes in dB as <save_dir>/posterior/std_spec.png (under
-        <save_dir>/item_<b>/ when B > 1).  All samples and both statistics come from one fused launch.  Returns the paths."""
+        <save_dir>/item_<b>/ when B > 1).  All samples and both statistics come from one fused launch.  flac_predictor: the
+        FLAC encoder's predictor, "fixed" or "lpc" (flac.encode_pcm).  Returns the paths."""
         from .posterior import PosteriorSampler
         H.require_gpu()
         if noisy_audio.dim() != 2:
@@ -213,7 +214,7 @@ class NPPCAudioValidator:
         root = Path(save_dir).absolute()
         dirs = [(root / f"item_{b}" if B > 1 else root) / "posterior" for b in range(B)]
         waves = [d / f"sample_{s}.{fmt}" for d in dirs for s in range(n_samples)]
-        FL.write_waves(waves, self._normalised(r["samples"].reshape(B * n_samples, -1)), 16000, fmt=fmt)
+        FL.write_waves(waves, self._normalised(r["samples"].reshape(B * n_samples, -1)), 16000, fmt=fmt, predictor=flac_predictor)
         std = torch.stack((r["mag_std"], torch.zeros_like(r["mag_std"])), dim=1)[:, None].contiguous()      # [B,1,2,F,T]
         pngs = [d / "std_spec.png" for d in dirs]
         PNG.write_files(pngs, render_png(std, [Sheet(b, [[Cell(p=0, g="db")]], sx=sx, sy=sy) for b in range(B)], palette=palette))

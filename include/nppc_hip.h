@@ -1023,7 +1023,8 @@ int nppc_flac_md5(const int* pcm, long pcm_elems, const long* meta, int nfiles, 
                   const int* status, unsigned char* digest, int* verdict, void* stream);
 
 /* ---- FLAC encoding (csrc/flac_enc_core.h + csrc/flac_enc.hip; specification tests/flac_enc_ref.py) ----
- * Lossless, fixed predictors only, one stated decision rule (csrc/flac_enc_core.h): the bytes are a function of the samples,
+ * Lossless, fixed predictors (LPC as well through the _lpc entry points below), one stated decision rule
+ * (csrc/flac_enc_core.h): the bytes are a function of the samples,
  * bits per sample (8, 12, 16, 20 or 24), rate (1 .. 2^20 - 1) and block size (16 .. 4608) alone.  The stream is fLaC, one
  * STREAMINFO (min = max blocksize = block_size, min / max frame size, total samples, MD5 of the samples) and frames of
  * block_size samples, the last one shorter.  An unsupported bps or block size: NPPC_EUNSUPPORTED. */
@@ -1058,6 +1059,26 @@ int nppc_flac_enc_scan(const int* plan, const int* ftab, long nframes, int nfile
 int nppc_flac_enc_write(const int* pcm, long pcm_elems, const long* meta, int nfiles, const int* ftab, long nframes, int bps,
                         int rate, int block_size, const int* plan, const long* goff, const long* stats,
                         const unsigned char* digest, unsigned char* out, long out_cap, void* stream);
+/* predictor "lpc" (the rule is stated in csrc/flac_enc_core.h, specification tests/flac_lpc_ref.py):
+ * every non-constant subframe also costs LPC orders 1 .. min(max_order, block) (integer Welch window, exact int64
+ * autocorrelation, Levinson-Durbin in fp64 without contraction, 12-bit coefficients up to 16 bits per sample and 15-bit
+ * above) exactly, beside the fixed orders; ties go to the fixed orders, so no frame is longer than the fixed one.
+ * max_order outside 1..12: NPPC_EBADARG; every other refusal as for the entry points above.  The plan record is wider:
+ * bytes, assignment, then per coded channel type (3 = LPC), order, partition order, shift and 12 coefficients.  The calls
+ * run as above: plan_lpc, scan_stride with stride NPPC_FLAC_ENC_PLAN_LPC (nppc_flac_enc_scan is the stride
+ * NPPC_FLAC_ENC_PLAN; a stride outside 1..1024: NPPC_EBADARG), nppc_flac_md5, write_lpc, which range-checks every field of
+ * the record and does not recompute it.  Host and device give the same bytes. */
+#define NPPC_FLAC_ENC_PLAN_LPC 34     /* ints per frame of the LPC plan: 2 + 2 x (4 + 12) */
+#define NPPC_FLAC_ENC_MAX_LPC 12
+int nppc_flac_encode_host_lpc(const int* pcm, long n, int channels, int bps, int rate, int block_size, int max_order,
+                              unsigned char* out, long cap, long* nbytes);
+int nppc_flac_enc_plan_lpc(const int* pcm, long pcm_elems, const long* meta, int nfiles, const int* ftab, long nframes, int bps,
+                           int block_size, int max_order, int* plan, void* stream);
+int nppc_flac_enc_scan_stride(const int* plan, int stride, const int* ftab, long nframes, int nfiles, long* goff, long* stats,
+                              void* stream);
+int nppc_flac_enc_write_lpc(const int* pcm, long pcm_elems, const long* meta, int nfiles, const int* ftab, long nframes, int bps,
+                            int rate, int block_size, const int* plan, const long* goff, const long* stats,
+                            const unsigned char* digest, unsigned char* out, long out_cap, void* stream);
 
 /* ---- windowed-sinc resampling of ragged batches (csrc/resample.hip; specification
  * tests/resample_ref.py): torchaudio's default Resample (Hann window).  With orig / new the two rates reduced by their gcd,
