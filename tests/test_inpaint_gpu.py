@@ -36,7 +36,8 @@ def q(x, dtype):
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,ks", [(2, 9, 13, 64, 64, 3), (1, 6, 37, 128, 192, 3), (2, 9, 13, 64, 128, 3), (1, 5, 21, 256, 256, 3),
                                                (2, 4, 6, 128, 128, 1), (3, 40, 37, 64, 64, 3), (1, 30, 61, 128, 100, 3),
-                                               (4, 126, 126, 64, 64, 3)])
+                                               (4, 126, 126, 64, 64, 3),
+                                               (2, 4, 6, 64, 64, 1), (1, 6, 37, 64, 128, 1)])     # ONE K stage in a ring of three
 @pytest.mark.parametrize("mode", ["1"])
 def test_conv_lds_dma_ring_kernel_equals_register_staged_kernel(B, H, W, Cin, Cout, ks, mode, monkeypatch):
     """csrc/unet.hip conv_dma_kernel (bf16: 256-row tiles, LDS-DMA ring with hand-counted waits) against conv_tiled_kernel:

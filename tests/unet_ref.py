@@ -1,8 +1,11 @@
-"""fp64 references and derived error bounds for the support kernels of csrc/unet.hip (BatchNorm, pooling, upsampling, the
-boundary maps) and the dropout bits of csrc/mc_pca.hip.  numpy / torch-CPU only: imports without a GPU.
+"""fp64 references and derived error bounds for the kernels of csrc/unet.hip (BatchNorm, pooling, upsampling, the boundary
+maps, the MFMA convolutions and their weight gradients) and the dropout bits of csrc/mc_pca.hip.  numpy / torch-CPU only:
+imports without a GPU.
 
 Every bound here is derived from the arithmetic the kernel is specified to do (how many fp32 roundings a value goes
 through, how long a chain of fp32 additions is), never from what a kernel returned."""
+from typing import NamedTuple
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -294,3 +297,93 @@ def keep_nchw(keep, B, H, W):
     """[rows][C] keep bits over the haloed rows -> [B,C,H,W] float64 (interior)"""
     C = keep.shape[1]
     return torch.from_numpy(keep.reshape(B, H + 2, W + 2, C)[:, 1:-1, 1:-1].astype(np.float64)).permute(0, 3, 1, 2).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ MFMA convolutions
+class ConvRef(NamedTuple):
+    ref: torch.Tensor        # [B,Cout,H,W] fp64: the convolution (+ bias), through the folded epilogue where one was given
+    mag: torch.Tensor        # sum |x| |w| + |bias| of the convolution itself (before the fold)
+    raw: torch.Tensor        # the convolution (+ bias) before the fold (== ref without one)
+
+
+def conv_ref(x, w, bias, ks, fold=None, slope=SLOPE):
+    """x [B,Cin,H,W], w [Cout,Cin,ks,ks]: the values the kernel reads (activations and packed weights already rounded to the
+    storage dtype, see q), bias [Cout] fp32 or None, fold = (scale, shift) fp32 or None.  fp64 F.conv2d with zero padding
+    ks // 2, then optionally leaky(v * scale + shift) with the slope as the fp32 the kernel is handed."""
+    b64 = None if bias is None else bias.double()
+    raw = F.conv2d(x.double(), w.double(), b64, padding=ks // 2)
+    mag = F.conv2d(x.double().abs(), w.double().abs(), None if b64 is None else b64.abs(), padding=ks // 2)
+    if fold is None:
+        return ConvRef(raw, mag, raw)
+    v = raw * _bc(fold[0].double()) + _bc(fold[1].double())
+    return ConvRef(torch.where(v > 0, v, float(np.float32(slope)) * v), mag, raw)
+
+
+def conv_dx_ref(dy, w, ks):
+    """input gradient of the same convolution: dy [B,Cout,H,W], w [Cout,Cin,ks,ks] (exact storage values) -> ConvRef of
+    [B,Cin,H,W] (the transposed convolution the forward kernel computes on the backward pack)"""
+    ref = F.conv_transpose2d(dy.double(), w.double(), padding=ks // 2)
+    return ConvRef(ref, F.conv_transpose2d(dy.double().abs(), w.double().abs(), padding=ks // 2), ref)
+
+
+def conv_bound(cr, K, storage_bf16, fold=None):
+    """Element-wise bound on |kernel - cr.ref| of nppc_conv_fwd, K = ntap * Cin products per output.
+
+    * The kernels add the K products (and the bias) in fp32.  bf16 x bf16 products are exact in fp32, so the error is that of
+      the summation alone: its roundings are each at most 2^-24 of a partial sum <= mag and of either sign, and the project
+      budgets such a chain at acc = 2 sqrt(K) 2^-24 mag (test_tcn_forward_gpu.py, test_wgrad_reduce_gpu.py) -- between the
+      sqrt(K) of independent roundings and the K of the worst case.  fp32 operands: every product is rounded too, at most
+      2^-24 |x w| each, together <= 2^-24 mag more.
+    * Folded epilogue v = raw * scale + shift, leaky(v): the error of raw goes through |scale|; the product and the sum are
+      rounded (one rounding where they fuse): <= 2^-24 (|raw scale| + |v|) <= 2 * 2^-24 (|raw scale| + |shift|) to first order.
+      LeakyReLU is 1-Lipschitz, so a branch decided differently at a v within that error of zero costs no more than the
+      error itself; on the negative side the slope (<= 1) shrinks both roundings to 0.4 and adds its own product rounding,
+      0.2 * 2^-24 |v|: less than the 2 budgeted.
+    * The store rounds once more: u_out (|ref| + e), u_out = 2^-8 (bf16, round to nearest even: exactly the worst case) or
+      2^-24.
+    bound = e + u_out (|ref| + e),   e = acc  or  |scale| acc + 2 * 2^-24 (|raw scale| + |shift|)."""
+    acc = (2.0 * np.sqrt(K) + (0.0 if storage_bf16 else 1.0)) * U24 * cr.mag
+    e = acc
+    if fold is not None:
+        sc, sh = _bc(fold[0].double()), _bc(fold[1].double())
+        e = sc.abs() * acc + 2 * U24 * ((cr.raw * sc).abs() + sh.abs())
+    return e + (U8 if storage_bf16 else U24) * (cr.ref.abs() + e)
+
+
+def conv_wgrad_ref(dy, x, ks):
+    """dW[co][ci][tap] = sum_p dY[p][co] X[p + off(tap)][ci] over the pixels, X zero outside the image: dy [B,Cout,H,W],
+    x [B,Cin,H,W] (exact storage values) -> (dW [Cout,Cin,ks,ks] fp64, sum |dY| |X| of the same shape)"""
+    r = ks // 2
+    H, W = x.shape[2:]
+    dy, xp = dy.double(), F.pad(x.double(), (r, r, r, r))
+    ref = torch.empty(dy.shape[1], x.shape[1], ks, ks, dtype=torch.float64)
+    mag = torch.empty_like(ref)
+    for ty in range(ks):
+        for tx in range(ks):
+            win = xp[:, :, ty:ty + H, tx:tx + W]
+            ref[:, :, ty, tx] = torch.einsum("bohw,bihw->oi", dy, win)
+            mag[:, :, ty, tx] = torch.einsum("bohw,bihw->oi", dy.abs(), win.abs())
+    return ref, mag
+
+
+def wgrad_rows_per_slab(P, ksplit, storage_bf16):
+    """rows of the haloed matrix that one split-K slab of nppc_conv_wgrad sums: bf16 rounds the row count up to
+    R = roundup(P, 64 ksplit) and gives every slice R / ksplit; the fp32 kernel gives roundup(ceil(P / ksplit), 16)"""
+    if storage_bf16:
+        return (P + 64 * ksplit - 1) // (64 * ksplit) * 64
+    return ((P + ksplit - 1) // ksplit + 15) // 16 * 16
+
+
+def conv_wgrad_bound(ref, mag, Rz, storage_bf16):
+    """Element-wise bound on dW after nppc_conv_wgrad_reduce.  A slab is an fp32 sum of Rz products (most of them the zeros
+    of the halo): 2 sqrt(Rz) 2^-24 of its own magnitude sum, as for the convolution above, and one more 2^-24 of it for the
+    slab as an fp32 number (the block sums a matrix instruction adds to its accumulator); over the slabs the magnitude sums
+    add up to mag.  The reduction adds the slabs in fp64 and rounds once: 2^-24 |ref|.  fp32 operands: the products are
+    rounded, 2^-24 mag more.
+    bound = (2 sqrt(Rz) + 1 [+ 1]) 2^-24 mag + 2^-24 |ref|"""
+    return (2.0 * np.sqrt(Rz) + 1.0 + (0.0 if storage_bf16 else 1.0)) * U24 * mag + U24 * ref.abs()
+
+
+def tap_offsets(ks, W):
+    """row offsets of the taps in the haloed matrix, in the kernels' tap order t = 3 ty + tx"""
+    return [(t // 3 - 1) * (W + 2) + (t % 3 - 1) for t in range(9)] if ks == 3 else [0]
